@@ -1,9 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the MI355X-native Gaussian-splatting raster path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times K steps and prints the headline line (`value`, `ms_per_step`, the counters of the
+timed region).  --dump-outputs DIR writes the last timed step's outputs as .npy files (see dump_outputs).  --full then
+adds everything else below (verification, percentiles, rooflines, sweeps, decode, train, CPU baseline) to the line.
 
 A "step" is ONE forward raster (preprocess -> scan -> read back R -> duplicateWithKeys -> radix sort -> tile
 ranges -> blend) of ONE synthetic frame whose inputs already sit in HBM; the workload is BASELINE.json's metric
@@ -12,7 +16,7 @@ Multi-GPU: the raster of one frame does not shard (global depth sort + per-tile 
 SCENES: every rank renders its own frames with no data-path collective (weak scaling); value = frames of all
 ranks / max-over-ranks time.
 
-Rank 0 prints ONE JSON line (contract in the task statement) including
+Rank 0 prints ONE JSON line; with --full it includes
   "roofline"     -- for the dominant kernel of the step (largest hipEvent stage time): algorithmic bytes per launch
                     (SURVEY.md 8d per-unit figures, restated in DESIGN.md) / its measured average duration, vs 8 TB/s
   "cpu_baseline" -- the pure-PyTorch CPU rasterizer (oracle/torch_raster.py) on the host's cores, same workload, one full
@@ -221,12 +225,28 @@ def pmc_traffic(workload, stage):
     return best
 
 
+def dump_outputs(dirname, out):
+    """--dump-outputs: what a caller of the timed forward receives from its last timed step -- the image, the per-Gaussian
+    screen radii and num_rendered -- as DIR/<name>.npy (float32; num_rendered float64).  16 MB at the largest workload; the
+    scene is seeded, so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "color.npy"), out[1].to(torch.float32).cpu().numpy())
+    np.save(os.path.join(dirname, "radii.npy"), out[2].to(torch.float32).cpu().numpy())   # (integers < 2^24: exact)
+    np.save(os.path.join(dirname, "num_rendered.npy"), np.array([int(out[0])], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="1M_1024_cube", choices=sorted(WORKLOADS))
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed frame's outputs (color, radii, num_rendered) "
+                    "as .npy files into DIR")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run every other measurement and check "
+                    "(verification against the exact forward forms, stage times and rooflines, frames in flight, other "
+                    "workloads, decode, train step, CPU baseline); the options below select among them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backward", action="store_true", help="also time forward+backward (reported under 'extra')")
     ap.add_argument("--no-train", action="store_true", help="skip the data-parallel train-step section")
@@ -239,6 +259,8 @@ def main():
     ap.add_argument("--train-points", type=int, default=500_000, help="positions per scene (reference: 500 000)")
     ap.add_argument("--scenes-per-gpu", type=int, default=4)
     args = ap.parse_args()
+    if args.backward and not args.full:
+        ap.error("--backward is one of the --full measurements: add --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -331,6 +353,36 @@ def main():
                   "two_launch_sort_frames_timed": c_after[0] - c_before[0],
                   "ordinary_sort_frames_timed": args.steps - (c_after[0] - c_before[0]),
                   "sort_reruns_timed": c_after[1] - c_before[1], "capacity_retries_timed": c_after[2] - c_before[2]}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    ms_per_step = elapsed / args.steps * 1e3
+    result = {
+        "metric": "forward raster frames/s, 1M Gaussians @ 1024x1024" if args.workload == "1M_1024_cube"
+        else f"forward raster frames/s ({args.workload})",
+        "value": world * args.steps / elapsed,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "timed_region_s": elapsed,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"{P} synthetic Gaussians ('{kind}' scene, seed 0, SH degree 0), {S}x{S}, forward "
+                               "raster fp32, inputs resident in HBM", "num_rendered": int(out[0]),
+                   "tiles": ((S + 15) // 16) ** 2, "parallelism": f"scene-parallel x{world} (no collective)"},
+        # what ran INSIDE the timed region (counters read around it)
+        "timed_path": timed_path,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # ---- the LAST TIMED frame against the exact forms, bit for bit: (a) the two-call form (ggd_forward_geometry
     #      -> host reads num_rendered -> ggd_forward_render into buffers laid out for exactly that; ordinary four-pass depth sort, no
     #      folding, no speculation) and (b) the literal duplicateWithKeys + 64-bit (tile | depth) radix sort path (debug = True), each
@@ -841,32 +893,13 @@ def main():
     # 16 B / visible Gaussian each or, in its two-launch form, one in-LDS finish of 16 B / visible Gaussian)
     path_bytes = (algorithmic_bytes("preprocess", P, num_rendered, S, S) + 4 * P + 8 * p_vis + (1 if msd_frames > 0 else 2) * 16 * p_vis
                   + 8 * row_entries + 4 * num_rendered + algorithmic_bytes("blend", P, num_rendered, S, S))
-    ms_per_step = elapsed / args.steps * 1e3
-    result = {
-        "metric": "forward raster frames/s, 1M Gaussians @ 1024x1024" if args.workload == "1M_1024_cube"
-        else f"forward raster frames/s ({args.workload})",
-        "value": world * args.steps / elapsed,
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "timed_region_s": elapsed,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": f"{P} synthetic Gaussians ('{kind}' scene, seed 0, SH degree 0), {S}x{S}, forward "
-                               "raster fp32, inputs resident in HBM", "num_rendered": num_rendered,
-                   "tiles": ((S + 15) // 16) ** 2, "tile_list_length_mean": tile_lists["mean"],
-                   "tile_list_length_max": tile_lists["max"], "parallelism": f"scene-parallel x{world} (no collective)"},
+    result["config"].update({"tile_list_length_mean": tile_lists["mean"], "tile_list_length_max": tile_lists["max"]})
+    result.update({
         # (the dominant kernel is VALU-bound by intensity, DESIGN.md section 4: its wave-level VALU instruction count is reported
         # beside the HBM figure; `traffic` and `valu_wave_insts` are REPLAYED from the committed PMC pass named in `replayed_from`,
         # `kernel_ms` is this run's own hipEvent time)
         "roofline": roofline_entry(args.workload, dom, P, num_rendered, S, S, stage_ms[dom]),
-        # what ran INSIDE the timed region (counters read around it) and the last timed frame against the exact forms
-        "timed_path": timed_path,
+        # the last timed frame against the exact forms
         "verified_vs_two_call": verified["verified_vs_two_call"],
         "verified_vs_radix_sort_path": verified["verified_vs_radix_sort_path"],
         "stage_ms": {k: round(v, 5) for k, v in stage_ms.items()},
@@ -881,7 +914,7 @@ def main():
                         "visible_gaussians": p_vis, "row_entries": row_entries,
                         "contract_formula_bytes": whole,
                         "contract_formula_frac_of_hbm_peak": whole / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
-    }
+    })
     moved = pmc_moved_bytes(args.workload)
     if moved is not None:
         result["whole_frame"].update({"moved_bytes_pmc": moved["bytes"], "moved_GBps": moved["bytes"] / (ms_per_step * 1e-3) / 1e9,

@@ -10,14 +10,15 @@
 #   pmc_hl/     ... of the reference-precision decoder kernels (forward with z, backward, weight gradients), 2 M points
 #   train_fp32/ kernel trace of the train step with the reference-precision fused decoder
 #   hd/         kernel trace of scripts/hd_timing.py (1080p, 2048^2, 4K: every binning path that applies)
-#   backward_blend_counters.txt, kernel_resources.txt, bench.json (plain `python bench.py`), full_size_errors.txt
+#   backward_blend_counters.txt, kernel_resources.txt, bench.json (`python bench.py --full`), full_size_errors.txt
 set -u
 TAG=${1:-r06}
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out/$TAG
+OUT=$_   # the tag's output directory, created above
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/$TAG/bench -o p --output-format csv -- \
-    python $R/bench.py --steps 100 --backward --no-train --no-decode --no-sweep --no-cpu-baseline --no-inflight --no-extra-rooflines \
+    python $R/bench.py --full --steps 100 --backward --no-train --no-decode --no-sweep --no-cpu-baseline --no-inflight --no-extra-rooflines \
     > $R/gpurun_out/$TAG/bench_under_rocprof.json 2> $R/gpurun_out/$TAG/bench.err
 # (the perceptual stand-in's convolutions: an untraced run of the same script first, so that MIOpen's algorithm search -- its
 # naive_conv* kernels were 93 % of round 4's table -- finds its results in the user database instead of running inside the
@@ -39,6 +40,6 @@ bash scripts/pmc_passes.sh $TAG/pmc_hl scripts/hl_only.py 3 > /dev/null
 bash scripts/frame_traces.sh gpurun_out/$TAG > /dev/null 2>&1
 python scripts/bwd_blend_stats.py > gpurun_out/$TAG/backward_blend_counters.txt 2> /dev/null
 python scripts/kernel_resources.py > gpurun_out/$TAG/kernel_resources.txt 2> /dev/null
-python bench.py > gpurun_out/$TAG/bench.json 2> gpurun_out/$TAG/bench_plain.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench_full.err
 python -m pytest tests/test_full_size_gpu.py -m gpu -q -x -s 2>&1 | grep -E "max\||passed|failed|dRGB" > gpurun_out/$TAG/full_size_errors.txt
 echo done

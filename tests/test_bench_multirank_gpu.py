@@ -16,7 +16,7 @@ def test_bench_two_ranks_on_one_gpu(native_lib):
     env = dict(os.environ, GGD_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-           "--warmup", "3", "--workload", "100k_512_cube", "--train-iters", "2", "--train-points", "20000",
+           "--warmup", "3", "--full", "--workload", "100k_512_cube", "--train-iters", "2", "--train-points", "20000",
            "--scenes-per-gpu", "2", "--no-decode", "--no-sweep", "--no-cpu-baseline"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
