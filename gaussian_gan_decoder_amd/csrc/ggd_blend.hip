@@ -25,6 +25,8 @@
 //     gfx950 lane-block swaps (no LDS round trip), parked in LDS per touched record, and flushed as (record, component) pairs
 //     over the lanes -- component fastest, so a record's nine float atomics form one 36-byte span -- instead of one atomic
 //     per (pixel, Gaussian, component).
+#include <type_traits>
+
 #include "ggd_common.h"
 
 namespace {
@@ -204,7 +206,11 @@ __device__ __forceinline__ float2 lds_read2(lds_cf4* p, int word) {
   return make_float2(v[0], v[1]);
 }
 
-template <int EXP_MODE, bool CULL, int PXL, int BW, bool STATS>
+// AUX (the depth / alpha extension, ggd_forward_aux): the gathering lane also loads the Gaussian's view-space depth
+// (depth_keys = the fp32 bits of z, the depth sort's key) and stages it in the record's twelfth word, which the plain blend
+// does not use (the cull extent ey, dead once the pre-cull has run) -- the staging area keeps its 48 bytes per record.  Per
+// record one more FMA under the colour's `upd` mask accumulates sum(alpha T z); the epilogue writes it and 1 - T.
+template <int EXP_MODE, bool CULL, int PXL, int BW, bool STATS, bool AUX = false>
 __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int W, int H, int gx, int T,
                                                     const ggd_splat* __restrict__ splat,
                                                     const uint32_t* __restrict__ list,
@@ -213,7 +219,10 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
                                                     float* __restrict__ out_color,
                                                     float* __restrict__ final_T,
                                                     uint32_t* __restrict__ n_contrib,
-                                                    unsigned long long* __restrict__ stats) {
+                                                    unsigned long long* __restrict__ stats,
+                                                    const uint32_t* __restrict__ depth_keys = nullptr,
+                                                    float* __restrict__ out_depth = nullptr,
+                                                    float* __restrict__ out_alpha = nullptr) {
 #ifndef GGD_FWD_GRP
 #define GGD_FWD_GRP 8
 #endif
@@ -227,12 +236,14 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
   uint32_t st_visited = 0, st_culled = 0, st_lanes = 0, st_pixels = 0, st_inloop = 0;  // wave-uniform debug counters (GGD stats)
   const uint64_t st_t0 = STATS ? wall_clock64() : 0ull;                // 100 MHz constant clock: the wave's residency
   float Tr[PXL], C[PXL][3];   // per pixel: transmittance, accumulated colour
+  float D[AUX ? PXL : 1];     // AUX: accumulated depth
   uint32_t last[PXL];
   float px[PXL];              // pixel x coordinates; +inf once the pixel is finished / outside the image
   const float pyf = (float)g.py;
 #pragma unroll
   for (int k = 0; k < PXL; ++k) {
     Tr[k] = 1.0f; C[k][0] = C[k][1] = C[k][2] = 0.0f;
+    if constexpr (AUX) D[k] = 0.0f;
     last[k] = 0;
     px[k] = (row_in && (g.px0 + k) < W) ? (float)(g.px0 + k) : INF;
   }
@@ -280,6 +291,7 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
   // memory round trips per round.)
   uint32_t id_nxt = 0;
   float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0;   // x y hA nB | hC thr opacity r | g b ex ey
+  uint32_t zk = 0;                                          // AUX: depth key of the record in r0..r2
   // (unconditional loads from clamped positions: a lane past the end of the list re-reads the last entry -- one cache
   // line for the whole wave -- and its record is never consumed; exec-masked loads made r0..r2 loop-carried merges that the
   // register allocator split with copies right behind the loads, i.e. waits)
@@ -288,6 +300,7 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
   auto load_rec = [&](uint32_t) {
     const float4* p = reinterpret_cast<const float4*>(splat + id_nxt);
     r0 = p[0]; r1 = p[1]; r2 = p[2];
+    if constexpr (AUX) zk = depth_keys[id_nxt];
   };
   auto consume = [&](uint32_t pos) {   // cull decision of the record in r0..r2, then its two in-place edits
     keep = false;
@@ -296,6 +309,7 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
                      record_reaches_block(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r2.z, lx0, lx1, ly0, ly1)) : true;
       if (!CULL) r1.y = -__builtin_huge_valf();
       r2.z = __uint_as_float(pos - g.lo + 1u);
+      if constexpr (AUX) r2.w = __uint_as_float(zk);   // view-space depth (the key is its fp32 bits)
     }
   };
   if (g.hi <= g.lo || !wave_alive()) goto all_done;
@@ -344,7 +358,7 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
         const float4 a = a_nx, b4 = b_nx, c = c_nx;
         // (the record's twelfth word is not used: left dead, the register allocator hands its VGPR out as a temporary while the
         // load is still in flight, and the write-after-write hazard puts a wait for the whole prefetch three instructions
-        // behind its issue)
+        // behind its issue; AUX: it is the depth)
         asm volatile("" : : "v"(c.w));
         const float2 b01 = make_float2(b4.x, b4.y);
         if (jj < GRP - 1) {
@@ -384,6 +398,7 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
           fma_into(C[k][0], b23.y, w);
           fma_into(C[k][1], c.x, w);
           fma_into(C[k][2], c.y, w);
+          if constexpr (AUX) fma_into(D[k], c.w, w);
           sel_into_after(Tr[k], test_T, upd, w);
           sel_into(last[k], contributor, upd);
           if (stop) sel_into(px[k], INF, stop);   // a pixel stops once: a scalar branch (SCC of the s_and above), not a select per update
@@ -413,6 +428,15 @@ all_done:
   const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
   const size_t HW = (size_t)H * W;
   const size_t pix0 = (size_t)g.py * W + g.px0;
+  if constexpr (AUX) {
+#pragma unroll
+    for (int k = 0; k < PXL; ++k) {
+      if (g.px0 + k < W) {
+        out_depth[pix0 + k] = D[k];
+        out_alpha[pix0 + k] = 1.0f - Tr[k];
+      }
+    }
+  }
   if (g.px0 + PXL - 1 < W && (W & 3) == 0) {
     if constexpr (PXL == 4) {
       *reinterpret_cast<float4*>(final_T + pix0) = make_float4(Tr[0], Tr[1], Tr[2], Tr[3]);
@@ -474,6 +498,26 @@ __global__ __launch_bounds__(64) void blend_forward_kernel(int W, int H, int gx,
   blend_forward_block<EXP_MODE, CULL, PXL, BW, STATS>((int)blockIdx.x, s_rec, W, H, gx, T, splat, list, ranges, capacity, bg,
                                                       out_color, final_T, n_contrib, stats);
 }
+// The same blend with the depth / alpha planes (AUX must be true: an overload, so that the plain instances keep their names)
+template <int EXP_MODE, bool CULL, int PXL, int BW, bool STATS, bool AUX>
+__global__ __launch_bounds__(64) void blend_forward_kernel(int W, int H, int gx, int T,
+                                                           const ggd_splat* __restrict__ splat,
+                                                           const uint32_t* __restrict__ list,
+                                                           const uint32_t* __restrict__ ranges, uint32_t capacity,
+                                                           const float* __restrict__ bg,
+                                                           float* __restrict__ out_color,
+                                                           float* __restrict__ final_T,
+                                                           uint32_t* __restrict__ n_contrib,
+                                                           unsigned long long* __restrict__ stats,
+                                                           const uint32_t* __restrict__ depth_keys,
+                                                           float* __restrict__ out_depth,
+                                                           float* __restrict__ out_alpha) {
+  static_assert(AUX, "the plain blend is the five-parameter template");
+  __shared__ float4 s_rec[64 * 3];
+  blend_forward_block<EXP_MODE, CULL, PXL, BW, STATS, true>((int)blockIdx.x, s_rec, W, H, gx, T, splat, list, ranges, capacity,
+                                                            bg, out_color, final_T, n_contrib, stats, depth_keys, out_depth,
+                                                            out_alpha);
+}
 
 // Backward blend: the per-record update of ONE pixel, shared by the two kernel forms below.  Records are visited back to
 // front; the body is SELECT-FREE: a pixel that does not see the record (culled, beyond its n_contrib, alpha < 1/255) gets
@@ -486,10 +530,19 @@ __global__ __launch_bounds__(64) void blend_forward_kernel(int W, int H, int gx,
 //     2 x 2 matrix, the opacity, the -1/2 and the 0.5 W / 0.5 H of the pixel-to-NDC map are applied once per (record,
 //     component) by the flush, not per pixel.
 struct BwdPixel { float T, nTfin, bgdot, acc[3], gpx[3]; };
+// AUX (depth / alpha extension): the depth is a fourth channel with background 0 (accD = the depth composited behind the
+// record, gD = dL/ddepth of the pixel); dL/dalpha of the pixel is folded into bgdot (bwd_aux_init)
+struct BwdPixelAux : BwdPixel { float accD, gD; };
+// alpha = 1 - T_final: dL/dT_final = bg . dL/dpix - dL/dalpha, folded into bgdot once (NULL gradients are passed as zero)
+template <bool AUX, typename Pix>
+__device__ __forceinline__ void bwd_aux_init(Pix& st, float gD, float gA) {
+  if constexpr (AUX) { st.accD = 0.0f; st.gD = gD; st.bgdot = st.bgdot - gA; }
+}
 
-template <int EXP_MODE>
-__device__ __forceinline__ uint64_t bwd_update(BwdPixel& st, float pw, float dx, float dy, uint64_t need, float opacity,
-                                               const float (&col)[3], float (&s)[8], float& sop) {
+template <int EXP_MODE, bool AUX = false, typename Pix = BwdPixel>
+__device__ __forceinline__ uint64_t bwd_update(Pix& st, float pw, float dx, float dy, uint64_t need, float opacity,
+                                               const float (&col)[3], float (&s)[8], float& sop, float z = 0.0f,
+                                               float* sz = nullptr) {
   float g0, adec;
   if constexpr (EXP_MODE == 3) {
     // the default pairing (bare v_exp_f32 in the forward, compensated 2^x here): the forward's G is exactly the `e` this form
@@ -522,6 +575,12 @@ __device__ __forceinline__ uint64_t bwd_update(BwdPixel& st, float pw, float dx,
     dL_dalpha = __builtin_fmaf(d, st.gpx[ch], dL_dalpha);
     fma_into(st.acc[ch], alpha, d);                       // in place: the culled path carries no copy
     s[ch] = dchannel_dcolor * st.gpx[ch];
+  }
+  if constexpr (AUX) {
+    const float d = z - st.accD;
+    dL_dalpha = __builtin_fmaf(d, st.gD, dL_dalpha);
+    fma_into(st.accD, alpha, d);
+    *sz = dchannel_dcolor * st.gD;
   }
   dL_dalpha = __builtin_fmaf(st.nTfin * inv, st.bgdot, dL_dalpha * st.T);
   const float wx = (G * dx) * dL_dalpha, wy = (G * dy) * dL_dalpha;
@@ -590,6 +649,55 @@ __device__ __forceinline__ float wave_reduce9_swap(float (&v)[8], float ninth, u
       "s_nop 1\n\t"
       "v_add_f32_e32 %0, %0, %4"
       : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(ninth)
+      : "s"(ninth_lanes));
+  return v[0];
+}
+
+// wave_reduce9_swap plus a tenth value (AUX: the depth sum), which takes the ninth's four in-row steps and rides in the
+// redundant lanes 4b + 1 of the OTHER folded register (v[4]): after the two swaps lanes 32 <= l < 64 with (l & 3) == 1 hold it.
+__device__ __forceinline__ float wave_reduce10_swap(float (&v)[8], float ninth, float tenth, uint64_t ninth_lanes /* 0x2222... */) {
+  asm volatile(
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+      "v_add_f32_dpp %2, %2, %2 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+      "v_add_f32_dpp %4, %4, %4 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+      "v_add_f32_dpp %6, %6, %6 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+      "v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %2, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %4, %5, %5 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %6, %7, %7 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %8, %8, %8 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %9, %9, %9 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 0\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+      "v_add_f32_dpp %4, %4, %4 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+      "v_add_f32_dpp %8, %8, %8 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %9, %9, %9 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %0, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+      "v_add_f32_dpp %4, %6, %6 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %4, %4, %4 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %8, %8, %8 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %9, %9, %9 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 0\n\t"
+      "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %4, %4, %4 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %8, %8, %8 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %9, %9, %9 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_cndmask_b32_e64 %0, %0, %8, %10\n\t"
+      "v_cndmask_b32_e64 %4, %4, %9, %10\n\t"
+      "s_nop 1\n\t"
+      "v_permlane32_swap_b32 %0, %4\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32_e32 %0, %0, %4\n\t"
+      "v_mov_b32_e32 %4, %0\n\t"
+      "s_nop 1\n\t"
+      "v_permlane16_swap_b32 %0, %4\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32_e32 %0, %0, %4"
+      : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(ninth), "+v"(tenth)
       : "s"(ninth_lanes));
   return v[0];
 }
@@ -785,208 +893,67 @@ __global__ __launch_bounds__(256) void blend_backward_tile_kernel(
 // STATS (ggd_blend_stats, debug): per-wave work counters added to stats[GGD_STATS_BWD ..] at the wave's end -- list entries the
 // wave walks (its share of the tile's list up to its last contributor), records staged after the pre-cull, staged records some
 // pixel still needed (`need`), records at least one pixel actually blended (`live`: a 9-sum reduction + a parked row each),
-// the live lanes of those, rows flushed (= 36-byte atomic spans), gather rounds.
+// the live lanes of those, rows flushed (= 36-byte atomic spans), gather rounds.  The body is ggd_blend_bwd_quarter.inc, shared with
+// the depth / alpha overload below.
 template <int EXP_MODE, bool CULL, bool STATS = false>
 __global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
     int W, int H, int gx, int gy, const ggd_splat* __restrict__ splat, const uint32_t* __restrict__ list,
     const uint32_t* __restrict__ ranges, const float* __restrict__ bg, const float* __restrict__ final_T,
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ grad_acc,
     unsigned long long* __restrict__ stats = nullptr) {
-  uint32_t st_staged = 0, st_need = 0, st_live = 0, st_lanes = 0, st_spans = 0, st_rounds = 0;
-  __shared__ float4 s_rec[64 * 3];
-  // [touched record, in processing order][9 sums | staging slot] (5632 B of LDS per wave with s_rec); ONE buffer: a round's
-  // rows are flushed at the top of the next round, before that round's first row is written (LDS operations of a wave
-  // execute in order)
-  __shared__ float s_sum[64][10];
-  const int lane = threadIdx.x;
-  int tile, sub;
-  ggd_block_to_tile((int)blockIdx.x, 4, gx, gy, gx * gy, tile, sub);
-  const int tx = tile % gx, ty = tile / gx;
-  const int qx = sub & 1, qy = sub >> 1;
-  const int px0 = tx * 16 + qx * 8 + (lane & 7), py = ty * 16 + qy * 8 + (lane >> 3);
-  const uint2 rg = reinterpret_cast<const uint2*>(ranges)[tile];
-  const bool in = py < H && px0 < W;
-  const size_t HW = (size_t)H * W;
-  const size_t pix0 = (size_t)py * W + px0;
+  constexpr bool AUX = false;
+  const uint32_t* const depth_keys = nullptr;
+  const float* const dL_ddepth = nullptr;
+  const float* const dL_dalpha = nullptr;
+  float* const s_z = nullptr;
+#include "ggd_blend_bwd_quarter.inc"
+}
 
-  BwdPixel st;
-  const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
-  const float pxf = (float)px0, pyf = (float)py;
-  const float tf = in ? final_T[pix0] : 0.0f;
-  const uint32_t lastn = in ? n_contrib[pix0] : 0u;
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) { st.gpx[ch] = in ? dL_dpix[ch * HW + pix0] : 0.0f; st.acc[ch] = 0.0f; }
-  st.bgdot = (bg0 * st.gpx[0] + bg1 * st.gpx[1]) + bg2 * st.gpx[2];
-  st.T = tf; st.nTfin = -tf;
-  uint32_t maxn = lastn;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, d, 64));
-  maxn = (uint32_t)__builtin_amdgcn_readfirstlane((int)maxn);
-  if (maxn == 0) return;
-  const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
-  const float wx0 = (float)(tx * 16 + qx * 8), wy0 = (float)(ty * 16 + qy * 8);   // this wave's pixel rectangle
-  const float wx1 = wx0 + 7.0f, wy1 = wy0 + 7.0f;
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
-  // lanes that hold a result of wave_reduce9_swap, and where it goes in the row (accumulator-record order: conic A B C |
-  // opacity | mean sums x y | colour r g b); lane 2 adds the record's staging slot to the same LDS store
-  const bool is_writer = (lane & 19) == 0 || lane == 1;
-  const int writer_val = lane == 1 ? 8 : 4 * (lane >> 5) + (((lane >> 2) & 1) << 1) + ((lane >> 3) & 1);
-  const int writer_comp = writer_val < 3 ? GGD_ACC_COLOR + writer_val
-                        : (writer_val < 6 ? GGD_ACC_CONIC + (writer_val - 3)
-                        : (writer_val < 8 ? GGD_ACC_MEAN2D + (writer_val - 6) : GGD_ACC_OPACITY));
-  const bool stores = is_writer || lane == 2;
-  const int store_col = is_writer ? writer_comp : 9;
-
-  // staged = the record as loaded with three words replaced in place:
-  //   {x, y, hA, nB} {hC, power threshold, opacity, 0-based list position} {g, b, r, Gaussian id}
-  bool keep = false;
-  uint32_t id_cur = 0, id_nxt = 0;
-  float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0;    // x y hA nB | hC thr opacity r | g b ex ey
-  const uint32_t last_pos = rg.x + maxn - 1u;
-  auto round_start = [&](uint32_t ce) { return (ce - rg.x > 64u) ? ce - 64u : rg.x; };   // ce > rg.x
-  auto load_id = [&](uint32_t ce) {
-    const uint32_t cs = ce > rg.x ? round_start(ce) : rg.x;
-    id_nxt = list[min(cs + (uint32_t)lane, last_pos)];
-  };
-  auto load_rec = [&]() {
-    id_cur = id_nxt;
-    const float4* p = reinterpret_cast<const float4*>(splat + id_nxt);
-    r0 = p[0]; r1 = p[1]; r2 = p[2];
-  };
-  // the pre-cull rectangle of a round = the bounding rectangle of the pixels that can see ANY record of the round (those
-  // whose last contributor lies at or behind the round's first position): walking back to front a wave starts at its
-  // deepest pixel, and until the others join, most records only reach pixels that are not live yet
-  float lx0 = wx0, lx1 = wx1, ly0 = wy0, ly1 = wy1;
-  auto shrink_rect = [&](uint32_t first_pos) {   // 0-based list position of the round's first record
-    const uint64_t live = __ballot(lastn > first_pos);
-    if (live != 0ull) {
-      const int rmin = __builtin_ctzll(live) >> 3, rmax = (63 - __builtin_clzll(live)) >> 3;
-      uint32_t m = (uint32_t)live | (uint32_t)(live >> 32);
-      m |= m >> 16; m |= m >> 8; m &= 0xffu;
-      const int cmin = __builtin_ctz(m), cmax = 31 - __builtin_clz(m);
-      lx0 = wx0 + (float)cmin; lx1 = wx0 + (float)cmax;
-      ly0 = wy0 + (float)rmin; ly1 = wy0 + (float)rmax;
-    }
-  };
-  auto consume = [&](uint32_t ce) {
-    keep = false;
-    const uint32_t cs = round_start(ce);
-    if (CULL) shrink_rect(cs - rg.x);
-    if ((uint32_t)lane < ce - cs) {
-      keep = CULL ? (record_box_hits(r0.x, r0.y, r2.z, r2.w, lx0, lx1, ly0, ly1) &&
-                     record_reaches_block(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r2.z, lx0, lx1, ly0, ly1)) : true;
-      if (!CULL) r1.y = -__builtin_huge_valf();
-      r2.z = r1.w;
-      r1.w = __uint_as_float((cs - rg.x) + (uint32_t)lane);
-      r2.w = __uint_as_float(id_cur);
-    }
-  };
-  // the flush of one round's parked sums (cnt rows), reading the round's records where they were staged
-  auto flush = [&](int cnt) {
-    const float* rows = &s_sum[0][0];
-    for (int p = lane; p < cnt * 9; p += 64) {
-      const int r = p / 9, comp = p - 9 * r;
-      const float v = rows[r * 10 + comp];
-      const float swx = rows[r * 10 + GGD_ACC_MEAN2D], swy = rows[r * 10 + GGD_ACC_MEAN2D + 1];
-      const int slot = (int)__float_as_uint(rows[r * 10 + 9]);
-      const float4 a = s_rec[slot * 3 + 0], b = s_rec[slot * 3 + 1];
-      const uint32_t id = __float_as_uint(s_rec[slot * 3 + 2].w);
-      atomicAdd(grad_acc + GGD_ACC_FLOATS * (size_t)id + comp,
-                bwd_scale(comp, v, swx, swy, a.z, a.w, b.x, b.z, ddelx_dx, ddely_dy));
-    }
-  };
-
-  uint32_t cend = rg.x + maxn;  // one past the last position this quarter needs
-  load_id(cend);
-  load_rec();
-  load_id(round_start(cend));
-  int prev_cnt = 0;
-  while (cend > rg.x) {
-    const uint32_t cstart = round_start(cend);
-    consume(cend);                                       // the records requested one round ago
-    __builtin_amdgcn_wave_barrier();                     // (the previous round's LDS reads are done: in-order per wave)
-    flush(prev_cnt);                                     // the previous round's sums: BEFORE its records are overwritten and
-    __builtin_amdgcn_wave_barrier();                     // before the new loads are issued
-    const uint64_t kept = __ballot(keep);
-    const int nk = __popcll(kept), n8 = (nk + 7) & ~7;
-    if (STATS) { st_staged += (uint32_t)nk; st_rounds += 1; st_spans += (uint32_t)prev_cnt; }
-    if (keep) {  // compacted, order preserved
-      const int slot = __popcll(kept & lt_mask);
-      s_rec[slot * 3 + 0] = r0; s_rec[slot * 3 + 1] = r1; s_rec[slot * 3 + 2] = r2;
-    }
-    if (lane >= nk && lane < n8) {   // padding: a record nobody sees
-      s_rec[lane * 3 + 0] = make_float4(0, 0, 0, 0);
-      s_rec[lane * 3 + 1] = make_float4(0, __builtin_huge_valf(), 0, 0);
-    }
-    load_rec();                                          // next round's records
-    load_id(cstart > rg.x ? round_start(cstart) : rg.x); // and the list entries of the round after it
-    __builtin_amdgcn_wave_barrier();
-    int cnt = 0;
-    float* rows = &s_sum[0][0];
-    for (int j0 = n8 - 8; j0 >= 0; j0 -= 8) {
-      uint32_t ga = (uint32_t)(uintptr_t)(lds_cf4*)(s_rec + j0 * 3);   // see blend_forward_kernel
-      asm volatile("" : "+v"(ga));
-      lds_cf4* grp = (lds_cf4*)(uintptr_t)ga;
-      // (all twelve words one record ahead, inside the group: see the forward)
-      float4 a_nx = lds_read4(grp + 7 * 3), b_nx = lds_read4(grp + 7 * 3 + 1), c_nx = lds_read4(grp + 7 * 3 + 2);
-#pragma unroll
-      for (int jj = 7; jj >= 0; --jj) {
-        const float4 a = a_nx, b = b_nx, c4 = c_nx;
-        asm volatile("" : : "v"(c4.w));   // (keeps the unused twelfth word's VGPR from being handed out while the load is in flight)
-        if (jj > 0) {
-          a_nx = lds_read4(grp + (jj - 1) * 3); b_nx = lds_read4(grp + (jj - 1) * 3 + 1); c_nx = lds_read4(grp + (jj - 1) * 3 + 2);
-        }
-        const float dy = a.y - pyf;
-        const float nBdy = a.w * dy, hCdy2 = (b.x * dy) * dy;
-        const uint32_t pos0 = __float_as_uint(b.w);
-        const float dx = a.x - pxf;
-        const float pw = __builtin_fmaf(__builtin_fmaf(a.z, dx, nBdy), dx, hCdy2);
-        const uint64_t need = __ballot(pos0 < lastn) & __ballot(pw >= b.y);
-        if (need == 0ull) continue;
-        if (STATS) st_need += 1;
-        const float col[3] = {c4.z, c4.x, c4.y};                     // r | g, b
-        float s[8], sop;                                             // colour r g b | conic A B C | mean sums x y ; opacity
-        const uint64_t live = bwd_update<EXP_MODE>(st, pw, dx, dy, need, b.z, col, s, sop);
-        if (live != 0ull) {   // wave-uniform: somebody in this wave saw the Gaussian
-          if (STATS) { st_live += 1; st_lanes += (uint32_t)__popcll(live); }
-          const float tot = wave_reduce9_swap(s, sop, 0x2222222222222222ull);
-          // writers: lanes 0,4,8,12 | 32,36,40,44 (component from the table above), lane 1 the opacity sum; lane 2 the
-          // record's slot in the staging area
-          const float v = is_writer ? tot : __uint_as_float((uint32_t)(j0 + jj));
-          if (stores) rows[cnt * 10 + store_col] = v;
-          ++cnt;
-        }
-      }
-    }
-    prev_cnt = cnt;
-    cend = cstart;
-  }
-  __builtin_amdgcn_wave_barrier();
-  flush(prev_cnt);
-  if (STATS && lane == 0 && stats) {
-    unsigned long long* o = stats + GGD_STATS_BWD;
-    atomicAdd(o + 0, (unsigned long long)maxn);
-    atomicAdd(o + 1, (unsigned long long)st_staged);
-    atomicAdd(o + 2, (unsigned long long)st_need);
-    atomicAdd(o + 3, (unsigned long long)st_live);
-    atomicAdd(o + 4, (unsigned long long)st_lanes);
-    atomicAdd(o + 5, (unsigned long long)(st_spans + (uint32_t)prev_cnt));
-    atomicAdd(o + 6, (unsigned long long)st_rounds);
-    atomicAdd(o + 7, 1ull);
-  }
+// The same with the depth / alpha gradients (AUX must be true: an overload, so that the plain instances keep their names).
+// AUX (ggd_backward_aux): the Gaussians' depths are staged in s_z next to their records; the depth is a fourth colour channel
+// (background 0) whose per-record sum alpha T dL/ddepth is the TENTH reduced value and goes to slot 9 of the accumulator
+// record (a pad word: layout and memset unchanged); dL/dalpha of a pixel only enters through its final transmittance, i.e. as
+// -dL/dalpha folded into bgdot once.  Rows of 10 sums + slot and the staged depths: 6144 B of LDS per wave.
+template <int EXP_MODE, bool CULL, bool STATS, bool AUX_>
+__global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
+    int W, int H, int gx, int gy, const ggd_splat* __restrict__ splat, const uint32_t* __restrict__ list,
+    const uint32_t* __restrict__ ranges, const float* __restrict__ bg, const float* __restrict__ final_T,
+    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ grad_acc,
+    unsigned long long* __restrict__ stats, const uint32_t* __restrict__ depth_keys, const float* __restrict__ dL_ddepth,
+    const float* __restrict__ dL_dalpha) {
+  static_assert(AUX_, "the plain backward is the three-parameter template");
+  constexpr bool AUX = true;
+  __shared__ float s_z[64];
+#include "ggd_blend_bwd_quarter.inc"
 }
 
 }  // namespace
 
 int ggd_launch_blend(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
                      const uint32_t* list, const uint32_t* ranges, uint32_t capacity, float* out_color, float* final_T,
-                     uint32_t* n_contrib) {
+                     uint32_t* n_contrib, const uint32_t* depth_keys, float* out_depth, float* out_alpha) {
   const int gx = (prm.width + 15) / 16, gy = (prm.height + 15) / 16;
   if (gx * gy == 0) return GGD_OK;
   const int em = ctx->opt[GGD_OPT_EXP_MODE] == 3 ? 1 : ctx->opt[GGD_OPT_EXP_MODE];   // 3 (default): bare v_exp_f32 in the forward
   const bool cull = ctx->opt[GGD_OPT_BLEND_CULL] != 0;
   const int T = gx * gy;
   static const int lds_pad = getenv("GGD_BLEND_LDS_PAD") ? atoi(getenv("GGD_BLEND_LDS_PAD")) : 0;   // experiment: caps the waves per CU
+  if (out_depth || out_alpha) {
+    // the depth / alpha extension: one instance per (exp mode, cull); no statistics variant (ggd_blend_stats counts plain frames only)
+    if (!out_depth || !out_alpha || !depth_keys) return ggd_fail(ctx, GGD_E_INVALID, "internal: depth / alpha blend needs both planes and the depth keys");
+#define GGD_LAUNCH_FWDA(EM, CU)                                                                                         \
+    hipLaunchKernelGGL((blend_forward_kernel<EM, CU, 1, 8, false, true>), dim3(4 * T), dim3(64), lds_pad, s, prm.width,   \
+                       prm.height, gx, T, splat, list, ranges, capacity, prm.bg, out_color, final_T, n_contrib,          \
+                       (unsigned long long*)nullptr, depth_keys, out_depth, out_alpha)
+    if (cull) {
+      if (em == 0) GGD_LAUNCH_FWDA(0, true); else if (em == 1) GGD_LAUNCH_FWDA(1, true); else GGD_LAUNCH_FWDA(2, true);
+    } else {
+      if (em == 0) GGD_LAUNCH_FWDA(0, false); else if (em == 1) GGD_LAUNCH_FWDA(1, false); else GGD_LAUNCH_FWDA(2, false);
+    }
+#undef GGD_LAUNCH_FWDA
+    GGD_HIP(hipGetLastError());
+    return GGD_OK;
+  }
 #define GGD_LAUNCH_FWD2(EM, CU, ST)                                                                                     \
   hipLaunchKernelGGL((blend_forward_kernel<EM, CU, 1, 8, ST>), dim3(4 * T), dim3(64), lds_pad, s, prm.width, prm.height, \
                      gx, T, splat, list, ranges, capacity, prm.bg, out_color, final_T, n_contrib, ctx->blend_stats)
@@ -1007,7 +974,8 @@ int ggd_launch_blend(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const g
 
 int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
                               const uint32_t* list, const uint32_t* ranges, const float* final_T,
-                              const uint32_t* n_contrib, const float* dL_dpix, float* grad_acc) {
+                              const uint32_t* n_contrib, const float* dL_dpix, float* grad_acc, bool aux,
+                              const uint32_t* depth_keys, const float* dL_ddepth, const float* dL_dalpha) {
   const int gx = (prm.width + 15) / 16, gy = (prm.height + 15) / 16;
   if (gx * gy == 0) return GGD_OK;
   const int em = ctx->opt[GGD_OPT_EXP_MODE];   // 3 (default): compensated 2^x, contribution decision on the forward's bare v_exp_f32 value
@@ -1023,6 +991,23 @@ int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm
   // 1 M / 704^2 225 vs 250 (profiles/r06/backward_blend_form_ab.txt)
   if (split == 1) split = 4;
   static const int lds_pad = getenv("GGD_BLEND_BWD_LDS_PAD") ? atoi(getenv("GGD_BLEND_BWD_LDS_PAD")) : 0;   // experiment
+  if (aux) {
+    // the depth / alpha backward exists in the quarter form only: it is used whatever GGD_OPT_BLEND_SPLIT says (the tile form
+    // is an explicit, non-default choice kept for measurements); no statistics variant
+    if (!depth_keys) return ggd_fail(ctx, GGD_E_INVALID, "internal: depth / alpha backward needs the depth keys");
+#define GGD_LAUNCH_BQA(EM, CU)                                                                                            \
+    hipLaunchKernelGGL((blend_backward_quarter_kernel<EM, CU, false, true>), dim3(4 * T), dim3(64), lds_pad, s, prm.width, \
+                       prm.height, gx, gy, splat, list, ranges, prm.bg, final_T, n_contrib, dL_dpix, grad_acc,             \
+                       (unsigned long long*)nullptr, depth_keys, dL_ddepth, dL_dalpha)
+    if (cull) {
+      if (em == 0) GGD_LAUNCH_BQA(0, true); else if (em == 1) GGD_LAUNCH_BQA(1, true); else if (em == 2) GGD_LAUNCH_BQA(2, true); else GGD_LAUNCH_BQA(3, true);
+    } else {
+      if (em == 0) GGD_LAUNCH_BQA(0, false); else if (em == 1) GGD_LAUNCH_BQA(1, false); else if (em == 2) GGD_LAUNCH_BQA(2, false); else GGD_LAUNCH_BQA(3, false);
+    }
+#undef GGD_LAUNCH_BQA
+    GGD_HIP(hipGetLastError());
+    return GGD_OK;
+  }
   if (split == 4) {
 #define GGD_LAUNCH_BQ(EM, CU)                                                                                             \
     do {                                                                                                                  \

@@ -480,8 +480,10 @@ extern "C" int ggd_forward_geometry(ggd_ctx* ctx, void* stream, const ggd_params
 
 // R = the value binning_buf was laid out for.  speculative: R is only a CAPACITY (the true num_rendered is still on
 // the device); only the tile-binning path can run that way (its launch geometry does not depend on R).
+// out_depth / out_alpha (both or neither): the depth / alpha planes of the *_aux entry points
 static int render_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const void* geom_buf, int64_t layout_R,
-                          int64_t R, void* binning_buf, void* img_buf, float* out_color, bool speculative) {
+                          int64_t R, void* binning_buf, void* img_buf, float* out_color, bool speculative,
+                          float* out_depth = nullptr, float* out_alpha = nullptr) {
   (void)hipGetLastError();   // a sticky error another library left in this thread is not ours to report
   // layout_R: what binning_buf was laid out for; R: number of instances to process (== layout_R unless the caller
   // over-allocated; in the speculative case the true count is still on the device and R is only its upper bound)
@@ -639,7 +641,8 @@ static int render_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, con
   }
   {
     StageTimer t(ctx, ST_BLEND, s);
-    rc = ggd_launch_blend(ctx, s, *prm, splat, list, ranges, capacity, out_color, final_T, n_contrib);
+    rc = ggd_launch_blend(ctx, s, *prm, splat, list, ranges, capacity, out_color, final_T, n_contrib, depth_keys_all, out_depth,
+                          out_alpha);
     if (rc != GGD_OK) return rc;
   }
   return GGD_OK;
@@ -654,6 +657,21 @@ extern "C" int ggd_forward_render(ggd_ctx* ctx, void* stream, const ggd_params* 
   return render_enqueue(ctx, stream, prm, geom_buf, R, R, binning_buf, img_buf, out_color, false);
 }
 
+static int check_aux_planes(ggd_ctx* ctx, const float* out_depth, const float* out_alpha) {
+  if (!ctx) return GGD_E_INVALID;
+  if (!out_depth || !out_alpha) return ggd_fail(ctx, GGD_E_INVALID, "out_depth / out_alpha is NULL");
+  return GGD_OK;
+}
+
+extern "C" int ggd_forward_render_aux(ggd_ctx* ctx, void* stream, const ggd_params* prm, const void* geom_buf,
+                                      int64_t R, void* binning_buf, void* img_buf, float* out_color, float* out_depth,
+                                      float* out_alpha) {
+  const int rc = check_aux_planes(ctx, out_depth, out_alpha);
+  if (rc != GGD_OK) return rc;
+  if (ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, kPendingMsg);
+  return render_enqueue(ctx, stream, prm, geom_buf, R, R, binning_buf, img_buf, out_color, false, out_depth, out_alpha);
+}
+
 extern "C" int ggd_forward_can_speculate(ggd_ctx* ctx, const ggd_params* prm, int64_t capacity) {
   if (!ctx || !prm || prm->debug || prm->P <= 0) return 0;
   const int bmode = ctx->opt[GGD_OPT_BINNING];
@@ -666,18 +684,21 @@ extern "C" int ggd_forward_can_speculate(ggd_ctx* ctx, const ggd_params* prm, in
 static int forward_spec_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D, const float* shs,
                                 const float* colors_precomp, const float* opacities, const float* scales,
                                 const float* rotations, const float* cov3D_precomp, void* geom_buf, int32_t* radii,
-                                void* binning_buf, int64_t capacity, void* img_buf, float* out_color, int64_t* num_rendered) {
+                                void* binning_buf, int64_t capacity, void* img_buf, float* out_color, int64_t* num_rendered,
+                                float* out_depth = nullptr, float* out_alpha = nullptr) {
   int rc = geometry_enqueue(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations,
                             cov3D_precomp, geom_buf, radii, num_rendered, true);
   if (rc != GGD_OK) return rc;
   ctx->spec3 = false; ctx->frame_folded = false; ctx->frame_flat = false; ctx->frame_msd_ok = false;
   ctx->frame_kmin = 0xffffffffu; ctx->frame_kmax = 0u; ctx->frame_msd_flags = 0u;
-  return render_enqueue(ctx, stream, prm, geom_buf, capacity, capacity, binning_buf, img_buf, out_color, true);
+  return render_enqueue(ctx, stream, prm, geom_buf, capacity, capacity, binning_buf, img_buf, out_color, true, out_depth,
+                        out_alpha);
 }
 // ... and the collection of num_rendered (+ "the depth keys' top byte was constant") once the launch that delivers it has run;
 // binning and blend may still be running.  A frame that needed the fourth sort pass it did not get is binned and blended again.
 static int forward_spec_collect(ggd_ctx* ctx, void* stream, const ggd_params* prm, const void* geom_buf, void* binning_buf,
-                                int64_t capacity, void* img_buf, float* out_color, int64_t* num_rendered) {
+                                int64_t capacity, void* img_buf, float* out_color, int64_t* num_rendered,
+                                float* out_depth = nullptr, float* out_alpha = nullptr) {
   int rc = geometry_finish(ctx, stream, prm, num_rendered);
   if (rc != GGD_OK) return rc;
   const bool spec3 = ctx->spec3, msd = ctx->msd_frame;
@@ -706,9 +727,38 @@ static int forward_spec_collect(ggd_ctx* ctx, void* stream, const ggd_params* pr
     return ggd_fail(ctx, GGD_E_CAPACITY, "binning_buf capacity is below num_rendered: re-run with a larger buffer");
   if (msd_missed || (spec3 && !ctx->frame_flat)) {   // the short form of the sort did not hold for this frame: bin and blend it again, in full
     ctx->spec3_misses += 1;
-    return render_enqueue(ctx, stream, prm, geom_buf, capacity, *num_rendered, binning_buf, img_buf, out_color, false);
+    return render_enqueue(ctx, stream, prm, geom_buf, capacity, *num_rendered, binning_buf, img_buf, out_color, false, out_depth,
+                          out_alpha);
   }
   return GGD_OK;
+}
+
+static int forward_single_call(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D, const float* shs,
+                               const float* colors_precomp, const float* opacities, const float* scales,
+                               const float* rotations, const float* cov3D_precomp, void* geom_buf, int32_t* radii,
+                               void* binning_buf, int64_t capacity, void* img_buf, float* out_color,
+                               int64_t* num_rendered, float* out_depth, float* out_alpha) {
+  if (capacity < 0) return ggd_fail(ctx, GGD_E_INVALID, "capacity < 0");
+  if (ctx && ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, kPendingMsg);
+  if (prm && prm->P > 0 && capacity > 0 && ggd_forward_can_speculate(ctx, prm, capacity)) {
+    const int rc = forward_spec_enqueue(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations,
+                                        cov3D_precomp, geom_buf, radii, binning_buf, capacity, img_buf, out_color, num_rendered,
+                                        out_depth, out_alpha);
+    if (rc != GGD_OK) return rc;
+    return forward_spec_collect(ctx, stream, prm, geom_buf, binning_buf, capacity, img_buf, out_color, num_rendered, out_depth,
+                                out_alpha);
+  }
+  int rc = geometry_enqueue(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations,
+                            cov3D_precomp, geom_buf, radii, num_rendered, false);
+  if (rc != GGD_OK) return rc;
+  if (prm->P == 0)
+    return render_enqueue(ctx, stream, prm, geom_buf, capacity, 0, binning_buf, img_buf, out_color, false, out_depth, out_alpha);
+  rc = geometry_finish(ctx, stream, prm, num_rendered);
+  if (rc != GGD_OK) return rc;
+  if (*num_rendered > capacity)
+    return ggd_fail(ctx, GGD_E_CAPACITY, "binning_buf capacity is below num_rendered: re-run with a larger buffer");
+  return render_enqueue(ctx, stream, prm, geom_buf, capacity, *num_rendered, binning_buf, img_buf, out_color, false, out_depth,
+                        out_alpha);
 }
 
 extern "C" int ggd_forward(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D, const float* shs,
@@ -716,23 +766,19 @@ extern "C" int ggd_forward(ggd_ctx* ctx, void* stream, const ggd_params* prm, co
                            const float* rotations, const float* cov3D_precomp, void* geom_buf, int32_t* radii,
                            void* binning_buf, int64_t capacity, void* img_buf, float* out_color,
                            int64_t* num_rendered) {
-  if (capacity < 0) return ggd_fail(ctx, GGD_E_INVALID, "capacity < 0");
-  if (ctx && ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, kPendingMsg);
-  if (prm && prm->P > 0 && capacity > 0 && ggd_forward_can_speculate(ctx, prm, capacity)) {
-    const int rc = forward_spec_enqueue(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations,
-                                        cov3D_precomp, geom_buf, radii, binning_buf, capacity, img_buf, out_color, num_rendered);
-    if (rc != GGD_OK) return rc;
-    return forward_spec_collect(ctx, stream, prm, geom_buf, binning_buf, capacity, img_buf, out_color, num_rendered);
-  }
-  int rc = geometry_enqueue(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations,
-                            cov3D_precomp, geom_buf, radii, num_rendered, false);
+  return forward_single_call(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                             geom_buf, radii, binning_buf, capacity, img_buf, out_color, num_rendered, nullptr, nullptr);
+}
+
+extern "C" int ggd_forward_aux(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D, const float* shs,
+                               const float* colors_precomp, const float* opacities, const float* scales,
+                               const float* rotations, const float* cov3D_precomp, void* geom_buf, int32_t* radii,
+                               void* binning_buf, int64_t capacity, void* img_buf, float* out_color, float* out_depth,
+                               float* out_alpha, int64_t* num_rendered) {
+  const int rc = check_aux_planes(ctx, out_depth, out_alpha);
   if (rc != GGD_OK) return rc;
-  if (prm->P == 0) return render_enqueue(ctx, stream, prm, geom_buf, capacity, 0, binning_buf, img_buf, out_color, false);
-  rc = geometry_finish(ctx, stream, prm, num_rendered);
-  if (rc != GGD_OK) return rc;
-  if (*num_rendered > capacity)
-    return ggd_fail(ctx, GGD_E_CAPACITY, "binning_buf capacity is below num_rendered: re-run with a larger buffer");
-  return render_enqueue(ctx, stream, prm, geom_buf, capacity, *num_rendered, binning_buf, img_buf, out_color, false);
+  return forward_single_call(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                             geom_buf, radii, binning_buf, capacity, img_buf, out_color, num_rendered, out_depth, out_alpha);
 }
 
 extern "C" int ggd_forward_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D, const float* shs,
@@ -761,13 +807,13 @@ extern "C" int ggd_forward_collect(ggd_ctx* ctx, void* stream, int64_t* num_rend
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------
-extern "C" int ggd_backward(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
-                            const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
-                            const float* rotations, const float* cov3D_precomp, const int32_t* radii,
-                            const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
-                            const float* dL_dpix, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                            float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
-                            float* dL_drots) {
+static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
+                         const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+                         const float* rotations, const float* cov3D_precomp, const int32_t* radii,
+                         const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
+                         const float* dL_dpix, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                         float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
+                         float* dL_drots, bool aux, const float* dL_ddepth, const float* dL_dalpha) {
   (void)hipGetLastError();   // a sticky error another library left in this thread is not ours to report
   int rc = check_params(ctx, prm);
   if (rc != GGD_OK) return rc;
@@ -792,6 +838,7 @@ extern "C" int ggd_backward(ggd_ctx* ctx, void* stream, const ggd_params* prm, c
   const uint32_t* ranges = reinterpret_cast<const uint32_t*>(ib + iv.ranges);
   const float* final_T = reinterpret_cast<const float*>(ib + iv.final_T);
   const uint32_t* n_contrib = reinterpret_cast<const uint32_t*>(ib + iv.n_contrib);
+  const uint32_t* depth_keys = reinterpret_cast<const uint32_t*>(gb + gv.depth_keys);
 
   const size_t acc_bytes = (size_t)P * GGD_ACC_FLOATS * sizeof(float);
   rc = ggd_reserve_scratch(ctx, ggd_align(acc_bytes), s);
@@ -808,17 +855,42 @@ extern "C" int ggd_backward(ggd_ctx* ctx, void* stream, const ggd_params* prm, c
 
   if (R > 0) {
     StageTimer t(ctx, ST_BLEND_BWD, s);
-    rc = ggd_launch_blend_backward(ctx, s, *prm, splat, list, ranges, final_T, n_contrib, dL_dpix, grad_acc);
+    rc = ggd_launch_blend_backward(ctx, s, *prm, splat, list, ranges, final_T, n_contrib, dL_dpix, grad_acc, aux, depth_keys,
+                                   dL_ddepth, dL_dalpha);
     if (rc != GGD_OK) return rc;
   }
   {
     StageTimer t(ctx, ST_PREPROCESS_BWD, s);
     rc = ggd_launch_preprocess_backward(ctx, s, *prm, means3D, shs, colors_precomp, opacities, dL_dopacity, scales, rotations,
                                         cov3D_precomp, radii, shs ? clamped : nullptr, grad_acc, dL_dmeans2D,
-                                        dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots);
+                                        dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots, aux);
     if (rc != GGD_OK) return rc;
   }
   return GGD_OK;
+}
+
+extern "C" int ggd_backward(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
+                            const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+                            const float* rotations, const float* cov3D_precomp, const int32_t* radii,
+                            const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
+                            const float* dL_dpix, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                            float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
+                            float* dL_drots) {
+  return backward_impl(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii,
+                       geom_buf, binning_buf, img_buf, R, dL_dpix, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D,
+                       dL_dcov3D, dL_dsh, dL_dscales, dL_drots, false, nullptr, nullptr);
+}
+
+extern "C" int ggd_backward_aux(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
+                                const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+                                const float* rotations, const float* cov3D_precomp, const int32_t* radii,
+                                const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
+                                const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, float* dL_dmeans2D,
+                                float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                                float* dL_dscales, float* dL_drots) {
+  return backward_impl(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii,
+                       geom_buf, binning_buf, img_buf, R, dL_dpix, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D,
+                       dL_dcov3D, dL_dsh, dL_dscales, dL_drots, true, dL_ddepth, dL_dalpha);
 }
 
 extern "C" int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D,

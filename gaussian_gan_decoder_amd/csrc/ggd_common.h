@@ -273,24 +273,33 @@ int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const 
                       // fold_rowtot / fold_status1 (folded front end, grids of <= 64 x 64 tiles): the entries per tile row were
                       // counted by the preprocess kernel -- level 1 is ONE launch (count, look-back over the chunks, scatter)
 int ggd_launch_ranges(ggd_ctx* ctx, hipStream_t s, const uint64_t* keys, int64_t n, uint32_t* ranges, int T);
+// out_depth / out_alpha non-null (both): the depth / alpha extension (blend_forward_kernel<..., AUX>), which also reads
+// depth_keys (the geometry buffer's: the fp32 bits of each Gaussian's view-space depth)
 int ggd_launch_blend(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
                      const uint32_t* list, const uint32_t* ranges, uint32_t capacity, float* out_color, float* final_T,
-                     uint32_t* n_contrib);
+                     uint32_t* n_contrib, const uint32_t* depth_keys = nullptr, float* out_depth = nullptr,
+                     float* out_alpha = nullptr);
 // Backward accumulator record (library scratch, one per Gaussian, zeroed with ONE memset): the blend backward adds its
 // per-(tile, Gaussian) sums here, the per-Gaussian backward reads it once and writes every caller-visible gradient
 // (zeros for culled Gaussians), so the caller's 8 gradient arrays need no zero-fill passes.
-constexpr int GGD_ACC_FLOATS = 12;   // 48 B: conic A,B,C | opacity | mean2D x,y | colour r,g,b | 3 pad
+constexpr int GGD_ACC_FLOATS = 12;   // 48 B: conic A,B,C | opacity | mean2D x,y | colour r,g,b | depth (aux only) | 2 pad
 constexpr int GGD_ACC_CONIC = 0, GGD_ACC_OPACITY = 3, GGD_ACC_MEAN2D = 4, GGD_ACC_COLOR = 6;
+constexpr int GGD_ACC_DEPTH = 9;     // dL/dz (view-space depth), written only by the depth / alpha backward
+// aux: the depth / alpha backward (blend_backward_quarter_kernel<..., AUX>, always the quarter form); depth_keys as in
+// ggd_launch_blend, dL_ddepth / dL_dalpha [H, W] (NULL = zero)
 int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
                               const uint32_t* list, const uint32_t* ranges, const float* final_T,
-                              const uint32_t* n_contrib, const float* dL_dpix, float* grad_acc /*[P][GGD_ACC_FLOATS]*/);
+                              const uint32_t* n_contrib, const float* dL_dpix, float* grad_acc /*[P][GGD_ACC_FLOATS]*/,
+                              bool aux = false, const uint32_t* depth_keys = nullptr, const float* dL_ddepth = nullptr,
+                              const float* dL_dalpha = nullptr);
+// aux: also adds dL/dz (accumulator slot GGD_ACC_DEPTH) times dz/dmean = (view[2], view[6], view[10]) to dL_dmeans3D
 int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const float* means3D,
                                    const float* shs, const float* colors_precomp, const float* opacities,
                                    float* dL_dopacity, const float* scales,
                                    const float* rotations, const float* cov3D_precomp, const int32_t* radii,
                                    const uint8_t* clamped, const float* grad_acc, float* dL_dmean2D,
                                    float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                                   float* dL_dscales, float* dL_drots);
+                                   float* dL_dscales, float* dL_drots, bool aux = false);
 
 // ---- device helpers -----------------------------------------------------------------------------------------
 #ifdef __HIPCC__

@@ -17,8 +17,9 @@ using namespace ggdm;
 // The per-Gaussian work of the kernels below.  dsh_stage: where this Gaussian's 3 M SH gradients go instead of
 // dL_dsh[i] (the staged kernel's LDS row), or nullptr.
 // SHVEC: the Gaussian's SH row is read with dwordx4 loads into registers (see preprocess_kernel); DREG: its gradients are
-// collected in registers too and leave as 3 M / 4 dwordx4 stores
-template <bool SHVEC, bool DREG = false>
+// collected in registers too and leave as 3 M / 4 dwordx4 stores.  AUX (depth / alpha extension): the accumulator record's
+// slot GGD_ACC_DEPTH holds dL/dz of the view-space depth z = view row 2 . (p, 1), added to dL/dmean (z is not clamped)
+template <bool SHVEC, bool DREG = false, bool AUX = false>
 __device__ __forceinline__ void preprocess_backward_body(
     int i, float* dsh_stage,
     int P, int M, int deg, int W, int H, float tanfovx, float tanfovy, float mod, int raw,
@@ -248,6 +249,11 @@ __device__ __forceinline__ void preprocess_backward_body(
       dmean[2] += (-v0 * v2 * ddir[0] - v1 * v2 * ddir[1] + (sum2 - v2 * v2) * ddir[2]) * invsum32;
     }
   }
+  if constexpr (AUX) {
+    static_assert(GGD_ACC_DEPTH == 9, "depth gradient is read from acc2.y");
+    const float gz = acc2.y;
+    dmean[0] += V.m[2] * gz; dmean[1] += V.m[6] * gz; dmean[2] += V.m[10] * gz;
+  }
   dL_dmeans3D[3 * ii] = dmean[0]; dL_dmeans3D[3 * ii + 1] = dmean[1]; dL_dmeans3D[3 * ii + 2] = dmean[2];
 #pragma unroll
   for (int k = 0; k < 6; ++k) dL_dcov3D[6 * ii + k] = dc[k];
@@ -337,39 +343,68 @@ __global__ __launch_bounds__(256) void preprocess_backward_vec_kernel(GGD_PPB_PA
   preprocess_backward_body<true, true>(i, nullptr, GGD_PPB_ARGS);
 }
 
+// depth / alpha extension (ggd_backward_aux): the same kernels with the depth term (AUX must be true: overloads, so that the
+// plain kernels keep their names)
+template <bool AUX>
+__global__ __launch_bounds__(256) void preprocess_backward_kernel(GGD_PPB_PARAMS) {
+  static_assert(AUX, "the plain kernel is the non-template one");
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  preprocess_backward_body<false, false, true>(i, nullptr, GGD_PPB_ARGS);
+}
+
+template <bool AUX>
+__global__ __launch_bounds__(256) void preprocess_backward_vec_kernel(GGD_PPB_PARAMS) {
+  static_assert(AUX, "the plain kernel is the non-template one");
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  preprocess_backward_body<true, true, true>(i, nullptr, GGD_PPB_ARGS);
+}
+
 // SH degree > 0 (M > 1 coefficients per channel): a Gaussian's 3 M gradients are 12 M bytes apart from its neighbour's, so
 // written by their owner lane they leave the wave as 3 M store instructions of 64 lone words each (1 M Gaussians, M = 16:
 // 494 us for this kernel against 88 us at M = 1).  Here every lane parks its row in LDS and the wave writes its 64 rows --
 // one contiguous 768 M-byte span of dL_dsh -- with lane-consecutive (16-byte where 3 M allows) stores.  (1 M Gaussians,
 // M = 16: 247 -> 146 us; preprocess_backward_vec_kernel above does as well without LDS where the rows allow dwordx4.)
+// (the body as a macro, so that the plain kernel stays the code it was; the arguments are those of preprocess_backward_body)
+#define GGD_PPB_STAGED_BODY(...)                                                                            \
+  extern __shared__ float s_dsh[];   /* [256][3 M + 1] */                                               \
+  const int i = blockIdx.x * 256 + threadIdx.x;                                                             \
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;                                                 \
+  const int rl = 3 * M, rowlen = rl + 1;                                                                    \
+  if (i < P) preprocess_backward_body<__VA_ARGS__>(i, s_dsh + (size_t)threadIdx.x * rowlen, GGD_PPB_ARGS);  \
+  __builtin_amdgcn_wave_barrier();                                                                          \
+  __threadfence_block();                                                                                    \
+  const int i0 = blockIdx.x * 256 + wv * 64;                                                                \
+  const int nrows = min(64, P - i0);                                                                        \
+  if (nrows <= 0) return;                                                                                   \
+  const float* rows = s_dsh + (size_t)wv * 64 * rowlen;                                                     \
+  float* dst = dL_dsh + (size_t)i0 * rl;                                                                    \
+  const int total = nrows * rl;                                                                             \
+  if ((rl & 3) == 0) {                                                                                      \
+    for (int e = 4 * lane; e < total; e += 256) {                                                           \
+      const int r = e / rl, k = e - r * rl;                                                                 \
+      const float* src = rows + r * rowlen + k;                                                             \
+      *reinterpret_cast<float4*>(dst + e) = make_float4(src[0], src[1], src[2], src[3]);                    \
+    }                                                                                                       \
+  } else {                                                                                                  \
+    for (int e = lane; e < total; e += 64) {                                                                \
+      const int r = e / rl, k = e - r * rl;                                                                 \
+      dst[e] = rows[r * rowlen + k];                                                                        \
+    }                                                                                                       \
+  }
+
 template <bool SHVEC>
 __global__ __launch_bounds__(256) void preprocess_backward_staged_kernel(GGD_PPB_PARAMS) {
-  extern __shared__ float s_dsh[];   // [256][3 M + 1]
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int rl = 3 * M, rowlen = rl + 1;
-  if (i < P) preprocess_backward_body<SHVEC>(i, s_dsh + (size_t)threadIdx.x * rowlen, GGD_PPB_ARGS);
-  __builtin_amdgcn_wave_barrier();
-  __threadfence_block();
-  const int i0 = blockIdx.x * 256 + wv * 64;
-  const int nrows = min(64, P - i0);
-  if (nrows <= 0) return;
-  const float* rows = s_dsh + (size_t)wv * 64 * rowlen;
-  float* dst = dL_dsh + (size_t)i0 * rl;
-  const int total = nrows * rl;
-  if ((rl & 3) == 0) {
-    for (int e = 4 * lane; e < total; e += 256) {
-      const int r = e / rl, k = e - r * rl;
-      const float* src = rows + r * rowlen + k;
-      *reinterpret_cast<float4*>(dst + e) = make_float4(src[0], src[1], src[2], src[3]);
-    }
-  } else {
-    for (int e = lane; e < total; e += 64) {
-      const int r = e / rl, k = e - r * rl;
-      dst[e] = rows[r * rowlen + k];
-    }
-  }
+GGD_PPB_STAGED_BODY(SHVEC)
 }
+
+template <bool SHVEC, bool AUX>
+__global__ __launch_bounds__(256) void preprocess_backward_staged_kernel(GGD_PPB_PARAMS) {
+  static_assert(AUX, "the plain kernel is the one-parameter template");
+GGD_PPB_STAGED_BODY(SHVEC, false, true)
+}
+#undef GGD_PPB_STAGED_BODY
 
 }  // namespace
 
@@ -379,13 +414,27 @@ int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params
                                    const float* rotations, const float* cov3D_precomp, const int32_t* radii,
                                    const uint8_t* clamped, const float* grad_acc, float* dL_dmean2D,
                                    float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                                   float* dL_dscales, float* dL_drots) {
+                                   float* dL_dscales, float* dL_drots, bool aux) {
   if (prm.P == 0) return GGD_OK;
   // the staged form whenever there is more than the band-0 coefficient per channel (and room: 256 rows of 3 M + 1 floats)
   const bool staged = !colors_precomp && prm.M > 1 && (size_t)256 * (3 * prm.M + 1) * sizeof(float) <= 64 * 1024;
   const bool shvec = staged && prm.M <= 16 && ((3 * prm.M) & 3) == 0;
   // rows that are a multiple of 16 bytes (M = 4, 8, 12, 16): read and written from registers with dwordx4 accesses (145 us
   // at M = 16, 1 M Gaussians; the LDS-staged form measures 152 with the same loads and is kept for the other M)
+#define GGD_PPB_LAUNCH(KERNEL, LDS)                                                                                  \
+  hipLaunchKernelGGL(KERNEL, dim3((prm.P + 255) / 256), dim3(256), (LDS), s, prm.P, prm.M, prm.sh_degree, prm.width,     \
+                     prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier, prm.raw_attributes, opacities, dL_dopacity,  \
+                     prm.viewmatrix, prm.projmatrix, prm.campos, means3D, shs, colors_precomp, scales, rotations,           \
+                     cov3D_precomp, radii, clamped, grad_acc, dL_dmean2D, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh,       \
+                     dL_dscales, dL_drots)
+  if (aux) {   // the depth / alpha extension: the same choice of form, with the depth term
+    if (shvec) GGD_PPB_LAUNCH(preprocess_backward_vec_kernel<true>, 0);
+    else if (staged) GGD_PPB_LAUNCH((preprocess_backward_staged_kernel<false, true>), (size_t)256 * (3 * prm.M + 1) * sizeof(float));
+    else GGD_PPB_LAUNCH(preprocess_backward_kernel<true>, 0);
+    GGD_HIP(hipGetLastError());
+    return GGD_OK;
+  }
+#undef GGD_PPB_LAUNCH
   if (shvec)
     hipLaunchKernelGGL(preprocess_backward_vec_kernel, dim3((prm.P + 255) / 256), dim3(256), 0, s, prm.P, prm.M,
                        prm.sh_degree, prm.width, prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier,

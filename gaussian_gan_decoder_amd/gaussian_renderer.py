@@ -29,9 +29,10 @@ def _screenspace_points(pc):
     return pts
 
 
-def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attributes=False):
+def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attributes=False, render_depth_alpha=False):
     return GaussianRasterizationSettings(
         raw_attributes=raw_attributes,
+        render_depth_alpha=render_depth_alpha,
         image_height=int(viewpoint_camera.image_height),
         image_width=int(viewpoint_camera.image_width),
         tanfovx=math.tan(viewpoint_camera.FoVx * 0.5),
@@ -47,10 +48,14 @@ def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attri
     )
 
 
-def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None):
-    """Stock 3DGS render (reference :19-102).  `pipe` needs .debug, .compute_cov3D_python, .convert_SHs_python."""
+def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
+           render_depth_alpha=False):
+    """Stock 3DGS render (reference :19-102).  `pipe` needs .debug, .compute_cov3D_python, .convert_SHs_python.
+    render_depth_alpha=True (extension): the dict also holds "depth" (sum alpha_i T_i z_i) and "alpha" (1 - final T),
+    differentiable float32 [1, H, W] maps."""
     screenspace_points = _screenspace_points(pc)
-    rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, pipe.debug))
+    rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, pipe.debug,
+                                              render_depth_alpha=render_depth_alpha))
     scales = rotations = cov3D_precomp = None
     if pipe.compute_cov3D_python:
         cov3D_precomp = pc.get_covariance(scaling_modifier)
@@ -68,23 +73,28 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
             shs = pc.get_features
     else:
         colors_precomp = override_color
-    rendered_image, radii = rasterizer(means3D=pc.get_xyz, means2D=screenspace_points, shs=shs,
-                                       colors_precomp=colors_precomp, opacities=pc.get_opacity, scales=scales,
-                                       rotations=rotations, cov3D_precomp=cov3D_precomp)
-    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-            "radii": radii}
+    out = rasterizer(means3D=pc.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
+                     opacities=pc.get_opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+    rendered_image, radii = out[0], out[1]
+    res = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+           "radii": radii}
+    if render_depth_alpha:
+        res["depth"], res["alpha"] = out[2], out[3]
+    return res
 
 
 def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None, scaling_modifier=1.0,
-                  override_color=None, debug=False, fused_activations=False):
+                  override_color=None, debug=False, fused_activations=False, render_depth_alpha=False):
     """Decoder-path render (reference :105-186): scale/rotation always from the model, SH unless override_color.
     "alpha" and "depth" are the radii placeholders the reference returns (:184-185).
     fused_activations=True (extension): hand the RAW `_opacity/_scaling/_rotation` to the
     rasterizer, which applies sigmoid / exp / normalize (and their Jacobians in the backward) inside its kernels
-    instead of three torch elementwise passes each way."""
+    instead of three torch elementwise passes each way.
+    render_depth_alpha=True (extension): "depth" (sum alpha_i T_i z_i, view-space z; depth / alpha is the expected depth)
+    and "alpha" (1 - final T) are the rasterizer's differentiable float32 [1, H, W] maps instead of the placeholders."""
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug,
-                                              raw_attributes=fused_activations))
+                                              raw_attributes=fused_activations, render_depth_alpha=render_depth_alpha))
     means3D = pc.get_xyz
     if xyz_offset is not None:
         means3D = means3D + xyz_offset
@@ -97,8 +107,9 @@ def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None,
         opacities, scales, rotations = pc._opacity, pc._scaling, pc._rotation
     else:
         opacities, scales, rotations = pc.get_opacity, pc.get_scaling, pc.get_rotation
-    rendered_image, radii = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs,
-                                       colors_precomp=colors_precomp, opacities=opacities,
-                                       scales=scales, rotations=rotations, cov3D_precomp=None)
+    out = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
+                     opacities=opacities, scales=scales, rotations=rotations, cov3D_precomp=None)
+    rendered_image, radii = out[0], out[1]
+    alpha, depth = (out[3], out[2]) if render_depth_alpha else (radii, radii)
     return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-            "radii": radii, "alpha": radii, "depth": radii}
+            "radii": radii, "alpha": alpha, "depth": depth}

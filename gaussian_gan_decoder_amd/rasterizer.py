@@ -46,6 +46,8 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
     raw_attributes: bool = False  # extension (default = upstream behaviour): opacities / scales / rotations are the raw
     #                               decoder outputs; sigmoid / exp / normalize are fused into the kernels (fwd + bwd)
+    render_depth_alpha: bool = False  # extension: the rasterizer also returns differentiable per-pixel depth
+    #                                   (sum alpha_i T_i z_i, view-space z) and alpha (1 - final T) maps, [1, H, W] each
 
 
 def _f32c(t: torch.Tensor, name: str, device) -> torch.Tensor:
@@ -162,11 +164,13 @@ def _marshal_forward(bg, means3D, colors_precomp, opacities, scales, rotations, 
 
 def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier,
                                cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, image_height, image_width,
-                               sh, degree, campos, prefiltered, debug, raw_attributes=False):
+                               sh, degree, campos, prefiltered, debug, raw_attributes=False, *, render_depth_alpha=False):
     """== upstream `_C.rasterize_gaussians(...)`: returns
     (num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer).  binningBuffer may be larger than
     num_rendered needs (single-call forward with a capacity hint); the sorted list sits at its offset 0 either way, so
-    the backward takes num_rendered as R exactly like upstream."""
+    the backward takes num_rendered as R exactly like upstream.  render_depth_alpha=True (extension): the tuple goes on
+    with the depth and alpha maps, float32 [1, H, W] each (ggd_forward_aux / ggd_forward_render_aux); everything else is
+    bit-identical to the plain call."""
     dev, P, (means3D, opacities, sh_c, col_c, sc_c, rot_c, cov_c), prm, keep = _marshal_forward(
         bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         tanfovx, tanfovy, image_height, image_width, sh, degree, campos, prefiltered, debug, raw_attributes)
@@ -180,6 +184,11 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
     geom = torch.empty((_sizes("g", P, 0),), **u8)
     img = torch.empty((_sizes("i", W, H),), **u8)
+    aux = ()
+    if render_depth_alpha:
+        depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+        alpha = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+        aux = (_ptr(depth), _ptr(alpha))
     R = C.c_int64(0)
     stream = C.c_void_p(stream_handle)
     key = (P, W, H)
@@ -191,9 +200,9 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
             # not wait for the num_rendered round trip.  Falls through to the exact two-phase path on overflow.
             cap = _capacity(hint)
             binning = torch.empty((_sizes("b", cap, 0),), **u8)
-            rc = lib.ggd_forward(ctx.handle, stream, C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c),
-                                 _ptr(opacities), _ptr(sc_c), _ptr(rot_c), _ptr(cov_c), _ptr(geom), _ptr(radii),
-                                 _ptr(binning), cap, _ptr(img), _ptr(color), C.byref(R))
+            rc = (lib.ggd_forward_aux if aux else lib.ggd_forward)(
+                ctx.handle, stream, C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c), _ptr(opacities), _ptr(sc_c),
+                _ptr(rot_c), _ptr(cov_c), _ptr(geom), _ptr(radii), _ptr(binning), cap, _ptr(img), _ptr(color), *aux, C.byref(R))
             if rc == -6:       # GGD_E_CAPACITY: R is valid, redo the render phase with an exact buffer
                 binning = None
                 ctx.capacity_retries += 1
@@ -205,12 +214,14 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
                                                _ptr(geom), _ptr(radii), C.byref(R)))
         if binning is None:
             binning = torch.empty((lib.ggd_binning_bytes(R.value),), **u8)
-            ctx.check(lib.ggd_forward_render(ctx.handle, stream, C.byref(prm), _ptr(geom), R.value, _ptr(binning),
-                                             _ptr(img), _ptr(color)))
+            ctx.check((lib.ggd_forward_render_aux if aux else lib.ggd_forward_render)(
+                ctx.handle, stream, C.byref(prm), _ptr(geom), R.value, _ptr(binning), _ptr(img), _ptr(color), *aux))
     # the hint is a DECAYING RUNNING MAXIMUM of num_rendered, not the last frame's value: consecutive scenes of a training
     # step differ several-fold (the reference draws fov ~ U[5, 17] degrees per scene, target_dataloader.py:71), and with
     # "last frame x 1.25" every upward swing took the overflow -> exact-retry path, i.e. a host sync
     ctx.capacity_hint[key] = max(int(R.value), int((hint or 0) * _HINT_DECAY))
+    if render_depth_alpha:
+        return int(R.value), color, radii, geom, binning, img, depth, alpha
     return int(R.value), color, radii, geom, binning, img
 
 
@@ -322,13 +333,20 @@ class FramePipeline:
 def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scales, rotations, scale_modifier,
                                         cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, dL_dout_color, sh,
                                         degree, campos, geomBuffer, R, binningBuffer, imgBuffer, debug,
-                                        raw_attributes=False, opacities=None):
+                                        raw_attributes=False, opacities=None, *, dL_ddepth=None, dL_dalpha=None):
     """== upstream `_C.rasterize_gaussians_backward(...)`: returns
-    (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)."""
+    (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
+    dL_ddepth / dL_dalpha (extension, [1, H, W] or [H, W]; None = zero): gradients of the depth and alpha maps of a
+    render_depth_alpha forward -- with either given the call is ggd_backward_aux, else today's ggd_backward."""
+    H, W = int(dL_dout_color.size(-2)), int(dL_dout_color.size(-1))
+    aux = dL_ddepth is not None or dL_dalpha is not None
+    for t, name in ((dL_ddepth, "dL_ddepth"), (dL_dalpha, "dL_dalpha")):
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) not in ((1, H, W), (H, W))):
+            raise ValueError(f"{name} must have dimensions (1, {H}, {W}) or ({H}, {W}) (got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__})")
     _require_cuda(means3D)
     dev = means3D.device
     P = means3D.size(0)
-    H, W = int(dL_dout_color.size(-2)), int(dL_dout_color.size(-1))
     means3D = _f32c(means3D, "means3D", dev)
     have = lambda t: t is not None and t.numel() > 0
     sh_c = _f32c(sh, "sh", dev) if have(sh) else None
@@ -337,6 +355,8 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
     rot_c = _f32c(rotations, "rotations", dev) if have(rotations) else None
     cov_c = _f32c(cov3D_precomp, "cov3D_precomp", dev) if have(cov3D_precomp) else None
     g = _f32c(dL_dout_color, "dL_dout_color", dev)
+    gD = _f32c(dL_ddepth, "dL_ddepth", dev) if dL_ddepth is not None else None
+    gA = _f32c(dL_dalpha, "dL_dalpha", dev) if dL_dalpha is not None else None
     M = sh_c.size(1) if sh_c is not None else 0
     rs = GaussianRasterizationSettings(H, W, tanfovx, tanfovy, bg, scale_modifier, viewmatrix, projmatrix, degree,
                                        campos, False, debug, raw_attributes)
@@ -359,11 +379,18 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
             t.fill_(float("nan"))
     if P > 0:
         with torch.cuda.device(dev):
-            ctx.check(lib.ggd_backward(ctx.handle, _stream(dev), C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c),
-                                       _ptr(op_c), _ptr(sc_c), _ptr(rot_c), _ptr(cov_c), _ptr(radii), _ptr(geomBuffer),
-                                       _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g), _ptr(dL_dmeans2D),
-                                       _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D), _ptr(dL_dcov3D),
-                                       _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations)))
+            if aux:
+                ctx.check(lib.ggd_backward_aux(ctx.handle, _stream(dev), C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c),
+                                               _ptr(op_c), _ptr(sc_c), _ptr(rot_c), _ptr(cov_c), _ptr(radii), _ptr(geomBuffer),
+                                               _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g), _ptr(gD), _ptr(gA),
+                                               _ptr(dL_dmeans2D), _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D),
+                                               _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations)))
+            else:
+                ctx.check(lib.ggd_backward(ctx.handle, _stream(dev), C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c),
+                                           _ptr(op_c), _ptr(sc_c), _ptr(rot_c), _ptr(cov_c), _ptr(radii), _ptr(geomBuffer),
+                                           _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g), _ptr(dL_dmeans2D),
+                                           _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D), _ptr(dL_dcov3D),
+                                           _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations)))
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
 
 
@@ -387,28 +414,40 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings):
         rs = raster_settings
-        num_rendered, color, radii, geom, binning, img = rasterize_gaussians_native(
+        depth_alpha = bool(getattr(rs, "render_depth_alpha", False))
+        out = rasterize_gaussians_native(
             rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree,
-            rs.campos, rs.prefiltered, rs.debug, getattr(rs, "raw_attributes", False))
+            rs.campos, rs.prefiltered, rs.debug, getattr(rs, "raw_attributes", False), render_depth_alpha=depth_alpha)
+        num_rendered, color, radii, geom, binning, img = out[:6]
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
                               img, opacities)
         ctx.mark_non_differentiable(radii)
+        if depth_alpha:
+            # unused outputs arrive as None in the backward: a graph that only reads the colour takes today's backward
+            ctx.set_materialize_grads(False)
+            return color, radii, out[6], out[7]
         return color, radii
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii):
+    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img, opacities = \
             ctx.saved_tensors
         raw = getattr(rs, "raw_attributes", False)
+        if grad_out_color is None:   # (render_depth_alpha: gradients are not materialised)
+            grad_out_color = torch.zeros((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32,
+                                         device=means3D.device)
+        aux = {}
+        if grad_depth is not None or grad_alpha is not None:
+            aux = dict(dL_ddepth=grad_depth, dL_dalpha=grad_alpha)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations) = rasterize_gaussians_backward_native(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, geom,
-            ctx.num_rendered, binning, img, rs.debug, raw, opacities if raw else None)
+            ctx.num_rendered, binning, img, rs.debug, raw, opacities if raw else None, **aux)
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
                 grad_rotations, grad_cov3Ds_precomp, None)
 

@@ -200,6 +200,39 @@ int ggd_backward(ggd_ctx* ctx, void* stream, const ggd_params* prm,
                  float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
                  float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots);
 
+/*
+ * Depth and alpha planes (opt-in extension; the entry points above are unchanged by it).  Per pixel p, over the same
+ * contributors, skip rules and stop rule as the colour:
+ *   depth[p] = sum_i alpha_i T_i z_i   (z_i = Gaussian i's view-space depth, the value the depth sort orders by; background 0;
+ *                                       the expected depth is depth / alpha)
+ *   alpha[p] = 1 - final_T[p]          (the pixel's opacity)
+ * out_depth, out_alpha : float[H,W] each, written (both required).  out_color, radii, the three buffers and num_rendered are
+ * bit-identical to those of the plain call.
+ *   ggd_forward_aux        == ggd_forward (speculative route, its re-render and GGD_E_CAPACITY included) + the two planes
+ *   ggd_forward_render_aux == ggd_forward_render + the two planes (phase 1 is ggd_forward_geometry, unchanged)
+ *   ggd_backward_aux       == ggd_backward + dL_ddepth[H,W], dL_dalpha[H,W] (device; NULL = zero).  The depth term reaches
+ *                             dL_dmeans3D through z (dz/dmean = row 2 of the view matrix), the alpha term every input through
+ *                             the final transmittance.  Runs the quarter form of the backward blend whatever
+ *                             GGD_OPT_BLEND_SPLIT says (the depth / alpha backward has no tile form).
+ */
+int ggd_forward_aux(ggd_ctx* ctx, void* stream, const ggd_params* prm,
+                    const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
+                    const float* scales, const float* rotations, const float* cov3D_precomp,
+                    void* geom_buf, int32_t* radii, void* binning_buf, int64_t capacity, void* img_buf,
+                    float* out_color, float* out_depth, float* out_alpha, int64_t* num_rendered);
+int ggd_forward_render_aux(ggd_ctx* ctx, void* stream, const ggd_params* prm,
+                           const void* geom_buf, int64_t num_rendered,
+                           void* binning_buf, void* img_buf, float* out_color, float* out_depth, float* out_alpha);
+int ggd_backward_aux(ggd_ctx* ctx, void* stream, const ggd_params* prm,
+                     const float* means3D, const float* shs, const float* colors_precomp,
+                     const float* opacities /* only read when prm->raw_attributes */,
+                     const float* scales, const float* rotations, const float* cov3D_precomp,
+                     const int32_t* radii,
+                     const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t num_rendered,
+                     const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
+                     float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                     float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots);
+
 /* present[i] = 1 iff Gaussian i passes the view-space z > 0.2 frustum test. */
 int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D,
                      const float* viewmatrix, const float* projmatrix, uint8_t* present);
