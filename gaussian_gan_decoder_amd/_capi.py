@@ -29,7 +29,7 @@ class Params(C.Structure):
                 ("height", C.c_int32), ("tanfovx", C.c_float), ("tanfovy", C.c_float),
                 ("scale_modifier", C.c_float), ("prefiltered", C.c_int32), ("debug", C.c_int32),
                 ("viewmatrix", C.c_void_p), ("projmatrix", C.c_void_p), ("campos", C.c_void_p),
-                ("bg", C.c_void_p), ("raw_attributes", C.c_int32), ("reserved_", C.c_int32)]
+                ("bg", C.c_void_p), ("raw_attributes", C.c_int32), ("antialiasing", C.c_int32)]
 
 
 class GeomView(C.Structure):

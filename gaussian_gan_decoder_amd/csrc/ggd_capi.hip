@@ -826,6 +826,8 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, cons
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward: NULL buffer");
   if (prm->raw_attributes && (!opacities || cov3D_precomp))
     return ggd_fail(ctx, GGD_E_INVALID, "raw_attributes needs opacities and scales/rotations (no cov3D_precomp)");
+  if (prm->antialiasing && !opacities)   // dL/dh of the opacity compensation is dL/do_eff times the opacity
+    return ggd_fail(ctx, GGD_E_INVALID, "antialiasing needs the opacities in the backward");
   hipStream_t s = static_cast<hipStream_t>(stream);
   ggd_geom_view gv; ggd_binning_view bv; ggd_img_view iv;
   ggd_geom_layout(P, &gv); ggd_binning_layout(R, &bv); ggd_img_layout(prm->width, prm->height, &iv);

@@ -18,8 +18,13 @@ using namespace ggdm;
 // dL_dsh[i] (the staged kernel's LDS row), or nullptr.
 // SHVEC: the Gaussian's SH row is read with dwordx4 loads into registers (see preprocess_kernel); DREG: its gradients are
 // collected in registers too and leave as 3 M / 4 dwordx4 stores.  AUX (depth / alpha extension): the accumulator record's
-// slot GGD_ACC_DEPTH holds dL/dz of the view-space depth z = view row 2 . (p, 1), added to dL/dmean (z is not clamped)
-template <bool SHVEC, bool DREG = false, bool AUX = false>
+// slot GGD_ACC_DEPTH holds dL/dz of the view-space depth z = view row 2 . (p, 1), added to dL/dmean (z is not clamped).
+// AA (anti-aliasing, ggd_params.antialiasing): the blend saw o_eff = o h, h = sqrt(max(2.5e-5, r)), r = det0 / det1 with
+// det0 = x y - z^2 and det1 = (x + w)(y + w) - z^2 the determinants of the 2D covariance (x, z, y) = abc before / after the
+// w = 0.3 dilation.  With g = dL/do_eff (acc0.w): dL/do = g h, and while the clamp is off dL/dr = g o / (2 h) adds
+//   dL/dx += k w (y^2 + w y + z^2),  dL/dy += k w (x^2 + w x + z^2),  dL/dz += -2 k w z (x + y + w),  k = g o / (2 h det1^2)
+// to the conic's dL/da, dL/dc, dL/db before they are taken on to cov3D and the view-space point
+template <bool SHVEC, bool DREG = false, bool AUX = false, bool AA = false>
 __device__ __forceinline__ void preprocess_backward_body(
     int i, float* dsh_stage,
     int P, int M, int deg, int W, int H, float tanfovx, float tanfovy, float mod, int raw,
@@ -84,6 +89,8 @@ __device__ __forceinline__ void preprocess_backward_body(
 
   float dmean[3];
   float dc[6] = {0, 0, 0, 0, 0, 0};
+  float aa_o = 0.0f, aa_h = 1.0f;   // AA: the opacity o (activated) and h of the forward
+  if constexpr (AA) aa_o = raw ? act_sigmoid(opacities_raw[i]) : opacities_raw[i];
   // (1) conic -> cov2D -> cov3D, view-space point
   {
     float t[3];
@@ -98,12 +105,28 @@ __device__ __forceinline__ void preprocess_backward_body(
     const float a = abc[0] + 0.3f, b = abc[1], c = abc[2] + 0.3f;
     const float denom = a * c - b * b;
     const float denom2inv = 1.0f / (denom * denom + 0.0000001f);
+    float aa_r = 0.0f;
+    if constexpr (AA) {   // the forward's h, bit for bit (same fp32 expressions, correctly rounded division and square root)
+      aa_r = (abc[0] * abc[2] - abc[1] * abc[1]) / denom;
+      aa_h = sqrtf(fmaxf(2.5e-5f, aa_r));
+    }
     const float gA = acc0.x, gB = acc0.y, gC = acc0.z;
     float dL_da = 0.0f, dL_db = 0.0f, dL_dc = 0.0f;
     if (denom2inv != 0.0f) {
       dL_da = denom2inv * (-c * c * gA + 2.0f * b * c * gB + (denom - a * c) * gC);
       dL_dc = denom2inv * (-a * a * gC + 2.0f * a * b * gB + (denom - a * c) * gA);
       dL_db = denom2inv * 2.0f * (b * c * gA - (denom + 2.0f * b * b) * gB + a * b * gC);
+      // AA: the h chain joins here, so that dc[] and dT below carry it.  Inside the guard: denom2inv == 0 means
+      // denom^2 overflowed, where k (1 / det1^2) is 0 as well
+      if constexpr (AA) {
+        if (aa_r > 2.5e-5f) {
+          const float x = abc[0], z = abc[1], y = abc[2], w = 0.3f;
+          const float k = acc0.w * aa_o / (2.0f * aa_h * denom * denom);
+          dL_da += k * w * (y * y + w * y + z * z);
+          dL_dc += k * w * (x * x + w * x + z * z);
+          dL_db += -2.0f * k * w * z * (x + y + w);
+        }
+      }
       dc[0] = T[0][0] * T[0][0] * dL_da + T[0][0] * T[1][0] * dL_db + T[1][0] * T[1][0] * dL_dc;
       dc[3] = T[0][1] * T[0][1] * dL_da + T[0][1] * T[1][1] * dL_db + T[1][1] * T[1][1] * dL_dc;
       dc[5] = T[0][2] * T[0][2] * dL_da + T[0][2] * T[1][2] * dL_db + T[1][2] * T[1][2] * dL_dc;
@@ -309,11 +332,12 @@ __device__ __forceinline__ void preprocess_backward_body(
     }
     reinterpret_cast<float4*>(dL_drots)[i] = dq;
   }
+  const float g_op = AA ? acc0.w * aa_h : acc0.w;   // AA: dL/do = dL/do_eff h
   if (raw) {  // sigmoid'(x) = s (1 - s) applied to the blend's dL/d(opacity)
     const float sg = act_sigmoid(opacities_raw[i]);
-    dL_dopacity[i] = acc0.w * (sg * (1.0f - sg));
+    dL_dopacity[i] = g_op * (sg * (1.0f - sg));
   } else {
-    dL_dopacity[i] = acc0.w;
+    dL_dopacity[i] = g_op;
   }
 }
 
@@ -404,6 +428,30 @@ __global__ __launch_bounds__(256) void preprocess_backward_staged_kernel(GGD_PPB
   static_assert(AUX, "the plain kernel is the one-parameter template");
 GGD_PPB_STAGED_BODY(SHVEC, false, true)
 }
+
+// anti-aliasing (ggd_params.antialiasing): the three forms with the h chain, depth term off / on (AA_ must be true; AUX last,
+// as in the depth / alpha overloads above)
+template <bool AA_, bool AUX>
+__global__ __launch_bounds__(256) void preprocess_backward_kernel(GGD_PPB_PARAMS) {
+  static_assert(AA_, "the plain kernels are the non-template one and the one-parameter template");
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  preprocess_backward_body<false, false, AUX, true>(i, nullptr, GGD_PPB_ARGS);
+}
+
+template <bool AA_, bool AUX>
+__global__ __launch_bounds__(256) void preprocess_backward_vec_kernel(GGD_PPB_PARAMS) {
+  static_assert(AA_, "the plain kernels are the non-template one and the one-parameter template");
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  preprocess_backward_body<true, true, AUX, true>(i, nullptr, GGD_PPB_ARGS);
+}
+
+template <bool SHVEC, bool AA_, bool AUX>
+__global__ __launch_bounds__(256) void preprocess_backward_staged_kernel(GGD_PPB_PARAMS) {
+  static_assert(AA_, "the plain kernels are the one- and two-parameter templates");
+GGD_PPB_STAGED_BODY(SHVEC, false, AUX, true)
+}
 #undef GGD_PPB_STAGED_BODY
 
 }  // namespace
@@ -427,6 +475,19 @@ int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params
                      prm.viewmatrix, prm.projmatrix, prm.campos, means3D, shs, colors_precomp, scales, rotations,           \
                      cov3D_precomp, radii, clamped, grad_acc, dL_dmean2D, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh,       \
                      dL_dscales, dL_drots)
+  if (prm.antialiasing) {   // the same choice of form, with the h chain (and the depth term when aux)
+    if (aux) {
+      if (shvec) GGD_PPB_LAUNCH((preprocess_backward_vec_kernel<true, true>), 0);
+      else if (staged) GGD_PPB_LAUNCH((preprocess_backward_staged_kernel<false, true, true>), (size_t)256 * (3 * prm.M + 1) * sizeof(float));
+      else GGD_PPB_LAUNCH((preprocess_backward_kernel<true, true>), 0);
+    } else {
+      if (shvec) GGD_PPB_LAUNCH((preprocess_backward_vec_kernel<true, false>), 0);
+      else if (staged) GGD_PPB_LAUNCH((preprocess_backward_staged_kernel<false, true, false>), (size_t)256 * (3 * prm.M + 1) * sizeof(float));
+      else GGD_PPB_LAUNCH((preprocess_backward_kernel<true, false>), 0);
+    }
+    GGD_HIP(hipGetLastError());
+    return GGD_OK;
+  }
   if (aux) {   // the depth / alpha extension: the same choice of form, with the depth term
     if (shvec) GGD_PPB_LAUNCH(preprocess_backward_vec_kernel<true>, 0);
     else if (staged) GGD_PPB_LAUNCH((preprocess_backward_staged_kernel<false, true>), (size_t)256 * (3 * prm.M + 1) * sizeof(float));

@@ -31,7 +31,7 @@ from torch import nn
 from . import _capi
 
 
-class GaussianRasterizationSettings(NamedTuple):
+class _SettingsFields(NamedTuple):
     image_height: int
     image_width: int
     tanfovx: float
@@ -48,6 +48,27 @@ class GaussianRasterizationSettings(NamedTuple):
     #                               decoder outputs; sigmoid / exp / normalize are fused into the kernels (fwd + bwd)
     render_depth_alpha: bool = False  # extension: the rasterizer also returns differentiable per-pixel depth
     #                                   (sum alpha_i T_i z_i, view-space z) and alpha (1 - final T) maps, [1, H, W] each
+
+
+class GaussianRasterizationSettings(_SettingsFields):
+    """The settings tuple: upstream's twelve fields, then raw_attributes and render_depth_alpha (extensions).
+
+    antialiasing (keyword only, default False): upstream's flag of the same name -- the opacity-compensated 2D filter,
+    each Gaussian's opacity times sqrt(det(cov2D) / det(cov2D + 0.3 I)).  It is an attribute, not a tuple field: upstream's
+    13th positional slot is our raw_attributes, and the fields and their positions stay what callers already rely on."""
+    antialiasing: bool = False   # (instances made without __new__, e.g. by _make, read this class default)
+
+    def __new__(cls, *args, antialiasing: bool = False, **kwargs):
+        self = super().__new__(cls, *args, **kwargs)
+        self.antialiasing = bool(antialiasing)
+        return self
+
+    def _replace(self, **kwargs):
+        aa = kwargs.pop("antialiasing", self.antialiasing)
+        return type(self)(*super()._replace(**kwargs), antialiasing=aa)
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", antialiasing={self.antialiasing})"
 
 
 def _f32c(t: torch.Tensor, name: str, device) -> torch.Tensor:
@@ -117,7 +138,7 @@ def _params(rs: GaussianRasterizationSettings, P: int, M: int, device, keep: lis
     return _capi.Params(P, M, int(rs.sh_degree), int(rs.image_width), int(rs.image_height), float(rs.tanfovx),
                         float(rs.tanfovy), float(rs.scale_modifier), int(bool(rs.prefiltered)),
                         int(bool(rs.debug)), view.data_ptr(), proj.data_ptr(), campos.data_ptr(), bg.data_ptr(),
-                        int(bool(getattr(rs, "raw_attributes", False))), 0)
+                        int(bool(getattr(rs, "raw_attributes", False))), int(bool(getattr(rs, "antialiasing", False))))
 
 
 def _require_cuda(t: torch.Tensor):
@@ -128,7 +149,7 @@ def _require_cuda(t: torch.Tensor):
 
 def _marshal_forward(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                      projmatrix, tanfovx, tanfovy, image_height, image_width, sh, degree, campos, prefiltered, debug,
-                     raw_attributes=False):
+                     raw_attributes=False, antialiasing=False):
     """Validation and marshalling of one forward call, shared by `rasterize_gaussians_native` and `FramePipeline.submit` (a
     mis-shaped input must become a ValueError on both paths, not an out-of-bounds device read).  Returns (dev, P, the seven
     contiguous fp32 input tensors or None, prm, keep): `keep` holds every tensor the C call reads, for as long as it may."""
@@ -156,7 +177,8 @@ def _marshal_forward(bg, means3D, colors_precomp, opacities, scales, rotations, 
             raise ValueError("sh must have dimensions (num_points, num_coeffs, 3)")
         M = sh_c.size(1)
     rs = GaussianRasterizationSettings(image_height, image_width, tanfovx, tanfovy, bg, scale_modifier,
-                                       viewmatrix, projmatrix, degree, campos, prefiltered, debug, raw_attributes)
+                                       viewmatrix, projmatrix, degree, campos, prefiltered, debug, raw_attributes,
+                                       antialiasing=bool(antialiasing))
     keep: list = [means3D, opacities, sh_c, col_c, sc_c, rot_c, cov_c]
     prm = _params(rs, P, M, dev, keep)
     return dev, P, (means3D, opacities, sh_c, col_c, sc_c, rot_c, cov_c), prm, keep
@@ -164,16 +186,18 @@ def _marshal_forward(bg, means3D, colors_precomp, opacities, scales, rotations, 
 
 def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier,
                                cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, image_height, image_width,
-                               sh, degree, campos, prefiltered, debug, raw_attributes=False, *, render_depth_alpha=False):
+                               sh, degree, campos, prefiltered, debug, raw_attributes=False, *, render_depth_alpha=False,
+                               antialiasing=False):
     """== upstream `_C.rasterize_gaussians(...)`: returns
     (num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer).  binningBuffer may be larger than
     num_rendered needs (single-call forward with a capacity hint); the sorted list sits at its offset 0 either way, so
     the backward takes num_rendered as R exactly like upstream.  render_depth_alpha=True (extension): the tuple goes on
     with the depth and alpha maps, float32 [1, H, W] each (ggd_forward_aux / ggd_forward_render_aux); everything else is
-    bit-identical to the plain call."""
+    bit-identical to the plain call.  antialiasing=True (extension): the opacity-compensated 2D filter (ggd_params.antialiasing);
+    radii and the three buffers' sort / binning contents are those of the plain call, the colour changes."""
     dev, P, (means3D, opacities, sh_c, col_c, sc_c, rot_c, cov_c), prm, keep = _marshal_forward(
         bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
-        tanfovx, tanfovy, image_height, image_width, sh, degree, campos, prefiltered, debug, raw_attributes)
+        tanfovx, tanfovy, image_height, image_width, sh, degree, campos, prefiltered, debug, raw_attributes, antialiasing)
     # (the GPU idles while this wrapper runs between two frames of a render loop: sizes are cached, the stream is looked
     # up once, and the device guard is only entered when another device is current)
     ctx, stream_handle = _capi.context_and_stream(dev)
@@ -268,7 +292,7 @@ class FramePipeline:
                     ctx.capacity_retries += 1
                     ctx.capacity_hint[pend["key"]] = max(int(R.value), ctx.capacity_hint.get(pend["key"]) or 0)
                     self.synchronous_frames += 1
-                    res = rasterize_gaussians_native(*pend["args"])
+                    res = rasterize_gaussians_native(*pend["args"], antialiasing=pend["antialiasing"])
                 else:
                     ctx.check(rc)
                     hint = ctx.capacity_hint.get(pend["key"]) or 0
@@ -280,14 +304,15 @@ class FramePipeline:
 
     def submit(self, bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                projmatrix, tanfovx, tanfovy, image_height, image_width, sh, degree, campos, prefiltered, debug,
-               raw_attributes=False):
+               raw_attributes=False, *, antialiasing=False):
         args = (bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
                 tanfovx, tanfovy, image_height, image_width, sh, degree, campos, prefiltered, debug, raw_attributes)
+        aa = bool(antialiasing)
         slot = self.slots[self._next]
         self._next = (self._next + 1) % len(self.slots)
         prev = self._collect(slot)
         # (validation and marshalling on the CALLER's stream: a conversion to contiguous fp32 is the caller's work)
-        dev, P, (means3D_c, opac_c, sh_c, col_c, sc_c, rot_c, cov_c), prm, keep = _marshal_forward(*args)
+        dev, P, (means3D_c, opac_c, sh_c, col_c, sc_c, rot_c, cov_c), prm, keep = _marshal_forward(*args, antialiasing=aa)
         slot["stream"].wait_stream(torch.cuda.current_stream(dev))
         for t in keep:                            # allocated on the caller's stream, read on the slot's: the caching allocator
             if t is not None:                     # must not hand the block out again before the slot's work at the time of the
@@ -299,13 +324,13 @@ class FramePipeline:
             hint = ctx.capacity_hint.get(key)
             if hint is None or P == 0 or debug:
                 self.synchronous_frames += 1
-                slot["pending"] = dict(result=rasterize_gaussians_native(*args), keep=keep)
+                slot["pending"] = dict(result=rasterize_gaussians_native(*args, antialiasing=aa), keep=keep)
                 return prev
             cap = _capacity(hint)
             lib = ctx.lib
             if not lib.ggd_forward_can_speculate(ctx.handle, C.byref(prm), cap):
                 self.synchronous_frames += 1
-                slot["pending"] = dict(result=rasterize_gaussians_native(*args), keep=keep)
+                slot["pending"] = dict(result=rasterize_gaussians_native(*args, antialiasing=aa), keep=keep)
                 return prev
             u8 = dict(dtype=torch.uint8, device=dev)
             color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
@@ -317,7 +342,8 @@ class FramePipeline:
                 ctx.check(lib.ggd_forward_enqueue(ctx.handle, C.c_void_p(handle), C.byref(prm), _ptr(means3D_c), _ptr(sh_c),
                                                   _ptr(col_c), _ptr(opac_c), _ptr(sc_c), _ptr(rot_c), _ptr(cov_c), _ptr(geom),
                                                   _ptr(radii), _ptr(binning), cap, _ptr(img), _ptr(color)))
-            slot["pending"] = dict(outputs=(color, radii, geom, binning, img), key=key, args=args, keep=keep, prm=prm)
+            slot["pending"] = dict(outputs=(color, radii, geom, binning, img), key=key, args=args, antialiasing=aa, keep=keep,
+                                   prm=prm)
         return prev
 
     def drain(self):
@@ -333,11 +359,15 @@ class FramePipeline:
 def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scales, rotations, scale_modifier,
                                         cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, dL_dout_color, sh,
                                         degree, campos, geomBuffer, R, binningBuffer, imgBuffer, debug,
-                                        raw_attributes=False, opacities=None, *, dL_ddepth=None, dL_dalpha=None):
+                                        raw_attributes=False, opacities=None, *, dL_ddepth=None, dL_dalpha=None,
+                                        antialiasing=False):
     """== upstream `_C.rasterize_gaussians_backward(...)`: returns
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
     dL_ddepth / dL_dalpha (extension, [1, H, W] or [H, W]; None = zero): gradients of the depth and alpha maps of a
-    render_depth_alpha forward -- with either given the call is ggd_backward_aux, else today's ggd_backward."""
+    render_depth_alpha forward -- with either given the call is ggd_backward_aux, else today's ggd_backward.
+    antialiasing=True: the backward of an antialiasing forward; it needs `opacities` (the forward's, as passed to it)."""
+    if antialiasing and opacities is None:
+        raise ValueError("the antialiasing backward needs the opacities of the forward (opacities=None)")
     H, W = int(dL_dout_color.size(-2)), int(dL_dout_color.size(-1))
     aux = dL_ddepth is not None or dL_dalpha is not None
     for t, name in ((dL_ddepth, "dL_ddepth"), (dL_dalpha, "dL_dalpha")):
@@ -359,8 +389,10 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
     gA = _f32c(dL_dalpha, "dL_dalpha", dev) if dL_dalpha is not None else None
     M = sh_c.size(1) if sh_c is not None else 0
     rs = GaussianRasterizationSettings(H, W, tanfovx, tanfovy, bg, scale_modifier, viewmatrix, projmatrix, degree,
-                                       campos, False, debug, raw_attributes)
-    op_c = _f32c(opacities, "opacities", dev) if (raw_attributes and opacities is not None) else None
+                                       campos, False, debug, raw_attributes, antialiasing=bool(antialiasing))
+    op_c = _f32c(opacities, "opacities", dev) if ((raw_attributes or antialiasing) and opacities is not None) else None
+    if antialiasing and op_c.numel() != P:
+        raise ValueError("opacities must hold one value per point")
     keep: list = []
     prm = _params(rs, P, M, dev, keep)
     ctx = _capi.context_for(dev)
@@ -418,7 +450,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         out = rasterize_gaussians_native(
             rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree,
-            rs.campos, rs.prefiltered, rs.debug, getattr(rs, "raw_attributes", False), render_depth_alpha=depth_alpha)
+            rs.campos, rs.prefiltered, rs.debug, getattr(rs, "raw_attributes", False), render_depth_alpha=depth_alpha,
+            **({"antialiasing": True} if getattr(rs, "antialiasing", False) else {}))
         num_rendered, color, radii, geom, binning, img = out[:6]
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
@@ -437,17 +470,20 @@ class _RasterizeGaussians(torch.autograd.Function):
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img, opacities = \
             ctx.saved_tensors
         raw = getattr(rs, "raw_attributes", False)
+        aa = bool(getattr(rs, "antialiasing", False))   # (its backward reads the opacities, raw or not)
         if grad_out_color is None:   # (render_depth_alpha: gradients are not materialised)
             grad_out_color = torch.zeros((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32,
                                          device=means3D.device)
         aux = {}
         if grad_depth is not None or grad_alpha is not None:
             aux = dict(dL_ddepth=grad_depth, dL_dalpha=grad_alpha)
+        if aa:   # (only when set: a plain render calls the backward exactly as before)
+            aux["antialiasing"] = True
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations) = rasterize_gaussians_backward_native(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, geom,
-            ctx.num_rendered, binning, img, rs.debug, raw, opacities if raw else None, **aux)
+            ctx.num_rendered, binning, img, rs.debug, raw, opacities if (raw or aa) else None, **aux)
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
                 grad_rotations, grad_cov3Ds_precomp, None)
 

@@ -81,7 +81,7 @@ class DecoderTrainer:
                  loss_fn=None, process_group=None, fused_activations: bool = False, fused_decoder: bool = False,
                  backbone_params: int = 0, perceptual_weight: float = 0.0, perceptual_width_div: int = 1,
                  scene_streams: bool = False, decoder_precision: str = "bf16", plane_axes: str = "eg3d",
-                 triplane_depth=None, fused_planes=None, force_comm=None):
+                 triplane_depth=None, fused_planes=None, force_comm=None, antialiasing: bool = False):
         """plane_axes / triplane_depth: the generator whose planes are decoded -- ("eg3d", None): tri-planes
         [3, C, res, res]; ("panohead", 3): PanoHead's tri-grids [3, C * 3, res, res] sampled with a 3-D grid_sample
         (the reference's default generator: main/train_pano2gaussian_decoder.py:43, PanoHead/train.py:230,318,
@@ -91,7 +91,9 @@ class DecoderTrainer:
         counts the gather kernels do not take (not a power of two <= 64) keep the materialised-planes path.
         force_comm (default: the environment variable GGD_FORCE_COMM): take the collective path -- hooks, async all-reduce
         units, waits -- whenever a process group exists, even with ONE rank (exercises the RCCL communicator, work handles
-        and their stream semantics on a single GPU; the sum over one rank is the identity)."""
+        and their stream semantics on a single GPU; the sum over one rank is the identity).
+        antialiasing: render with the rasterizer's opacity-compensated 2D filter (render_simple's antialiasing=True; it is
+        passed to render_fn only when set)."""
         import os
         import torch.distributed as dist
         self.force_comm = bool(int(os.environ.get("GGD_FORCE_COMM", "0"))) if force_comm is None else bool(force_comm)
@@ -149,6 +151,8 @@ class DecoderTrainer:
         self.render_fn = render_fn
         # fused_activations: sigmoid / exp / normalize inside the raster kernels (HIP render_simple only)
         self.render_kwargs = {"fused_activations": True} if fused_activations else {}
+        if antialiasing:
+            self.render_kwargs["antialiasing"] = True
         self.bg = torch.tensor([0.55717, 0.52256, 0.51045], dtype=torch.float32, device=self.device)
         # scene_streams: every local scene's raster + loss on its own HIP stream (own ggd_ctx).  Measured on one MI355X
         # (4 scenes x 500 k points, fused decoder): 21.13 ms / step with and without -- the single-call forward already

@@ -66,7 +66,10 @@ typedef struct ggd_params {
   int32_t raw_attributes;   /* 1: `scales`, `rotations`, `opacities` are the RAW decoder outputs and the activation
                                prologue of gaussian_model.py:100-121 (exp / L2-normalise (eps 1e-12) / sigmoid) is fused
                                into the per-Gaussian kernels, forward and backward; 0: as upstream */
-  int32_t reserved_;
+  int32_t antialiasing;     /* 1: opacity-compensated 2D filter (Mip-Splatting): each Gaussian's opacity is scaled by
+                               h = sqrt(max(2.5e-5, det(cov2D) / det(cov2D + 0.3 I))) before blending, forward and
+                               backward; the conic, radii and every sort / binning output are unchanged.  The backward
+                               then reads `opacities` (NULL -> GGD_E_INVALID).  0: as upstream */
 } ggd_params;
 
 /* One record per Gaussian, written by the preprocess kernel and gathered by the blend kernels: exactly what a blended
@@ -192,7 +195,7 @@ int ggd_forward_can_speculate(ggd_ctx* ctx, const ggd_params* prm, int64_t capac
  */
 int ggd_backward(ggd_ctx* ctx, void* stream, const ggd_params* prm,
                  const float* means3D, const float* shs, const float* colors_precomp,
-                 const float* opacities /* only read when prm->raw_attributes */,
+                 const float* opacities /* only read when prm->raw_attributes or prm->antialiasing */,
                  const float* scales, const float* rotations, const float* cov3D_precomp,
                  const int32_t* radii,
                  const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t num_rendered,
@@ -225,7 +228,7 @@ int ggd_forward_render_aux(ggd_ctx* ctx, void* stream, const ggd_params* prm,
                            void* binning_buf, void* img_buf, float* out_color, float* out_depth, float* out_alpha);
 int ggd_backward_aux(ggd_ctx* ctx, void* stream, const ggd_params* prm,
                      const float* means3D, const float* shs, const float* colors_precomp,
-                     const float* opacities /* only read when prm->raw_attributes */,
+                     const float* opacities /* only read when prm->raw_attributes or prm->antialiasing */,
                      const float* scales, const float* rotations, const float* cov3D_precomp,
                      const int32_t* radii,
                      const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t num_rendered,
