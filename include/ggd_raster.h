@@ -430,6 +430,33 @@ size_t ggd_image_loss_tmp_bytes(int32_t W, int32_t H);
 int ggd_image_loss(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, const float* image, const float* target,
                    const float* weights4, float* terms5, float* grad_image, void* tmp, size_t tmp_bytes);
 
+/*
+ * Exact 3-nearest-neighbour search: the `distCUDA2` of the simple_knn module that gaussian_splatting/scene/gaussian_model.py
+ * imports (:20) to seed the scales of a new model (:132, :160).  points: DEVICE float32 [P][3], 4 <= P <= ggd_knn_max_points()
+ * (2^26; fewer than 4 points have no three neighbours: GGD_E_INVALID).  For every point i, over all j != i (a different INDEX:
+ * coincident points count, distance 0), d = (dx*dx + dy*dy) + dz*dz in fp32 without contraction, the three smallest kept
+ * ascending b0 <= b1 <= b2:
+ *   mean_dist2[i] = ((b0 + b1) + b2) / 3.0f     dist2[i] = {b0, b1, b2}     idx[i] = rows of the three points
+ * (each output may be NULL; all are indexed by the ORIGINAL row order; among equal distances any candidate may be named).
+ * The values are exact: bit-identical to a brute force that evaluates the same expression, from run to run and under any
+ * permutation of the rows.  Rows with non-finite coordinates get unspecified values; the call still terminates.
+ * examined: NULL, or a DEVICE counter the call ADDS the number of evaluated candidate points to (summed over all queries;
+ * a separately compiled kernel instance, the plain call pays nothing) -- a work measure: a small multiple of
+ * P * ggd_knn_leaf_size() on well-spread input, and just under P * ggd_knn_leaf_size() for P copies of one point.
+ * tmp: ggd_knn_tmp_bytes(P) bytes of device scratch, 16-byte aligned (about 22 bytes per point).  No allocation, no host
+ * synchronisation, no float atomics inside the call.
+ * ggd_knn3_stage (timing aid, scripts/knn_timing.py): runs ONE stage (0 box, 1 Morton codes, 2 sort, 3 leaves, 4 search) on
+ * a tmp that holds the results of the earlier stages of a previous call on the same points.
+ */
+size_t ggd_knn_tmp_bytes(int32_t P);
+int32_t ggd_knn_leaf_size(void);
+int32_t ggd_knn_max_points(void);
+int ggd_knn3(ggd_ctx* ctx, void* stream, const float* points, int32_t P, float* mean_dist2 /* [P] or NULL */,
+             float* dist2 /* [P,3] ascending, or NULL */, int32_t* idx /* [P,3] or NULL */,
+             unsigned long long* examined /* device counter or NULL */, void* tmp, size_t tmp_bytes);
+int ggd_knn3_stage(ggd_ctx* ctx, void* stream, const float* points, int32_t P, float* mean_dist2, float* dist2, int32_t* idx,
+                   unsigned long long* examined, void* tmp, size_t tmp_bytes, int32_t stage);
+
 /* ggd_decoder_backward + ggd_decoder_wgrad over point chunks of `chunk` points (<= 0: one chunk), each chunk's weight-
  * gradient kernel launched right behind its backward kernel so that it reads dz / z from the Infinity Cache. */
 int ggd_decoder_backward_wgrad(ggd_ctx* ctx, void* stream, int32_t N, int32_t chunk, const void* packed_t,

@@ -3,8 +3,9 @@
     pip install submodules/diff-gaussian-rasterization          (/root/reference/environment.yml:35)
 
 Pointing that line at this repository instead (`pip install --no-build-isolation /path/to/this/repo`, or `-e` for a
-development install) installs `gaussian_gan_decoder_amd` AND the top-level shim package `diff_gaussian_rasterization`,
-so the reference's import line (gaussian_splatting/gaussian_renderer/__init__.py:14) resolves to the gfx950 library.
+development install) installs `gaussian_gan_decoder_amd` AND the top-level shim packages `diff_gaussian_rasterization` and `simple_knn`,
+so the reference's import lines (gaussian_splatting/gaussian_renderer/__init__.py:14, scene/gaussian_model.py:20) resolve
+to the gfx950 library.
 The build step compiles the HIP kernels in-tree with hipcc (gaussian_gan_decoder_amd/build.py; hipcc cross-compiles
 gfx950 without a GPU) before the package files are collected; GGD_SKIP_NATIVE_BUILD=1 skips it (the library is then
 built on first use by `python -m gaussian_gan_decoder_amd.build`)."""
@@ -47,7 +48,7 @@ setup(
     version="0.3.0",
     description="MI355X-native (gfx950) Gaussian-splatting decode/render path: drop-in for diff_gaussian_rasterization",
     python_requires=">=3.9",
-    packages=["gaussian_gan_decoder_amd", "diff_gaussian_rasterization"],
+    packages=["gaussian_gan_decoder_amd", "diff_gaussian_rasterization", "simple_knn"],
     package_data={"gaussian_gan_decoder_amd": ["libggd_raster.so", "csrc/*"]},
     cmdclass={"build_py": BuildPyWithHip, "develop": DevelopWithHip},
 )
