@@ -220,9 +220,9 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
                                                     float* __restrict__ final_T,
                                                     uint32_t* __restrict__ n_contrib,
                                                     unsigned long long* __restrict__ stats,
-                                                    const uint32_t* __restrict__ depth_keys = nullptr,
-                                                    float* __restrict__ out_depth = nullptr,
-                                                    float* __restrict__ out_alpha = nullptr) {
+                                                    const uint32_t* __restrict__ depth_keys,
+                                                    float* __restrict__ out_depth,
+                                                    float* __restrict__ out_alpha) {
 #ifndef GGD_FWD_GRP
 #define GGD_FWD_GRP 8
 #endif
@@ -484,22 +484,9 @@ all_done:
 // 104 us for this one-shot launch at 1 M / 1024^2 (shell 260 vs 194, 100 k / 512^2 79 vs 25): the same waves take the same
 // time per tile, but 3.8 instead of 5.4 of them are at work per SIMD -- a ticket is a returning atomic's round trip through
 // memory, the hardware dispatcher back-fills a finished wave's slot without one.  Removed again.
-template <int EXP_MODE, bool CULL, int PXL, int BW, bool STATS>
-__global__ __launch_bounds__(64) void blend_forward_kernel(int W, int H, int gx, int T,
-                                                           const ggd_splat* __restrict__ splat,
-                                                           const uint32_t* __restrict__ list,
-                                                           const uint32_t* __restrict__ ranges, uint32_t capacity,
-                                                           const float* __restrict__ bg,
-                                                           float* __restrict__ out_color,
-                                                           float* __restrict__ final_T,
-                                                           uint32_t* __restrict__ n_contrib,
-                                                           unsigned long long* __restrict__ stats) {
-  __shared__ float4 s_rec[64 * 3];
-  blend_forward_block<EXP_MODE, CULL, PXL, BW, STATS>((int)blockIdx.x, s_rec, W, H, gx, T, splat, list, ranges, capacity, bg,
-                                                      out_color, final_T, n_contrib, stats);
-}
-// The same blend with the depth / alpha planes (AUX must be true: an overload, so that the plain instances keep their names)
-template <int EXP_MODE, bool CULL, int PXL, int BW, bool STATS, bool AUX>
+// AUX: the same blend with the depth / alpha planes (blend_forward_block); depth_keys, out_depth and out_alpha are NULL, and
+// never read, in a plain frame.
+template <int EXP_MODE, bool CULL, int PXL, int BW, bool STATS, bool AUX = false>
 __global__ __launch_bounds__(64) void blend_forward_kernel(int W, int H, int gx, int T,
                                                            const ggd_splat* __restrict__ splat,
                                                            const uint32_t* __restrict__ list,
@@ -512,11 +499,10 @@ __global__ __launch_bounds__(64) void blend_forward_kernel(int W, int H, int gx,
                                                            const uint32_t* __restrict__ depth_keys,
                                                            float* __restrict__ out_depth,
                                                            float* __restrict__ out_alpha) {
-  static_assert(AUX, "the plain blend is the five-parameter template");
   __shared__ float4 s_rec[64 * 3];
-  blend_forward_block<EXP_MODE, CULL, PXL, BW, STATS, true>((int)blockIdx.x, s_rec, W, H, gx, T, splat, list, ranges, capacity,
-                                                            bg, out_color, final_T, n_contrib, stats, depth_keys, out_depth,
-                                                            out_alpha);
+  blend_forward_block<EXP_MODE, CULL, PXL, BW, STATS, AUX>((int)blockIdx.x, s_rec, W, H, gx, T, splat, list, ranges, capacity,
+                                                           bg, out_color, final_T, n_contrib, stats, depth_keys, out_depth,
+                                                           out_alpha);
 }
 
 // Backward blend: the per-record update of ONE pixel, shared by the two kernel forms below.  Records are visited back to
@@ -893,38 +879,216 @@ __global__ __launch_bounds__(256) void blend_backward_tile_kernel(
 // STATS (ggd_blend_stats, debug): per-wave work counters added to stats[GGD_STATS_BWD ..] at the wave's end -- list entries the
 // wave walks (its share of the tile's list up to its last contributor), records staged after the pre-cull, staged records some
 // pixel still needed (`need`), records at least one pixel actually blended (`live`: a 9-sum reduction + a parked row each),
-// the live lanes of those, rows flushed (= 36-byte atomic spans), gather rounds.  The body is ggd_blend_bwd_quarter.inc, shared with
-// the depth / alpha overload below.
-template <int EXP_MODE, bool CULL, bool STATS = false>
-__global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
-    int W, int H, int gx, int gy, const ggd_splat* __restrict__ splat, const uint32_t* __restrict__ list,
-    const uint32_t* __restrict__ ranges, const float* __restrict__ bg, const float* __restrict__ final_T,
-    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ grad_acc,
-    unsigned long long* __restrict__ stats = nullptr) {
-  constexpr bool AUX = false;
-  const uint32_t* const depth_keys = nullptr;
-  const float* const dL_ddepth = nullptr;
-  const float* const dL_dalpha = nullptr;
-  float* const s_z = nullptr;
-#include "ggd_blend_bwd_quarter.inc"
-}
-
-// The same with the depth / alpha gradients (AUX must be true: an overload, so that the plain instances keep their names).
+// the live lanes of those, rows flushed (= 36-byte atomic spans), gather rounds.
 // AUX (ggd_backward_aux): the Gaussians' depths are staged in s_z next to their records; the depth is a fourth colour channel
 // (background 0) whose per-record sum alpha T dL/ddepth is the TENTH reduced value and goes to slot 9 of the accumulator
 // record (a pad word: layout and memset unchanged); dL/dalpha of a pixel only enters through its final transmittance, i.e. as
-// -dL/dalpha folded into bgdot once.  Rows of 10 sums + slot and the staged depths: 6144 B of LDS per wave.
-template <int EXP_MODE, bool CULL, bool STATS, bool AUX_>
+// -dL/dalpha folded into bgdot once.  Rows of 10 sums + slot and the staged depths: 6144 B of LDS per wave.  depth_keys,
+// dL_ddepth and dL_dalpha are NULL, and never read, in a plain backward.
+template <int EXP_MODE, bool CULL, bool STATS = false, bool AUX = false>
 __global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
     int W, int H, int gx, int gy, const ggd_splat* __restrict__ splat, const uint32_t* __restrict__ list,
     const uint32_t* __restrict__ ranges, const float* __restrict__ bg, const float* __restrict__ final_T,
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ grad_acc,
     unsigned long long* __restrict__ stats, const uint32_t* __restrict__ depth_keys, const float* __restrict__ dL_ddepth,
     const float* __restrict__ dL_dalpha) {
-  static_assert(AUX_, "the plain backward is the three-parameter template");
-  constexpr bool AUX = true;
-  __shared__ float s_z[64];
-#include "ggd_blend_bwd_quarter.inc"
+  constexpr int NS = AUX ? 10 : 9, ROW = NS + 1;   // reduced sums per record; parked row = sums | staging slot
+  uint32_t st_staged = 0, st_need = 0, st_live = 0, st_lanes = 0, st_spans = 0, st_rounds = 0;
+  __shared__ float4 s_rec[64 * 3];
+  // [touched record, in processing order][NS sums | staging slot] (5632 B of LDS per wave with s_rec; AUX: 6144 with s_z); ONE
+  // buffer: a round's rows are flushed at the top of the next round, before that round's first row is written (LDS operations
+  // of a wave execute in order)
+  __shared__ float s_sum[64][ROW];
+  __shared__ float s_z[AUX ? 64 : 1];   // AUX: the staged records' depths (unused, and not allocated, otherwise)
+  const int lane = threadIdx.x;
+  int tile, sub;
+  ggd_block_to_tile((int)blockIdx.x, 4, gx, gy, gx * gy, tile, sub);
+  const int tx = tile % gx, ty = tile / gx;
+  const int qx = sub & 1, qy = sub >> 1;
+  const int px0 = tx * 16 + qx * 8 + (lane & 7), py = ty * 16 + qy * 8 + (lane >> 3);
+  const uint2 rg = reinterpret_cast<const uint2*>(ranges)[tile];
+  const bool in = py < H && px0 < W;
+  const size_t HW = (size_t)H * W;
+  const size_t pix0 = (size_t)py * W + px0;
+
+  std::conditional_t<AUX, BwdPixelAux, BwdPixel> st;
+  const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
+  const float pxf = (float)px0, pyf = (float)py;
+  const float tf = in ? final_T[pix0] : 0.0f;
+  const uint32_t lastn = in ? n_contrib[pix0] : 0u;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) { st.gpx[ch] = in ? dL_dpix[ch * HW + pix0] : 0.0f; st.acc[ch] = 0.0f; }
+  st.bgdot = (bg0 * st.gpx[0] + bg1 * st.gpx[1]) + bg2 * st.gpx[2];
+  if constexpr (AUX) bwd_aux_init<AUX>(st, (in && dL_ddepth) ? dL_ddepth[pix0] : 0.0f, (in && dL_dalpha) ? dL_dalpha[pix0] : 0.0f);
+  st.T = tf; st.nTfin = -tf;
+  uint32_t maxn = lastn;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, d, 64));
+  maxn = (uint32_t)__builtin_amdgcn_readfirstlane((int)maxn);
+  if (maxn == 0) return;
+  const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
+  const float wx0 = (float)(tx * 16 + qx * 8), wy0 = (float)(ty * 16 + qy * 8);   // this wave's pixel rectangle
+  const float wx1 = wx0 + 7.0f, wy1 = wy0 + 7.0f;
+  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  // lanes that hold a result of wave_reduce9_swap, and where it goes in the row (accumulator-record order: conic A B C |
+  // opacity | mean sums x y | colour r g b); lane 2 adds the record's staging slot to the same LDS store.  AUX: lane 33
+  // holds the tenth sum (wave_reduce10_swap), the depth, for slot 9
+  const bool is_writer = (lane & 19) == 0 || lane == 1 || (AUX && lane == 33);
+  const int writer_val = lane == 1 ? 8 : ((AUX && lane == 33) ? 9 : 4 * (lane >> 5) + (((lane >> 2) & 1) << 1) + ((lane >> 3) & 1));
+  const int writer_comp = writer_val < 3 ? GGD_ACC_COLOR + writer_val
+                        : (writer_val < 6 ? GGD_ACC_CONIC + (writer_val - 3)
+                        : (writer_val < 8 ? GGD_ACC_MEAN2D + (writer_val - 6)
+                        : ((AUX && writer_val == 9) ? GGD_ACC_DEPTH : GGD_ACC_OPACITY)));
+  const bool stores = is_writer || lane == 2;
+  const int store_col = is_writer ? writer_comp : NS;
+
+  // staged = the record as loaded with three words replaced in place:
+  //   {x, y, hA, nB} {hC, power threshold, opacity, 0-based list position} {g, b, r, Gaussian id}
+  bool keep = false;
+  uint32_t id_cur = 0, id_nxt = 0;
+  float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0;    // x y hA nB | hC thr opacity r | g b ex ey
+  uint32_t zk = 0;                                          // AUX: depth key of the record in r0..r2
+  const uint32_t last_pos = rg.x + maxn - 1u;
+  auto round_start = [&](uint32_t ce) { return (ce - rg.x > 64u) ? ce - 64u : rg.x; };   // ce > rg.x
+  auto load_id = [&](uint32_t ce) {
+    const uint32_t cs = ce > rg.x ? round_start(ce) : rg.x;
+    id_nxt = list[min(cs + (uint32_t)lane, last_pos)];
+  };
+  auto load_rec = [&]() {
+    id_cur = id_nxt;
+    const float4* p = reinterpret_cast<const float4*>(splat + id_nxt);
+    r0 = p[0]; r1 = p[1]; r2 = p[2];
+    if constexpr (AUX) zk = depth_keys[id_nxt];
+  };
+  // the pre-cull rectangle of a round = the bounding rectangle of the pixels that can see ANY record of the round (those
+  // whose last contributor lies at or behind the round's first position): walking back to front a wave starts at its
+  // deepest pixel, and until the others join, most records only reach pixels that are not live yet
+  float lx0 = wx0, lx1 = wx1, ly0 = wy0, ly1 = wy1;
+  auto shrink_rect = [&](uint32_t first_pos) {   // 0-based list position of the round's first record
+    const uint64_t live = __ballot(lastn > first_pos);
+    if (live != 0ull) {
+      const int rmin = __builtin_ctzll(live) >> 3, rmax = (63 - __builtin_clzll(live)) >> 3;
+      uint32_t m = (uint32_t)live | (uint32_t)(live >> 32);
+      m |= m >> 16; m |= m >> 8; m &= 0xffu;
+      const int cmin = __builtin_ctz(m), cmax = 31 - __builtin_clz(m);
+      lx0 = wx0 + (float)cmin; lx1 = wx0 + (float)cmax;
+      ly0 = wy0 + (float)rmin; ly1 = wy0 + (float)rmax;
+    }
+  };
+  auto consume = [&](uint32_t ce) {
+    keep = false;
+    const uint32_t cs = round_start(ce);
+    if (CULL) shrink_rect(cs - rg.x);
+    if ((uint32_t)lane < ce - cs) {
+      keep = CULL ? (record_box_hits(r0.x, r0.y, r2.z, r2.w, lx0, lx1, ly0, ly1) &&
+                     record_reaches_block(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r2.z, lx0, lx1, ly0, ly1)) : true;
+      if (!CULL) r1.y = -__builtin_huge_valf();
+      r2.z = r1.w;
+      r1.w = __uint_as_float((cs - rg.x) + (uint32_t)lane);
+      r2.w = __uint_as_float(id_cur);
+    }
+  };
+  // the flush of one round's parked sums (cnt rows), reading the round's records where they were staged
+  auto flush = [&](int cnt) {
+    const float* rows = &s_sum[0][0];
+    for (int p = lane; p < cnt * NS; p += 64) {
+      const int r = p / NS, comp = p - NS * r;
+      const float v = rows[r * ROW + comp];
+      const float swx = rows[r * ROW + GGD_ACC_MEAN2D], swy = rows[r * ROW + GGD_ACC_MEAN2D + 1];
+      const int slot = (int)__float_as_uint(rows[r * ROW + NS]);
+      const float4 a = s_rec[slot * 3 + 0], b = s_rec[slot * 3 + 1];
+      const uint32_t id = __float_as_uint(s_rec[slot * 3 + 2].w);
+      atomicAdd(grad_acc + GGD_ACC_FLOATS * (size_t)id + comp,
+                bwd_scale(comp, v, swx, swy, a.z, a.w, b.x, b.z, ddelx_dx, ddely_dy));
+    }
+  };
+
+  uint32_t cend = rg.x + maxn;  // one past the last position this quarter needs
+  load_id(cend);
+  load_rec();
+  load_id(round_start(cend));
+  int prev_cnt = 0;
+  while (cend > rg.x) {
+    const uint32_t cstart = round_start(cend);
+    consume(cend);                                       // the records requested one round ago
+    __builtin_amdgcn_wave_barrier();                     // (the previous round's LDS reads are done: in-order per wave)
+    flush(prev_cnt);                                     // the previous round's sums: BEFORE its records are overwritten and
+    __builtin_amdgcn_wave_barrier();                     // before the new loads are issued
+    const uint64_t kept = __ballot(keep);
+    const int nk = __popcll(kept), n8 = (nk + 7) & ~7;
+    if (STATS) { st_staged += (uint32_t)nk; st_rounds += 1; st_spans += (uint32_t)prev_cnt; }
+    if (keep) {  // compacted, order preserved
+      const int slot = __popcll(kept & lt_mask);
+      s_rec[slot * 3 + 0] = r0; s_rec[slot * 3 + 1] = r1; s_rec[slot * 3 + 2] = r2;
+      if constexpr (AUX) s_z[slot] = __uint_as_float(zk);   // view-space depth (the key is its fp32 bits)
+    }
+    if (lane >= nk && lane < n8) {   // padding: a record nobody sees
+      s_rec[lane * 3 + 0] = make_float4(0, 0, 0, 0);
+      s_rec[lane * 3 + 1] = make_float4(0, __builtin_huge_valf(), 0, 0);
+    }
+    load_rec();                                          // next round's records
+    load_id(cstart > rg.x ? round_start(cstart) : rg.x); // and the list entries of the round after it
+    __builtin_amdgcn_wave_barrier();
+    int cnt = 0;
+    float* rows = &s_sum[0][0];
+    for (int j0 = n8 - 8; j0 >= 0; j0 -= 8) {
+      uint32_t ga = (uint32_t)(uintptr_t)(lds_cf4*)(s_rec + j0 * 3);   // see blend_forward_kernel
+      asm volatile("" : "+v"(ga));
+      lds_cf4* grp = (lds_cf4*)(uintptr_t)ga;
+      // (all twelve words one record ahead, inside the group: see the forward)
+      float4 a_nx = lds_read4(grp + 7 * 3), b_nx = lds_read4(grp + 7 * 3 + 1), c_nx = lds_read4(grp + 7 * 3 + 2);
+      const float* zgrp = AUX ? s_z + j0 : nullptr;
+      float z_nx = 0.0f;
+      if constexpr (AUX) z_nx = zgrp[7];
+#pragma unroll
+      for (int jj = 7; jj >= 0; --jj) {
+        const float4 a = a_nx, b = b_nx, c4 = c_nx;
+        const float z = z_nx;
+        asm volatile("" : : "v"(c4.w));   // (keeps the unused twelfth word's VGPR from being handed out while the load is in flight)
+        if (jj > 0) {
+          a_nx = lds_read4(grp + (jj - 1) * 3); b_nx = lds_read4(grp + (jj - 1) * 3 + 1); c_nx = lds_read4(grp + (jj - 1) * 3 + 2);
+          if constexpr (AUX) z_nx = zgrp[jj - 1];
+        }
+        const float dy = a.y - pyf;
+        const float nBdy = a.w * dy, hCdy2 = (b.x * dy) * dy;
+        const uint32_t pos0 = __float_as_uint(b.w);
+        const float dx = a.x - pxf;
+        const float pw = __builtin_fmaf(__builtin_fmaf(a.z, dx, nBdy), dx, hCdy2);
+        const uint64_t need = __ballot(pos0 < lastn) & __ballot(pw >= b.y);
+        if (need == 0ull) continue;
+        if (STATS) st_need += 1;
+        const float col[3] = {c4.z, c4.x, c4.y};                     // r | g, b
+        float s[8], sop, sz = 0.0f;                                  // colour r g b | conic A B C | mean sums x y ; opacity ; depth
+        const uint64_t live = bwd_update<EXP_MODE, AUX>(st, pw, dx, dy, need, b.z, col, s, sop, z, &sz);
+        if (live != 0ull) {   // wave-uniform: somebody in this wave saw the Gaussian
+          if (STATS) { st_live += 1; st_lanes += (uint32_t)__popcll(live); }
+          float tot;
+          if constexpr (AUX) tot = wave_reduce10_swap(s, sop, sz, 0x2222222222222222ull);
+          else tot = wave_reduce9_swap(s, sop, 0x2222222222222222ull);
+          // writers: lanes 0,4,8,12 | 32,36,40,44 (component from the table above), lane 1 the opacity sum (AUX: lane 33 the
+          // depth sum); lane 2 the record's slot in the staging area
+          const float v = is_writer ? tot : __uint_as_float((uint32_t)(j0 + jj));
+          if (stores) rows[cnt * ROW + store_col] = v;
+          ++cnt;
+        }
+      }
+    }
+    prev_cnt = cnt;
+    cend = cstart;
+  }
+  __builtin_amdgcn_wave_barrier();
+  flush(prev_cnt);
+  if (STATS && lane == 0 && stats) {
+    unsigned long long* o = stats + GGD_STATS_BWD;
+    atomicAdd(o + 0, (unsigned long long)maxn);
+    atomicAdd(o + 1, (unsigned long long)st_staged);
+    atomicAdd(o + 2, (unsigned long long)st_need);
+    atomicAdd(o + 3, (unsigned long long)st_live);
+    atomicAdd(o + 4, (unsigned long long)st_lanes);
+    atomicAdd(o + 5, (unsigned long long)(st_spans + (uint32_t)prev_cnt));
+    atomicAdd(o + 6, (unsigned long long)st_rounds);
+    atomicAdd(o + 7, 1ull);
+  }
 }
 
 }  // namespace
@@ -938,36 +1102,23 @@ int ggd_launch_blend(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const g
   const bool cull = ctx->opt[GGD_OPT_BLEND_CULL] != 0;
   const int T = gx * gy;
   static const int lds_pad = getenv("GGD_BLEND_LDS_PAD") ? atoi(getenv("GGD_BLEND_LDS_PAD")) : 0;   // experiment: caps the waves per CU
-  if (out_depth || out_alpha) {
-    // the depth / alpha extension: one instance per (exp mode, cull); no statistics variant (ggd_blend_stats counts plain frames only)
-    if (!out_depth || !out_alpha || !depth_keys) return ggd_fail(ctx, GGD_E_INVALID, "internal: depth / alpha blend needs both planes and the depth keys");
-#define GGD_LAUNCH_FWDA(EM, CU)                                                                                         \
-    hipLaunchKernelGGL((blend_forward_kernel<EM, CU, 1, 8, false, true>), dim3(4 * T), dim3(64), lds_pad, s, prm.width,   \
-                       prm.height, gx, T, splat, list, ranges, capacity, prm.bg, out_color, final_T, n_contrib,          \
-                       (unsigned long long*)nullptr, depth_keys, out_depth, out_alpha)
-    if (cull) {
-      if (em == 0) GGD_LAUNCH_FWDA(0, true); else if (em == 1) GGD_LAUNCH_FWDA(1, true); else GGD_LAUNCH_FWDA(2, true);
-    } else {
-      if (em == 0) GGD_LAUNCH_FWDA(0, false); else if (em == 1) GGD_LAUNCH_FWDA(1, false); else GGD_LAUNCH_FWDA(2, false);
-    }
-#undef GGD_LAUNCH_FWDA
-    GGD_HIP(hipGetLastError());
-    return GGD_OK;
-  }
-#define GGD_LAUNCH_FWD2(EM, CU, ST)                                                                                     \
-  hipLaunchKernelGGL((blend_forward_kernel<EM, CU, 1, 8, ST>), dim3(4 * T), dim3(64), lds_pad, s, prm.width, prm.height, \
-                     gx, T, splat, list, ranges, capacity, prm.bg, out_color, final_T, n_contrib, ctx->blend_stats)
-#define GGD_LAUNCH_FWD(EM, CU)                                                                                          \
-  do {                                                                                                                  \
-    if (ctx->blend_stats) GGD_LAUNCH_FWD2(EM, CU, true); else GGD_LAUNCH_FWD2(EM, CU, false);                           \
-  } while (0)
-  if (cull) {
-    if (em == 0) GGD_LAUNCH_FWD(0, true); else if (em == 1) GGD_LAUNCH_FWD(1, true); else GGD_LAUNCH_FWD(2, true);
-  } else {
-    if (em == 0) GGD_LAUNCH_FWD(0, false); else if (em == 1) GGD_LAUNCH_FWD(1, false); else GGD_LAUNCH_FWD(2, false);
-  }
-#undef GGD_LAUNCH_FWD
-#undef GGD_LAUNCH_FWD2
+  const bool aux = out_depth || out_alpha;   // the depth / alpha extension
+  if (aux && (!out_depth || !out_alpha || !depth_keys)) return ggd_fail(ctx, GGD_E_INVALID, "internal: depth / alpha blend needs both planes and the depth keys");
+  // one instance per (exp mode, cull, variant); the variants exclude each other: an aux frame has no statistics instance
+  // (ggd_blend_stats counts plain frames only)
+  enum { PLAIN = 0, STATS = 1, AUX = 2 };
+  const int variant = aux ? AUX : (ctx->blend_stats ? STATS : PLAIN);
+  ggd_dispatch<3>(em, [&](auto e) {
+    ggd_dispatch<2>(cull, [&](auto c) {
+      ggd_dispatch<3>(variant, [&](auto v) {
+        constexpr int V = decltype(v)::value;
+        hipLaunchKernelGGL((blend_forward_kernel<decltype(e)::value, decltype(c)::value != 0, 1, 8, V == STATS, V == AUX>),
+                           dim3(4 * T), dim3(64), lds_pad, s, prm.width, prm.height, gx, T, splat, list, ranges, capacity, prm.bg,
+                           out_color, final_T, n_contrib, V == STATS ? ctx->blend_stats : nullptr,
+                           V == AUX ? depth_keys : nullptr, out_depth, out_alpha);
+      });
+    });
+  });
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }
@@ -991,53 +1142,34 @@ int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm
   // 1 M / 704^2 225 vs 250 (profiles/r06/backward_blend_form_ab.txt)
   if (split == 1) split = 4;
   static const int lds_pad = getenv("GGD_BLEND_BWD_LDS_PAD") ? atoi(getenv("GGD_BLEND_BWD_LDS_PAD")) : 0;   // experiment
-  if (aux) {
-    // the depth / alpha backward exists in the quarter form only: it is used whatever GGD_OPT_BLEND_SPLIT says (the tile form
-    // is an explicit, non-default choice kept for measurements); no statistics variant
-    if (!depth_keys) return ggd_fail(ctx, GGD_E_INVALID, "internal: depth / alpha backward needs the depth keys");
-#define GGD_LAUNCH_BQA(EM, CU)                                                                                            \
-    hipLaunchKernelGGL((blend_backward_quarter_kernel<EM, CU, false, true>), dim3(4 * T), dim3(64), lds_pad, s, prm.width, \
-                       prm.height, gx, gy, splat, list, ranges, prm.bg, final_T, n_contrib, dL_dpix, grad_acc,             \
-                       (unsigned long long*)nullptr, depth_keys, dL_ddepth, dL_dalpha)
-    if (cull) {
-      if (em == 0) GGD_LAUNCH_BQA(0, true); else if (em == 1) GGD_LAUNCH_BQA(1, true); else if (em == 2) GGD_LAUNCH_BQA(2, true); else GGD_LAUNCH_BQA(3, true);
-    } else {
-      if (em == 0) GGD_LAUNCH_BQA(0, false); else if (em == 1) GGD_LAUNCH_BQA(1, false); else if (em == 2) GGD_LAUNCH_BQA(2, false); else GGD_LAUNCH_BQA(3, false);
-    }
-#undef GGD_LAUNCH_BQA
+  // the depth / alpha backward exists in the quarter form only: it is used whatever GGD_OPT_BLEND_SPLIT says (the tile form
+  // is an explicit, non-default choice kept for measurements)
+  if (aux && !depth_keys) return ggd_fail(ctx, GGD_E_INVALID, "internal: depth / alpha backward needs the depth keys");
+  if (!aux && split != 4) {
+    ggd_dispatch<4>(em, [&](auto e) {
+      ggd_dispatch<2>(cull, [&](auto c) {
+        hipLaunchKernelGGL((blend_backward_tile_kernel<decltype(e)::value, decltype(c)::value != 0>), dim3(T), dim3(256), 0, s,
+                           prm.width, prm.height, gx, gy, splat, list, ranges, prm.bg, final_T, n_contrib, dL_dpix, grad_acc);
+      });
+    });
     GGD_HIP(hipGetLastError());
     return GGD_OK;
   }
-  if (split == 4) {
-#define GGD_LAUNCH_BQ(EM, CU)                                                                                             \
-    do {                                                                                                                  \
-      if (ctx->blend_stats)                                                                                               \
-        hipLaunchKernelGGL((blend_backward_quarter_kernel<EM, CU, true>), dim3(4 * T), dim3(64), lds_pad, s, prm.width,   \
-                           prm.height, gx, gy, splat, list, ranges, prm.bg, final_T, n_contrib, dL_dpix, grad_acc,        \
-                           ctx->blend_stats);                                                                             \
-      else                                                                                                                \
-        hipLaunchKernelGGL((blend_backward_quarter_kernel<EM, CU>), dim3(4 * T), dim3(64), lds_pad, s, prm.width,         \
-                           prm.height, gx, gy, splat, list, ranges, prm.bg, final_T, n_contrib, dL_dpix, grad_acc,        \
-                           (unsigned long long*)nullptr);                                                                 \
-    } while (0)
-    if (cull) {
-      if (em == 0) GGD_LAUNCH_BQ(0, true); else if (em == 1) GGD_LAUNCH_BQ(1, true); else if (em == 2) GGD_LAUNCH_BQ(2, true); else GGD_LAUNCH_BQ(3, true);
-    } else {
-      if (em == 0) GGD_LAUNCH_BQ(0, false); else if (em == 1) GGD_LAUNCH_BQ(1, false); else if (em == 2) GGD_LAUNCH_BQ(2, false); else GGD_LAUNCH_BQ(3, false);
-    }
-#undef GGD_LAUNCH_BQ
-    GGD_HIP(hipGetLastError());
-    return GGD_OK;
-  }
-#define GGD_LAUNCH_BT(EM, CU)                                                                                             \
-  hipLaunchKernelGGL((blend_backward_tile_kernel<EM, CU>), dim3(T), dim3(256), 0, s, prm.width, prm.height, gx,           \
-                     gy, splat, list, ranges, prm.bg, final_T, n_contrib, dL_dpix, grad_acc)
-  if (cull) {
-    if (em == 0) GGD_LAUNCH_BT(0, true); else if (em == 1) GGD_LAUNCH_BT(1, true); else if (em == 2) GGD_LAUNCH_BT(2, true); else GGD_LAUNCH_BT(3, true);
-  } else {
-    if (em == 0) GGD_LAUNCH_BT(0, false); else if (em == 1) GGD_LAUNCH_BT(1, false); else if (em == 2) GGD_LAUNCH_BT(2, false); else GGD_LAUNCH_BT(3, false);
-  }
-#undef GGD_LAUNCH_BT
+  // quarter form, one instance per (exp mode, cull, variant); the variants exclude each other: no statistics instance of the
+  // depth / alpha backward
+  enum { PLAIN = 0, STATS = 1, AUX = 2 };
+  const int variant = aux ? AUX : (ctx->blend_stats ? STATS : PLAIN);
+  ggd_dispatch<4>(em, [&](auto e) {
+    ggd_dispatch<2>(cull, [&](auto c) {
+      ggd_dispatch<3>(variant, [&](auto v) {
+        constexpr int V = decltype(v)::value;
+        hipLaunchKernelGGL((blend_backward_quarter_kernel<decltype(e)::value, decltype(c)::value != 0, V == STATS, V == AUX>),
+                           dim3(4 * T), dim3(64), lds_pad, s, prm.width, prm.height, gx, gy, splat, list, ranges, prm.bg, final_T,
+                           n_contrib, dL_dpix, grad_acc, V == STATS ? ctx->blend_stats : nullptr,
+                           V == AUX ? depth_keys : nullptr, V == AUX ? dL_ddepth : nullptr, V == AUX ? dL_dalpha : nullptr);
+      });
+    });
+  });
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 
 #include "ggd_raster.h"
 
@@ -206,6 +207,17 @@ struct StageTimer {  // RAII hipEvent pair around one pipeline stage (no-op unle
 };
 
 static inline size_t ggd_align(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+
+// Runtime value -> template argument, for the launchers: calls f(std::integral_constant<int, I>{}) with I = v for
+// 0 <= v < N - 1 and I = N - 1 for every other v (a bool is N = 2).  Kernel templates take their feature flags as trailing
+// defaulted parameters (preprocess_kernel<..., AA>, blend_forward_kernel<..., AUX>, ...): one definition per kernel, the
+// plain instance is <..., false>, and a launcher names the instance inside nested ggd_dispatch calls around ONE launch.
+template <int N, int I = 0, typename F>
+static inline void ggd_dispatch(int v, F&& f) {
+  if constexpr (I == N - 1) f(std::integral_constant<int, I>{});
+  else if (v == I) f(std::integral_constant<int, I>{});
+  else ggd_dispatch<N, I + 1>(v, f);
+}
 
 // ---- kernels launched by the C API (defined in the .hip files) ------------------------------------------------
 int ggd_launch_preprocess(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const float* means3D,

@@ -355,34 +355,20 @@ __device__ __forceinline__ void preprocess_backward_body(
     colors_precomp, scales, rotations, cov3D_precomp, radii, clamped, grad_acc, dL_dmean2D, dL_dcolors, dL_dmeans3D,    \
     dL_dcov3D, dL_dsh, dL_dscales, dL_drots
 
+// The three forms of the kernel.  AA: the anti-aliasing h chain (ggd_params.antialiasing); AUX: the depth term of the
+// depth / alpha extension (ggd_backward_aux).  Both off: the plain backward.
+template <bool AA = false, bool AUX = false>
 __global__ __launch_bounds__(256) void preprocess_backward_kernel(GGD_PPB_PARAMS) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= P) return;
-  preprocess_backward_body<false>(i, nullptr, GGD_PPB_ARGS);
+  preprocess_backward_body<false, false, AUX, AA>(i, nullptr, GGD_PPB_ARGS);
 }
 
+template <bool AA = false, bool AUX = false>
 __global__ __launch_bounds__(256) void preprocess_backward_vec_kernel(GGD_PPB_PARAMS) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= P) return;
-  preprocess_backward_body<true, true>(i, nullptr, GGD_PPB_ARGS);
-}
-
-// depth / alpha extension (ggd_backward_aux): the same kernels with the depth term (AUX must be true: overloads, so that the
-// plain kernels keep their names)
-template <bool AUX>
-__global__ __launch_bounds__(256) void preprocess_backward_kernel(GGD_PPB_PARAMS) {
-  static_assert(AUX, "the plain kernel is the non-template one");
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= P) return;
-  preprocess_backward_body<false, false, true>(i, nullptr, GGD_PPB_ARGS);
-}
-
-template <bool AUX>
-__global__ __launch_bounds__(256) void preprocess_backward_vec_kernel(GGD_PPB_PARAMS) {
-  static_assert(AUX, "the plain kernel is the non-template one");
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= P) return;
-  preprocess_backward_body<true, true, true>(i, nullptr, GGD_PPB_ARGS);
+  preprocess_backward_body<true, true, AUX, AA>(i, nullptr, GGD_PPB_ARGS);
 }
 
 // SH degree > 0 (M > 1 coefficients per channel): a Gaussian's 3 M gradients are 12 M bytes apart from its neighbour's, so
@@ -390,69 +376,34 @@ __global__ __launch_bounds__(256) void preprocess_backward_vec_kernel(GGD_PPB_PA
 // 494 us for this kernel against 88 us at M = 1).  Here every lane parks its row in LDS and the wave writes its 64 rows --
 // one contiguous 768 M-byte span of dL_dsh -- with lane-consecutive (16-byte where 3 M allows) stores.  (1 M Gaussians,
 // M = 16: 247 -> 146 us; preprocess_backward_vec_kernel above does as well without LDS where the rows allow dwordx4.)
-// (the body as a macro, so that the plain kernel stays the code it was; the arguments are those of preprocess_backward_body)
-#define GGD_PPB_STAGED_BODY(...)                                                                            \
-  extern __shared__ float s_dsh[];   /* [256][3 M + 1] */                                               \
-  const int i = blockIdx.x * 256 + threadIdx.x;                                                             \
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;                                                 \
-  const int rl = 3 * M, rowlen = rl + 1;                                                                    \
-  if (i < P) preprocess_backward_body<__VA_ARGS__>(i, s_dsh + (size_t)threadIdx.x * rowlen, GGD_PPB_ARGS);  \
-  __builtin_amdgcn_wave_barrier();                                                                          \
-  __threadfence_block();                                                                                    \
-  const int i0 = blockIdx.x * 256 + wv * 64;                                                                \
-  const int nrows = min(64, P - i0);                                                                        \
-  if (nrows <= 0) return;                                                                                   \
-  const float* rows = s_dsh + (size_t)wv * 64 * rowlen;                                                     \
-  float* dst = dL_dsh + (size_t)i0 * rl;                                                                    \
-  const int total = nrows * rl;                                                                             \
-  if ((rl & 3) == 0) {                                                                                      \
-    for (int e = 4 * lane; e < total; e += 256) {                                                           \
-      const int r = e / rl, k = e - r * rl;                                                                 \
-      const float* src = rows + r * rowlen + k;                                                             \
-      *reinterpret_cast<float4*>(dst + e) = make_float4(src[0], src[1], src[2], src[3]);                    \
-    }                                                                                                       \
-  } else {                                                                                                  \
-    for (int e = lane; e < total; e += 64) {                                                                \
-      const int r = e / rl, k = e - r * rl;                                                                 \
-      dst[e] = rows[r * rowlen + k];                                                                        \
-    }                                                                                                       \
+template <bool SHVEC, bool AA = false, bool AUX = false>
+__global__ __launch_bounds__(256) void preprocess_backward_staged_kernel(GGD_PPB_PARAMS) {
+  extern __shared__ float s_dsh[];   // [256][3 M + 1]
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int rl = 3 * M, rowlen = rl + 1;
+  if (i < P) preprocess_backward_body<SHVEC, false, AUX, AA>(i, s_dsh + (size_t)threadIdx.x * rowlen, GGD_PPB_ARGS);
+  __builtin_amdgcn_wave_barrier();
+  __threadfence_block();
+  const int i0 = blockIdx.x * 256 + wv * 64;
+  const int nrows = min(64, P - i0);
+  if (nrows <= 0) return;
+  const float* rows = s_dsh + (size_t)wv * 64 * rowlen;
+  float* dst = dL_dsh + (size_t)i0 * rl;
+  const int total = nrows * rl;
+  if ((rl & 3) == 0) {
+    for (int e = 4 * lane; e < total; e += 256) {
+      const int r = e / rl, k = e - r * rl;
+      const float* src = rows + r * rowlen + k;
+      *reinterpret_cast<float4*>(dst + e) = make_float4(src[0], src[1], src[2], src[3]);
+    }
+  } else {
+    for (int e = lane; e < total; e += 64) {
+      const int r = e / rl, k = e - r * rl;
+      dst[e] = rows[r * rowlen + k];
+    }
   }
-
-template <bool SHVEC>
-__global__ __launch_bounds__(256) void preprocess_backward_staged_kernel(GGD_PPB_PARAMS) {
-GGD_PPB_STAGED_BODY(SHVEC)
 }
-
-template <bool SHVEC, bool AUX>
-__global__ __launch_bounds__(256) void preprocess_backward_staged_kernel(GGD_PPB_PARAMS) {
-  static_assert(AUX, "the plain kernel is the one-parameter template");
-GGD_PPB_STAGED_BODY(SHVEC, false, true)
-}
-
-// anti-aliasing (ggd_params.antialiasing): the three forms with the h chain, depth term off / on (AA_ must be true; AUX last,
-// as in the depth / alpha overloads above)
-template <bool AA_, bool AUX>
-__global__ __launch_bounds__(256) void preprocess_backward_kernel(GGD_PPB_PARAMS) {
-  static_assert(AA_, "the plain kernels are the non-template one and the one-parameter template");
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= P) return;
-  preprocess_backward_body<false, false, AUX, true>(i, nullptr, GGD_PPB_ARGS);
-}
-
-template <bool AA_, bool AUX>
-__global__ __launch_bounds__(256) void preprocess_backward_vec_kernel(GGD_PPB_PARAMS) {
-  static_assert(AA_, "the plain kernels are the non-template one and the one-parameter template");
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= P) return;
-  preprocess_backward_body<true, true, AUX, true>(i, nullptr, GGD_PPB_ARGS);
-}
-
-template <bool SHVEC, bool AA_, bool AUX>
-__global__ __launch_bounds__(256) void preprocess_backward_staged_kernel(GGD_PPB_PARAMS) {
-  static_assert(AA_, "the plain kernels are the one- and two-parameter templates");
-GGD_PPB_STAGED_BODY(SHVEC, false, AUX, true)
-}
-#undef GGD_PPB_STAGED_BODY
 
 }  // namespace
 
@@ -466,55 +417,23 @@ int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params
   if (prm.P == 0) return GGD_OK;
   // the staged form whenever there is more than the band-0 coefficient per channel (and room: 256 rows of 3 M + 1 floats)
   const bool staged = !colors_precomp && prm.M > 1 && (size_t)256 * (3 * prm.M + 1) * sizeof(float) <= 64 * 1024;
-  const bool shvec = staged && prm.M <= 16 && ((3 * prm.M) & 3) == 0;
   // rows that are a multiple of 16 bytes (M = 4, 8, 12, 16): read and written from registers with dwordx4 accesses (145 us
   // at M = 16, 1 M Gaussians; the LDS-staged form measures 152 with the same loads and is kept for the other M)
-#define GGD_PPB_LAUNCH(KERNEL, LDS)                                                                                  \
-  hipLaunchKernelGGL(KERNEL, dim3((prm.P + 255) / 256), dim3(256), (LDS), s, prm.P, prm.M, prm.sh_degree, prm.width,     \
-                     prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier, prm.raw_attributes, opacities, dL_dopacity,  \
-                     prm.viewmatrix, prm.projmatrix, prm.campos, means3D, shs, colors_precomp, scales, rotations,           \
-                     cov3D_precomp, radii, clamped, grad_acc, dL_dmean2D, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh,       \
-                     dL_dscales, dL_drots)
-  if (prm.antialiasing) {   // the same choice of form, with the h chain (and the depth term when aux)
-    if (aux) {
-      if (shvec) GGD_PPB_LAUNCH((preprocess_backward_vec_kernel<true, true>), 0);
-      else if (staged) GGD_PPB_LAUNCH((preprocess_backward_staged_kernel<false, true, true>), (size_t)256 * (3 * prm.M + 1) * sizeof(float));
-      else GGD_PPB_LAUNCH((preprocess_backward_kernel<true, true>), 0);
-    } else {
-      if (shvec) GGD_PPB_LAUNCH((preprocess_backward_vec_kernel<true, false>), 0);
-      else if (staged) GGD_PPB_LAUNCH((preprocess_backward_staged_kernel<false, true, false>), (size_t)256 * (3 * prm.M + 1) * sizeof(float));
-      else GGD_PPB_LAUNCH((preprocess_backward_kernel<true, false>), 0);
-    }
-    GGD_HIP(hipGetLastError());
-    return GGD_OK;
-  }
-  if (aux) {   // the depth / alpha extension: the same choice of form, with the depth term
-    if (shvec) GGD_PPB_LAUNCH(preprocess_backward_vec_kernel<true>, 0);
-    else if (staged) GGD_PPB_LAUNCH((preprocess_backward_staged_kernel<false, true>), (size_t)256 * (3 * prm.M + 1) * sizeof(float));
-    else GGD_PPB_LAUNCH(preprocess_backward_kernel<true>, 0);
-    GGD_HIP(hipGetLastError());
-    return GGD_OK;
-  }
-#undef GGD_PPB_LAUNCH
-  if (shvec)
-    hipLaunchKernelGGL(preprocess_backward_vec_kernel, dim3((prm.P + 255) / 256), dim3(256), 0, s, prm.P, prm.M,
-                       prm.sh_degree, prm.width, prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier,
-                       prm.raw_attributes, opacities, dL_dopacity, prm.viewmatrix, prm.projmatrix, prm.campos, means3D, shs, colors_precomp, scales, rotations,
-                       cov3D_precomp, radii, clamped, grad_acc, dL_dmean2D, dL_dcolors, dL_dmeans3D, dL_dcov3D,
-                       dL_dsh, dL_dscales, dL_drots);
-  else if (staged)
-    hipLaunchKernelGGL(preprocess_backward_staged_kernel<false>, dim3((prm.P + 255) / 256), dim3(256),
-                       (size_t)256 * (3 * prm.M + 1) * sizeof(float), s, prm.P, prm.M,
-                       prm.sh_degree, prm.width, prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier,
-                       prm.raw_attributes, opacities, dL_dopacity, prm.viewmatrix, prm.projmatrix, prm.campos, means3D, shs, colors_precomp, scales, rotations,
-                       cov3D_precomp, radii, clamped, grad_acc, dL_dmean2D, dL_dcolors, dL_dmeans3D, dL_dcov3D,
-                       dL_dsh, dL_dscales, dL_drots);
-  else
-  hipLaunchKernelGGL(preprocess_backward_kernel, dim3((prm.P + 255) / 256), dim3(256), 0, s, prm.P, prm.M,
-                     prm.sh_degree, prm.width, prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier,
-                     prm.raw_attributes, opacities, dL_dopacity, prm.viewmatrix, prm.projmatrix, prm.campos, means3D, shs, colors_precomp, scales, rotations,
-                     cov3D_precomp, radii, clamped, grad_acc, dL_dmean2D, dL_dcolors, dL_dmeans3D, dL_dcov3D,
-                     dL_dsh, dL_dscales, dL_drots);
+  const bool shvec = staged && prm.M <= 16 && ((3 * prm.M) & 3) == 0;
+  // the feature flags (h chain, depth term) pick the instance, the SH layout picks the form
+  ggd_dispatch<2>(prm.antialiasing != 0, [&](auto aa) {
+    ggd_dispatch<2>(aux, [&](auto ax) {
+      constexpr bool AA = decltype(aa)::value != 0, AUX = decltype(ax)::value != 0;
+      const auto kernel = shvec ? preprocess_backward_vec_kernel<AA, AUX>
+                        : staged ? preprocess_backward_staged_kernel<false, AA, AUX> : preprocess_backward_kernel<AA, AUX>;
+      const size_t lds = (staged && !shvec) ? (size_t)256 * (3 * prm.M + 1) * sizeof(float) : 0;
+      hipLaunchKernelGGL(kernel, dim3((prm.P + 255) / 256), dim3(256), lds, s, prm.P, prm.M, prm.sh_degree, prm.width,
+                         prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier, prm.raw_attributes, opacities, dL_dopacity,
+                         prm.viewmatrix, prm.projmatrix, prm.campos, means3D, shs, colors_precomp, scales, rotations,
+                         cov3D_precomp, radii, clamped, grad_acc, dL_dmean2D, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh,
+                         dL_dscales, dL_drots);
+    });
+  });
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }

@@ -25,45 +25,56 @@ def demangle(names):
         return list(names)
 
 
+def parse_metadata(text: str, res: dict) -> None:
+    """Adds {mangled kernel symbol: figures} from the AMDGPU metadata in text (llvm-readelf --notes, or a -S listing)."""
+    keys = {"vgpr_count": "vgpr", "sgpr_count": "sgpr", "vgpr_spill_count": "vgpr_spill", "sgpr_spill_count": "sgpr_spill",
+            "group_segment_fixed_size": "lds", "private_segment_fixed_size": "scratch", "max_flat_workgroup_size": "wg",
+            "kernarg_segment_size": "kernarg", "agpr_count": "agpr"}
+    cur = None
+
+    def commit(c):
+        if c and "_sym" in c:
+            res[c["_sym"]] = {a: b for a, b in c.items() if not a.startswith("_")}
+    for line in text.splitlines():
+        if re.match(r"\s*- \.agpr_count:", line):    # the first (alphabetical) key of a kernel record
+            commit(cur)
+            cur = {}
+        m = re.match(r"\s*-?\s*\.(\w+):\s+(\S.*)$", line)
+        if not m or cur is None:
+            continue
+        k, v = m.group(1), m.group(2).strip()
+        if k in keys:
+            cur[keys[k]] = int(v)
+        elif k == "symbol":
+            cur["_sym"] = v.replace(".kd", "")
+    commit(cur)
+
+
+def code_objects(lib_path: str, td: str) -> list:
+    """The gfx950 code objects of the library (one per translation unit), unbundled into directory td."""
+    fat = os.path.join(td, "fat.bin")
+    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat], check=True)
+    blob = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
+    out = []
+    for i, s in enumerate(starts):
+        part = os.path.join(td, f"b{i}.bin")
+        open(part, "wb").write(blob[s:starts[i + 1] if i + 1 < len(starts) else len(blob)])
+        co = os.path.join(td, f"k{i}.co")
+        r = subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o",
+                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={part}", f"--output={co}"],
+                           capture_output=True, text=True)
+        if r.returncode == 0 and os.path.exists(co) and os.path.getsize(co) > 0:
+            out.append(co)
+    return out
+
+
 def kernel_resources(lib_path: str) -> dict:
     """{demangled kernel name: {vgpr, agpr, sgpr, lds, scratch, vgpr_spill, sgpr_spill, wg, kernarg}}"""
     res = {}
     with tempfile.TemporaryDirectory() as td:
-        fat = os.path.join(td, "fat.bin")
-        subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat], check=True)
-        blob = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
-        for i, s in enumerate(starts):
-            part = os.path.join(td, f"b{i}.bin")
-            open(part, "wb").write(blob[s:starts[i + 1] if i + 1 < len(starts) else len(blob)])
-            co = os.path.join(td, f"k{i}.co")
-            r = subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o",
-                                "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={part}", f"--output={co}"],
-                               capture_output=True, text=True)
-            if r.returncode != 0 or not os.path.exists(co) or os.path.getsize(co) == 0:
-                continue
-            notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True).stdout
-            cur = None
-            keys = {"vgpr_count": "vgpr", "sgpr_count": "sgpr", "vgpr_spill_count": "vgpr_spill", "sgpr_spill_count": "sgpr_spill",
-                    "group_segment_fixed_size": "lds", "private_segment_fixed_size": "scratch", "max_flat_workgroup_size": "wg",
-                    "kernarg_segment_size": "kernarg", "agpr_count": "agpr"}
-
-            def commit(c):
-                if c and "_sym" in c:
-                    res[c["_sym"]] = {a: b for a, b in c.items() if not a.startswith("_")}
-            for line in notes.splitlines():
-                if re.match(r"\s*- \.agpr_count:", line):    # the first (alphabetical) key of a kernel record
-                    commit(cur)
-                    cur = {}
-                m = re.match(r"\s*-?\s*\.(\w+):\s+(\S.*)$", line)
-                if not m or cur is None:
-                    continue
-                k, v = m.group(1), m.group(2).strip()
-                if k in keys:
-                    cur[keys[k]] = int(v)
-                elif k == "symbol":
-                    cur["_sym"] = v.replace(".kd", "")
-            commit(cur)
+        for co in code_objects(lib_path, td):
+            parse_metadata(subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True).stdout, res)
     names = list(res)
     return dict(zip(demangle(names), (res[n] for n in names)))
 

@@ -44,20 +44,23 @@ def test_params_field_replaces_the_spare_word():
 
 def test_antialiasing_kernels_are_built_without_spills(native_lib):
     tab = _resources()
-    fwd = {k: v for k, v in tab.items() if k.startswith("preprocess_kernel<") and len(_targs(k)) == 3}
-    assert sorted(_targs(k)[-1] for k in fwd) == ["true"] * 4, sorted(fwd)     # SHVEC x FOLD, AA last
-    bwd = {k: v for k, v in tab.items() if k.startswith("preprocess_backward")
-           and ((len(_targs(k)) == 2 and "staged" not in k) or len(_targs(k)) == 3)}
-    # AA_ then AUX: the plain / vec / staged forms with the depth term off and on
+    # AA is the last template argument of preprocess_kernel<SHVEC, FOLD, AA> and the one before AUX in
+    # preprocess_backward{,_vec}_kernel<AA, AUX> / preprocess_backward_staged_kernel<SHVEC, AA, AUX>
+    fwd = {k: v for k, v in tab.items() if k.startswith("preprocess_kernel<") and _targs(k)[-1] == "true"}
+    assert sorted(fwd) == sorted(f"preprocess_kernel<{sv}, {fo}, true>" for sv in ("false", "true")
+                                 for fo in ("false", "true")), sorted(tab)          # SHVEC x FOLD
+    bwd = {k: v for k, v in tab.items() if k.startswith("preprocess_backward") and _targs(k)[-2] == "true"}
+    # the plain / vec / staged forms with the depth term off and on
     assert sorted(bwd) == sorted(["preprocess_backward_kernel<true, false>", "preprocess_backward_kernel<true, true>",
                                   "preprocess_backward_vec_kernel<true, false>", "preprocess_backward_vec_kernel<true, true>",
                                   "preprocess_backward_staged_kernel<false, true, false>",
                                   "preprocess_backward_staged_kernel<false, true, true>"]), sorted(tab)
     for name, r in {**fwd, **bwd}.items():
         assert r["vgpr_spill"] == 0 and r["scratch"] == 0, (name, r)
-    # the plain instances are still there under their old names
-    for name in ("preprocess_kernel<false, false>", "preprocess_kernel<true, true>", "preprocess_backward_kernel",
-                 "preprocess_backward_kernel<true>", "preprocess_backward_staged_kernel<false>"):
+    # the plain instances are the same templates with AA = false
+    for name in ("preprocess_kernel<false, false, false>", "preprocess_kernel<true, true, false>",
+                 "preprocess_backward_kernel<false, false>", "preprocess_backward_kernel<false, true>",
+                 "preprocess_backward_staged_kernel<false, false, false>"):
         assert name in tab, name
 
 
