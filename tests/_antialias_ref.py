@@ -116,14 +116,65 @@ def vjp(d, g_oeff):
     return out
 
 
+def chain_conditioning(d):
+    """(magnitude, rounding share) of the h chain d(o h)/dp, from one evaluation of (x, z, y) and h:
+
+    magnitude[array] = sum_u |d(o h)/du du/dp| over u in (x, z, y), float64 numpy per gradient array, >= |d(o h)/dp|: the three
+    terms the kernels add up (dL/da, dL/db, dL/dc taken on through T) before any of them cancels.
+
+    share = sum_j |d^2(o h) / dSigma_k dSigma_j| dSigma_j, float64 numpy [P, 6] in units of eps32: where Sigma = R S S R^T is
+    evaluated in fp32 (scales / rotations given) its entries carry the rounding the oracle's error analysis gives them
+    (ggo_cov3d_all_err) -- for a nearly isotropic Gaussian the off-diagonal entries are what is left of cancelling terms -- and
+    d(o h)/dSigma is taken at that rounded Sigma.  Zeros for a precomputed covariance."""
+    import ctypes as C
+    from oracle import ggd_oracle as O
+    means3D, scales, rotations, cov6 = _inputs(d, True)
+    params = dict(dL_dmeans3D=means3D, dL_dcov3D=cov6)
+    if scales is not None:
+        params.update(dL_dscales=scales, dL_drots=rotations)
+    P = means3D.shape[0]
+    o = _f64(d["opacities"]).reshape(-1)
+    xzy = cov2d(d, means3D, cov6)
+    oh = (o * h_of(*xzy)).sum()
+    d_du = torch.autograd.grad(oh, xzy, retain_graph=True)                      # d(o h)/dx, /dz, /dy  [P] each
+    mag = {k: np.zeros(tuple(t.shape)) for k, t in params.items()}
+    for u in range(3):
+        grads = torch.autograd.grad(xzy[u], list(params.values()), grad_outputs=d_du[u], retain_graph=True)
+        for k, gr in zip(params, grads):
+            mag[k] += np.abs(gr.numpy())
+    share = np.zeros((P, 6))
+    if scales is not None:
+        er = lambda t: np.ascontiguousarray(np.stack([_f64(t).numpy(), np.zeros(tuple(t.shape))], axis=-1))
+        cov_err = np.zeros((P, 6, 2), np.float64)
+        mod = float(np.float32(d["scale_modifier"]))
+        O.lib().ggo_cov3d_all_err(P, O._p(er(d["scales"])), C.c_double(mod), O._p(er(d["rotations"])), O._p(cov_err))
+        dS = torch.as_tensor(cov_err[..., 1])
+        (G,) = torch.autograd.grad(oh, cov6, create_graph=True)                  # [P, 6]
+        for k in range(6):
+            (Hk,) = torch.autograd.grad(G[:, k].sum(), cov6, retain_graph=True)
+            share[:, k] = (Hk.abs() * dS).sum(1).numpy()
+        share = np.nan_to_num(share, nan=0.0, posinf=0.0)
+    return mag, share
+
+
 def compose_backward(d, ref, budget, rel=64.0, kappa=0.25):
     """The plain fp64 reference `ref` / `budget` (oracle backward_ref64 at o_eff) turned into the anti-aliasing one: its
-    dL_dopacity (= dL/do_eff) is replaced by g h and the h chain is added to the geometric gradients.  The added terms get
-    an explicit allowance of rel * eps32 * cond * |term| on top of the plain budget (cond from h_and_conditioning: the fp32
-    h carries the cancellation of det0), expressed in the units check_gradients applies kappa * eps32 to."""
+    dL_dopacity (= dL/do_eff) is replaced by g h and the h chain g d(o h)/dp is added to the geometric gradients.  The fp32
+    chain differs from that product in three ways, each allowed for on top of the plain budget, in the units check_gradients
+    applies kappa * eps32 to:
+      * its own arithmetic: rel * eps32 * cond per term (cond from h_and_conditioning: the fp32 h carries the cancellation of
+        det0), over the magnitude sum_u |g d(o h)/du du/dp| of the three terms it adds (chain_conditioning) -- not over their
+        sum, which cancels for the off-diagonal covariance entries;
+      * g itself is the blend's fp32 sum with the error budget[dL_dopacity] of its own, which the chain multiplies by
+        |d(o h)/dp| <= that magnitude: thousands for a sub-pixel splat on a small image (d h / d x ~ h / (2 x), T^2 ~ (f / z)^2),
+        where an error of g far inside its own bound is the whole error of dL/dcov3D;
+      * dL/dcov3D is taken at the fp32 Sigma (the rounding share of chain_conditioning).  The off-diagonal 2D covariance z of a nearly isotropic
+        splat is a few 1e-5 px^2 made of Sigma's off-diagonal entries, themselves cancellation residues: d(o h)/dSigma_01 is
+        linear in z and inherits hundreds of eps32."""
     g = ref["dL_dopacity"].reshape(-1)
     aa = vjp(d, g)
     h, cond = h_and_conditioning(d)
+    mag, share = chain_conditioning(d)
     out_ref, out_bud = dict(ref), dict(budget)
     scale = rel / kappa
     out_ref["dL_dopacity"] = aa["dL_dopacity"].reshape(ref["dL_dopacity"].shape)
@@ -133,6 +184,10 @@ def compose_backward(d, ref, budget, rel=64.0, kappa=0.25):
         if k not in aa or ref.get(k) is None:
             continue
         t = aa[k].reshape(ref[k].shape)
+        col = lambda v: np.asarray(v, np.float64).reshape((-1,) + (1,) * (t.ndim - 1))
         out_ref[k] = ref[k] + t
-        out_bud[k] = budget[k] + scale * cond.reshape((-1,) + (1,) * (t.ndim - 1)) * np.abs(t)
+        # (a culled Gaussian has g = 0 and no budget of it: its gradients stay exact zeros)
+        out_bud[k] = budget[k] + (scale * col(cond) * col(np.abs(g)) + col(budget["dL_dopacity"])) * mag[k].reshape(t.shape)
+        if k == "dL_dcov3D":
+            out_bud[k] = out_bud[k] + col(np.abs(g)) * share.reshape(t.shape)
     return out_ref, out_bud
