@@ -20,7 +20,7 @@ EXPORTS = [
     "ggd_forward_geometry", "ggd_forward_render", "ggd_forward", "ggd_forward_enqueue", "ggd_forward_collect", "ggd_forward_can_speculate", "ggd_backward",
     "ggd_forward_aux", "ggd_forward_render_aux", "ggd_backward_aux", "ggd_mark_visible", "ggd_debug_unsorted",
     "ggd_triplane_forward", "ggd_triplane_backward", "ggd_trigrid_forward", "ggd_trigrid_backward", "ggd_planes_gather", "ggd_planes_scatter", "ggd_surface_tmp_bytes", "ggd_surface_sample", "ggd_attrs_split", "ggd_attrs_merge", "ggd_decoder_packed_bytes", "ggd_decoder_pack", "ggd_decoder_forward", "ggd_decoder_zbuf_bytes", "ggd_decoder_packed_t_bytes",
-    "ggd_decoder_forward_train", "ggd_decoder_backward", "ggd_decoder_wgrad_floats", "ggd_decoder_wgrad", "ggd_decoder_backward_wgrad", "ggd_decoder_packed_hl_bytes", "ggd_decoder_packed_t_hl_bytes", "ggd_decoder_dzbuf_hl_bytes", "ggd_decoder_pack_hl", "ggd_decoder_forward_hl", "ggd_decoder_backward_wgrad_hl", "ggd_image_loss_tmp_bytes", "ggd_image_loss", "ggd_set_option", "ggd_get_option", "ggd_blend_stats", "ggd_blend_backward_stats", "ggd_blend_timeline", "ggd_set_profiling", "ggd_stage_count", "ggd_stage_name", "ggd_stage_times",
+    "ggd_decoder_forward_train", "ggd_decoder_backward", "ggd_decoder_wgrad_floats", "ggd_decoder_wgrad", "ggd_decoder_backward_wgrad", "ggd_decoder_packed_hl_bytes", "ggd_decoder_packed_t_hl_bytes", "ggd_decoder_dzbuf_hl_bytes", "ggd_decoder_pack_hl", "ggd_decoder_forward_hl", "ggd_decoder_backward_wgrad_hl", "ggd_image_loss_tmp_bytes", "ggd_image_loss", "ggd_image_loss_masked", "ggd_mask_composite", "ggd_set_option", "ggd_get_option", "ggd_blend_stats", "ggd_blend_backward_stats", "ggd_blend_timeline", "ggd_set_profiling", "ggd_stage_count", "ggd_stage_name", "ggd_stage_times",
     "ggd_knn_tmp_bytes", "ggd_knn_leaf_size", "ggd_knn_max_points", "ggd_knn3", "ggd_knn3_stage",
 ]
 
@@ -118,6 +118,8 @@ def load():
         lib.ggd_decoder_backward_wgrad_hl.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.ggd_image_loss_tmp_bytes.restype = sz; lib.ggd_image_loss_tmp_bytes.argtypes = [i32, i32]
         lib.ggd_image_loss.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz]
+        lib.ggd_image_loss_masked.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz]
+        lib.ggd_mask_composite.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp]
         lib.ggd_set_option.argtypes = [vp, C.c_int, C.c_int]
         lib.ggd_get_option.argtypes = [vp, C.c_int]
         lib.ggd_blend_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_ulonglong)]

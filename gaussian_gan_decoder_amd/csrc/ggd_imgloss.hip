@@ -19,6 +19,16 @@
 // path.  SSIM algebra: S = A1 A2 / (B1 B2), A1 = 2 mu1 mu2 + C1, A2 = 2 s12 + C2, B1 = mu1^2 + mu2^2 + C1,
 // B2 = s11 + s22 + C2 with s11 = G*x^2 - mu1^2, s12 = G*xy - mu1 mu2;  c = dS/ds12 = 2 A1/(B1 B2),
 // b = dS/ds11 = -S/B2,  a = dS/dmu1 (total) = 2 mu2 A2/(B1 B2) - 2 mu1 S/B1 - 2 mu1 b - mu2 c.
+//
+// MASKED instances (ggd_image_loss_masked; --apply_mask_to_rendering, main/train_pano2gaussian_decoder.py:237-241): the
+// generator's low-resolution mask [mask_h, mask_w] is upsampled bilinearly by the integer factors H / mask_h, W / mask_w
+// (PyTorch's interpolate, align_corners=False) and image and target are composited onto white, x' = (x*m + 1) - m, at the
+// place where each of the three kernels reads a pixel INSIDE the image -- no full-resolution mask, no composited image, no
+// extra launch, the same tmp layout.  Pixels outside the image stay 0 (the reference zero-pads the composited image).
+// grad_kernel forms the gradient from x', y' and applies the chain rule dL/dx = m dL/dx' before the store; target and mask
+// get no gradient (the reference's mask comes out of a no_grad synthesis).  The <false> instances are the unmasked code.
+// mask_composite_kernel is the same composite as an operator of its own (forward x', backward g*m) for the consumers that
+// need the composited image itself (the perceptual term, logging, eval).
 #include "ggd_common.h"
 
 namespace {
@@ -28,6 +38,37 @@ constexpr int HALO = 5;
 constexpr int EXT = TILE + 2 * HALO;  // 42
 
 struct Win { float g[11]; };
+
+// The low-resolution mask and the upsample factors; m == nullptr in the unmasked instances (never read there).
+struct Mask { const float* m; int w, h; float fx, fy; };
+
+// One axis of PyTorch's bilinear upsample with align_corners=False: the two source cells and the weight of the second.
+struct MaskAxis { int i0, i1; float l; };
+
+__device__ __forceinline__ MaskAxis mask_axis(int dst, float f, int n) {
+  const float src = fmaxf(((float)dst + 0.5f) / f - 0.5f, 0.f);
+  MaskAxis a;
+  a.i0 = min((int)src, n - 1);
+  a.i1 = min(a.i0 + 1, n - 1);
+  a.l = src - (float)a.i0;
+  return a;
+}
+
+// along x for both rows, then along y; a factor of 1 gives l = 0 and returns the cell unchanged
+__device__ __forceinline__ float mask_value(const Mask& mk, const MaskAxis& ay, const MaskAxis& ax) {
+  const float* r0 = mk.m + (size_t)ay.i0 * mk.w;
+  const float* r1 = mk.m + (size_t)ay.i1 * mk.w;
+  const float top = r0[ax.i0] * (1.f - ax.l) + r0[ax.i1] * ax.l;
+  const float bot = r1[ax.i0] * (1.f - ax.l) + r1[ax.i1] * ax.l;
+  return top * (1.f - ay.l) + bot * ay.l;
+}
+
+__device__ __forceinline__ float mask_at(const Mask& mk, int gy, int gx) {
+  return mask_value(mk, mask_axis(gy, mk.fy, mk.h), mask_axis(gx, mk.fx, mk.w));
+}
+
+// onto white, in the reference's order (image * m + 1 - m)
+__device__ __forceinline__ float composite(float v, float m) { return (v * m + 1.f) - m; }
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
   const int tid = threadIdx.x;
@@ -41,9 +82,10 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return s;
 }
 
+template <bool MASKED>
 __global__ __launch_bounds__(256) void ssim_stats_kernel(int W, int H, Win win, const float* __restrict__ img,
                                                          const float* __restrict__ tgt, float* __restrict__ abc,
-                                                         float* __restrict__ sums) {
+                                                         float* __restrict__ sums, Mask mk) {
   __shared__ float sx[EXT][EXT + 1], sy[EXT][EXT + 1];
   __shared__ float hb[5][EXT][TILE + 1];
   __shared__ float red[4];
@@ -56,8 +98,18 @@ __global__ __launch_bounds__(256) void ssim_stats_kernel(int W, int H, Win win, 
     const int r = i / EXT, c = i % EXT;
     const int gy = y0 + r - HALO, gx = x0 + c - HALO;
     const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-    sx[r][c] = in ? X[(size_t)gy * W + gx] : 0.f;
-    sy[r][c] = in ? Y[(size_t)gy * W + gx] : 0.f;
+    if constexpr (MASKED) {   // halo pixels outside the image stay 0, not 1 - m
+      float a = 0.f, b = 0.f;
+      if (in) {
+        const float m = mask_at(mk, gy, gx);
+        a = composite(X[(size_t)gy * W + gx], m);
+        b = composite(Y[(size_t)gy * W + gx], m);
+      }
+      sx[r][c] = a; sy[r][c] = b;
+    } else {
+      sx[r][c] = in ? X[(size_t)gy * W + gx] : 0.f;
+      sy[r][c] = in ? Y[(size_t)gy * W + gx] : 0.f;
+    }
   }
   __syncthreads();
   for (int i = tid; i < EXT * TILE; i += 256) {
@@ -104,15 +156,24 @@ __global__ __launch_bounds__(256) void ssim_stats_kernel(int W, int H, Win win, 
   if (tid == 0) { atomicAdd(sums + 0, t1); atomicAdd(sums + 1, t2); atomicAdd(sums + 2, t0); }
 }
 
+template <bool MASKED>
 __global__ __launch_bounds__(256) void sobel_kernel(int W, int H, const float* __restrict__ img,
                                                     const float* __restrict__ tgt, float* __restrict__ gxy,
-                                                    float* __restrict__ sums) {
+                                                    float* __restrict__ sums, Mask mk) {
   __shared__ float red[4];
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   const size_t plane = (size_t)H * W;
   float v = 0.f;
   if (x < W && y < H) {
     float d[3][3];
+    [[maybe_unused]] MaskAxis ay[3], ax[3];   // the upsample is separable: three rows and three columns serve the nine stencil pixels
+    if constexpr (MASKED) {
+#pragma unroll
+      for (int u = 0; u < 3; ++u) {   // (clamped: the axes of pixels outside the image are never used)
+        ay[u] = mask_axis(min(max(y + u - 1, 0), H - 1), mk.fy, mk.h);
+        ax[u] = mask_axis(min(max(x + u - 1, 0), W - 1), mk.fx, mk.w);
+      }
+    }
 #pragma unroll
     for (int u = -1; u <= 1; ++u)
 #pragma unroll
@@ -121,7 +182,14 @@ __global__ __launch_bounds__(256) void sobel_kernel(int W, int H, const float* _
         float s = 0.f;
         if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
           const size_t p = (size_t)yy * W + xx;
-          s = (img[p] - tgt[p]) + (img[plane + p] - tgt[plane + p]) + (img[2 * plane + p] - tgt[2 * plane + p]);
+          if constexpr (MASKED) {
+            const float m = mask_value(mk, ay[u + 1], ax[w + 1]);
+            s = (composite(img[p], m) - composite(tgt[p], m)) +
+                (composite(img[plane + p], m) - composite(tgt[plane + p], m)) +
+                (composite(img[2 * plane + p], m) - composite(tgt[2 * plane + p], m));
+          } else {
+            s = (img[p] - tgt[p]) + (img[plane + p] - tgt[plane + p]) + (img[2 * plane + p] - tgt[2 * plane + p]);
+          }
         }
         d[u + 1][w + 1] = s;
       }
@@ -136,11 +204,12 @@ __global__ __launch_bounds__(256) void sobel_kernel(int W, int H, const float* _
   if (threadIdx.x == 0) atomicAdd(sums + 3, t);
 }
 
+template <bool MASKED>
 __global__ __launch_bounds__(256) void grad_kernel(int W, int H, Win win, const float* __restrict__ img,
                                                    const float* __restrict__ tgt, const float* __restrict__ abc,
                                                    const float* __restrict__ gxy, const float* __restrict__ sums,
                                                    float w_l1, float w_l2, float w_ssim, float w_sobel,
-                                                   float* __restrict__ grad, float* __restrict__ terms) {
+                                                   float* __restrict__ grad, float* __restrict__ terms, Mask mk) {
   __shared__ float sm[3][EXT][EXT + 1];
   __shared__ float hb[3][EXT][TILE + 1];
   const int tid = threadIdx.x, ch = blockIdx.z;
@@ -185,7 +254,12 @@ __global__ __launch_bounds__(256) void grad_kernel(int W, int H, Win win, const 
       Ga += g * hb[0][r + k][tx]; Gb += g * hb[1][r + k][tx]; Gc += g * hb[2][r + k][tx];
     }
     const size_t p = (size_t)gy * W + gx;
-    const float x = img[ch * plane + p], y = tgt[ch * plane + p];
+    float x = img[ch * plane + p], y = tgt[ch * plane + p];
+    [[maybe_unused]] float m = 1.f;
+    if constexpr (MASKED) {   // everything below is d loss / d x' of the composited pair
+      m = mask_at(mk, gy, gx);
+      x = composite(x, m); y = composite(y, m);
+    }
     const float d = x - y;
     float gsum = -w_ssim / n3 * (Ga + 2.f * x * Gb + y * Gc);
     gsum += w_l1 / n3 * (float)((d > 0.f) - (d < 0.f));
@@ -204,8 +278,19 @@ __global__ __launch_bounds__(256) void grad_kernel(int W, int H, Win win, const 
         sob += kx * gxy[pp] + ky * gxy[plane + pp];
       }
     gsum += w_sobel * 2.f / n1 * sob;
+    if constexpr (MASKED) gsum *= m;   // dx'/dx = m
     grad[ch * plane + p] = gsum;
   }
+}
+
+// dst = (src*m + 1) - m (forward) or src*m (backward: the gradient w.r.t. src) over [channels, H, W], one mask value per pixel.
+__global__ __launch_bounds__(256) void mask_composite_kernel(int W, int H, int channels, const float* __restrict__ src,
+                                                             Mask mk, int backward, float* __restrict__ dst) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= W || y >= H) return;
+  const float m = mask_at(mk, y, x);
+  const size_t plane = (size_t)H * W, p = (size_t)y * W + x;
+  for (int c = 0; c < channels; ++c) dst[c * plane + p] = backward ? src[c * plane + p] * m : composite(src[c * plane + p], m);
 }
 
 }  // namespace
@@ -215,14 +300,23 @@ extern "C" size_t ggd_image_loss_tmp_bytes(int32_t W, int32_t H) {
   return ggd_align(64) + ggd_align((size_t)11 * H * W * sizeof(float));   // sums | 9 abc maps + 2 Sobel maps
 }
 
-extern "C" int ggd_image_loss(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, const float* image,
-                              const float* target, const float* weights4, float* terms5, float* grad_image,
-                              void* tmp, size_t tmp_bytes) {
+// Shared body of ggd_image_loss (mask == nullptr) and ggd_image_loss_masked.
+static int image_loss_launch(ggd_ctx* ctx, const char* who, void* stream, int32_t W, int32_t H, const float* image,
+                             const float* target, const float* mask, int32_t mask_w, int32_t mask_h, bool masked,
+                             const float* weights4, float* terms5, float* grad_image, void* tmp, size_t tmp_bytes) {
   if (!ctx) return GGD_E_INVALID;
-  if (W <= 0 || H <= 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_image_loss: empty image");
-  if (!image || !target || !weights4 || !terms5 || !grad_image || !tmp)
-    return ggd_fail(ctx, GGD_E_INVALID, "ggd_image_loss: NULL pointer");
-  if (tmp_bytes < ggd_image_loss_tmp_bytes(W, H)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_image_loss: tmp too small");
+  const std::string name(who);
+  if (W <= 0 || H <= 0) return ggd_fail(ctx, GGD_E_INVALID, name + ": empty image");
+  if (!image || !target || !weights4 || !terms5 || !grad_image || !tmp || (masked && !mask))
+    return ggd_fail(ctx, GGD_E_INVALID, name + ": NULL pointer");
+  Mask mk{nullptr, 0, 0, 1.f, 1.f};
+  if (masked) {
+    if (mask_w <= 0 || mask_h <= 0) return ggd_fail(ctx, GGD_E_INVALID, name + ": empty mask");
+    if (H % mask_h != 0 || W % mask_w != 0)
+      return ggd_fail(ctx, GGD_E_INVALID, name + ": the mask size must divide the image size");
+    mk = Mask{mask, mask_w, mask_h, (float)(W / mask_w), (float)(H / mask_h)};
+  }
+  if (tmp_bytes < ggd_image_loss_tmp_bytes(W, H)) return ggd_fail(ctx, GGD_E_INVALID, name + ": tmp too small");
   hipStream_t s = static_cast<hipStream_t>(stream);
   Win win;
   {  // loss_utils.py:23-25: exp(-(x - 5)^2 / (2 sigma^2)) as float32, normalised by its float32 sum
@@ -235,10 +329,43 @@ extern "C" int ggd_image_loss(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, 
   float* gxy = abc + (size_t)9 * H * W;
   GGD_HIP(hipMemsetAsync(sums, 0, 64, s));
   const dim3 tiles((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, 3);
-  hipLaunchKernelGGL(ssim_stats_kernel, tiles, dim3(256), 0, s, W, H, win, image, target, abc, sums);
-  hipLaunchKernelGGL(sobel_kernel, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, s, W, H, image, target, gxy, sums);
-  hipLaunchKernelGGL(grad_kernel, tiles, dim3(256), 0, s, W, H, win, image, target, abc, gxy, sums, weights4[0],
-                     weights4[1], weights4[2], weights4[3], grad_image, terms5);
+  ggd_dispatch<2>(masked, [&](auto mf) {
+    constexpr bool M = decltype(mf)::value != 0;
+    hipLaunchKernelGGL(ssim_stats_kernel<M>, tiles, dim3(256), 0, s, W, H, win, image, target, abc, sums, mk);
+    hipLaunchKernelGGL(sobel_kernel<M>, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, s, W, H, image, target, gxy, sums, mk);
+    hipLaunchKernelGGL(grad_kernel<M>, tiles, dim3(256), 0, s, W, H, win, image, target, abc, gxy, sums, weights4[0],
+                       weights4[1], weights4[2], weights4[3], grad_image, terms5, mk);
+  });
+  GGD_HIP(hipGetLastError());
+  return GGD_OK;
+}
+
+extern "C" int ggd_image_loss(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, const float* image,
+                              const float* target, const float* weights4, float* terms5, float* grad_image,
+                              void* tmp, size_t tmp_bytes) {
+  return image_loss_launch(ctx, "ggd_image_loss", stream, W, H, image, target, nullptr, 0, 0, false, weights4, terms5,
+                           grad_image, tmp, tmp_bytes);
+}
+
+extern "C" int ggd_image_loss_masked(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, const float* image,
+                                     const float* target, const float* mask, int32_t mask_w, int32_t mask_h,
+                                     const float* weights4, float* terms5, float* grad_image, void* tmp,
+                                     size_t tmp_bytes) {
+  return image_loss_launch(ctx, "ggd_image_loss_masked", stream, W, H, image, target, mask, mask_w, mask_h, true,
+                           weights4, terms5, grad_image, tmp, tmp_bytes);
+}
+
+extern "C" int ggd_mask_composite(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, int32_t channels, const float* src,
+                                  const float* mask, int32_t mask_w, int32_t mask_h, int32_t backward, float* dst) {
+  if (!ctx) return GGD_E_INVALID;
+  if (W <= 0 || H <= 0 || channels <= 0 || mask_w <= 0 || mask_h <= 0)
+    return ggd_fail(ctx, GGD_E_INVALID, "ggd_mask_composite: empty image or mask");
+  if (!src || !mask || !dst) return ggd_fail(ctx, GGD_E_INVALID, "ggd_mask_composite: NULL pointer");
+  if (H % mask_h != 0 || W % mask_w != 0)
+    return ggd_fail(ctx, GGD_E_INVALID, "ggd_mask_composite: the mask size must divide the image size");
+  const Mask mk{mask, mask_w, mask_h, (float)(W / mask_w), (float)(H / mask_h)};
+  hipLaunchKernelGGL(mask_composite_kernel, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), W, H, channels, src, mk, backward, dst);
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }

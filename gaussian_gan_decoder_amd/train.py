@@ -28,12 +28,13 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 
 from .cameras import CustomCam, look_at_cam2world
 from .decoder import SequentialDecoderReverse
-from .losses import fused_image_loss, PerceptualStandIn
+from .losses import composite_mask, fused_image_loss, PerceptualStandIn
 from .gaussian_model import GaussianModel
 
 BUCKET_BYTES = 32 << 20
@@ -46,13 +47,24 @@ class SceneBatch:
     fov_deg: torch.Tensor     # [B]
     target: torch.Tensor      # [B, 3, S, S]
     scene_id: torch.Tensor    # [B] global scene indices (which latent / plane set)
+    mask: Optional[torch.Tensor] = None   # [B, 1, S/8, S/8]  the generator's image_mask (apply_mask_to_rendering)
 
 
-def make_scene_batch(scene_ids, n_points: int, size: int, device, seed: int = 0) -> SceneBatch:
+def make_scene_batch(scene_ids, n_points: int, size: int, device, seed: int = 0, with_mask: bool = False) -> SceneBatch:
     """Deterministic synthetic stand-in for TargetDataloader.get_data (target_dataloader.py:59-132): head-like
     shell positions, camera h,v ~ U around pi/2 (main/decoder_utils/camera.py:6-35), fov ~ U[5,17]
-    (target_dataloader.py:71).  Each global scene id gets its own seed, so any rank can build any scene."""
+    (target_dataloader.py:71).  Each global scene id gets its own seed, so any rank can build any scene.
+    with_mask: also a stand-in for the generator's image_mask at 1/8 resolution, derived from the target's blob without a
+    draw from the generator (every other field is the same with and without it): clip((blob - 0.2) / 0.5, 0, 1) -- an
+    exact-0 rim, an exact-1 core and a ramp between them."""
     pos, c2w, fov, tgt = [], [], [], []
+    mask = None
+    if with_mask:
+        if size % 8 != 0:
+            raise ValueError("make_scene_batch(with_mask=True) needs an image size that is a multiple of 8")
+        yy, xx = torch.meshgrid(torch.linspace(-1, 1, size // 8), torch.linspace(-1, 1, size // 8), indexing="ij")
+        low = torch.clip((torch.exp(-(xx ** 2 + yy ** 2) * 3.0) - 0.2) / 0.5, 0.0, 1.0)
+        mask = low[None, None].repeat(len(list(scene_ids)), 1, 1, 1).to(device)
     for sid in scene_ids:
         g = torch.Generator().manual_seed(seed * 1000003 + int(sid))
         d = torch.randn(n_points, 3, generator=g)
@@ -68,7 +80,7 @@ def make_scene_batch(scene_ids, n_points: int, size: int, device, seed: int = 0)
         col = torch.rand(3, generator=g)
         tgt.append(0.5 + (col[:, None, None] - 0.5) * blob[None])
     return SceneBatch(torch.stack(pos).to(device), torch.stack(c2w), torch.tensor(fov),
-                      torch.stack(tgt).to(device), torch.tensor(list(scene_ids)))
+                      torch.stack(tgt).to(device), torch.tensor(list(scene_ids)), mask)
 
 
 class DecoderTrainer:
@@ -81,7 +93,8 @@ class DecoderTrainer:
                  loss_fn=None, process_group=None, fused_activations: bool = False, fused_decoder: bool = False,
                  backbone_params: int = 0, perceptual_weight: float = 0.0, perceptual_width_div: int = 1,
                  scene_streams: bool = False, decoder_precision: str = "bf16", plane_axes: str = "eg3d",
-                 triplane_depth=None, fused_planes=None, force_comm=None, antialiasing: bool = False):
+                 triplane_depth=None, fused_planes=None, force_comm=None, antialiasing: bool = False,
+                 apply_mask_to_rendering: bool = False):
         """plane_axes / triplane_depth: the generator whose planes are decoded -- ("eg3d", None): tri-planes
         [3, C, res, res]; ("panohead", 3): PanoHead's tri-grids [3, C * 3, res, res] sampled with a 3-D grid_sample
         (the reference's default generator: main/train_pano2gaussian_decoder.py:43, PanoHead/train.py:230,318,
@@ -93,7 +106,11 @@ class DecoderTrainer:
         units, waits -- whenever a process group exists, even with ONE rank (exercises the RCCL communicator, work handles
         and their stream semantics on a single GPU; the sum over one rank is the identity).
         antialiasing: render with the rasterizer's opacity-compensated 2D filter (render_simple's antialiasing=True; it is
-        passed to render_fn only when set)."""
+        passed to render_fn only when set).
+        apply_mask_to_rendering: the reference's option of that name (main/train_pano2gaussian_decoder.py:52,237-241): the
+        batch's mask, upsampled bilinearly, composites the rendered image and the target onto white before every loss
+        term -- `mask=` of loss_fn (passed only when set), composite_mask for the perceptual term; a batch without a mask
+        is an error."""
         import os
         import torch.distributed as dist
         self.force_comm = bool(int(os.environ.get("GGD_FORCE_COMM", "0"))) if force_comm is None else bool(force_comm)
@@ -153,6 +170,7 @@ class DecoderTrainer:
         self.render_kwargs = {"fused_activations": True} if fused_activations else {}
         if antialiasing:
             self.render_kwargs["antialiasing"] = True
+        self.apply_mask_to_rendering = bool(apply_mask_to_rendering)
         self.bg = torch.tensor([0.55717, 0.52256, 0.51045], dtype=torch.float32, device=self.device)
         # scene_streams: every local scene's raster + loss on its own HIP stream (own ggd_ctx).  Measured on one MI355X
         # (4 scenes x 500 k points, fused decoder): 21.13 ms / step with and without -- the single-call forward already
@@ -397,7 +415,8 @@ class DecoderTrainer:
             setattr(cam, name, getattr(cam, name).to(self.device, non_blocking=True))
         image = self.render_fn(cam, gs, bg_color=self.bg, **self.render_kwargs)["render"][:3]
         target = batch.target[b]
-        loss = self.loss_fn(image, target, **self.loss_w)[0]
+        mask_kw = {"mask": batch.mask[b]} if self.apply_mask_to_rendering else {}
+        loss = self.loss_fn(image, target, **self.loss_w, **mask_kw)[0]
         if self.perceptual is not None:
             # the reference evaluates its perceptual network on the whole batch at once (lpips.py:29-31): the rendered
             # images are collected and local_loss makes ONE call on the stack
@@ -408,6 +427,9 @@ class DecoderTrainer:
         """Decoder + raster forward for the local scenes; returns the mean loss over them."""
         B = batch.positions.shape[0]
         scene_ids = batch.scene_id.tolist()
+        if self.apply_mask_to_rendering and batch.mask is None:
+            raise ValueError("DecoderTrainer(apply_mask_to_rendering=True) needs a batch with a mask "
+                             "(make_scene_batch(..., with_mask=True))")
         attrs = None
         feats = self._scene_features(batch, scene_ids) if self.fused_planes else None
         if feats is not None and not self.fused_decoder:
@@ -439,7 +461,10 @@ class DecoderTrainer:
         for l in losses[1:]:
             total = total + l
         if self.perceptual is not None:
-            total = total + self.perceptual_weight * self.perceptual(torch.stack(self._perc_images), batch.target[:B])
+            images, targets = torch.stack(self._perc_images), batch.target[:B]
+            if self.apply_mask_to_rendering:
+                images, targets = composite_mask(images, batch.mask[:B]), composite_mask(targets, batch.mask[:B])
+            total = total + self.perceptual_weight * self.perceptual(images, targets)
             self._perc_images = []
         total = total / B
         if self.backbone is not None:

@@ -431,6 +431,22 @@ int ggd_image_loss(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, const float
                    const float* weights4, float* terms5, float* grad_image, void* tmp, size_t tmp_bytes);
 
 /*
+ * The same losses with --apply_mask_to_rendering (main/train_pano2gaussian_decoder.py:237-241): mask (device
+ * [mask_h, mask_w] fp32, H % mask_h == 0 and W % mask_w == 0, otherwise GGD_E_INVALID) is upsampled bilinearly by the
+ * integer factors H / mask_h, W / mask_w (torch.nn.functional.interpolate, align_corners=False) to m, and image and target
+ * are composited onto white, x' = (x*m + 1) - m, before every term; terms5 are those of the composited pair and
+ * grad_image = m * dloss/dimage'.  No gradient for target or mask.  Still three launches and the same tmp; neither the
+ * full-resolution mask nor the composited images are materialised.
+ * ggd_mask_composite: the composite as an operator of its own over src [channels,H,W] (for consumers that need the
+ * composited image itself): backward == 0: dst = (src*m + 1) - m; backward != 0: dst = src*m (src is then d/d dst).
+ */
+int ggd_image_loss_masked(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, const float* image, const float* target,
+                          const float* mask, int32_t mask_w, int32_t mask_h, const float* weights4, float* terms5,
+                          float* grad_image, void* tmp, size_t tmp_bytes);
+int ggd_mask_composite(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, int32_t channels, const float* src,
+                       const float* mask, int32_t mask_w, int32_t mask_h, int32_t backward, float* dst);
+
+/*
  * Exact 3-nearest-neighbour search: the `distCUDA2` of the simple_knn module that gaussian_splatting/scene/gaussian_model.py
  * imports (:20) to seed the scales of a new model (:132, :160).  points: DEVICE float32 [P][3], 4 <= P <= ggd_knn_max_points()
  * (2^26; fewer than 4 points have no three neighbours: GGD_E_INVALID).  For every point i, over all j != i (a different INDEX:
