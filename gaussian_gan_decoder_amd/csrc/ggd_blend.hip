@@ -7,9 +7,10 @@
 //   * The unit of work is an 8x8 QUARTER of a 16x16 tile, one pixel per lane: forward = one single-wave workgroup per
 //     quarter (the four quarters of a tile in consecutive dispatch slots of one XCD, so that they share its L2); backward =
 //     four independent quarter waves (large grids) or four quarter waves in one workgroup that combine their per-record sums
-//     in LDS (small grids).  Wider blocks (16x8 with 2 pixels per lane, 16x16 with 4) are kept as options: the VALU cost of a
-//     blended record is proportional to the pixels a wave holds (packed fp32 brings no throughput on gfx950), while a
-//     record typically reaches less than half of a block, so the smallest block culls finest and idles fewest lanes.
+//     in LDS (an explicit, non-default choice).  Why the smallest block: the VALU cost of a blended record is proportional to the
+//     pixels a wave holds (packed fp32 brings no throughput on gfx950), while a record typically reaches less than half of
+//     a block, so the smallest block culls finest and idles fewest lanes.  The wider blocks (16x8 with 2 pixels per lane,
+//     16x16 with 4) were measured and removed: DESIGN.md section 4 has the figures, git history the code.
 //   * A tile's depth-sorted list is consumed 64 records per round: lane j gathers record j (one 48-byte ggd_splat, three
 //     16-byte loads).  The gather is a two-stage software pipeline -- the list entries of round k + 2 and the records of
 //     round k + 1 are in flight while round k is blended.  The gathering lane tests its record against the wave's pixel
@@ -33,15 +34,6 @@ namespace {
 
 constexpr float ALPHA_FLOOR = 1.0f / 255.0f;
 
-typedef float f2 __attribute__((ext_vector_type(2)));  // -> v_pk_{add,mul,fma}_f32: two pixels per VALU issue
-
-// power = -1/2 (A dx^2 + C dy^2) - B dx dy for a pixel PAIR, in the project's fixed operation order (same as the
-// oracle's gauss_power):  fma( fma(-A/2, dx, -B*dy), dx, ((-C/2)*dy)*dy ).  hA = -A/2; nBdy, hCdy2 are per-lane.
-__device__ __forceinline__ f2 gauss_power2(float hA, float nBdy, float hCdy2, f2 dx) {
-  const f2 inner = __builtin_elementwise_fma((f2){hA, hA}, dx, (f2){nBdy, nBdy});
-  return __builtin_elementwise_fma(inner, dx, (f2){hCdy2, hCdy2});
-}
-
 // exp() variants for the blend (GGD_OPT_EXP_MODE).
 // The bare hardware exponential, written out: ONE expression shared by the forward (mode 1, and the forward half of the default
 // mode 3) and by the backward's contribution decision (bwd_update<3>), so that the two passes cannot drift apart with the way a
@@ -60,20 +52,6 @@ __device__ __forceinline__ float blend_exp(float x) {
     return __builtin_fmaf(e, lo * 0.693147182464599609375f, e);
   }
   return expf(x);                   // ocml, <= 1 ulp
-}
-
-// Two exps per call; MODE 2 is the same arithmetic as blend_exp<2> per component, with the multiplies / FMAs packed.
-template <int MODE>
-__device__ __forceinline__ f2 blend_exp2v(f2 x) {
-  if (MODE == 2) {
-    const f2 L2E = {1.44269502162933349609375f, 1.44269502162933349609375f};
-    const f2 t = x * L2E;
-    f2 lo = __builtin_elementwise_fma(x, L2E, -t);
-    lo = __builtin_elementwise_fma(x, (f2){1.925963033500011e-08f, 1.925963033500011e-08f}, lo);
-    const f2 e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-    return __builtin_elementwise_fma(e, lo * 0.693147182464599609375f, e);
-  }
-  return (f2){blend_exp<MODE>(x.x), blend_exp<MODE>(x.y)};
 }
 
 // Record-level pre-cull, done ONCE per gathered record by the lane that gathers it (the per-pixel cull costs every lane
@@ -125,31 +103,24 @@ __device__ __forceinline__ bool record_reaches_block(float x, float y, float hA,
 // on top of that halves the fetches again (23 MB) but costs time (151 us; shell 335 -> 354 us): neighbouring tiles
 // finish together and leave the XCDs unevenly loaded -- not used.  Tile counts that are not multiples of 8 keep
 // tile = b % T.
-__device__ __forceinline__ void ggd_block_to_tile(int b, int nsub, int gx, int gy, int T, int& tile, int& sub) {
-  (void)gx; (void)gy;
+__device__ __forceinline__ void ggd_block_to_tile(int b, int nsub, int T, int& tile, int& sub) {
   if ((T & 7) == 0) { const int q = b >> 3; sub = q % nsub; tile = (q / nsub) * 8 + (b & 7); }
   else { tile = b % T; sub = b / T; }
 }
 
-// Wave <-> pixel mapping of the blend kernels: a wave owns a BW x BH pixel block of a 16x16 tile, PXL horizontally
-// adjacent pixels per lane (BW / PXL lanes per row, BH = 64 * PXL / BW rows):
-//   PXL = 4, BW = 16: one wave per tile;      PXL = 2, BW = 16: two waves per tile (16x8 halves);
-//   PXL = 1, BW = 8 : four waves per tile (8x8 quarters).
-// The VALU cost of a blended record is proportional to the pixels a wave holds (packed fp32 brings no throughput on
-// gfx950), while a record typically reaches ~40 % of a 16x8 block: smaller blocks cull finer and leave fewer idle
-// lanes, at the price of more list scans.
-template <int PXL, int BW = 16>
-struct WaveGeom {
-  static constexpr int LPR = BW / PXL, BH = 64 / LPR, NSX = 16 / BW, NSUB = NSX * (16 / BH);
+// Wave <-> pixel mapping of the forward blend: a wave owns one 8x8 quarter of a 16x16 tile (2 x 2 quarters per tile), one
+// pixel per lane, 8 lanes per row and 8 rows.  (16x8 blocks with two pixels per lane and 16x16 blocks with four were
+// measured and removed: DESIGN.md section 4 has the figures, git history the code.)
+struct QuarterGeom {
   int px0, py;
   uint32_t lo, hi;
-  __device__ __forceinline__ WaveGeom(int b, int gx, int T, const uint32_t* __restrict__ ranges, uint32_t capacity = 0xffffffffu) {
+  __device__ __forceinline__ QuarterGeom(int b, int gx, int T, const uint32_t* __restrict__ ranges, uint32_t capacity) {
     int tile, sub;
-    ggd_block_to_tile(b, NSUB, gx, T / gx, T, tile, sub);
+    ggd_block_to_tile(b, 4, T, tile, sub);
     const int tx = tile % gx, ty = tile / gx;
     const int lane = threadIdx.x;
-    px0 = tx * 16 + (sub % NSX) * BW + (lane % LPR) * PXL;
-    py = ty * 16 + (sub / NSX) * BH + lane / LPR;
+    px0 = tx * 16 + (sub % 2) * 8 + lane % 8;
+    py = ty * 16 + (sub / 2) * 8 + lane / 8;
     const uint2 r = reinterpret_cast<const uint2*>(ranges)[tile];
     lo = min(r.x, capacity); hi = min(r.y, capacity);  // capacity < R only in a speculative forward that is retried
   }
@@ -183,7 +154,7 @@ __device__ __forceinline__ void fma_into(float& acc, float a, float b) {
 }
 
 // Forward blend.  Per staged record:
-//   (1) the `power` values of the lane's pixels (operation order == the published form),
+//   (1) the `power` value of the lane's pixel (operation order == the published form),
 //   (2) CULL: if no pixel of the wave can reach alpha >= 1/255 -- tested in the power domain against a per-record
 //       threshold ln(1/(255*opacity)) lowered by a safety margin, so the decision is exact w.r.t. the float alpha
 //       test that follows -- the whole wave skips the record before any exp,
@@ -197,20 +168,14 @@ __device__ __forceinline__ void fma_into(float& acc, float a, float b) {
 // in ramp and tail.
 // LDS reads through an explicit address-space-3 pointer (plain vector types: HIP's float4 class does not bind there)
 typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const v4f lds_cf4;
-typedef __attribute__((address_space(3))) const v2f lds_cf2;
 __device__ __forceinline__ float4 lds_read4(lds_cf4* p) { const v4f v = *p; return make_float4(v[0], v[1], v[2], v[3]); }
-__device__ __forceinline__ float2 lds_read2(lds_cf4* p, int word) {
-  const v2f v = *(lds_cf2*)((__attribute__((address_space(3))) const float*)p + word);
-  return make_float2(v[0], v[1]);
-}
 
 // AUX (the depth / alpha extension, ggd_forward_aux): the gathering lane also loads the Gaussian's view-space depth
 // (depth_keys = the fp32 bits of z, the depth sort's key) and stages it in the record's twelfth word, which the plain blend
 // does not use (the cull extent ey, dead once the pre-cull has run) -- the staging area keeps its 48 bytes per record.  Per
 // record one more FMA under the colour's `upd` mask accumulates sum(alpha T z); the epilogue writes it and 1 - T.
-template <int EXP_MODE, bool CULL, int PXL, int BW, bool STATS, bool AUX = false>
+template <int EXP_MODE, bool CULL, bool STATS, bool AUX = false>
 __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int W, int H, int gx, int T,
                                                     const ggd_splat* __restrict__ splat,
                                                     const uint32_t* __restrict__ list,
@@ -228,52 +193,37 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
 #endif
   constexpr int GRP = GGD_FWD_GRP;   // staged records per straight-line group
   const int lane = threadIdx.x;
-  using Geom = WaveGeom<PXL, BW>;
-  const Geom g(blk, gx, T, ranges, capacity);
+  const QuarterGeom g(blk, gx, T, ranges, capacity);
   const bool row_in = g.py < H;
   float INF = __builtin_huge_valf();
   asm volatile("" : "+v"(INF));   // keep it in a VGPR (VOP3 selects take no 32-bit literal)
   uint32_t st_visited = 0, st_culled = 0, st_lanes = 0, st_pixels = 0, st_inloop = 0;  // wave-uniform debug counters (GGD stats)
   const uint64_t st_t0 = STATS ? wall_clock64() : 0ull;                // 100 MHz constant clock: the wave's residency
-  float Tr[PXL], C[PXL][3];   // per pixel: transmittance, accumulated colour
-  float D[AUX ? PXL : 1];     // AUX: accumulated depth
-  uint32_t last[PXL];
-  float px[PXL];              // pixel x coordinates; +inf once the pixel is finished / outside the image
+  float Tr = 1.0f, C[3] = {0.0f, 0.0f, 0.0f};   // the lane's pixel: transmittance, accumulated colour
+  float D = 0.0f;                               // AUX: accumulated depth
+  uint32_t last = 0;
+  float px = (row_in && g.px0 < W) ? (float)g.px0 : INF;   // pixel x coordinate; +inf once the pixel is finished / outside the image
   const float pyf = (float)g.py;
-#pragma unroll
-  for (int k = 0; k < PXL; ++k) {
-    Tr[k] = 1.0f; C[k][0] = C[k][1] = C[k][2] = 0.0f;
-    if constexpr (AUX) D[k] = 0.0f;
-    last[k] = 0;
-    px[k] = (row_in && (g.px0 + k) < W) ? (float)(g.px0 + k) : INF;
-  }
-  auto wave_alive = [&]() {
-    uint64_t m = 0ull;
-#pragma unroll
-    for (int k = 0; k < PXL; ++k) m |= __ballot(px[k] < INF);
-    return m != 0ull;
-  };
+  auto wave_alive = [&]() { return __ballot(px < INF) != 0ull; };
 
   // the wave's pixel rectangle (pixel centres), for the record-level pre-cull
-  const float wx0 = (float)(g.px0 - (lane % Geom::LPR) * PXL), wx1 = wx0 + (float)(BW - 1);
-  const float wy0 = (float)(g.py - lane / Geom::LPR), wy1 = wy0 + (float)(Geom::BH - 1);
+  const float wx0 = (float)(g.px0 - lane % 8), wx1 = wx0 + 7.0f;
+  const float wy0 = (float)(g.py - lane / 8), wy1 = wy0 + 7.0f;
   const uint64_t lt_mask = (1ull << lane) - 1ull;
-  // ... shrunk, round by round, to the bounding rectangle of the pixels that are still LIVE (8x8 one-pixel-per-lane form):
+  // ... shrunk, round by round, to the bounding rectangle of the pixels that are still LIVE:
   // a wave runs until its last pixel is finished, and towards the end most records reach the block but none of the few
   // pixels left -- each such record cost a whole-wave test in the blend loop instead of one lane of the pre-cull.  Exact:
   // a finished pixel ignores every record.
   float lx0 = wx0, lx1 = wx1, ly0 = wy0, ly1 = wy1;
   auto shrink_rect = [&]() {
-    if constexpr (PXL == 1 && BW == 8) {
-      const uint64_t live = __ballot(px[0] < INF);
-      if (live != 0ull) {
-        const int rmin = __builtin_ctzll(live) >> 3, rmax = (63 - __builtin_clzll(live)) >> 3;
-        uint32_t m = (uint32_t)live | (uint32_t)(live >> 32);
-        m |= m >> 16; m |= m >> 8; m &= 0xffu;
-        const int cmin = __builtin_ctz(m), cmax = 31 - __builtin_clz(m);
-        lx0 = wx0 + (float)cmin; lx1 = wx0 + (float)cmax;
-        ly0 = wy0 + (float)rmin; ly1 = wy0 + (float)rmax;
-      }
+    const uint64_t live = __ballot(px < INF);
+    if (live != 0ull) {
+      const int rmin = __builtin_ctzll(live) >> 3, rmax = (63 - __builtin_clzll(live)) >> 3;
+      uint32_t m = (uint32_t)live | (uint32_t)(live >> 32);
+      m |= m >> 16; m |= m >> 8; m &= 0xffu;
+      const int cmin = __builtin_ctz(m), cmax = 31 - __builtin_clz(m);
+      lx0 = wx0 + (float)cmin; lx1 = wx0 + (float)cmax;
+      ly0 = wy0 + (float)rmin; ly1 = wy0 + (float)rmax;
     }
   };
 
@@ -297,7 +247,7 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
   // register allocator split with copies right behind the loads, i.e. waits)
   const uint32_t last_pos = g.hi - 1u;   // only used when g.hi > g.lo
   auto load_id = [&](uint32_t pos) { id_nxt = list[min(pos, last_pos)]; };
-  auto load_rec = [&](uint32_t) {
+  auto load_rec = [&]() {
     const float4* p = reinterpret_cast<const float4*>(splat + id_nxt);
     r0 = p[0]; r1 = p[1]; r2 = p[2];
     if constexpr (AUX) zk = depth_keys[id_nxt];
@@ -314,7 +264,7 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
   };
   if (g.hi <= g.lo || !wave_alive()) goto all_done;
   load_id(g.lo + lane);
-  load_rec(g.lo + lane);
+  load_rec();
   load_id(g.lo + 64 + lane);
   for (uint32_t base = g.lo; base < g.hi; base += 64) {
     if (CULL) shrink_rect();
@@ -335,8 +285,11 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
       st_visited += min(64u, g.hi - base);
       st_culled += min(64u, g.hi - base) - (uint32_t)__popcll(kept);
     }
-    load_rec(base + 64 + lane);    // next round's records (their list entries were requested one round ago)
-    load_id(base + 128 + lane);    // and the list entries of the round after it
+    load_rec();                    // next round's records (their list entries were requested one round ago)
+    // (that round's first position, named HERE: it is the loop's own increment, and formed only at the bottom of the loop it
+    // makes the compiler rotate the loop, which costs the instances without pre-cull two VGPRs)
+    const uint32_t next = base + 64;
+    load_id(next + 64 + lane);     // and the list entries of the round after it
     __syncthreads();
     for (int j0 = 0; j0 < n8; j0 += GRP) {
       if (!wave_alive()) goto all_done;
@@ -368,41 +321,27 @@ __device__ __forceinline__ void blend_forward_block(int blk, float4* s_rec, int 
         }
         const float dy = a.y - pyf;
         const float nBdy = a.w * dy, hCdy2 = (b01.x * dy) * dy;
-        float pw[PXL];
-        uint64_t need[PXL], any = 0ull;
-#pragma unroll
-        for (int k = 0; k < PXL; ++k) {
-          const float dx = a.x - px[k];
-          pw[k] = __builtin_fmaf(__builtin_fmaf(a.z, dx, nBdy), dx, hCdy2);
-          need[k] = __ballot(pw[k] >= b01.y);
-          any |= need[k];
-        }
-        if (any == 0ull) { if (STATS && j0 + jj < n) { st_culled += 1; st_inloop += 1; } continue; }
-        if (STATS) {
-          uint64_t lanes = 0ull;
-#pragma unroll
-          for (int k = 0; k < PXL; ++k) { lanes |= need[k]; st_pixels += (uint32_t)__popcll(need[k]); }
-          st_lanes += (uint32_t)__popcll(lanes);
-        }
+        const float dx = a.x - px;
+        const float pw = __builtin_fmaf(__builtin_fmaf(a.z, dx, nBdy), dx, hCdy2);
+        const uint64_t need = __ballot(pw >= b01.y);
+        if (need == 0ull) { if (STATS && j0 + jj < n) { st_culled += 1; st_inloop += 1; } continue; }
+        if (STATS) { st_pixels += (uint32_t)__popcll(need); st_lanes += (uint32_t)__popcll(need); }
         const float2 b23 = make_float2(b4.z, b4.w);                                                                   // opacity, r
         const uint32_t contributor = __float_as_uint(c.z);
-#pragma unroll
-        for (int k = 0; k < PXL; ++k) {
-          const float G = blend_exp<EXP_MODE>(pw[k]);
-          const float alpha = fminf(0.99f, G * b23.x);
-          const uint64_t live = need[k] & ~__ballot(pw[k] > 0.0f) & ~__ballot(alpha < ALPHA_FLOOR);
-          const float test_T = Tr[k] * (1.0f - alpha);
-          const uint64_t low = __ballot(test_T < 0.0001f);
-          const uint64_t upd = live & ~low, stop = live & low;
-          const float w = sel_or_zero(alpha * Tr[k], upd);
-          fma_into(C[k][0], b23.y, w);
-          fma_into(C[k][1], c.x, w);
-          fma_into(C[k][2], c.y, w);
-          if constexpr (AUX) fma_into(D[k], c.w, w);
-          sel_into_after(Tr[k], test_T, upd, w);
-          sel_into(last[k], contributor, upd);
-          if (stop) sel_into(px[k], INF, stop);   // a pixel stops once: a scalar branch (SCC of the s_and above), not a select per update
-        }
+        const float G = blend_exp<EXP_MODE>(pw);
+        const float alpha = fminf(0.99f, G * b23.x);
+        const uint64_t live = need & ~__ballot(pw > 0.0f) & ~__ballot(alpha < ALPHA_FLOOR);
+        const float test_T = Tr * (1.0f - alpha);
+        const uint64_t low = __ballot(test_T < 0.0001f);
+        const uint64_t upd = live & ~low, stop = live & low;
+        const float w = sel_or_zero(alpha * Tr, upd);
+        fma_into(C[0], b23.y, w);
+        fma_into(C[1], c.x, w);
+        fma_into(C[2], c.y, w);
+        if constexpr (AUX) fma_into(D, c.w, w);
+        sel_into_after(Tr, test_T, upd, w);
+        sel_into(last, contributor, upd);
+        if (stop) sel_into(px, INF, stop);   // a pixel stops once: a scalar branch (SCC of the s_and above), not a select per update
       }
     }
   }
@@ -424,57 +363,18 @@ all_done:
     atomicAdd(stats + 4, (unsigned long long)(g.hi - g.lo));
     atomicAdd(stats + 5, (unsigned long long)st_inloop);
   }
-  if (!row_in) return;
-  const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
+  if (!row_in || g.px0 >= W) return;
   const size_t HW = (size_t)H * W;
   const size_t pix0 = (size_t)g.py * W + g.px0;
   if constexpr (AUX) {
-#pragma unroll
-    for (int k = 0; k < PXL; ++k) {
-      if (g.px0 + k < W) {
-        out_depth[pix0 + k] = D[k];
-        out_alpha[pix0 + k] = 1.0f - Tr[k];
-      }
-    }
+    out_depth[pix0] = D;
+    out_alpha[pix0] = 1.0f - Tr;
   }
-  if (g.px0 + PXL - 1 < W && (W & 3) == 0) {
-    if constexpr (PXL == 4) {
-      *reinterpret_cast<float4*>(final_T + pix0) = make_float4(Tr[0], Tr[1], Tr[2], Tr[3]);
-      *reinterpret_cast<uint4*>(n_contrib + pix0) = make_uint4(last[0], last[1], last[2], last[3]);
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const float bgc = ch == 0 ? bg0 : (ch == 1 ? bg1 : bg2);
-        *reinterpret_cast<float4*>(out_color + ch * HW + pix0) = make_float4(
-            C[0][ch] + Tr[0] * bgc, C[1][ch] + Tr[1] * bgc, C[2][ch] + Tr[2] * bgc, C[3][ch] + Tr[3] * bgc);
-      }
-    } else if constexpr (PXL == 2) {
-      *reinterpret_cast<float2*>(final_T + pix0) = make_float2(Tr[0], Tr[1]);
-      *reinterpret_cast<uint2*>(n_contrib + pix0) = make_uint2(last[0], last[1]);
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const float bgc = ch == 0 ? bg0 : (ch == 1 ? bg1 : bg2);
-        *reinterpret_cast<float2*>(out_color + ch * HW + pix0) =
-            make_float2(C[0][ch] + Tr[0] * bgc, C[1][ch] + Tr[1] * bgc);
-      }
-    } else {
-      final_T[pix0] = Tr[0];
-      n_contrib[pix0] = last[0];
-      out_color[pix0] = C[0][0] + Tr[0] * bg0;
-      out_color[HW + pix0] = C[0][1] + Tr[0] * bg1;
-      out_color[2 * HW + pix0] = C[0][2] + Tr[0] * bg2;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < PXL; ++k) {
-      if (g.px0 + k < W) {
-        final_T[pix0 + k] = Tr[k];
-        n_contrib[pix0 + k] = last[k];
-        out_color[pix0 + k] = C[k][0] + Tr[k] * bg0;
-        out_color[HW + pix0 + k] = C[k][1] + Tr[k] * bg1;
-        out_color[2 * HW + pix0 + k] = C[k][2] + Tr[k] * bg2;
-      }
-    }
-  }
+  final_T[pix0] = Tr;
+  n_contrib[pix0] = last;
+  out_color[pix0] = C[0] + Tr * bg[0];
+  out_color[HW + pix0] = C[1] + Tr * bg[1];
+  out_color[2 * HW + pix0] = C[2] + Tr * bg[2];
 }
 
 // One 8x8 quarter per single-wave workgroup (the launch has 4 T workgroups; workgroup b -> (XCD, tile, quarter), see
@@ -486,7 +386,7 @@ all_done:
 // memory, the hardware dispatcher back-fills a finished wave's slot without one.  Removed again.
 // AUX: the same blend with the depth / alpha planes (blend_forward_block); depth_keys, out_depth and out_alpha are NULL, and
 // never read, in a plain frame.
-template <int EXP_MODE, bool CULL, int PXL, int BW, bool STATS, bool AUX = false>
+template <int EXP_MODE, bool CULL, bool STATS, bool AUX = false>
 __global__ __launch_bounds__(64) void blend_forward_kernel(int W, int H, int gx, int T,
                                                            const ggd_splat* __restrict__ splat,
                                                            const uint32_t* __restrict__ list,
@@ -500,7 +400,7 @@ __global__ __launch_bounds__(64) void blend_forward_kernel(int W, int H, int gx,
                                                            float* __restrict__ out_depth,
                                                            float* __restrict__ out_alpha) {
   __shared__ float4 s_rec[64 * 3];
-  blend_forward_block<EXP_MODE, CULL, PXL, BW, STATS, AUX>((int)blockIdx.x, s_rec, W, H, gx, T, splat, list, ranges, capacity,
+  blend_forward_block<EXP_MODE, CULL, STATS, AUX>((int)blockIdx.x, s_rec, W, H, gx, T, splat, list, ranges, capacity,
                                                            bg, out_color, final_T, n_contrib, stats, depth_keys, out_depth,
                                                            out_alpha);
 }
@@ -517,12 +417,53 @@ __global__ __launch_bounds__(64) void blend_forward_kernel(int W, int H, int gx,
 //     component) by the flush, not per pixel.
 struct BwdPixel { float T, nTfin, bgdot, acc[3], gpx[3]; };
 // AUX (depth / alpha extension): the depth is a fourth channel with background 0 (accD = the depth composited behind the
-// record, gD = dL/ddepth of the pixel); dL/dalpha of the pixel is folded into bgdot (bwd_aux_init)
+// record, gD = dL/ddepth of the pixel); dL/dalpha of the pixel is folded into bgdot (bwd_pixel_init)
 struct BwdPixelAux : BwdPixel { float accD, gD; };
-// alpha = 1 - T_final: dL/dT_final = bg . dL/dpix - dL/dalpha, folded into bgdot once (NULL gradients are passed as zero)
+// The pixel's state at the back of its list (`in`: the pixel lies inside the image); returns the 1-based list position of its
+// last contributor.  AUX: alpha = 1 - T_final, so dL/dT_final = bg . dL/dpix - dL/dalpha, folded into bgdot once (NULL
+// gradients are taken as zero)
 template <bool AUX, typename Pix>
-__device__ __forceinline__ void bwd_aux_init(Pix& st, float gD, float gA) {
-  if constexpr (AUX) { st.accD = 0.0f; st.gD = gD; st.bgdot = st.bgdot - gA; }
+__device__ __forceinline__ uint32_t bwd_pixel_init(Pix& st, bool in, size_t pix0, size_t HW, const float* __restrict__ bg,
+                                                   const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
+                                                   const float* __restrict__ dL_dpix, const float* __restrict__ dL_ddepth,
+                                                   const float* __restrict__ dL_dalpha) {
+  const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
+  const float tf = in ? final_T[pix0] : 0.0f;
+  const uint32_t lastn = in ? n_contrib[pix0] : 0u;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) { st.gpx[ch] = in ? dL_dpix[ch * HW + pix0] : 0.0f; st.acc[ch] = 0.0f; }
+  st.bgdot = (bg0 * st.gpx[0] + bg1 * st.gpx[1]) + bg2 * st.gpx[2];
+  if constexpr (AUX) {
+    st.accD = 0.0f;
+    st.gD = (in && dL_ddepth) ? dL_ddepth[pix0] : 0.0f;
+    st.bgdot = st.bgdot - ((in && dL_dalpha) ? dL_dalpha[pix0] : 0.0f);
+  }
+  st.T = tf; st.nTfin = -tf;
+  return lastn;
+}
+
+// Lanes that hold a result of wave_reduce_swap (is_writer: lanes 0,4,8,12 | 32,36,40,44, lane 1 the opacity sum, AUX: lane 33
+// the depth sum) and the word of the accumulator record it belongs to: reduction output index (colour r g b | conic A B C |
+// mean sums x y | opacity | AUX: depth) -> slot in the record's order (conic A B C | opacity | mean x y | colour r g b | depth)
+template <bool AUX>
+__device__ __forceinline__ int bwd_writer_comp(int lane, bool& is_writer) {
+  is_writer = (lane & 19) == 0 || lane == 1 || (AUX && lane == 33);
+  const int val = lane == 1 ? 8 : ((AUX && lane == 33) ? 9 : 4 * (lane >> 5) + (((lane >> 2) & 1) << 1) + ((lane >> 3) & 1));
+  return val < 3 ? GGD_ACC_COLOR + val
+       : (val < 6 ? GGD_ACC_CONIC + (val - 3)
+       : (val < 8 ? GGD_ACC_MEAN2D + (val - 6) : ((AUX && val == 9) ? GGD_ACC_DEPTH : GGD_ACC_OPACITY)));
+}
+
+// The list is walked back to front in rounds of at most 64 entries: first position of the round that ends at `ce` (exclusive,
+// ce > lo = the list's first position)
+__device__ __forceinline__ uint32_t bwd_round_start(uint32_t ce, uint32_t lo) { return (ce - lo > 64u) ? ce - 64u : lo; }
+
+// The staged list is walked in groups of 8: slots nk .. n8 - 1 are filled with a record nobody sees (power threshold +inf)
+__device__ __forceinline__ void bwd_stage_padding(float4* rec, int lane, int nk, int n8) {
+  if (lane >= nk && lane < n8) {
+    rec[lane * 3 + 0] = make_float4(0, 0, 0, 0);
+    rec[lane * 3 + 1] = make_float4(0, __builtin_huge_valf(), 0, 0);
+  }
 }
 
 template <int EXP_MODE, bool AUX = false, typename Pix = BwdPixel>
@@ -597,96 +538,66 @@ __device__ __forceinline__ float bwd_scale(int comp, float v, float swx, float s
 // {x0 rows 2,3 | x1 rows 2,3}, whose sum holds x0's values in lanes 0-31 and x1's in lanes 32-63 (two rows each);
 // v_permlane16_swap of that sum with a copy of itself pairs the remaining two rows.  Result per lane l:
 //   (l & 3) != 1:  value 4 * (l >> 5) + {0, 2, 1, 3}[(l >> 2) & 3]     l < 32 and (l & 3) == 1:  the ninth value
-__device__ __forceinline__ float wave_reduce9_swap(float (&v)[8], float ninth, uint64_t ninth_lanes /* 0x2222... */) {
-  asm volatile(
-      "s_nop 1\n\t"
-      "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-      "v_add_f32_dpp %2, %2, %2 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-      "v_add_f32_dpp %4, %4, %4 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-      "v_add_f32_dpp %6, %6, %6 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-      "v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-      "v_add_f32_dpp %2, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-      "v_add_f32_dpp %4, %5, %5 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-      "v_add_f32_dpp %6, %7, %7 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-      "v_add_f32_dpp %8, %8, %8 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 0\n\t"
-      "v_add_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
-      "v_add_f32_dpp %4, %4, %4 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
-      "v_add_f32_dpp %8, %8, %8 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %0, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
-      "v_add_f32_dpp %4, %6, %6 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
-      "s_nop 1\n\t"
-      "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %4, %4, %4 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %8, %8, %8 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 0\n\t"
-      "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %4, %4, %4 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %8, %8, %8 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_cndmask_b32_e64 %0, %0, %8, %9\n\t"
-      "s_nop 1\n\t"
-      "v_permlane32_swap_b32 %0, %4\n\t"
-      "s_nop 1\n\t"
-      "v_add_f32_e32 %0, %0, %4\n\t"
-      "v_mov_b32_e32 %4, %0\n\t"
-      "s_nop 1\n\t"
-      "v_permlane16_swap_b32 %0, %4\n\t"
-      "s_nop 1\n\t"
+// TENTH (AUX: the depth sum): a tenth value takes the ninth's four in-row steps and rides in the redundant lanes 4b + 1 of the
+// OTHER folded register (v[4]): after the two swaps lanes 32 <= l < 64 with (l & 3) == 1 hold it.
+// The text of the two forms is assembled from the same pieces: ONLY10(x) is x in the ten-value form and nothing in the other.
+#define GGD_RED_ROWSUM(r, ctl) "v_add_f32_dpp " r ", " r ", " r " " ctl " row_mask:0xf bank_mask:0xf\n\t"
+#define GGD_RED_KEEP(x) x
+#define GGD_RED_DROP(x)
+#define GGD_RED_TEXT(ONLY10)                                                                  \
+      "s_nop 1\n\t"                                                                           \
+      "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"                     \
+      "v_add_f32_dpp %2, %2, %2 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"                     \
+      "v_add_f32_dpp %4, %4, %4 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"                     \
+      "v_add_f32_dpp %6, %6, %6 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"                     \
+      "v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                     \
+      "v_add_f32_dpp %2, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                     \
+      "v_add_f32_dpp %4, %5, %5 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                     \
+      "v_add_f32_dpp %6, %7, %7 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                     \
+      GGD_RED_ROWSUM("%[ninth]", "row_ror:8") ONLY10(GGD_RED_ROWSUM("%[tenth]", "row_ror:8"))  \
+      "s_nop 0\n\t"                                                                           \
+      "v_add_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"                     \
+      "v_add_f32_dpp %4, %4, %4 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"                     \
+      GGD_RED_ROWSUM("%[ninth]", "row_ror:4") ONLY10(GGD_RED_ROWSUM("%[tenth]", "row_ror:4"))  \
+      "v_add_f32_dpp %0, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"                     \
+      "v_add_f32_dpp %4, %6, %6 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"                     \
+      "s_nop 1\n\t"                                                                           \
+      GGD_RED_ROWSUM("%0", "quad_perm:[2,3,0,1]") GGD_RED_ROWSUM("%4", "quad_perm:[2,3,0,1]")  \
+      GGD_RED_ROWSUM("%[ninth]", "quad_perm:[2,3,0,1]") ONLY10(GGD_RED_ROWSUM("%[tenth]", "quad_perm:[2,3,0,1]")) \
+      "s_nop 0\n\t"                                                                           \
+      GGD_RED_ROWSUM("%0", "quad_perm:[1,0,3,2]") GGD_RED_ROWSUM("%4", "quad_perm:[1,0,3,2]")  \
+      GGD_RED_ROWSUM("%[ninth]", "quad_perm:[1,0,3,2]") ONLY10(GGD_RED_ROWSUM("%[tenth]", "quad_perm:[1,0,3,2]")) \
+      "s_nop 1\n\t"                                                                           \
+      "v_cndmask_b32_e64 %0, %0, %[ninth], %[mask]\n\t"                                       \
+      ONLY10("v_cndmask_b32_e64 %4, %4, %[tenth], %[mask]\n\t")                               \
+      "s_nop 1\n\t"                                                                           \
+      "v_permlane32_swap_b32 %0, %4\n\t"                                                      \
+      "s_nop 1\n\t"                                                                           \
+      "v_add_f32_e32 %0, %0, %4\n\t"                                                          \
+      "v_mov_b32_e32 %4, %0\n\t"                                                              \
+      "s_nop 1\n\t"                                                                           \
+      "v_permlane16_swap_b32 %0, %4\n\t"                                                      \
+      "s_nop 1\n\t"                                                                           \
       "v_add_f32_e32 %0, %0, %4"
-      : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(ninth)
-      : "s"(ninth_lanes));
+template <bool TENTH>
+__device__ __forceinline__ float wave_reduce_swap(float (&v)[8], float ninth, float tenth) {
+  const uint64_t ninth_lanes = 0x2222222222222222ull;   // lane 4b + 1 of every bank
+  if constexpr (TENTH)
+    asm volatile(GGD_RED_TEXT(GGD_RED_KEEP)
+                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
+                   [ninth] "+v"(ninth), [tenth] "+v"(tenth)
+                 : [mask] "s"(ninth_lanes));
+  else
+    asm volatile(GGD_RED_TEXT(GGD_RED_DROP)
+                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
+                   [ninth] "+v"(ninth)
+                 : [mask] "s"(ninth_lanes));
   return v[0];
 }
-
-// wave_reduce9_swap plus a tenth value (AUX: the depth sum), which takes the ninth's four in-row steps and rides in the
-// redundant lanes 4b + 1 of the OTHER folded register (v[4]): after the two swaps lanes 32 <= l < 64 with (l & 3) == 1 hold it.
-__device__ __forceinline__ float wave_reduce10_swap(float (&v)[8], float ninth, float tenth, uint64_t ninth_lanes /* 0x2222... */) {
-  asm volatile(
-      "s_nop 1\n\t"
-      "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-      "v_add_f32_dpp %2, %2, %2 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-      "v_add_f32_dpp %4, %4, %4 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-      "v_add_f32_dpp %6, %6, %6 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-      "v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-      "v_add_f32_dpp %2, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-      "v_add_f32_dpp %4, %5, %5 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-      "v_add_f32_dpp %6, %7, %7 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-      "v_add_f32_dpp %8, %8, %8 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %9, %9, %9 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 0\n\t"
-      "v_add_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
-      "v_add_f32_dpp %4, %4, %4 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
-      "v_add_f32_dpp %8, %8, %8 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %9, %9, %9 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %0, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
-      "v_add_f32_dpp %4, %6, %6 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
-      "s_nop 1\n\t"
-      "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %4, %4, %4 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %8, %8, %8 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %9, %9, %9 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 0\n\t"
-      "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %4, %4, %4 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %8, %8, %8 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %9, %9, %9 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_cndmask_b32_e64 %0, %0, %8, %10\n\t"
-      "v_cndmask_b32_e64 %4, %4, %9, %10\n\t"
-      "s_nop 1\n\t"
-      "v_permlane32_swap_b32 %0, %4\n\t"
-      "s_nop 1\n\t"
-      "v_add_f32_e32 %0, %0, %4\n\t"
-      "v_mov_b32_e32 %4, %0\n\t"
-      "s_nop 1\n\t"
-      "v_permlane16_swap_b32 %0, %4\n\t"
-      "s_nop 1\n\t"
-      "v_add_f32_e32 %0, %0, %4"
-      : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(ninth), "+v"(tenth)
-      : "s"(ninth_lanes));
-  return v[0];
-}
+#undef GGD_RED_TEXT
+#undef GGD_RED_DROP
+#undef GGD_RED_KEEP
+#undef GGD_RED_ROWSUM
 
 // ---- backward blend, tile form: the four 8x8 quarter waves of a tile in ONE workgroup --------------------------------
 // (~60 VGPRs -> 8 waves per SIMD.)  Per round of 64 list entries every wave gathers the records itself (the other waves'
@@ -710,7 +621,7 @@ __global__ __launch_bounds__(256) void blend_backward_tile_kernel(
   __shared__ uint32_t s_maxn[NW];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int tile, sub_unused;
-  ggd_block_to_tile((int)blockIdx.x, 1, gx, gy, gx * gy, tile, sub_unused);
+  ggd_block_to_tile((int)blockIdx.x, 1, gx * gy, tile, sub_unused);
   const int tx = tile % gx, ty = tile / gx;
   const int qx = wv & 1, qy = wv >> 1;
   const int px0 = tx * 16 + qx * 8 + (lane & 7), py = ty * 16 + qy * 8 + (lane >> 3);
@@ -720,14 +631,8 @@ __global__ __launch_bounds__(256) void blend_backward_tile_kernel(
   const size_t pix0 = (size_t)py * W + px0;
 
   BwdPixel st;
-  const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
   const float pxf = (float)px0, pyf = (float)py;
-  const float tf = in ? final_T[pix0] : 0.0f;
-  const uint32_t lastn = in ? n_contrib[pix0] : 0u;
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) { st.gpx[ch] = in ? dL_dpix[ch * HW + pix0] : 0.0f; st.acc[ch] = 0.0f; }
-  st.bgdot = (bg0 * st.gpx[0] + bg1 * st.gpx[1]) + bg2 * st.gpx[2];
-  st.T = tf; st.nTfin = -tf;
+  const uint32_t lastn = bwd_pixel_init<false>(st, in, pix0, HW, bg, final_T, n_contrib, dL_dpix, nullptr, nullptr);
   uint32_t maxn = lastn;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, d, 64));
@@ -742,12 +647,8 @@ __global__ __launch_bounds__(256) void blend_backward_tile_kernel(
   const float wx1 = wx0 + 7.0f, wy1 = wy0 + 7.0f;
   const uint64_t lt_mask = (1ull << lane) - 1ull;
   float4* rec = s_rec[wv];
-  const bool is_writer = (lane & 19) == 0 || lane == 1;
-  // reduction output index (colour r g b | conic A B C | mean sums x y | opacity) -> slot in the accumulator record's order
-  const int writer_val = lane == 1 ? 8 : 4 * (lane >> 5) + (((lane >> 2) & 1) << 1) + ((lane >> 3) & 1);
-  const int writer_comp = writer_val < 3 ? GGD_ACC_COLOR + writer_val
-                        : (writer_val < 6 ? GGD_ACC_CONIC + (writer_val - 3)
-                        : (writer_val < 8 ? GGD_ACC_MEAN2D + (writer_val - 6) : GGD_ACC_OPACITY));
+  bool is_writer;
+  const int writer_comp = bwd_writer_comp<false>(lane, is_writer);
 
   // staged = the record as loaded with three words replaced in place (no component changes its 16-byte word, see the forward):
   //   {x, y, hA, nB} {hC, power threshold, opacity, 0-based list position} {g, b, r, index inside the round}
@@ -756,20 +657,19 @@ __global__ __launch_bounds__(256) void blend_backward_tile_kernel(
   // (the round in FRONT of it: the list is walked back to front) and the list entries of round k + 2 are in flight.
   uint32_t id_cur = 0, id_nxt = 0;     // Gaussian ids of the round whose records are in r0..r2 / of the round after it
   float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0;    // x y hA nB | hC thr opacity r | g b ex ey
-  auto round_start = [&](uint32_t ce) { return (ce - rg.x > 64u) ? ce - 64u : rg.x; };   // ce > rg.x
   // (unconditional loads from clamped positions, see the forward; maxn > 0 here, so the list is not empty)
   auto load_id = [&](uint32_t ce) {    // the round that ends at list position ce (exclusive); ce <= rg.x: a dummy re-read
-    const uint32_t cs = ce > rg.x ? round_start(ce) : rg.x;
+    const uint32_t cs = ce > rg.x ? bwd_round_start(ce, rg.x) : rg.x;
     id_nxt = list[min(cs + (uint32_t)lane, rg.x + maxn - 1u)];
   };
-  auto load_rec = [&](uint32_t) {
+  auto load_rec = [&]() {
     id_cur = id_nxt;
     const float4* p = reinterpret_cast<const float4*>(splat + id_nxt);
     r0 = p[0]; r1 = p[1]; r2 = p[2];
   };
   auto consume = [&](uint32_t ce) {
     keep = false;
-    const uint32_t cs = round_start(ce);
+    const uint32_t cs = bwd_round_start(ce, rg.x);
     if ((uint32_t)lane < ce - cs) {
       keep = CULL ? (record_box_hits(r0.x, r0.y, r2.z, r2.w, wx0, wx1, wy0, wy1) &&
                      record_reaches_block(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r2.z, wx0, wx1, wy0, wy1)) : true;
@@ -782,11 +682,11 @@ __global__ __launch_bounds__(256) void blend_backward_tile_kernel(
 
   uint32_t cend = rg.x + maxn;  // one past the last position that matters
   load_id(cend);
-  load_rec(cend);
-  load_id(round_start(cend));
+  load_rec();
+  load_id(bwd_round_start(cend, rg.x));
   int par = 0;
   while (cend > rg.x) {
-    const uint32_t cstart = round_start(cend);
+    const uint32_t cstart = bwd_round_start(cend, rg.x);
     const int n = (int)(cend - cstart);
     consume(cend);                                       // the records requested one round ago
     const uint64_t kept = __ballot(keep);
@@ -795,13 +695,10 @@ __global__ __launch_bounds__(256) void blend_backward_tile_kernel(
       const int slot = __popcll(kept & lt_mask);
       rec[slot * 3 + 0] = r0; rec[slot * 3 + 1] = r1; rec[slot * 3 + 2] = r2;
     }
-    if (lane >= nk && lane < n8) {   // padding: a record nobody sees
-      rec[lane * 3 + 0] = make_float4(0, 0, 0, 0);
-      rec[lane * 3 + 1] = make_float4(0, __builtin_huge_valf(), 0, 0);
-    }
+    bwd_stage_padding(rec, lane, nk, n8);
     if (wv == 0 && lane < n) { s_id[par][lane] = id_cur; s_cop[par][lane] = make_float4(r0.z, r0.w, r1.x, r1.z); }
-    load_rec(cstart);                                    // next round's records
-    load_id(cstart > rg.x ? round_start(cstart) : rg.x); // and the list entries of the round after it
+    load_rec();                                          // next round's records
+    load_id(cstart > rg.x ? bwd_round_start(cstart, rg.x) : rg.x); // and the list entries of the round after it
     __builtin_amdgcn_wave_barrier();
     __threadfence_block();
     uint64_t touched = 0ull;
@@ -824,8 +721,7 @@ __global__ __launch_bounds__(256) void blend_backward_tile_kernel(
         if (live != 0ull) {   // wave-uniform: somebody in this wave saw the Gaussian
           const uint32_t ridx = (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(c.w));
           touched |= 1ull << ridx;
-          const float tot = wave_reduce9_swap(s, sop, 0x2222222222222222ull);
-          // writers: lanes 0,4,8,12 | 32,36,40,44 (component from the table above), lane 1 the opacity sum
+          const float tot = wave_reduce_swap<false>(s, sop, 0.0f);
           if (is_writer) s_sum[par][wv][ridx][writer_comp] = tot;
         }
       }
@@ -902,7 +798,7 @@ __global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
   __shared__ float s_z[AUX ? 64 : 1];   // AUX: the staged records' depths (unused, and not allocated, otherwise)
   const int lane = threadIdx.x;
   int tile, sub;
-  ggd_block_to_tile((int)blockIdx.x, 4, gx, gy, gx * gy, tile, sub);
+  ggd_block_to_tile((int)blockIdx.x, 4, gx * gy, tile, sub);
   const int tx = tile % gx, ty = tile / gx;
   const int qx = sub & 1, qy = sub >> 1;
   const int px0 = tx * 16 + qx * 8 + (lane & 7), py = ty * 16 + qy * 8 + (lane >> 3);
@@ -912,15 +808,8 @@ __global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
   const size_t pix0 = (size_t)py * W + px0;
 
   std::conditional_t<AUX, BwdPixelAux, BwdPixel> st;
-  const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
   const float pxf = (float)px0, pyf = (float)py;
-  const float tf = in ? final_T[pix0] : 0.0f;
-  const uint32_t lastn = in ? n_contrib[pix0] : 0u;
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) { st.gpx[ch] = in ? dL_dpix[ch * HW + pix0] : 0.0f; st.acc[ch] = 0.0f; }
-  st.bgdot = (bg0 * st.gpx[0] + bg1 * st.gpx[1]) + bg2 * st.gpx[2];
-  if constexpr (AUX) bwd_aux_init<AUX>(st, (in && dL_ddepth) ? dL_ddepth[pix0] : 0.0f, (in && dL_dalpha) ? dL_dalpha[pix0] : 0.0f);
-  st.T = tf; st.nTfin = -tf;
+  const uint32_t lastn = bwd_pixel_init<AUX>(st, in, pix0, HW, bg, final_T, n_contrib, dL_dpix, dL_ddepth, dL_dalpha);
   uint32_t maxn = lastn;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, d, 64));
@@ -930,15 +819,10 @@ __global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
   const float wx0 = (float)(tx * 16 + qx * 8), wy0 = (float)(ty * 16 + qy * 8);   // this wave's pixel rectangle
   const float wx1 = wx0 + 7.0f, wy1 = wy0 + 7.0f;
   const uint64_t lt_mask = (1ull << lane) - 1ull;
-  // lanes that hold a result of wave_reduce9_swap, and where it goes in the row (accumulator-record order: conic A B C |
-  // opacity | mean sums x y | colour r g b); lane 2 adds the record's staging slot to the same LDS store.  AUX: lane 33
-  // holds the tenth sum (wave_reduce10_swap), the depth, for slot 9
-  const bool is_writer = (lane & 19) == 0 || lane == 1 || (AUX && lane == 33);
-  const int writer_val = lane == 1 ? 8 : ((AUX && lane == 33) ? 9 : 4 * (lane >> 5) + (((lane >> 2) & 1) << 1) + ((lane >> 3) & 1));
-  const int writer_comp = writer_val < 3 ? GGD_ACC_COLOR + writer_val
-                        : (writer_val < 6 ? GGD_ACC_CONIC + (writer_val - 3)
-                        : (writer_val < 8 ? GGD_ACC_MEAN2D + (writer_val - 6)
-                        : ((AUX && writer_val == 9) ? GGD_ACC_DEPTH : GGD_ACC_OPACITY)));
+  // the writer lanes put their sum where it goes in the row (accumulator-record order); lane 2 adds the record's staging slot
+  // to the same LDS store
+  bool is_writer;
+  const int writer_comp = bwd_writer_comp<AUX>(lane, is_writer);
   const bool stores = is_writer || lane == 2;
   const int store_col = is_writer ? writer_comp : NS;
 
@@ -949,9 +833,8 @@ __global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
   float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0;    // x y hA nB | hC thr opacity r | g b ex ey
   uint32_t zk = 0;                                          // AUX: depth key of the record in r0..r2
   const uint32_t last_pos = rg.x + maxn - 1u;
-  auto round_start = [&](uint32_t ce) { return (ce - rg.x > 64u) ? ce - 64u : rg.x; };   // ce > rg.x
   auto load_id = [&](uint32_t ce) {
-    const uint32_t cs = ce > rg.x ? round_start(ce) : rg.x;
+    const uint32_t cs = ce > rg.x ? bwd_round_start(ce, rg.x) : rg.x;
     id_nxt = list[min(cs + (uint32_t)lane, last_pos)];
   };
   auto load_rec = [&]() {
@@ -977,7 +860,7 @@ __global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
   };
   auto consume = [&](uint32_t ce) {
     keep = false;
-    const uint32_t cs = round_start(ce);
+    const uint32_t cs = bwd_round_start(ce, rg.x);
     if (CULL) shrink_rect(cs - rg.x);
     if ((uint32_t)lane < ce - cs) {
       keep = CULL ? (record_box_hits(r0.x, r0.y, r2.z, r2.w, lx0, lx1, ly0, ly1) &&
@@ -1006,10 +889,10 @@ __global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
   uint32_t cend = rg.x + maxn;  // one past the last position this quarter needs
   load_id(cend);
   load_rec();
-  load_id(round_start(cend));
+  load_id(bwd_round_start(cend, rg.x));
   int prev_cnt = 0;
   while (cend > rg.x) {
-    const uint32_t cstart = round_start(cend);
+    const uint32_t cstart = bwd_round_start(cend, rg.x);
     consume(cend);                                       // the records requested one round ago
     __builtin_amdgcn_wave_barrier();                     // (the previous round's LDS reads are done: in-order per wave)
     flush(prev_cnt);                                     // the previous round's sums: BEFORE its records are overwritten and
@@ -1022,12 +905,9 @@ __global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
       s_rec[slot * 3 + 0] = r0; s_rec[slot * 3 + 1] = r1; s_rec[slot * 3 + 2] = r2;
       if constexpr (AUX) s_z[slot] = __uint_as_float(zk);   // view-space depth (the key is its fp32 bits)
     }
-    if (lane >= nk && lane < n8) {   // padding: a record nobody sees
-      s_rec[lane * 3 + 0] = make_float4(0, 0, 0, 0);
-      s_rec[lane * 3 + 1] = make_float4(0, __builtin_huge_valf(), 0, 0);
-    }
+    bwd_stage_padding(s_rec, lane, nk, n8);
     load_rec();                                          // next round's records
-    load_id(cstart > rg.x ? round_start(cstart) : rg.x); // and the list entries of the round after it
+    load_id(cstart > rg.x ? bwd_round_start(cstart, rg.x) : rg.x); // and the list entries of the round after it
     __builtin_amdgcn_wave_barrier();
     int cnt = 0;
     float* rows = &s_sum[0][0];
@@ -1062,11 +942,8 @@ __global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
         const uint64_t live = bwd_update<EXP_MODE, AUX>(st, pw, dx, dy, need, b.z, col, s, sop, z, &sz);
         if (live != 0ull) {   // wave-uniform: somebody in this wave saw the Gaussian
           if (STATS) { st_live += 1; st_lanes += (uint32_t)__popcll(live); }
-          float tot;
-          if constexpr (AUX) tot = wave_reduce10_swap(s, sop, sz, 0x2222222222222222ull);
-          else tot = wave_reduce9_swap(s, sop, 0x2222222222222222ull);
-          // writers: lanes 0,4,8,12 | 32,36,40,44 (component from the table above), lane 1 the opacity sum (AUX: lane 33 the
-          // depth sum); lane 2 the record's slot in the staging area
+          const float tot = wave_reduce_swap<AUX>(s, sop, sz);
+          // the writer lanes' sums (bwd_writer_comp); lane 2 the record's slot in the staging area
           const float v = is_writer ? tot : __uint_as_float((uint32_t)(j0 + jj));
           if (stores) rows[cnt * ROW + store_col] = v;
           ++cnt;
@@ -1112,7 +989,7 @@ int ggd_launch_blend(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const g
     ggd_dispatch<2>(cull, [&](auto c) {
       ggd_dispatch<3>(variant, [&](auto v) {
         constexpr int V = decltype(v)::value;
-        hipLaunchKernelGGL((blend_forward_kernel<decltype(e)::value, decltype(c)::value != 0, 1, 8, V == STATS, V == AUX>),
+        hipLaunchKernelGGL((blend_forward_kernel<decltype(e)::value, decltype(c)::value != 0, V == STATS, V == AUX>),
                            dim3(4 * T), dim3(64), lds_pad, s, prm.width, prm.height, gx, T, splat, list, ranges, capacity, prm.bg,
                            out_color, final_T, n_contrib, V == STATS ? ctx->blend_stats : nullptr,
                            V == AUX ? depth_keys : nullptr, out_depth, out_alpha);

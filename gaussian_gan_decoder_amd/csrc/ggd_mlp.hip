@@ -69,21 +69,6 @@ typedef float f2v __attribute__((ext_vector_type(2)));
 // max |GELU error| 2e-4 on [-4, 4] and 4.9e-5 * |x| beyond -- an order below the bf16 rounding the activation gets
 // next).  12 VALU ops per pair.  (History: exact-erf Abramowitz-Stegun cost a v_rcp and a v_exp per value -- 14k of
 // 17k cycles per slab; an erf polynomial of degree 17 cost 17 ops per pair.)
-__device__ __forceinline__ f2v gelu2(f2v x) {
-  const f2v xc = {__builtin_amdgcn_fmed3f(x.x, -4.0f, 4.0f), __builtin_amdgcn_fmed3f(x.y, -4.0f, 4.0f)};
-  const f2v s2 = xc * xc;
-  f2v p = {-1.520480094e-09f, -1.520480094e-09f};
-  p = __builtin_elementwise_fma(p, s2, (f2v){1.180964698e-07f, 1.180964698e-07f});
-  p = __builtin_elementwise_fma(p, s2, (f2v){-4.014221549e-06f, -4.014221549e-06f});
-  p = __builtin_elementwise_fma(p, s2, (f2v){7.960997496e-05f, 7.960997496e-05f});
-  p = __builtin_elementwise_fma(p, s2, (f2v){-1.041295812e-03f, -1.041295812e-03f});
-  p = __builtin_elementwise_fma(p, s2, (f2v){9.641715482e-03f, 9.641715482e-03f});
-  p = __builtin_elementwise_fma(p, s2, (f2v){-6.614117560e-02f, -6.614117560e-02f});
-  p = __builtin_elementwise_fma(p, s2, (f2v){3.988329117e-01f, 3.988329117e-01f});
-  const f2v phi = __builtin_elementwise_fma(xc, p, (f2v){0.5f, 0.5f});
-  return x * phi;
-}
-
 // Four GELU pairs in lock step: the Horner recurrences of a packed polynomial are serial, and a v_pk_* op that reads the
 // result of the previous packed op needs a wait state (the compiler pads every step with s_nop 0: 800 of them per
 // slab and head) -- with four independent chains advanced together every dependent pair is four instructions apart

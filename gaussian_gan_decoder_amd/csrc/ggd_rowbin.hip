@@ -399,14 +399,6 @@ __global__ __launch_bounds__(RB_THREADS) void rb_level1_kernel(const uint2* __re
 // level-2 block -> (row, chunk within the row)
 // (one load per lane + a ballot: a binary search over the table is six DEPENDENT global loads, which was most of a
 // level-2 workgroup's lifetime)
-__device__ __forceinline__ bool rb_block_row(const uint32_t* __restrict__ tab, uint32_t blk, int& row, uint32_t& chunk) {
-  const uint32_t first = tab[RB_TAB_ROWBLK + (threadIdx.x & 63)];   // first block of row `lane` (non-decreasing)
-  const uint32_t total = tab[RB_TAB_ROWBLK + 64];
-  if (blk >= total) return false;
-  const int r = __popcll(__ballot(first <= blk)) - 1;               // last row that starts at or before blk
-  row = r; chunk = blk - (uint32_t)__shfl((int)first, r, 64);
-  return true;
-}
 // ... and the row's entry range with it: the block table and the row starts are requested TOGETHER (a level-2 workgroup is a
 // chain of dependent memory round trips at full occupancy -- block table -> row start -> entries -> tile starts was four of
 // them; this form makes it two: {block table, row starts}, then {entries, tile starts, chunk prefixes})

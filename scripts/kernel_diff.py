@@ -4,8 +4,9 @@ OLD / NEW: two libggd_raster.so, or two directories of `-S` listings (python -m 
 Prints, per kernel, `same` or `DIFF` for the instruction stream (comments, directives, addresses and encodings stripped, `.LBB<n>_`
 labels normalised) and VGPR / SGPR / LDS / scratch / kernarg of both builds side by side; then one summary line and the kernels
 whose kernarg size changed.  A kernel of OLD whose name is gone is compared with the kernel of NEW whose template arguments are
-OLD's with `false` arguments added (a feature flag that became a defaulted template parameter).  Exit status 1 on any DIFF,
-resource change or unmatched kernel."""
+OLD's with `false` arguments added (a feature flag that became a defaulted template parameter), or, with
+`--dropped KERNEL:I,J` (0-based positions, repeatable), OLD's without the listed arguments.  Exit status 1 on any DIFF, resource
+change or unmatched kernel."""
 from __future__ import annotations
 
 import glob
@@ -73,12 +74,18 @@ def padded(old, new) -> bool:   # new = old with `false` arguments inserted
 
 
 if __name__ == "__main__":
+    dropped = {}   # kernel -> template argument positions that NEW no longer has
+    while "--dropped" in sys.argv:
+        k, pos = sys.argv.pop(sys.argv.index("--dropped") + 1).split(":")
+        sys.argv.remove("--dropped")
+        dropped[k] = [int(i) for i in pos.split(",")]
     old, new = load(sys.argv[1]), load(sys.argv[2])
     left = [n for n in new if n not in old]
     same = bad = 0
     kernarg = []
     for name in sorted(old):
         base, args = targs(name)
+        args = [a for i, a in enumerate(args) if i not in dropped.get(base, ())]
         cands = [name] if name in new else [n for n in left if targs(n)[0] == base and padded(args, targs(n)[1])]
         if len(cands) != 1:
             print(f"{'UNMATCHED':9s} {name}  (candidates: {cands})")

@@ -240,7 +240,7 @@ def forward_blend_instance(case):
     if not has_aux(case):
         return None
     em = case["options"]["exp_mode"]
-    return f"blend_forward_kernel<{1 if em == 3 else em}, {_b(case['options']['cull'])}, 1, 8, false, true>"
+    return f"blend_forward_kernel<{1 if em == 3 else em}, {_b(case['options']['cull'])}, false, true>"
 
 
 def backward_blend_instance(case):

@@ -33,14 +33,14 @@ def test_aux_kernels_are_built_without_spills(native_lib):
     ppb = {k: v for k, v in tab.items() if k.startswith("preprocess_backward") and _targs(k)[-1:] == ["true"]}
     assert len(fwd) == 6, sorted(tab)          # exp modes 0..2 x cull on / off
     assert len(bwd) == 8, sorted(tab)          # exp modes 0..3 x cull on / off
-    assert sorted(fwd) == sorted(f"blend_forward_kernel<{em}, {cu}, 1, 8, false, true>"       # no statistics variant
+    assert sorted(fwd) == sorted(f"blend_forward_kernel<{em}, {cu}, false, true>"       # no statistics variant
                                  for em in range(3) for cu in ("false", "true")), sorted(fwd)
     assert sorted(bwd) == sorted(f"blend_backward_quarter_kernel<{em}, {cu}, false, true>"
                                  for em in range(4) for cu in ("false", "true")), sorted(bwd)
     assert {re.sub(r"<.*", "", k) for k in ppb} == {"preprocess_backward_kernel", "preprocess_backward_vec_kernel",
                                                      "preprocess_backward_staged_kernel"}, sorted(ppb)
     # the plain instances are the same templates with AUX = false
-    for name in ("blend_forward_kernel<1, true, 1, 8, false, false>", "blend_forward_kernel<1, true, 1, 8, true, false>",
+    for name in ("blend_forward_kernel<1, true, false, false>", "blend_forward_kernel<1, true, true, false>",
                  "blend_backward_quarter_kernel<3, true, false, false>", "blend_backward_quarter_kernel<3, true, true, false>",
                  "preprocess_backward_kernel<false, false>", "preprocess_backward_vec_kernel<false, false>",
                  "preprocess_backward_staged_kernel<false, false, false>"):
