@@ -1,11 +1,21 @@
 // ggd_capi.hip -- the C ABI declared in include/ggd_raster.h (host side: ctx, workspace, stage sequencing).
 //
-// Stage sequence of one forward: preprocess -> inclusive scan -> read back R ->
-// duplicateWithKeys -> stable radix sort -> tile ranges -> blend.  The one host sync is the read-back of
-// R = num_rendered, exactly where the CUDA original has it; everything else is enqueued on the caller's stream.
+// A single-call frame on the tile-binning path (ggd_forward, ggd_forward_enqueue) is enqueued whole before the host knows
+// num_rendered -- binning_buf's capacity stands in for it -- in eight launches when the two-launch sort is planned:
+//   geometry_enqueue  preprocess; with GGD_OPT_FOLD it also builds the depth sort's histograms (which ones: this frame's plan,
+//                     ggd_spec.h), step 1 of the offsets scan and the binning's per-row counts (ggd_fold)
+//   render_enqueue    depth sort (two launches over the planned key window, or three / four onesweep passes), row / column binning,
+//                     blend; steps 2 and 3 of the scan ride on the sort's first and the binning's last launch
+//   collect           the ONE host wait: geometry_finish polls the pinned word (flags | tag | num_rendered) that scan step 2 stores
+//                     and returns while binning and blend still run.  Flags + kept-key range are the frame's report to the policy;
+//                     a frame whose short sort did not hold is rendered again from its geometry buffer: depth sort with its own
+//                     histogram launch and four passes, binning, blend -- no second preprocess
+// The frame in flight (ggd_frame) is assigned fresh where a frame begins, in geometry_enqueue, and where it is collected.
+// Every other frame: preprocess -> scan -> read-back of num_rendered (a stream synchronise) -> either binning path -> blend.
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <new>
 
 #include "ggd_common.h"
@@ -89,10 +99,49 @@ extern "C" int ggd_sort_bits(int32_t W, int32_t H) {
   return 32 + (int)higher_msb(T);
 }
 
-// auto (GGD_OPT_BINNING = 1): the row / column binning path whenever the grid allows it.  It used to start at 0.79 M
-// instances (the fixed cost of its launches); since the single-call forward stopped waiting for the end of the frame it
-// wins at every size measured (18 k instances: 95 vs 123 us per frame, 170 k: 120 vs 158, 1.25 M: 207 vs 296).
-constexpr int64_t GGD_ROWBIN_MIN_R = 1;
+// The binning path of R instances: true = depth sort + row / column binning, false = duplicate + 64-bit sort + ranges.
+// GGD_OPT_BINNING: 0 = the latter; 3 (2: alias) = the former wherever it can run (grids <= 255 x 255 tiles, no debug taps); 1 = auto:
+// the same for R > 0 -- since the single-call forward stopped waiting for the end of the frame the binning wins at every size
+// measured (18 k instances: 95 vs 123 us per frame, 170 k: 120 vs 158, 1.25 M: 207 vs 296; the threshold used to be 0.79 M).
+static bool use_tile_binning(const ggd_ctx* ctx, const ggd_params* prm, int64_t R) {
+  const int mode = ctx->opt[GGD_OPT_BINNING];
+  return !prm->debug && ggd_rowbin_supported(prm->width, prm->height) && (mode >= 2 || (mode == 1 && R > 0));
+}
+
+// Grow-only device buffers that share one capacity (in elements): nothing to do while *cap >= need; else they are freed -- behind
+// the stream's work when sync is set -- and allocated again for `want` elements (need + the site's own head-room).
+struct ggd_buf { void** ptr; size_t elem; };
+static int grow_buffers(ggd_ctx* ctx, std::initializer_list<ggd_buf> bufs, size_t* cap, size_t need, size_t want,
+                        const hipStream_t* sync = nullptr) {
+  if (*cap >= need) return GGD_OK;
+  if (sync) GGD_HIP(hipStreamSynchronize(*sync));
+  for (const ggd_buf& b : bufs) { if (*b.ptr) (void)hipFree(*b.ptr); *b.ptr = nullptr; }
+  *cap = 0;
+  for (const ggd_buf& b : bufs) GGD_HIP(hipMalloc(b.ptr, want * b.elem));
+  *cap = want;
+  return GGD_OK;
+}
+
+// Typed views of the three caller buffers (ggd_geom_layout / ggd_binning_layout / ggd_img_layout).
+template <class T> static T* ggd_at(const void* base, size_t off) {
+  return reinterpret_cast<T*>(static_cast<char*>(const_cast<void*>(base)) + off);
+}
+struct geom_ptrs { ggd_splat* splat; uint32_t *tiles, *offsets; uint8_t* clamped; uint32_t* depth_keys; uint2* rect; };
+struct binning_ptrs { uint32_t *list, *list_alt; uint64_t *keys, *keys_alt; };
+struct img_ptrs { uint32_t* ranges; float* final_T; uint32_t* n_contrib; };
+static geom_ptrs geom_view(const ggd_params* prm, const void* buf) {
+  ggd_geom_view v; ggd_geom_layout(prm->P, &v);
+  return {ggd_at<ggd_splat>(buf, v.splat), ggd_at<uint32_t>(buf, v.tiles_touched), ggd_at<uint32_t>(buf, v.point_offsets),
+          ggd_at<uint8_t>(buf, v.clamped), ggd_at<uint32_t>(buf, v.depth_keys), ggd_at<uint2>(buf, v.rect)};
+}
+static binning_ptrs binning_view(int64_t layout_R, const void* buf) {
+  ggd_binning_view v; ggd_binning_layout(layout_R, &v);
+  return {ggd_at<uint32_t>(buf, v.list), ggd_at<uint32_t>(buf, v.list_alt), ggd_at<uint64_t>(buf, v.keys), ggd_at<uint64_t>(buf, v.keys_alt)};
+}
+static img_ptrs img_view(int32_t W, int32_t H, const void* buf) {
+  ggd_img_view v; ggd_img_layout(W, H, &v);
+  return {ggd_at<uint32_t>(buf, v.ranges), ggd_at<float>(buf, v.final_T), ggd_at<uint32_t>(buf, v.n_contrib)};
+}
 
 // ---- ctx -----------------------------------------------------------------------------------------------------
 extern "C" const char* ggd_version(void) { return "ggd-raster 0.1 (gfx950)"; }
@@ -114,7 +163,7 @@ extern "C" ggd_ctx* ggd_create(int device) {
   if (const char* e = getenv("GGD_BLEND_CULL")) ctx->opt[GGD_OPT_BLEND_CULL] = atoi(e) != 0;
   if (const char* e = getenv("GGD_FOLD")) ctx->opt[GGD_OPT_FOLD] = atoi(e) != 0;
   if (const char* e = getenv("GGD_MSD_SORT")) ctx->opt[GGD_OPT_MSD_SORT] = atoi(e) != 0;
-  if (const char* e = getenv("GGD_MSD_BUCKETS")) { const int v = atoi(e); if (v >= 16 && v <= GGD_MSD_BINS) ctx->msd_buckets = v; }   // timing experiments
+  if (const char* e = getenv("GGD_MSD_BUCKETS")) { const int v = atoi(e); if (v >= 16 && v <= GGD_MSD_BINS) ctx->spec.msd_buckets = v; }   // timing experiments
   int prev = 0;
   (void)hipGetDevice(&prev);
   bool ok = hipSetDevice(device) == hipSuccess &&
@@ -149,16 +198,10 @@ extern "C" ggd_ctx* ggd_create(int device) {
 
 extern "C" void ggd_destroy(ggd_ctx* ctx) {
   if (!ctx) return;
-  if (ctx->scratch) (void)hipFree(ctx->scratch);
-  if (ctx->d_words) (void)hipFree(ctx->d_words);
+  void* const device_buffers[] = {ctx->scratch, ctx->d_words, ctx->sortctl, ctx->foldctl[0], ctx->foldctl[1], ctx->gelu_tables,
+                                  ctx->scan_sums, ctx->stats_buf, ctx->dbg_keys, ctx->dbg_vals};
+  for (void* p : device_buffers) if (p) (void)hipFree(p);
   if (ctx->h_words) (void)hipHostFree(ctx->h_words);
-  if (ctx->sortctl) (void)hipFree(ctx->sortctl);
-  for (int b = 0; b < 2; ++b) if (ctx->foldctl[b]) (void)hipFree(ctx->foldctl[b]);
-  if (ctx->gelu_tables) (void)hipFree(ctx->gelu_tables);
-  if (ctx->scan_sums) (void)hipFree(ctx->scan_sums);
-  if (ctx->stats_buf) (void)hipFree(ctx->stats_buf);
-  if (ctx->dbg_keys) (void)hipFree(ctx->dbg_keys);
-  if (ctx->dbg_vals) (void)hipFree(ctx->dbg_vals);
   for (int i = 0; i < 2 * ST_COUNT; ++i)
     if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
   delete ctx;
@@ -175,7 +218,7 @@ extern "C" int ggd_set_option(ggd_ctx* ctx, int option, int value) {
   if (option == GGD_OPT_MSD_SORT || option == GGD_OPT_FOLD) {
     // (re)setting the sort options restarts the cross-frame speculation state: the window of recent key ranges, the pause after
     // a miss, the flat-frame streak -- a caller (or a test) that switches forms gets a defined starting point
-    ctx->win_n = 0; ctx->win_pos = 0; ctx->msd_ban = 0; ctx->msd_oversize_streak = 0; ctx->flat_streak = 0;
+    ctx->spec.reset();
   }
   return GGD_OK;
 }
@@ -213,9 +256,9 @@ extern "C" int ggd_blend_timeline(ggd_ctx* ctx, unsigned long long* out, int wav
 }
 
 extern "C" int ggd_get_option(ggd_ctx* ctx, int option) {
-  if (ctx && option == GGD_STAT_FLAT_STREAK) return ctx->flat_streak;
-  if (ctx && option == GGD_STAT_SORT_RERUNS) return (int)(ctx->spec3_misses & 0x7fffffffull);
-  if (ctx && option == GGD_STAT_MSD_FRAMES) return (int)(ctx->msd_frames & 0x7fffffffull);
+  if (ctx && option == GGD_STAT_FLAT_STREAK) return ctx->spec.flat_streak;
+  if (ctx && option == GGD_STAT_SORT_RERUNS) return (int)(ctx->spec.reruns & 0x7fffffffull);
+  if (ctx && option == GGD_STAT_MSD_FRAMES) return (int)(ctx->spec.msd_frames & 0x7fffffffull);
   if (!ctx || option < 0 || option >= GGD_OPT_COUNT) return GGD_E_INVALID;
   return ctx->opt[option];
 }
@@ -270,28 +313,55 @@ static int check_inputs(ggd_ctx* ctx, const ggd_params* prm, const float* means3
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------
-// The two-launch depth sort's key window for the next frame: the union of the kept-key ranges of the last folded frames, a margin
-// of 1/8 of its width either side, and the smallest shift that spreads it over at most ctx->msd_buckets buckets.  False when no
-// range is known yet or the window is too wide for two 8-bit finishing passes.
-static bool msd_fit_window(const ggd_ctx* ctx, uint32_t* lo_out, int* shift_out) {
-  const int n = ctx->win_n < GGD_MSD_WIN ? ctx->win_n : GGD_MSD_WIN;
-  if (n <= 0) return false;
-  uint32_t lo = 0xffffffffu, hi = 0u;
-  for (int i = 0; i < n; ++i) { lo = ctx->win_lo[i] < lo ? ctx->win_lo[i] : lo; hi = ctx->win_hi[i] > hi ? ctx->win_hi[i] : hi; }
-  if (lo > hi) return false;
-  const uint64_t margin = ((uint64_t)(hi - lo) >> 3) + 4096u;
-  const uint64_t wlo = (uint64_t)lo > margin ? (uint64_t)lo - margin : 0u;
-  uint64_t whi = (uint64_t)hi + margin;
-  if (whi > 0xfffffffeull) whi = 0xfffffffeull;
-  const uint64_t span = whi - wlo;            // bucket of the largest key = span >> shift, must stay below the bucket count
-  int shift = 0;
-  while ((span >> shift) >= (uint64_t)ctx->msd_buckets) ++shift;
-  if (shift > GGD_MSD_MAX_SHIFT) return false;
-  *lo_out = (uint32_t)wlo; *shift_out = shift;
-  return true;
+static const char* const kPendingMsg = "a frame enqueued with ggd_forward_enqueue is pending on this context: call ggd_forward_collect first";
+
+// A frame begins (or, in the collection, ends): the context gets a fresh ggd_frame -- only the tag's sequence carries over -- and
+// the caller the old one.
+static ggd_frame frame_renew(ggd_ctx* ctx) {
+  const ggd_frame old = ctx->frame;
+  ctx->frame = ggd_frame();
+  ctx->frame.r_tag = old.r_tag;
+  return old;
 }
 
-static const char* const kPendingMsg = "a frame enqueued with ggd_forward_enqueue is pending on this context: call ggd_forward_collect first";
+// The folded front end's share of geometry_enqueue: workspace, the two alternating control blocks, this frame's plan.
+static int fold_prepare(ggd_ctx* ctx, hipStream_t s, const ggd_params* prm, ggd_fold* fold) {
+  const int nwg = (prm->P + 255) / 256;
+  // [exclusive prefixes: nwg words | {sum, kept, ~min key, max key}: nwg uint4]
+  int rc = grow_buffers(ctx, {{(void**)&ctx->scan_sums, sizeof(uint32_t)}}, &ctx->scan_sums_cap, 5 * (size_t)nwg + 64,
+                        5 * (size_t)(nwg + nwg / 2) + 64);
+  if (rc != GGD_OK) return rc;
+  const size_t need = ggd_fold_ctl_words(prm->P);
+  const bool fresh = ctx->foldctl_cap < need;   // (grow-only; both blocks start clean)
+  rc = grow_buffers(ctx, {{(void**)&ctx->foldctl[0], sizeof(uint32_t)}, {(void**)&ctx->foldctl[1], sizeof(uint32_t)}},
+                    &ctx->foldctl_cap, need, need + need / 2, &s);
+  if (rc != GGD_OK) return rc;
+  if (fresh) ctx->fold_cur = 0;
+  if (fresh || ctx->fold_poisoned) {
+    for (int b = 0; b < 2; ++b) {
+      GGD_HIP(hipMemsetAsync(ctx->foldctl[b], 0, ctx->foldctl_cap * sizeof(uint32_t), s));
+      ctx->foldctl_dirty[b] = 0;
+    }
+    ctx->fold_poisoned = false;
+  }
+  const int cur = ctx->fold_cur, oth = cur ^ 1;
+  fold->ctl = ctx->foldctl[cur];
+  fold->clear = ctx->foldctl[oth];
+  fold->clear_words = (uint32_t)ctx->foldctl_dirty[oth];
+  fold->wg_info = reinterpret_cast<uint4*>(ctx->scan_sums + (((size_t)nwg + 3) & ~(size_t)3));
+  fold->rows = ((prm->width + 15) / 16 <= 64 && (prm->height + 15) / 16 <= 64) ? 1 : 0;
+  // the two-launch depth sort is decided HERE because it selects the histograms this launch builds
+  const ggd_spec_plan plan = ctx->spec.plan(ctx->opt[GGD_OPT_FOLD], ctx->opt[GGD_OPT_MSD_SORT], ggd_sort32_msd_supported(prm->P));
+  fold->msd = plan.msd ? 1 : 0;
+  fold->msd_lo = plan.lo; fold->msd_shift = plan.shift;
+  ctx->foldctl_dirty[oth] = 0;       // (clean once this launch has run)
+  ctx->foldctl_dirty[cur] = need;    // what this frame may write
+  ctx->fold_cur = oth;
+  ctx->frame.plan = plan;
+  ctx->frame.geom.folded = true;
+  return GGD_OK;
+}
+
 // Enqueue the per-Gaussian kernels + scan + the asynchronous read-back of {R, prefilter trap}; no host sync.
 static int geometry_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
                             const float* shs, const float* colors_precomp, const float* opacities,
@@ -304,107 +374,50 @@ static int geometry_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, c
   if (rc != GGD_OK) return rc;
   if (!num_rendered) return ggd_fail(ctx, GGD_E_INVALID, "num_rendered is NULL");
   *num_rendered = 0;
-  ctx->r_pending = false;      // (a previous call that failed half way may have left these set)
-  ctx->scan_deferred = false;
+  frame_renew(ctx);            // whatever an earlier frame left -- one that failed half way too -- ends here
+  ggd_frame& fr = ctx->frame;
   if (prm->P == 0) return GGD_OK;
   if (!geom_buf || !radii || !opacities) return ggd_fail(ctx, GGD_E_INVALID, "geom_buf / radii / opacities is NULL");
   if (prm->raw_attributes && cov3D_precomp)
     return ggd_fail(ctx, GGD_E_INVALID, "raw_attributes needs scales/rotations (no cov3D_precomp)");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  ggd_geom_view gv;
-  ggd_geom_layout(prm->P, &gv);
-  char* gb = static_cast<char*>(geom_buf);
-  ggd_splat* splat = reinterpret_cast<ggd_splat*>(gb + gv.splat);
-  uint32_t* tiles = reinterpret_cast<uint32_t*>(gb + gv.tiles_touched);
-  uint32_t* offsets = reinterpret_cast<uint32_t*>(gb + gv.point_offsets);
-  uint8_t* clamped = reinterpret_cast<uint8_t*>(gb + gv.clamped);
-  uint32_t* depth_keys = reinterpret_cast<uint32_t*>(gb + gv.depth_keys);
-  uint2* rect = reinterpret_cast<uint2*>(gb + gv.rect);
+  const geom_ptrs g = geom_view(prm, geom_buf);
 
-  const size_t scan_tmp = ggd_scan_tmp_bytes(prm->P);
-  rc = ggd_reserve_scratch(ctx, scan_tmp, s);
+  rc = ggd_reserve_scratch(ctx, ggd_scan_tmp_bytes(prm->P), s);
   if (rc != GGD_OK) return rc;
   if (prm->prefiltered) GGD_HIP(hipMemsetAsync(ctx->d_words + 1, 0, sizeof(uint32_t), s));
-  // single-call forward on a tile-binning path: the scan (offsets + num_rendered) rides on the depth sort's launches, and the
+  // single-call forward on the tile-binning path: the scan (offsets + num_rendered) rides on the depth sort's launches, and the
   // sort's histograms + the scan's first step are produced by the preprocess kernel itself (ggd_fold)
   const bool ride = defer_scan && ctx->h_words_dev;
   ggd_fold fold;
-  ctx->fold_active = false;
-  ctx->msd_frame = false;
   if (ride && ctx->opt[GGD_OPT_FOLD] != 0) {
-    const int nwg = (prm->P + 255) / 256;
-    if (ctx->scan_sums_cap < 5 * nwg + 64) {   // [exclusive prefixes: nwg words | {sum, kept, ~min key, max key}: nwg uint4]
-      if (ctx->scan_sums) (void)hipFree(ctx->scan_sums);
-      ctx->scan_sums = nullptr; ctx->scan_sums_cap = 0;
-      const int cap = 5 * (nwg + nwg / 2) + 64;
-      GGD_HIP(hipMalloc((void**)&ctx->scan_sums, (size_t)cap * sizeof(uint32_t)));
-      ctx->scan_sums_cap = cap;
-    }
-    const size_t need = ggd_fold_ctl_words(prm->P);
-    if (ctx->foldctl_cap < need) {   // (grow-only; both blocks start clean)
-      GGD_HIP(hipStreamSynchronize(s));
-      for (int b = 0; b < 2; ++b) { if (ctx->foldctl[b]) (void)hipFree(ctx->foldctl[b]); ctx->foldctl[b] = nullptr; }
-      ctx->foldctl_cap = 0;
-      const size_t cap = need + need / 2;
-      for (int b = 0; b < 2; ++b) {
-        GGD_HIP(hipMalloc((void**)&ctx->foldctl[b], cap * sizeof(uint32_t)));
-        GGD_HIP(hipMemsetAsync(ctx->foldctl[b], 0, cap * sizeof(uint32_t), s));
-        ctx->foldctl_dirty[b] = 0;
-      }
-      ctx->foldctl_cap = cap;
-      ctx->fold_cur = 0;
-    }
-    if (ctx->fold_poisoned) {
-      for (int b = 0; b < 2; ++b) {
-        GGD_HIP(hipMemsetAsync(ctx->foldctl[b], 0, ctx->foldctl_cap * sizeof(uint32_t), s));
-        ctx->foldctl_dirty[b] = 0;
-      }
-      ctx->fold_poisoned = false;
-    }
-    const int cur = ctx->fold_cur, oth = cur ^ 1;
-    fold.ctl = ctx->foldctl[cur];
-    fold.clear = ctx->foldctl[oth];
-    fold.clear_words = (uint32_t)ctx->foldctl_dirty[oth];
-    fold.wg_info = reinterpret_cast<uint4*>(ctx->scan_sums + (((size_t)nwg + 3) & ~(size_t)3));
-    fold.rows = ((prm->width + 15) / 16 <= 64 && (prm->height + 15) / 16 <= 64) ? 1 : 0;
-    // two-launch depth sort: speculated once the key ranges of GGD_FLAT_STREAK folded frames are known (render_enqueue: folded,
-    // tile binning, speculative), decided HERE because it selects the histograms this launch builds
-    ctx->msd_frame = ctx->opt[GGD_OPT_MSD_SORT] != 0 && ctx->opt[GGD_OPT_FOLD] == 1 && ctx->win_n >= GGD_FLAT_STREAK &&
-                     ctx->msd_ban == 0 && ggd_sort32_msd_supported(prm->P) && msd_fit_window(ctx, &ctx->msd_lo, &ctx->msd_shift);
-    fold.msd = ctx->msd_frame ? 1 : 0;
-    fold.msd_lo = ctx->msd_lo; fold.msd_shift = ctx->msd_shift;
-    ctx->foldctl_dirty[oth] = 0;       // (clean once this launch has run)
-    ctx->foldctl_dirty[cur] = need;    // what this frame may write
-    ctx->fold_cur = oth;
-    ctx->fold_active = true;
+    rc = fold_prepare(ctx, s, prm, &fold);
+    if (rc != GGD_OK) return rc;
   }
   {
     StageTimer t(ctx, ST_PREPROCESS, s);
-    const bool old_ctl = !ctx->fold_active && ctx->sortctl;
+    const bool old_ctl = !fr.geom.folded && ctx->sortctl;
     rc = ggd_launch_preprocess(ctx, s, *prm, means3D, shs, colors_precomp, opacities, scales, rotations,
-                               cov3D_precomp, splat, tiles, shs ? clamped : nullptr, radii, depth_keys, rect,
+                               cov3D_precomp, g.splat, g.tiles, shs ? g.clamped : nullptr, radii, g.depth_keys, g.rect,
                                ctx->d_words + 1, old_ctl ? ctx->sortctl : nullptr, old_ctl ? (int)ggd_sort_ctrl_words() : 0,
-                               ctx->fold_active ? &fold : nullptr);
-    if (rc != GGD_OK) { ctx->fold_poisoned = ctx->fold_active; ctx->fold_active = false; return rc; }
-    ctx->sortctl_clean = old_ctl;
+                               fr.geom.folded ? &fold : nullptr);
+    if (rc != GGD_OK) { ctx->fold_poisoned = fr.geom.folded; return rc; }
+    fr.geom.sortctl_clean = old_ctl;
   }
-  ctx->scan_deferred = false;
   if (ride) {
-    const int nb = ggd_scan_blocks(prm->P);
-    if (!ctx->fold_active && ctx->scan_sums_cap < nb) {
-      if (ctx->scan_sums) (void)hipFree(ctx->scan_sums);
-      ctx->scan_sums = nullptr; ctx->scan_sums_cap = 0;
-      GGD_HIP(hipMalloc((void**)&ctx->scan_sums, (size_t)(nb + nb / 2 + 64) * sizeof(uint32_t)));
-      ctx->scan_sums_cap = nb + nb / 2 + 64;
+    const size_t nb = (size_t)ggd_scan_blocks(prm->P);
+    if (!fr.geom.folded) {
+      rc = grow_buffers(ctx, {{(void**)&ctx->scan_sums, sizeof(uint32_t)}}, &ctx->scan_sums_cap, nb, nb + nb / 2 + 64);
+      if (rc != GGD_OK) return rc;
     }
-    ctx->scan_deferred = true;
     if (prm->prefiltered)
       GGD_HIP(hipMemcpyAsync(ctx->h_words + 1, ctx->d_words + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    fr.geom.ride = true;
     return GGD_OK;
   }
   {
     StageTimer t(ctx, ST_SCAN, s);
-    rc = ggd_launch_inclusive_scan_ex(ctx, s, tiles, offsets, prm->P, ctx->d_words, ctx->scratch, ctx->scratch_bytes,
+    rc = ggd_launch_inclusive_scan_ex(ctx, s, g.tiles, g.offsets, prm->P, ctx->d_words, ctx->scratch, ctx->scratch_bytes,
                                       ctx->h_words_dev);
     if (rc != GGD_OK) return rc;
   }
@@ -424,13 +437,13 @@ static int geometry_finish(ggd_ctx* ctx, void* stream, const ggd_params* prm, in
   // The host needs num_rendered, not the finished frame: in the single-call forward it waits for the word written by the
   // launch that delivers R (early in the depth sort) and returns while binning and blend are still running -- as
   // upstream returns with its render kernels in flight.  Outputs are ordered on the caller's stream as usual.
-  if (ctx->r_pending) {
-    ctx->r_pending = false;
+  ggd_frame& fr = ctx->frame;
+  if (fr.r_pending) {
     // the launch that carries the scan's block-sum step stores (tag << 32 | R) into the pinned mirror; poll for this
     // call's tag (an event record behind that launch would cost the GPU a ~6 us bubble between two kernels).  Every few
     // thousand polls the stream is queried: if it has drained without the tag (a failed launch), fall back to the copy.
     volatile unsigned long long* slot = reinterpret_cast<volatile unsigned long long*>(ctx->h_words + 2);
-    const unsigned long long want = ctx->r_tag;   // (30 bits; bit 63 of the word: this frame's top depth digit is constant,
+    const unsigned long long want = fr.r_tag;     // (30 bits; bit 63 of the word: this frame's top depth digit is constant,
                                                   // bit 62: the two-launch sort's histograms say it was valid for this frame)
     unsigned long long v = *slot;
     for (unsigned spins = 0; ((v >> 32) & 0x3fffffffull) != want; ++spins) {
@@ -439,7 +452,7 @@ static int geometry_finish(ggd_ctx* ctx, void* stream, const ggd_params* prm, in
         const hipError_t q = hipStreamQuery(static_cast<hipStream_t>(stream));
         if (q == hipSuccess) {
           v = *slot;
-          if (((v >> 32) & 0x3fffffffull) != want) {
+          if (((v >> 32) & 0x3fffffffull) != want) {   // fill the mirror as the launch would have
             uint32_t w6[6] = {0u, 0u, 0u, 0u, 0u, 0u};
             GGD_HIP(hipMemcpy(w6, ctx->d_words, sizeof(w6), hipMemcpyDeviceToHost));
             v = ((unsigned long long)(w6[2] & 1u) << 63) | ((unsigned long long)((w6[2] >> 1) & 1u) << 62) | (want << 32) | w6[0];
@@ -453,11 +466,13 @@ static int geometry_finish(ggd_ctx* ctx, void* stream, const ggd_params* prm, in
       v = *slot;
     }
     ctx->h_words[0] = (uint32_t)v;
-    ctx->frame_flat = (v >> 63) != 0ull;
-    ctx->frame_msd_ok = ((v >> 62) & 1ull) != 0ull;
-    // (stored by the same device thread before the tagged word's release store; x86 loads are not reordered with earlier loads)
-    volatile uint32_t* hw = ctx->h_words;
-    ctx->frame_kmin = hw[4]; ctx->frame_kmax = hw[5]; ctx->frame_msd_flags = hw[6];
+    fr.report.flat = (v >> 63) != 0ull;
+    fr.report.msd_ok = ((v >> 62) & 1ull) != 0ull;
+    if (fr.report.folded) {   // only a folded frame's front end delivers the kept-key range: any other leaves the words as they were
+      // (stored by the same device thread before the tagged word's release store; x86 loads are not reordered with earlier loads)
+      volatile uint32_t* hw = ctx->h_words;
+      fr.report.kmin = hw[4]; fr.report.kmax = hw[5]; fr.report.msd_flags = hw[6];
+    }
   } else {
     GGD_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
   }
@@ -478,181 +493,142 @@ extern "C" int ggd_forward_geometry(ggd_ctx* ctx, void* stream, const ggd_params
   return geometry_finish(ctx, stream, prm, num_rendered);
 }
 
-// R = the value binning_buf was laid out for.  speculative: R is only a CAPACITY (the true num_rendered is still on
-// the device); only the tile-binning path can run that way (its launch geometry does not depend on R).
-// out_depth / out_alpha (both or neither): the depth / alpha planes of the *_aux entry points
+// Binning path 1: depth-sort the Gaussians once (32-bit keys), then one stable row / column binning pass.  speculative: the true
+// instance count is still on the device and `capacity` is only its upper bound (the launch geometry does not depend on it).
+static int sort_depth_and_bin_tiles(ggd_ctx* ctx, hipStream_t s, const ggd_params* prm, const geom_ptrs& g, uint32_t* list,
+                                    uint32_t* ranges, uint32_t capacity, bool speculative) {
+  ggd_frame& fr = ctx->frame;
+  const bool riding = fr.geom.ride;                  // this call's geometry half left the scan to us
+  const bool folded = riding && fr.geom.folded;      // ... and its preprocess filled the histograms
+  const bool msd = folded && fr.plan.msd;            // ... those of the two-launch sort
+  // the control block this frame's preprocess cleared, if nobody has used it since (a second render of the same geometry
+  // falls back to the memset)
+  uint32_t* clean_ctl = fr.geom.sortctl_clean ? ctx->sortctl : nullptr;
+  fr.geom = {};
+  const size_t pairs = ggd_align((size_t)prm->P * sizeof(uint32_t));
+  const size_t sort_tmp = ggd_sort32_tmp_bytes(prm->P);
+  const size_t bin_tmp = ggd_rowbin_tmp_bytes(prm->P, capacity, prm->width, prm->height);
+  const size_t msd_tab = msd ? ggd_sort32_msd_table_bytes(prm->P) : 0;
+  int rc = ggd_reserve_scratch(ctx, 4 * pairs + sort_tmp + bin_tmp + msd_tab, s);
+  if (rc != GGD_OK) return rc;
+  char* sc = static_cast<char*>(ctx->scratch);
+  uint32_t* ka = reinterpret_cast<uint32_t*>(sc);
+  uint32_t* va = reinterpret_cast<uint32_t*>(sc + pairs);
+  uint32_t* kb = reinterpret_cast<uint32_t*>(sc + 2 * pairs);
+  uint32_t* vb = reinterpret_cast<uint32_t*>(sc + 3 * pairs);
+  void* tmp = sc + 4 * pairs;
+  void* bin_tmp_ptr = sc + 4 * pairs + sort_tmp;  // the sort's histogram block stays alive for the binning pass
+  ggd_scan_piggy pg;          // a scan that rides on this call's launches (see geometry_enqueue)
+  ggd_fold fold;              // the folded front end's control block, if this call has one
+  const uint32_t *n_vis_ptr = nullptr, *flat_ptr = nullptr;   // device words: kept keys, "last pass was flat"
+  {
+    StageTimer t(ctx, ST_SORT, s);
+    if (riding) {
+      pg.in = g.tiles; pg.out = g.offsets;
+      pg.n = prm->P; pg.nb = ggd_scan_blocks(prm->P); pg.block_sums = ctx->scan_sums;
+      pg.d_total = ctx->d_words; pg.h_total = ctx->h_words_dev;
+      pg.h_tagged = reinterpret_cast<unsigned long long*>(ctx->h_words_dev + 2);
+      pg.tag = fr.r_tag = fr.r_tag % 0x3fffffffu + 1u;   // 1 .. 2^30 - 1 in turn
+      if (folded) {
+        const int nwg = (prm->P + 255) / 256;
+        fold.ctl = ctx->foldctl[ctx->fold_cur ^ 1];   // (fold_cur already points at the next frame's block)
+        pg.wg_info = reinterpret_cast<const uint4*>(ctx->scan_sums + (((size_t)nwg + 3) & ~(size_t)3));
+        pg.n_info = nwg;
+        pg.sum_stride = 8;                            // 2048-element scan blocks over 256-point workgroup prefixes
+      }
+    }
+    if (msd && !speculative) return ggd_fail(ctx, GGD_E_INVALID, "internal: two-launch sort outside the speculative tile-binning path");
+    // the fourth pass is an empty launch when the depths' top byte is constant: after GGD_FLAT_STREAK such frames it is not
+    // launched; the collection re-renders a frame for which that was wrong (report.flat arrives with num_rendered)
+    fr.three_passes = ctx->spec.three_passes(fr.plan, folded, speculative, ctx->opt[GGD_OPT_FOLD]);
+    fr.report.folded = folded;
+    fold.msd = msd ? 1 : 0;
+    fold.msd_lo = fr.plan.lo; fold.msd_shift = fr.plan.shift;
+    if (msd)
+      rc = ggd_launch_sort32_msd(ctx, s, g.depth_keys, ka, va, kb, vb, prm->P,
+                                 reinterpret_cast<uint32_t*>(sc + 4 * pairs + sort_tmp + bin_tmp), &pg, &fold);
+    else
+      rc = ggd_launch_sort32_iota(ctx, s, g.depth_keys, ka, va, kb, vb, prm->P, 32, tmp, sort_tmp, folded ? nullptr : clean_ctl,
+                                  riding ? &pg : nullptr, true, false, folded ? &fold : nullptr, fr.three_passes);
+    if (rc != GGD_OK) return rc;
+    fr.r_pending = riding;
+    if (folded) { n_vis_ptr = ggd_fold_nvalid_ptr(fold.ctl); flat_ptr = ggd_fold_flat_ptr(fold.ctl); }
+    else {
+      const void* ctl = clean_ctl ? static_cast<const void*>(clean_ctl) : tmp;
+      n_vis_ptr = ggd_sort32_nvalid_ptr(ctl); flat_ptr = ggd_sort32_flat_ptr(ctl);
+    }
+  }
+  StageTimer t(ctx, ST_DUPLICATE, s);
+  // the depth sort dropped the culled Gaussians (key 0xFFFFFFFF) and left the number of kept ones on the device
+  const bool l1 = folded && (prm->width + 15) / 16 <= 64 && (prm->height + 15) / 16 <= 64;
+  return ggd_launch_rowbin(ctx, s, *prm, g.rect, va, n_vis_ptr, list, ranges, capacity, bin_tmp_ptr, bin_tmp, vb,
+                           flat_ptr, riding ? &pg : nullptr, l1 ? fold.ctl + GGD_FOLD_ROWTOT : nullptr,
+                           l1 ? fold.ctl + ggd_fold_l1_offset(prm->P) : nullptr);
+}
+
+// Binning path 2 (GGD_OPT_BINNING = 0, the debug taps, grids beyond 255 x 255 tiles, R = 0): one (tile | depth) key per instance,
+// a 64-bit sort, tile ranges by boundary detection.
+static int duplicate_sort_ranges(ggd_ctx* ctx, hipStream_t s, const ggd_params* prm, const geom_ptrs& g, const binning_ptrs& b,
+                                 uint32_t* ranges, int64_t R) {
+  const int T = ((prm->width + 15) / 16) * ((prm->height + 15) / 16);
+  int rc = GGD_OK;
+  if (R > 0) {
+    const int nbits = ggd_sort_bits(prm->width, prm->height);
+    const size_t sort_tmp = ggd_sort_tmp_bytes(R);
+    rc = ggd_reserve_scratch(ctx, sort_tmp, s);
+    if (rc != GGD_OK) return rc;
+    const bool to_alt = ggd_sort_input_is_alt(nbits) != 0;
+    uint64_t* k0 = to_alt ? b.keys_alt : b.keys;
+    uint32_t* v0 = to_alt ? b.list_alt : b.list;
+    {
+      StageTimer t(ctx, ST_DUPLICATE, s);
+      rc = ggd_launch_duplicate(ctx, s, *prm, g.rect, g.depth_keys, g.tiles, g.offsets, k0, v0);
+      if (rc != GGD_OK) return rc;
+    }
+    if (prm->debug) {
+      rc = grow_buffers(ctx, {{&ctx->dbg_keys, sizeof(uint64_t)}, {&ctx->dbg_vals, sizeof(uint32_t)}}, &ctx->dbg_cap, (size_t)R, (size_t)R);
+      if (rc != GGD_OK) return rc;
+      GGD_HIP(hipMemcpyAsync(ctx->dbg_keys, k0, (size_t)R * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+      GGD_HIP(hipMemcpyAsync(ctx->dbg_vals, v0, (size_t)R * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    }
+    StageTimer t(ctx, ST_SORT, s);
+    rc = ggd_launch_sort(ctx, s, b.keys, b.list, b.keys_alt, b.list_alt, R, nbits, ctx->scratch, ctx->scratch_bytes);
+    if (rc != GGD_OK) return rc;
+  }
+  StageTimer t(ctx, ST_RANGES, s);
+  return ggd_launch_ranges(ctx, s, b.keys, R, ranges, T);
+}
+
+// layout_R: what binning_buf was laid out for; R: number of instances to process (== layout_R unless the caller
+// over-allocated).  speculative: R is only a CAPACITY (the true num_rendered is still on the device); only the tile-binning
+// path can run that way.  out_depth / out_alpha (both or neither): the depth / alpha planes of the *_aux entry points
 static int render_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const void* geom_buf, int64_t layout_R,
                           int64_t R, void* binning_buf, void* img_buf, float* out_color, bool speculative,
                           float* out_depth = nullptr, float* out_alpha = nullptr) {
   (void)hipGetLastError();   // a sticky error another library left in this thread is not ours to report
-  // layout_R: what binning_buf was laid out for; R: number of instances to process (== layout_R unless the caller
-  // over-allocated; in the speculative case the true count is still on the device and R is only its upper bound)
   int rc = check_params(ctx, prm);
   if (rc != GGD_OK) return rc;
   if (R < 0) return ggd_fail(ctx, GGD_E_INVALID, "num_rendered < 0");
   if (!img_buf || !out_color) return ggd_fail(ctx, GGD_E_INVALID, "img_buf / out_color is NULL");
   if (R > 0 && (!geom_buf || !binning_buf)) return ggd_fail(ctx, GGD_E_INVALID, "geom_buf / binning_buf is NULL");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  ggd_geom_view gv; ggd_binning_view bv; ggd_img_view iv;
-  ggd_geom_layout(prm->P, &gv); ggd_binning_layout(layout_R, &bv); ggd_img_layout(prm->width, prm->height, &iv);
-  const char* gb = static_cast<const char*>(geom_buf);
-  char* bb = static_cast<char*>(binning_buf);
-  char* ib = static_cast<char*>(img_buf);
-  const ggd_splat* splat = reinterpret_cast<const ggd_splat*>(gb + gv.splat);
-  const uint32_t* tiles = reinterpret_cast<const uint32_t*>(gb + gv.tiles_touched);
-  const uint32_t* offsets = reinterpret_cast<const uint32_t*>(gb + gv.point_offsets);
-  const uint2* rect = reinterpret_cast<const uint2*>(gb + gv.rect);
-  const uint32_t* depth_keys_all = reinterpret_cast<const uint32_t*>(gb + gv.depth_keys);
-  uint64_t* keys = reinterpret_cast<uint64_t*>(bb + bv.keys);
-  uint32_t* list = reinterpret_cast<uint32_t*>(bb + bv.list);
-  uint64_t* keys_alt = reinterpret_cast<uint64_t*>(bb + bv.keys_alt);
-  uint32_t* list_alt = reinterpret_cast<uint32_t*>(bb + bv.list_alt);
-  uint32_t* ranges = reinterpret_cast<uint32_t*>(ib + iv.ranges);
-  float* final_T = reinterpret_cast<float*>(ib + iv.final_T);
-  uint32_t* n_contrib = reinterpret_cast<uint32_t*>(ib + iv.n_contrib);
-  const int T = ((prm->width + 15) / 16) * ((prm->height + 15) / 16);
-  const int nbits = ggd_sort_bits(prm->width, prm->height);
-
-  const int bmode = ctx->opt[GGD_OPT_BINNING];
-  // binning path: 0 = duplicate + radix sort; 3 (2: alias) = two-level row / column binning; 1 = auto: row binning when the
-  // grid is <= 255 x 255 tiles (and R is past its fixed costs), else the sort
-  const bool rowbin_ok = !prm->debug && ggd_rowbin_supported(prm->width, prm->height);
-  const bool rowbin = rowbin_ok && (bmode == 2 || bmode == 3 || (bmode == 1 && R >= GGD_ROWBIN_MIN_R));
-  const bool tilebin = rowbin;
-  if (speculative && !tilebin) return ggd_fail(ctx, GGD_E_INVALID, "speculative render needs the tile-binning path");
+  const geom_ptrs g = geom_view(prm, geom_buf);
+  const binning_ptrs b = binning_view(layout_R, binning_buf);
+  const img_ptrs im = img_view(prm->width, prm->height, img_buf);
+  const bool tiles = use_tile_binning(ctx, prm, R);
+  if (speculative && !tiles) return ggd_fail(ctx, GGD_E_INVALID, "speculative render needs the tile-binning path");
   const uint32_t capacity = R > 0xffffffffll ? 0xffffffffu : (uint32_t)R;
-  if (R > 0 && tilebin) {
-    // depth-sort the Gaussians once (32-bit keys), then one stable tile-binning pass
-    const uint32_t* depth_keys = reinterpret_cast<const uint32_t*>(gb + gv.depth_keys);
-    const size_t pairs = ggd_align((size_t)prm->P * sizeof(uint32_t));
-    const size_t sort_tmp = ggd_sort32_tmp_bytes(prm->P);
-    const size_t bin_tmp = ggd_rowbin_tmp_bytes(prm->P, capacity, prm->width, prm->height);
-    const size_t msd_tab = (ctx->msd_frame && ctx->scan_deferred && ctx->fold_active) ? ggd_sort32_msd_table_bytes(prm->P) : 0;
-    rc = ggd_reserve_scratch(ctx, 4 * pairs + sort_tmp + bin_tmp + msd_tab, s);
-    if (rc != GGD_OK) return rc;
-    char* sc = static_cast<char*>(ctx->scratch);
-    uint32_t* ka = reinterpret_cast<uint32_t*>(sc);
-    uint32_t* va = reinterpret_cast<uint32_t*>(sc + pairs);
-    uint32_t* kb = reinterpret_cast<uint32_t*>(sc + 2 * pairs);
-    uint32_t* vb = reinterpret_cast<uint32_t*>(sc + 3 * pairs);
-    void* tmp = sc + 4 * pairs;
-    void* bin_tmp_ptr = sc + 4 * pairs + sort_tmp;  // the sort's histogram block stays alive for the binning pass
-    uint32_t* clean_ctl = nullptr;
-    ggd_scan_piggy pg;          // a scan that rides on this call's launches (see geometry_enqueue)
-    bool riding = false;
-    const uint32_t *n_vis_ptr = nullptr, *flat_ptr = nullptr;   // device words: kept keys, "last pass was flat"
-    uint32_t* folded_l1 = nullptr;                              // the folded front end's control block, if this call has one
-    {
-      StageTimer t(ctx, ST_SORT, s);
-      // the control block this frame's scan cleared, if nobody has used it since (a second render of the same geometry
-      // falls back to the memset)
-      clean_ctl = ctx->sortctl_clean ? ctx->sortctl : nullptr;
-      ctx->sortctl_clean = false;
-      ggd_fold fold;
-      const bool folded = ctx->scan_deferred && ctx->fold_active;   // this call's preprocess filled the histograms
-      if (ctx->scan_deferred) {   // this call's geometry half left the scan to us
-        uint32_t* tiles_w = reinterpret_cast<uint32_t*>(const_cast<char*>(gb) + gv.tiles_touched);
-        pg.in = tiles_w; pg.out = reinterpret_cast<uint32_t*>(const_cast<char*>(gb) + gv.point_offsets);
-        pg.n = prm->P; pg.nb = ggd_scan_blocks(prm->P); pg.block_sums = ctx->scan_sums;
-        pg.d_total = ctx->d_words; pg.h_total = ctx->h_words_dev;
-        pg.h_tagged = reinterpret_cast<unsigned long long*>(ctx->h_words_dev + 2);
-        ctx->r_tag = (ctx->r_tag + 1u) & 0x3fffffffu;
-        if (ctx->r_tag == 0u) ctx->r_tag = 1u;
-        pg.tag = ctx->r_tag;
-        if (folded) {
-          const int nwg = (prm->P + 255) / 256;
-          fold.ctl = ctx->foldctl[ctx->fold_cur ^ 1];   // (fold_cur already points at the next frame's block)
-          pg.wg_info = reinterpret_cast<const uint4*>(ctx->scan_sums + (((size_t)nwg + 3) & ~(size_t)3));
-          pg.n_info = nwg;
-          pg.sum_stride = 8;                            // 2048-element scan blocks over 256-point workgroup prefixes
-        }
-      }
-      ctx->fold_active = false;
-      riding = ctx->scan_deferred;
-      // the fourth pass is an empty launch when the depths' top byte is constant: after GGD_FLAT_STREAK such frames it is not
-      // launched; ggd_forward re-renders a frame for which that was wrong (frame_flat arrives with num_rendered)
-      ctx->frame_folded = folded;
-      const bool msd = folded && ctx->msd_frame;   // (this call's preprocess built the two-launch sort's histograms)
-      if (msd && !(rowbin && speculative)) return ggd_fail(ctx, GGD_E_INVALID, "internal: two-launch sort outside the speculative tile-binning path");
-      ctx->spec3 = !msd && folded && rowbin && speculative && ctx->flat_streak >= GGD_FLAT_STREAK && ctx->opt[GGD_OPT_FOLD] == 1;
-      if (!msd) ctx->msd_frame = false;
-      fold.msd = msd ? 1 : 0;
-      fold.msd_lo = ctx->msd_lo; fold.msd_shift = ctx->msd_shift;
-      if (msd)
-        rc = ggd_launch_sort32_msd(ctx, s, depth_keys, ka, va, kb, vb, prm->P,
-                                   reinterpret_cast<uint32_t*>(sc + 4 * pairs + sort_tmp + bin_tmp), &pg, &fold);
-      else
-      rc = ggd_launch_sort32_iota(ctx, s, depth_keys, ka, va, kb, vb, prm->P, 32, tmp, sort_tmp, folded ? nullptr : clean_ctl,
-                                  riding ? &pg : nullptr, rowbin, !rowbin, folded ? &fold : nullptr, ctx->spec3);
-      ctx->r_pending = riding && rc == GGD_OK;
-      ctx->scan_deferred = false;
-      if (rc != GGD_OK) return rc;
-      if (folded) { n_vis_ptr = ggd_fold_nvalid_ptr(fold.ctl); flat_ptr = ggd_fold_flat_ptr(fold.ctl); folded_l1 = fold.ctl; }
-      else {
-        const void* ctl = clean_ctl ? static_cast<const void*>(clean_ctl) : tmp;
-        n_vis_ptr = ggd_sort32_nvalid_ptr(ctl); flat_ptr = ggd_sort32_flat_ptr(ctl);
-      }
-    }
-    {
-      StageTimer t(ctx, ST_DUPLICATE, s);
-      // the depth sort dropped the culled Gaussians (key 0xFFFFFFFF) and left the number of kept ones on the device
-      const bool l1 = folded_l1 != nullptr && (prm->width + 15) / 16 <= 64 && (prm->height + 15) / 16 <= 64;
-      rc = ggd_launch_rowbin(ctx, s, *prm, rect, va, n_vis_ptr, list, ranges, capacity, bin_tmp_ptr, bin_tmp, vb,
-                             flat_ptr, riding ? &pg : nullptr, l1 ? folded_l1 + GGD_FOLD_ROWTOT : nullptr,
-                             l1 ? folded_l1 + ggd_fold_l1_offset(prm->P) : nullptr);
-      if (rc != GGD_OK) return rc;
-    }
-  } else {
-  if (R > 0) {
-    const size_t sort_tmp = ggd_sort_tmp_bytes(R);
-    rc = ggd_reserve_scratch(ctx, sort_tmp, s);
-    if (rc != GGD_OK) return rc;
-    const bool to_alt = ggd_sort_input_is_alt(nbits) != 0;
-    uint64_t* k0 = to_alt ? keys_alt : keys;
-    uint32_t* v0 = to_alt ? list_alt : list;
-    {
-      StageTimer t(ctx, ST_DUPLICATE, s);
-      rc = ggd_launch_duplicate(ctx, s, *prm, rect, depth_keys_all, tiles, offsets, k0, v0);
-      if (rc != GGD_OK) return rc;
-    }
-    if (prm->debug) {
-      if (ctx->dbg_cap < (size_t)R) {
-        if (ctx->dbg_keys) (void)hipFree(ctx->dbg_keys);
-        if (ctx->dbg_vals) (void)hipFree(ctx->dbg_vals);
-        ctx->dbg_keys = ctx->dbg_vals = nullptr; ctx->dbg_cap = 0;
-        GGD_HIP(hipMalloc(&ctx->dbg_keys, (size_t)R * sizeof(uint64_t)));
-        GGD_HIP(hipMalloc(&ctx->dbg_vals, (size_t)R * sizeof(uint32_t)));
-        ctx->dbg_cap = (size_t)R;
-      }
-      GGD_HIP(hipMemcpyAsync(ctx->dbg_keys, k0, (size_t)R * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-      GGD_HIP(hipMemcpyAsync(ctx->dbg_vals, v0, (size_t)R * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    }
-    {
-      StageTimer t(ctx, ST_SORT, s);
-      rc = ggd_launch_sort(ctx, s, keys, list, keys_alt, list_alt, R, nbits, ctx->scratch, ctx->scratch_bytes);
-      if (rc != GGD_OK) return rc;
-    }
-  }
-  {
-    StageTimer t(ctx, ST_RANGES, s);
-    rc = ggd_launch_ranges(ctx, s, keys, R, ranges, T);
-    if (rc != GGD_OK) return rc;
-  }
-  }
-  {
-    StageTimer t(ctx, ST_BLEND, s);
-    rc = ggd_launch_blend(ctx, s, *prm, splat, list, ranges, capacity, out_color, final_T, n_contrib, depth_keys_all, out_depth,
-                          out_alpha);
-    if (rc != GGD_OK) return rc;
-  }
-  return GGD_OK;
+  rc = (R > 0 && tiles) ? sort_depth_and_bin_tiles(ctx, s, prm, g, b.list, im.ranges, capacity, speculative)
+                        : duplicate_sort_ranges(ctx, s, prm, g, b, im.ranges, R);
+  if (rc != GGD_OK) return rc;
+  StageTimer t(ctx, ST_BLEND, s);
+  return ggd_launch_blend(ctx, s, *prm, g.splat, b.list, im.ranges, capacity, out_color, im.final_T, im.n_contrib, g.depth_keys,
+                          out_depth, out_alpha);
 }
 
 extern "C" int ggd_forward_render(ggd_ctx* ctx, void* stream, const ggd_params* prm, const void* geom_buf,
                                   int64_t R, void* binning_buf, void* img_buf, float* out_color) {
-  // (the speculation state of a frame between ggd_forward_enqueue and ggd_forward_collect -- spec3, msd_frame, frame_folded, the
-  // tagged read-back -- lives on the context: another forward on it would clear that state and a missed speculation would
-  // never be rendered again)
+  // (another forward would begin a new ctx->frame: the pending one's missed speculation would never be rendered again)
   if (ctx && ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, kPendingMsg);
   return render_enqueue(ctx, stream, prm, geom_buf, R, R, binning_buf, img_buf, out_color, false);
 }
@@ -673,10 +649,7 @@ extern "C" int ggd_forward_render_aux(ggd_ctx* ctx, void* stream, const ggd_para
 }
 
 extern "C" int ggd_forward_can_speculate(ggd_ctx* ctx, const ggd_params* prm, int64_t capacity) {
-  if (!ctx || !prm || prm->debug || prm->P <= 0) return 0;
-  const int bmode = ctx->opt[GGD_OPT_BINNING];
-  return (ggd_rowbin_supported(prm->width, prm->height) &&
-          (bmode == 2 || bmode == 3 || (bmode == 1 && capacity >= GGD_ROWBIN_MIN_R))) ? 1 : 0;
+  return ctx && prm && prm->P > 0 && use_tile_binning(ctx, prm, capacity) ? 1 : 0;
 }
 
 // The speculative route of the single-call forward in its two halves: everything is enqueued before the host looks at
@@ -689,48 +662,24 @@ static int forward_spec_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* pr
   int rc = geometry_enqueue(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations,
                             cov3D_precomp, geom_buf, radii, num_rendered, true);
   if (rc != GGD_OK) return rc;
-  ctx->spec3 = false; ctx->frame_folded = false; ctx->frame_flat = false; ctx->frame_msd_ok = false;
-  ctx->frame_kmin = 0xffffffffu; ctx->frame_kmax = 0u; ctx->frame_msd_flags = 0u;
   return render_enqueue(ctx, stream, prm, geom_buf, capacity, capacity, binning_buf, img_buf, out_color, true, out_depth,
                         out_alpha);
 }
-// ... and the collection of num_rendered (+ "the depth keys' top byte was constant") once the launch that delivers it has run;
-// binning and blend may still be running.  A frame that needed the fourth sort pass it did not get is binned and blended again.
+// ... and the collection of num_rendered and the frame's report once the launch that delivers them has run; binning and blend
+// may still be running.  A frame for which the short form of the sort did not hold is binned and blended again, in full.
 static int forward_spec_collect(ggd_ctx* ctx, void* stream, const ggd_params* prm, const void* geom_buf, void* binning_buf,
                                 int64_t capacity, void* img_buf, float* out_color, int64_t* num_rendered,
                                 float* out_depth = nullptr, float* out_alpha = nullptr) {
-  int rc = geometry_finish(ctx, stream, prm, num_rendered);
+  const int rc = geometry_finish(ctx, stream, prm, num_rendered);
   if (rc != GGD_OK) return rc;
-  const bool spec3 = ctx->spec3, msd = ctx->msd_frame;
-  ctx->spec3 = false; ctx->msd_frame = false;
-  if (ctx->frame_folded) ctx->flat_streak = ctx->frame_flat ? (ctx->flat_streak < (1 << 30) ? ctx->flat_streak + 1 : ctx->flat_streak) : 0;
-  if (ctx->frame_folded && ctx->msd_ban > 0) ctx->msd_ban -= 1;
-  const bool msd_missed = msd && !ctx->frame_msd_ok;
-  const bool msd_oversize = msd_missed && (ctx->frame_msd_flags & 4u) == 0u;   // a bucket above the finish kernel's capacity
-  if (msd_oversize) {
-    // the window was too coarse for this data -- typically fitted to another scene: forget the older frames' ranges (the window
-    // re-forms from this scene's in GGD_FLAT_STREAK frames) -- or the data has > GGD_MSD_CAP equal keys, which no window cures:
-    // the pause doubles with every consecutive such miss (8, 16, 32, GGD_MSD_BAN frames)
-    ctx->msd_oversize_streak = ctx->msd_oversize_streak < 4 ? ctx->msd_oversize_streak + 1 : 4;
-    ctx->msd_ban = GGD_MSD_BAN >> (4 - ctx->msd_oversize_streak);
-    ctx->win_n = 0; ctx->win_pos = 0;
-  } else if (msd_missed) {
-    ctx->msd_ban = 2;   // a key outside the window: this frame's range joins the window below, the next frames fit again
-  }
-  if (ctx->frame_folded && ctx->frame_kmin <= ctx->frame_kmax) {   // (something was kept) -> the ring of recent key ranges
-    ctx->win_lo[ctx->win_pos] = ctx->frame_kmin; ctx->win_hi[ctx->win_pos] = ctx->frame_kmax;
-    ctx->win_pos = (ctx->win_pos + 1) % GGD_MSD_WIN;
-    if (ctx->win_n < (1 << 30)) ctx->win_n += 1;
-  }
-  if (msd && !msd_missed) { ctx->msd_frames += 1; ctx->msd_oversize_streak = 0; }
-  if (*num_rendered > capacity)
+  const ggd_frame done = frame_renew(ctx);   // (a re-render below is a frame of its own: nothing to ride on, nothing to collect)
+  const bool too_small = *num_rendered > capacity;
+  const bool again = ctx->spec.observe(done.plan, done.three_passes, done.report, too_small);
+  if (too_small)
     return ggd_fail(ctx, GGD_E_CAPACITY, "binning_buf capacity is below num_rendered: re-run with a larger buffer");
-  if (msd_missed || (spec3 && !ctx->frame_flat)) {   // the short form of the sort did not hold for this frame: bin and blend it again, in full
-    ctx->spec3_misses += 1;
-    return render_enqueue(ctx, stream, prm, geom_buf, capacity, *num_rendered, binning_buf, img_buf, out_color, false, out_depth,
-                          out_alpha);
-  }
-  return GGD_OK;
+  if (!again) return GGD_OK;
+  return render_enqueue(ctx, stream, prm, geom_buf, capacity, *num_rendered, binning_buf, img_buf, out_color, false, out_depth,
+                        out_alpha);
 }
 
 static int forward_single_call(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D, const float* shs,
@@ -793,8 +742,7 @@ extern "C" int ggd_forward_enqueue(ggd_ctx* ctx, void* stream, const ggd_params*
   const int rc = forward_spec_enqueue(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations,
                                       cov3D_precomp, geom_buf, radii, binning_buf, capacity, img_buf, out_color, &dummy);
   if (rc != GGD_OK) return rc;
-  ctx->pending.valid = true; ctx->pending.prm = *prm; ctx->pending.geom = geom_buf; ctx->pending.binning = binning_buf;
-  ctx->pending.capacity = capacity; ctx->pending.img = img_buf; ctx->pending.out = out_color;
+  ctx->pending = {true, *prm, geom_buf, binning_buf, capacity, img_buf, out_color};
   return GGD_OK;
 }
 
@@ -829,18 +777,9 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, cons
   if (prm->antialiasing && !opacities)   // dL/dh of the opacity compensation is dL/do_eff times the opacity
     return ggd_fail(ctx, GGD_E_INVALID, "antialiasing needs the opacities in the backward");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  ggd_geom_view gv; ggd_binning_view bv; ggd_img_view iv;
-  ggd_geom_layout(P, &gv); ggd_binning_layout(R, &bv); ggd_img_layout(prm->width, prm->height, &iv);
-  const char* gb = static_cast<const char*>(geom_buf);
-  const char* bb = static_cast<const char*>(binning_buf);
-  const char* ib = static_cast<const char*>(img_buf);
-  const ggd_splat* splat = reinterpret_cast<const ggd_splat*>(gb + gv.splat);
-  const uint8_t* clamped = reinterpret_cast<const uint8_t*>(gb + gv.clamped);
-  const uint32_t* list = reinterpret_cast<const uint32_t*>(bb + bv.list);
-  const uint32_t* ranges = reinterpret_cast<const uint32_t*>(ib + iv.ranges);
-  const float* final_T = reinterpret_cast<const float*>(ib + iv.final_T);
-  const uint32_t* n_contrib = reinterpret_cast<const uint32_t*>(ib + iv.n_contrib);
-  const uint32_t* depth_keys = reinterpret_cast<const uint32_t*>(gb + gv.depth_keys);
+  const geom_ptrs g = geom_view(prm, geom_buf);
+  const binning_ptrs b = binning_view(R, binning_buf);
+  const img_ptrs im = img_view(prm->width, prm->height, img_buf);
 
   const size_t acc_bytes = (size_t)P * GGD_ACC_FLOATS * sizeof(float);
   rc = ggd_reserve_scratch(ctx, ggd_align(acc_bytes), s);
@@ -857,14 +796,14 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, cons
 
   if (R > 0) {
     StageTimer t(ctx, ST_BLEND_BWD, s);
-    rc = ggd_launch_blend_backward(ctx, s, *prm, splat, list, ranges, final_T, n_contrib, dL_dpix, grad_acc, aux, depth_keys,
-                                   dL_ddepth, dL_dalpha);
+    rc = ggd_launch_blend_backward(ctx, s, *prm, g.splat, b.list, im.ranges, im.final_T, im.n_contrib, dL_dpix, grad_acc, aux,
+                                   g.depth_keys, dL_ddepth, dL_dalpha);
     if (rc != GGD_OK) return rc;
   }
   {
     StageTimer t(ctx, ST_PREPROCESS_BWD, s);
     rc = ggd_launch_preprocess_backward(ctx, s, *prm, means3D, shs, colors_precomp, opacities, dL_dopacity, scales, rotations,
-                                        cov3D_precomp, radii, shs ? clamped : nullptr, grad_acc, dL_dmeans2D,
+                                        cov3D_precomp, radii, shs ? g.clamped : nullptr, grad_acc, dL_dmeans2D,
                                         dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots, aux);
     if (rc != GGD_OK) return rc;
   }

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "ggd_raster.h"
+#include "ggd_spec.h"
 
 #define GGD_WAVE 64
 
@@ -29,12 +30,25 @@ constexpr int GGD_STATS_BWD = 16;            // eight counters of the backward b
 constexpr int GGD_STATS_HEAD = 32;           // first timeline slot (3 words per wave: start, end, listed << 32 | gathered)
 constexpr int GGD_STATS_MAX_WAVES = 1 << 17;
 
-// two-launch depth sort (described at ggd_fold below)
-constexpr int GGD_MSD_SHIFT = 14, GGD_MSD_BINS = 1024, GGD_MSD_CAP = 12288, GGD_MSD_MAX_TILES = 2048, GGD_MSD_BAN = 64;
-constexpr int GGD_MSD_WIN = 32, GGD_MSD_MAX_SHIFT = 16;   // frames whose key ranges form the window; two 8-bit passes finish a bucket
-constexpr int GGD_MSD_TARGET = 512;   // buckets the window is spread over: 512 = one resident round of the finish kernel (two workgroups
-                                      // per CU); measured at 1 M / 1024^2, sort stage cube / shell: 1024 -> 27.4 / 35.8 us, 512 -> 23.5 / 33.5,
-                                      // 256 -> 25.8 / 34.1 (gpurun_out r06b; round 5's fixed bits 14..23: 23.2 / 34.5)
+// two-launch depth sort (described at ggd_fold below; the constants the host's policy needs are in ggd_spec.h)
+constexpr int GGD_MSD_BINS = 1024, GGD_MSD_CAP = 12288, GGD_MSD_MAX_TILES = 2048;
+
+// The frame in flight: what geometry_enqueue leaves for render_enqueue, and render_enqueue for the collection of num_rendered.
+// A frame begins in geometry_enqueue, which assigns a fresh one (only the tag carries over); nothing else clears these.
+struct ggd_frame {
+  // geometry_enqueue -> the first render_enqueue behind it, which takes them (a second render of the same geometry rides on nothing)
+  struct {
+    bool ride = false;            // the offsets scan was left to the depth sort's launches
+    bool folded = false;          // ... and the preprocess built the sort's histograms + the scan's first step (ggd_fold below)
+    bool sortctl_clean = false;   // the preprocess cleared ctx->sortctl and no sort has used it since
+  } geom;
+  ggd_spec_plan plan;             // decided before the preprocess launch
+  // render_enqueue -> collection
+  bool three_passes = false;      // the fourth sort pass was not launched
+  bool r_pending = false;         // the host waits for the tagged word (h_words[2..3]), not for the end of the frame
+  uint32_t r_tag = 0;             // ... which carries this sequence number (30 bits, never 0)
+  ggd_spec_report report;         // `folded` by render_enqueue, the rest read with num_rendered (the key range only when folded)
+};
 
 struct ggd_ctx {
   int device = 0;
@@ -45,48 +59,21 @@ struct ggd_ctx {
   uint32_t* h_words = nullptr;  // pinned host mirror
   uint32_t* h_words_dev = nullptr;  // the same memory as the device sees it (the scan writes num_rendered there itself)
   uint32_t* sortctl = nullptr;      // depth sort's control block (histograms, tickets, kept-key count) in its own allocation
-  bool sortctl_clean = false;       // cleared by this frame's preprocess and not yet consumed by a sort
   uint32_t* scan_sums = nullptr;    // block sums of a scan that rides on the depth sort (own allocation, grow-only)
-  int scan_sums_cap = 0;
+  size_t scan_sums_cap = 0;
   // depth-sort front end folded into the preprocess kernel (ggd_fold below): two control blocks used alternately
   uint32_t* foldctl[2] = {nullptr, nullptr};
   size_t foldctl_cap = 0;           // words per block
   size_t foldctl_dirty[2] = {0, 0}; // words of each block its last user may have written (what the next clear must cover)
   int fold_cur = 0;                 // block the next folding preprocess accumulates into (cleared by the previous one)
   bool fold_poisoned = false;       // a folding launch failed: nothing is known about the blocks -- clear both before the next use
-  bool fold_active = false;         // this call's preprocess left histograms + workgroup sums for the sort of the same call
-  // the depth keys' top byte (sign + 7 exponent bits) is constant in most scenes: after GGD_FLAT_STREAK such frames in a row
-  // the fourth sort pass -- an empty launch, 4.9 us -- is not launched at all; the frame's own histogram says whether that
-  // was right (bit 63 of the tagged num_rendered word), and a frame it was wrong for is binned and blended again
-  int flat_streak = 0;
-  bool spec3 = false;               // this call launched three passes
-  bool frame_flat = false;          // this call's top byte was constant (read with num_rendered)
-  bool frame_folded = false;        // ... and it ran the folded front end (frame_flat is meaningful)
-  unsigned long long spec3_misses = 0;
-  // two-launch sort (GGD_OPT_MSD_SORT): decided per frame before the preprocess launch (it selects the histograms to build)
-  bool msd_frame = false;           // this call's front end built the two-launch sort's histograms
-  bool frame_msd_ok = false;        // ... and they say the two-launch sort was valid for this frame (read with num_rendered)
-  int msd_ban = 0;                  // frames to wait before speculating again after a frame it was not valid for
-  int msd_oversize_streak = 0;      // consecutive oversized-bucket misses: the pause doubles (8, 16, 32, 64 frames) until a frame succeeds
-  unsigned long long msd_frames = 0;
-  // ... over a speculated KEY WINDOW (round 6): buckets = (key - msd_lo) >> msd_shift, window and shift fitted to the depth
-  // keys of the recent folded frames (their min / max arrive with num_rendered), so a depth range that straddles a binade
-  // (2.0: top byte 0x3F | 0x40) no longer falls back to the four-pass sort
-  uint32_t msd_lo = 0;              // this frame's window start and bucket shift
-  int msd_shift = GGD_MSD_SHIFT;
-  uint32_t win_lo[GGD_MSD_WIN], win_hi[GGD_MSD_WIN];   // ring: kept-key min / max of the last folded frames
-  int win_n = 0, win_pos = 0;
-  uint32_t frame_kmin = 0xffffffffu, frame_kmax = 0u, frame_msd_flags = 0u;   // read with num_rendered
-  int msd_buckets = GGD_MSD_TARGET; // buckets the window is spread over (GGD_MSD_BUCKETS: timing experiments)
+  ggd_spec spec;                    // cross-frame speculation policy: three sort passes / the two-launch sort (ggd_spec.h)
+  ggd_frame frame;                  // the one frame in flight
   // ggd_forward_enqueue ... ggd_forward_collect: the frame whose num_rendered has not been collected yet
   struct { bool valid = false; ggd_params prm; const void* geom = nullptr; void* binning = nullptr; int64_t capacity = 0;
            void* img = nullptr; float* out = nullptr; } pending;
-  bool scan_deferred = false;       // geometry_enqueue left the scan to the sort launches of the same call
   void* gelu_tables = nullptr;      // GELU / GELU' interpolation tables of the reference-precision decoder kernels (built on first use)
-  uint32_t r_tag = 0;               // sequence number of the single-call forward whose num_rendered the host is waiting for
-  bool r_pending = false;           // the host waits for the tagged word (h_words[2..3]), not for the end of the frame
-  void* dbg_keys = nullptr;     // debug copy of the unsorted list
-  void* dbg_vals = nullptr;
+  void *dbg_keys = nullptr, *dbg_vals = nullptr;   // debug copy of the unsorted list
   size_t dbg_cap = 0;
   int opt[GGD_OPT_COUNT] = {3, 1, 1, 1, 1, 1};  // exp: bare v_exp_f32 in the forward blend, compensated 2^x (1-2 ulp) in the backward
   unsigned long long* blend_stats = nullptr;  // debug: device counters filled by the forward blend when non-null
@@ -264,7 +251,6 @@ int ggd_launch_sort32_iota(ggd_ctx* ctx, hipStream_t s, const uint32_t* keys_src
 //       num_rendered word and in d_total[2].
 // skip_last (fold only): the last pass is not launched (the caller expects a constant top digit); the consumers' flat word is
 //       set regardless, so that they read the third pass's output (a valid permutation either way)
-constexpr int GGD_FLAT_STREAK = 8;
 const uint32_t* ggd_sort32_flat_ptr(const void* ctl);
 size_t ggd_sort32_msd_table_bytes(int64_t n);
 bool ggd_sort32_msd_supported(int64_t n);
@@ -324,45 +310,5 @@ __device__ __forceinline__ int ggd_tile_rect(float px, float py, int irad, int g
   maxx = min(gx, max(0, (int)((px + fr + 15.0f) / 16.0f)));
   maxy = min(gy, max(0, (int)((py + fr + 15.0f) / 16.0f)));
   return (maxx - minx) * (maxy - miny);
-}
-
-// Nine wave sums at once (the blend backward's per-Gaussian partials), totals valid in lane 63.  Same six DPP steps as
-// ggd_wave_sum_to63, written as v_add_f32_dpp so that each step is ONE instruction per value (through the builtin the
-// compiler emits v_mov_b32_dpp + a packed add: 1.5 per value).  The nine chains are interleaved step by step, which
-// also provides the wait states a DPP read of a freshly written VGPR needs (the hazard recogniser does not look inside
-// inline asm); the leading s_nop covers the producers of the inputs.
-#define GGD_DPP9(ctrl)                                                                                          \
-  asm volatile("v_add_f32_dpp %0, %0, %0 " ctrl "\n\tv_add_f32_dpp %1, %1, %1 " ctrl "\n\t"                      \
-               "v_add_f32_dpp %2, %2, %2 " ctrl "\n\tv_add_f32_dpp %3, %3, %3 " ctrl "\n\t"                      \
-               "v_add_f32_dpp %4, %4, %4 " ctrl "\n\tv_add_f32_dpp %5, %5, %5 " ctrl "\n\t"                      \
-               "v_add_f32_dpp %6, %6, %6 " ctrl "\n\tv_add_f32_dpp %7, %7, %7 " ctrl "\n\t"                      \
-               "v_add_f32_dpp %8, %8, %8 " ctrl                                                                 \
-               : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), \
-                 "+v"(v[8]))
-__device__ __forceinline__ void ggd_wave_sum9_to63(float (&v)[9]) {
-  asm volatile("s_nop 1");
-  GGD_DPP9("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0");
-  GGD_DPP9("row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0");
-  GGD_DPP9("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0");
-  GGD_DPP9("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:0");
-  GGD_DPP9("row_bcast:15 row_mask:0xa bank_mask:0xf");
-  GGD_DPP9("row_bcast:31 row_mask:0xc bank_mask:0xf");
-  asm volatile("s_nop 1");
-}
-#undef GGD_DPP9
-
-// Sum over the 64 lanes of a wave with DPP row shifts / broadcasts; the total is valid in lane 63.
-// (Hillis-Steele inclusive scan inside each 16-lane row, then row_bcast:15 into rows 1/3 and row_bcast:31 into
-// rows 2/3; lanes without a valid source add the `old` operand = 0.)
-#define GGD_DPP_ADD(v, ctrl, rowmask)                                                                         \
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, rowmask, 0xf, false))
-__device__ __forceinline__ float ggd_wave_sum_to63(float v) {
-  GGD_DPP_ADD(v, 0x111, 0xf);  // row_shr:1
-  GGD_DPP_ADD(v, 0x112, 0xf);  // row_shr:2
-  GGD_DPP_ADD(v, 0x114, 0xf);  // row_shr:4
-  GGD_DPP_ADD(v, 0x118, 0xf);  // row_shr:8
-  GGD_DPP_ADD(v, 0x142, 0xa);  // row_bcast:15 -> rows 1, 3
-  GGD_DPP_ADD(v, 0x143, 0xc);  // row_bcast:31 -> rows 2, 3
-  return v;
 }
 #endif

@@ -262,7 +262,7 @@ def check_gradients(d, got: dict, ref: dict, budget: dict, fragile, kappa=KAPPA,
 
 
 def msd_window(ranges, buckets=512):
-    """The two-launch depth sort's key window (csrc/ggd_capi.hip::msd_fit_window) for frames whose kept depth keys (uint32 views of
+    """The two-launch depth sort's key window (csrc/ggd_spec.h::fit_window) for frames whose kept depth keys (uint32 views of
     the fp32 depths) span `ranges` = [(min, max), ...]: returns (lo, shift), or None when the window is too wide for the two
     finishing passes.  A frame's bucket sizes are then np.bincount(np.minimum((keys - lo) >> shift, 1023))."""
     lo, hi = min(int(r[0]) for r in ranges), max(int(r[1]) for r in ranges)
