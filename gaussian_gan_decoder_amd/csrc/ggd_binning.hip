@@ -18,6 +18,7 @@
 namespace {
 
 #include "ggd_scan.inc"
+#include "ggd_lookback.inc"
 
 __global__ __launch_bounds__(SCAN_THREADS) void scan_reduce_kernel(const uint32_t* __restrict__ in, int64_t n,
                                                                    uint32_t* __restrict__ block_sums) {
@@ -32,30 +33,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_blocksums_kernel(uint32_t* 
   scan_blocksums_block(block_sums, nb, d_total, h_total, lds4);
 }
 
-template <bool EXCLUSIVE>
 __global__ __launch_bounds__(SCAN_THREADS) void scan_apply_kernel(const uint32_t* __restrict__ in,
                                                                   uint32_t* __restrict__ out, int64_t n,
                                                                   const uint32_t* __restrict__ block_prefix) {
   __shared__ uint32_t lds4[4];
-  scan_apply_block<EXCLUSIVE>(in, out, n, block_prefix, (int)blockIdx.x, lds4);
-}
-
-template <bool EXCLUSIVE>
-int launch_scan(ggd_ctx* ctx, hipStream_t s, const uint32_t* in, uint32_t* out, int64_t n, uint32_t* d_total,
-                void* tmp, size_t tmp_bytes, uint32_t* h_total = nullptr) {
-  if (n <= 0) {
-    if (d_total) GGD_HIP(hipMemsetAsync(d_total, 0, sizeof(uint32_t), s));
-    if (h_total) *h_total = 0u;
-    return GGD_OK;
-  }
-  const int nb = (int)((n + SCAN_TILE - 1) / SCAN_TILE);
-  if (tmp_bytes < (size_t)nb * sizeof(uint32_t)) return ggd_fail(ctx, GGD_E_INVALID, "scan tmp too small");
-  uint32_t* block_sums = static_cast<uint32_t*>(tmp);
-  hipLaunchKernelGGL(scan_reduce_kernel, dim3(nb), dim3(SCAN_THREADS), 0, s, in, n, block_sums);
-  hipLaunchKernelGGL(scan_blocksums_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, block_sums, nb, d_total, h_total);
-  hipLaunchKernelGGL(scan_apply_kernel<EXCLUSIVE>, dim3(nb), dim3(SCAN_THREADS), 0, s, in, out, n, block_sums);
-  GGD_HIP(hipGetLastError());
-  return GGD_OK;
+  scan_apply_block(in, out, n, block_prefix, (int)blockIdx.x, lds4);
 }
 
 // ------------------------------------------------------------------------------------------------- duplicate --
@@ -122,45 +104,11 @@ __global__ __launch_bounds__(256) void duplicate_kernel(int P, int W, int H, con
 // "Onesweep" LSD radix sort: ONE kernel per 8-bit digit pass (+ one up-front kernel that histograms every digit).
 //   * global digit histograms are permutation-invariant, so all passes' bin bases come from one read of the keys;
 //   * inside a pass every 4096-pair tile computes its digit counts, publishes them, and obtains the sum over all
-//     EARLIER tiles from a fixed two-level tree: tiles form groups of G = 2^gshift (G ~ sqrt(#tiles)); the last tile
-//     of a group sums the group's counts and publishes the group aggregate; a tile then adds the aggregates of the
-//     earlier groups and the counts of the earlier tiles of its own group -- at most 2G independent loads, three
-//     dependent memory round trips per pass.  (The classic decoupled look-back chain needs ~#tiles / 16 dependent
-//     round trips here: all tiles of a pass start together, so nobody finds an inclusive prefix nearby -- 15 round
-//     trips and 7.5 M uncached status loads per pass at 245 tiles, the 14 us floor the passes used to have.)
-//     A status word per (tile | group, digit) = flag bit | 30-bit count, written / read as single agent-scope relaxed
-//     atomics (the value IS the flag, so no fence is needed and the protocol is placement independent: per-XCD L2s
-//     are not coherent, agent-scope atomics bypass them); tiles take their index from an atomic ticket and only ever
-//     wait for lower-numbered tiles, i.e. for tiles that are already running;
+//     EARLIER tiles from the two-level look-back of ggd_lookback.inc (a status word per (tile | group, digit)); tiles
+//     take their index from an atomic ticket and only ever wait for lower-numbered tiles, i.e. for tiles that are
+//     already running;
 //   * stability: element order inside a tile = (wave, round, lane); rank inside a wave by ballot matching.
-constexpr int RS_THREADS = 256;
-constexpr int RS_ITEMS = 16;                      // keys per lane
-constexpr int RS_TILE = RS_THREADS * RS_ITEMS;    // 4096 pairs per tile
-constexpr int RS_BINS = 256;
-constexpr int RS_MAX_PASSES = 8;
-constexpr int RS32_ITEMS = 16;                   // tile size of the 32-bit (depth) sort (4 was slower: longer look-back)
-constexpr int RS32_TILE = RS_THREADS * RS32_ITEMS;
-constexpr int RS_HWORDS = RS_MAX_PASSES * RS_BINS;
-constexpr int RS_RESIDENT = 1024;   // tiles (256-thread workgroups, 5 KB LDS) that are certainly resident together on 256 CUs
-constexpr int RS_BATCH = 16;     // status words requested together while summing predecessors (batches are dependent round trips)
-constexpr uint32_t RS_FLAG = 1u << 30, RS_COUNT_MASK = (1u << 30) - 1u;
-// tiles per group of the two-level prefix: the power of two nearest to sqrt(ntiles) from above
-static inline int rs_gshift(int64_t ntiles) { int g = 2; while (((int64_t)1 << (2 * g)) < ntiles) ++g; return g; }
-// per pass: tile words, then group words.  A pass picks its group size from the number of tiles that hold elements (a
-// device-side count in the compacting sort): g <= rs_gshift(ntiles) with up to 2^g groups in use -- more than
-// ntiles >> rs_gshift(ntiles) when the count falls just below a power of four (257 launched tiles, 256 live ones: 16 groups
-// against 9 rows; the overflow landed in the next pass's tile words).  2^rs_gshift + 1 rows cover every choice.
-static inline int64_t rs_status_words(int64_t ntiles) {
-  return (ntiles + ((int64_t)1 << rs_gshift(ntiles)) + 1) * RS_BINS;
-}
-
-__device__ __forceinline__ uint32_t rs_load(uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void rs_store(uint32_t* p, uint32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
+// Constants, the control block and the status words' layout: ggd_binning_layout.h.
 // ghist[pass * 256 + digit] += occurrences, for every pass at once.  High key bytes are heavily skewed (tile bits of
 // consecutive instances, exponent byte of the depth): when a whole wave shares the digit one lane adds the count
 // instead of 64 conflicting LDS atomics.
@@ -235,6 +183,14 @@ __device__ __forceinline__ void fold_publish_range(const ggd_scan_piggy& pg, uin
   if (pg.h_total) { pg.h_total[4] = ~nmin; pg.h_total[5] = kmax; pg.h_total[6] = flags; }
 }
 
+// What the workgroups appended to a onesweep launch run instead of sorting (the kernel's `piggy_role`): a step of the offsets
+// scan that rides on the depth sort (ggd_scan_piggy).
+enum ggd_passenger_role : int {
+  GGD_PASSENGER_SCAN_SUMS = 2,    // step 2, ONE workgroup (pass 0): block sums -> prefixes, num_rendered to the host; folded front
+                                  // end: the preprocess workgroups' records instead, plus the sum of the histogram replicas
+  GGD_PASSENGER_SCAN_APPLY = 3,   // step 3, one workgroup per scan block (pass 1): the offsets
+};
+
 // COMPACT (depth sort): pass 0 (IOTA) drops keys equal to ~0 -- they are neither ranked nor written -- and every later
 // pass takes its element count from *n_dev (= number of kept keys, written by the histogram kernel).  A later pass
 // whose digit is the same for all elements (ghist[d] == n: e.g. the exponent byte of a scene's depth range) degrades to
@@ -250,8 +206,8 @@ __global__ __launch_bounds__(RS_THREADS) void sort_onesweep_kernel(
     const uint32_t* __restrict__ n_dev = nullptr, int piggy_role = 0, ggd_scan_piggy pg = ggd_scan_piggy{},
     uint32_t* __restrict__ flat_flag = nullptr, int hist_reps = 1) {
   __shared__ uint32_t s_cnt[4][RS_BINS];   // per-wave running digit counts -> per-wave scatter bases
-  if ((int)blockIdx.x >= ntiles) {   // appended workgroups: steps 2 / 3 of the offsets scan (see ggd_scan_piggy)
-    if (piggy_role == 2 && pg.wg_info) {
+  if ((int)blockIdx.x >= ntiles) {   // appended workgroups: a passenger, not the sort (ggd_passenger_role)
+    if (piggy_role == GGD_PASSENGER_SCAN_SUMS && pg.wg_info) {
       const uint4 tv = scan_info_block(pg.wg_info, pg.n_info, pg.block_sums, pg.n_valid, pg.d_total, pg.h_total, &s_cnt[0][0]);
       int flat = 0;
       if (pg.fold_hist) {   // passes 1 .. 3 then read ONE histogram (pass 0's tiles, running beside us, read their own 256 bins
@@ -278,10 +234,10 @@ __global__ __launch_bounds__(RS_THREADS) void sort_onesweep_kernel(
                              __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
-    else if (piggy_role == 2)
+    else if (piggy_role == GGD_PASSENGER_SCAN_SUMS)
       scan_blocksums_block(pg.block_sums, pg.nb, pg.d_total, pg.h_total, &s_cnt[0][0], pg.h_tagged, pg.tag);
     else
-      scan_apply_block<false>(pg.in, pg.out, pg.n, pg.block_sums, (int)blockIdx.x - ntiles, &s_cnt[0][0], pg.sum_stride);
+      scan_apply_block(pg.in, pg.out, pg.n, pg.block_sums, (int)blockIdx.x - ntiles, &s_cnt[0][0], pg.sum_stride);
     return;
   }
   __shared__ uint32_t s_scan[4];
@@ -370,38 +326,11 @@ __global__ __launch_bounds__(RS_THREADS) void sort_onesweep_kernel(
     const int d = threadIdx.x;
     const uint32_t c0 = s_cnt[0][d], c1 = s_cnt[1][d], c2 = s_cnt[2][d], c3 = s_cnt[3][d];
     const uint32_t local = c0 + c1 + c2 + c3;
-    // sum of `cnt` published words p[0], p[stride], ...: RS_BATCH requests in flight, unpublished ones are polled
-    auto sum_words = [&](uint32_t* p, int cnt) {
-      uint32_t acc = 0;
-      for (int b0 = 0; b0 < cnt; b0 += RS_BATCH) {
-        uint32_t v[RS_BATCH];
-#pragma unroll
-        for (int i = 0; i < RS_BATCH; ++i) v[i] = (b0 + i < cnt) ? rs_load(p + (size_t)(b0 + i) * RS_BINS) : RS_FLAG;
-#pragma unroll
-        for (int i = 0; i < RS_BATCH; ++i) {
-          uint32_t x = v[i];
-          if ((x >> 30) == 0u) {
-            uint32_t* q = p + (size_t)(b0 + i) * RS_BINS;
-            do { __builtin_amdgcn_s_sleep(1); x = rs_load(q); } while ((x >> 30) == 0u);
-          }
-          acc += x & RS_COUNT_MASK;
-        }
-      }
-      return acc;
-    };
     // group size from the number of tiles that hold elements (known on the device only in the compacting sort):
     // G = 2^gshift ~ sqrt(live tiles), never above the launch's (the group words were laid out for that)
     const int64_t live_tiles = (n + RS_THREADS * ITEMS - 1) / (RS_THREADS * ITEMS);
-    int gs = 2;
-    while (((int64_t)1 << (2 * gs)) < live_tiles) ++gs;
-    gshift = min(gshift, gs);
-    const int grp = (int)(tile >> gshift), mem = (int)(tile & ((1u << gshift) - 1u));
-    uint32_t* tile_words = status + d;                               // [tile][256]
-    uint32_t* group_words = status + (size_t)ntiles * RS_BINS + d;   // [group][256]
-    rs_store(tile_words + (size_t)tile * RS_BINS, RS_FLAG | local);
-    const uint32_t in_group = sum_words(tile_words + ((size_t)grp << gshift) * RS_BINS, mem);   // earlier tiles of my group
-    if (mem == (1 << gshift) - 1) rs_store(group_words + (size_t)grp * RS_BINS, RS_FLAG | (in_group + local));
-    const uint32_t excl = in_group + sum_words(group_words, grp);                              // earlier groups
+    gshift = min(gshift, ggd_group_shift(live_tiles));
+    const uint32_t excl = lookback_two_level<RS_BINS>(status, d, ntiles, tile, gshift, local, 0u);
     uint32_t tot;
     const uint32_t gbase = block_exclusive_scan_256(my_bin, &tot, s_scan);  // contains __syncthreads
     const uint32_t base = gbase + excl;
@@ -668,13 +597,20 @@ size_t ggd_scan_tmp_bytes(int64_t n) {
 }
 
 int ggd_launch_inclusive_scan(ggd_ctx* ctx, hipStream_t s, const uint32_t* in, uint32_t* out, int64_t n,
-                              uint32_t* d_total, void* tmp, size_t tmp_bytes) {
-  return launch_scan<false>(ctx, s, in, out, n, d_total, tmp, tmp_bytes);
-}
-
-int ggd_launch_inclusive_scan_ex(ggd_ctx* ctx, hipStream_t s, const uint32_t* in, uint32_t* out, int64_t n,
-                                 uint32_t* d_total, void* tmp, size_t tmp_bytes, uint32_t* h_total) {
-  return launch_scan<false>(ctx, s, in, out, n, d_total, tmp, tmp_bytes, h_total);
+                              uint32_t* d_total, void* tmp, size_t tmp_bytes, uint32_t* h_total) {
+  if (n <= 0) {
+    if (d_total) GGD_HIP(hipMemsetAsync(d_total, 0, sizeof(uint32_t), s));
+    if (h_total) *h_total = 0u;
+    return GGD_OK;
+  }
+  const int nb = (int)((n + SCAN_TILE - 1) / SCAN_TILE);
+  if (tmp_bytes < (size_t)nb * sizeof(uint32_t)) return ggd_fail(ctx, GGD_E_INVALID, "scan tmp too small");
+  uint32_t* block_sums = static_cast<uint32_t*>(tmp);
+  hipLaunchKernelGGL(scan_reduce_kernel, dim3(nb), dim3(SCAN_THREADS), 0, s, in, n, block_sums);
+  hipLaunchKernelGGL(scan_blocksums_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, block_sums, nb, d_total, h_total);
+  hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(SCAN_THREADS), 0, s, in, out, n, block_sums);
+  GGD_HIP(hipGetLastError());
+  return GGD_OK;
 }
 int ggd_scan_blocks(int64_t n) { return n > 0 ? (int)((n + SCAN_TILE - 1) / SCAN_TILE) : 0; }
 
@@ -690,18 +626,6 @@ int ggd_launch_duplicate(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, con
 static inline int sort_passes(int nbits) { return (nbits + 7) / 8; }
 int ggd_sort_input_is_alt(int nbits) { return sort_passes(nbits) & 1; }
 
-// tmp layout: [ghist: MAX_PASSES*256 u32][tickets: MAX_PASSES u32 (padded)][status: passes * ntiles * 256 u32]
-static inline size_t sort_ctrl_bytes() { return ggd_align((size_t)(RS_HWORDS + 64) * sizeof(uint32_t)); }
-size_t ggd_sort_tmp_bytes(int64_t n) {
-  const int64_t ntiles = (n + RS_TILE - 1) / RS_TILE;
-  return sort_ctrl_bytes() + ggd_align((size_t)RS_MAX_PASSES * (size_t)rs_status_words(ntiles > 0 ? ntiles : 1) * sizeof(uint32_t));
-}
-
-size_t ggd_sort32_tmp_bytes(int64_t n) {
-  const int64_t ntiles = (n + RS32_TILE - 1) / RS32_TILE;
-  return sort_ctrl_bytes() + ggd_align((size_t)4 * (size_t)rs_status_words(ntiles > 0 ? ntiles : 1) * sizeof(uint32_t));
-}
-
 template <typename KeyT>
 static int launch_sort_t(ggd_ctx* ctx, hipStream_t s, KeyT* keys_a, uint32_t* vals_a, KeyT* keys_b, uint32_t* vals_b,
                          int64_t n, int nbits, void* tmp, size_t tmp_bytes) {
@@ -710,22 +634,18 @@ static int launch_sort_t(ggd_ctx* ctx, hipStream_t s, KeyT* keys_a, uint32_t* va
   if (passes > RS_MAX_PASSES) return ggd_fail(ctx, GGD_E_INVALID, "sort: too many key bits");
   if (tmp_bytes < ggd_sort_tmp_bytes(n)) return ggd_fail(ctx, GGD_E_INVALID, "sort tmp too small");
   const int ntiles = (int)((n + RS_TILE - 1) / RS_TILE);
-  uint32_t* ghist = static_cast<uint32_t*>(tmp);
-  uint32_t* tickets = ghist + RS_HWORDS;
-  uint32_t* status = reinterpret_cast<uint32_t*>(static_cast<char*>(tmp) + sort_ctrl_bytes());
-  const size_t pass_words = (size_t)rs_status_words(ntiles);
-  const int gshift = rs_gshift(ntiles);
-  const size_t status_bytes = (size_t)passes * pass_words * sizeof(uint32_t);
-  GGD_HIP(hipMemsetAsync(tmp, 0, sort_ctrl_bytes() + status_bytes, s));   // histograms, tickets, status words
+  const ggd_sort_ctl ctl = ggd_sort_ctl::in_tmp(tmp);
+  const int gshift = ggd_group_shift((int64_t)ntiles);
+  GGD_HIP(hipMemsetAsync(tmp, 0, ggd_sort_clear_bytes(passes, ntiles), s));   // histograms, tickets, status words
   KeyT* kin = (passes & 1) ? keys_b : keys_a;
   uint32_t* vin = (passes & 1) ? vals_b : vals_a;
   KeyT* kout = (passes & 1) ? keys_a : keys_b;
   uint32_t* vout = (passes & 1) ? vals_a : vals_b;
   hipLaunchKernelGGL((sort_global_hist_kernel<KeyT, RS_ITEMS>), dim3(ntiles), dim3(RS_THREADS), 0, s, kin, n, passes,
-                     ghist);
+                     ctl.ghist);
   for (int p = 0; p < passes; ++p) {
     hipLaunchKernelGGL((sort_onesweep_kernel<KeyT, false, RS_ITEMS>), dim3(ntiles), dim3(RS_THREADS), 0, s, kin, vin, kout, vout, n,
-                       8 * p, ghist + p * RS_BINS, status + (size_t)p * pass_words, ntiles, gshift, tickets + p);
+                       8 * p, ctl.pass_hist(p), ctl.pass_status(p, ntiles), ntiles, gshift, ctl.pass_ticket(p));
     KeyT* tk = kin; kin = kout; kout = tk;
     uint32_t* tv = vin; vin = vout; vout = tv;
   }
@@ -733,94 +653,63 @@ static int launch_sort_t(ggd_ctx* ctx, hipStream_t s, KeyT* keys_a, uint32_t* va
   return GGD_OK;
 }
 
-const uint32_t* ggd_sort32_nvalid_ptr(const void* tmp) {
-  return static_cast<const uint32_t*>(tmp) + RS_HWORDS + RS_MAX_PASSES;
-}
-
-const uint32_t* ggd_sort32_flat_ptr(const void* ctl) {
-  return static_cast<const uint32_t*>(ctl) + RS_HWORDS + RS_MAX_PASSES + 1;
-}
-
-size_t ggd_sort_ctrl_words() { return sort_ctrl_bytes() / sizeof(uint32_t); }
-
-const uint32_t* ggd_fold_nvalid_ptr(const uint32_t* fold_ctl) { return fold_ctl + GGD_FOLD_REPS * GGD_FOLD_REP_STRIDE + RS_MAX_PASSES; }
-const uint32_t* ggd_fold_flat_ptr(const uint32_t* fold_ctl) { return fold_ctl + GGD_FOLD_REPS * GGD_FOLD_REP_STRIDE + RS_MAX_PASSES + 1; }
-size_t ggd_fold_l1_offset(int64_t P) {
-  const int64_t ntiles = (P + RS32_TILE - 1) / RS32_TILE;
-  return (size_t)GGD_FOLD_HEAD + (size_t)4 * (size_t)rs_status_words(ntiles > 0 ? ntiles : 1);
-}
-size_t ggd_fold_ctl_words(int64_t P) {   // + level-1 binning: one 64-word row per 1024-Gaussian chunk and per group of chunks
-  const int64_t chunks = (P + 1023) / 1024;
-  return ggd_fold_l1_offset(P) + (size_t)(chunks + ((int64_t)1 << rs_gshift(chunks > 0 ? chunks : 1)) + 2) * 64;
-}
-
 int ggd_launch_sort32_iota(ggd_ctx* ctx, hipStream_t s, const uint32_t* keys_src, uint32_t* keys_a, uint32_t* vals_a,
                            uint32_t* keys_b, uint32_t* vals_b, int64_t n, int nbits, void* tmp, size_t tmp_bytes,
-                           uint32_t* clean_ctl, const ggd_scan_piggy* piggy, bool flag_flat_last, bool apply_here,
-                           const ggd_fold* fold, bool skip_last) {
+                           const ggd_sort32_opts& o) {
   if (n <= 0) return GGD_OK;
+  const ggd_fold* fold = o.fold;
   const int passes = sort_passes(nbits);
   if (passes > RS_MAX_PASSES || (passes & 1)) return ggd_fail(ctx, GGD_E_INVALID, "sort32: need an even pass count");
-  if (fold && (passes != 4 || !piggy || !piggy->wg_info)) return ggd_fail(ctx, GGD_E_INVALID, "sort32: folded front end needs 4 passes and the workgroup sums");
+  if (fold && (passes != 4 || !o.piggy || !o.piggy->wg_info)) return ggd_fail(ctx, GGD_E_INVALID, "sort32: folded front end needs 4 passes and the workgroup sums");
   if (!fold && tmp_bytes < ggd_sort32_tmp_bytes(n)) return ggd_fail(ctx, GGD_E_INVALID, "sort tmp too small");
+  if (o.skip_last && !(fold && o.flag_flat_last)) return ggd_fail(ctx, GGD_E_INVALID, "sort32: skip_last needs the folded front end");
   const int ntiles = (int)((n + RS32_TILE - 1) / RS32_TILE);
   // control block (histograms, tickets, n_valid): `clean_ctl` = a block an earlier kernel of this frame has already
   // cleared (then the status words are cleared by the histogram kernel and the sort needs no memset launch), else the
   // head of tmp.  fold: a whole block (status words included) the previous frame's preprocess cleared, histograms (in
   // GGD_FOLD_REPS replicas) filled by this frame's.
-  uint32_t* ghist = fold ? fold->ctl : (clean_ctl ? clean_ctl : static_cast<uint32_t*>(tmp));
-  uint32_t* tickets = ghist + (fold ? GGD_FOLD_REPS * GGD_FOLD_REP_STRIDE : RS_HWORDS);
-  uint32_t* status = fold ? fold->ctl + GGD_FOLD_HEAD : reinterpret_cast<uint32_t*>(static_cast<char*>(tmp) + sort_ctrl_bytes());
-  const int reps = fold ? GGD_FOLD_REPS : 1;
-  const size_t pass_words = (size_t)rs_status_words(ntiles);
-  const int gshift = rs_gshift(ntiles);
-  const size_t status_bytes = (size_t)passes * pass_words * sizeof(uint32_t);
-  if (!clean_ctl && !fold) GGD_HIP(hipMemsetAsync(tmp, 0, sort_ctrl_bytes() + status_bytes, s));
-  // keys equal to 0xFFFFFFFF (culled Gaussians) are dropped by pass 0; n_valid (device) = number of kept keys, the
-  // element count of every later pass and of the binning that consumes the order (word RS_MAX_PASSES of the tickets)
-  uint32_t* n_valid = tickets + RS_MAX_PASSES;
+  const ggd_sort_ctl ctl = ggd_sort_ctl::select(tmp, o.clean_ctl, fold ? fold->ctl : nullptr);
+  const bool own_ctl = !o.clean_ctl && !fold;
+  const int gshift = ggd_group_shift((int64_t)ntiles);
+  if (own_ctl) GGD_HIP(hipMemsetAsync(tmp, 0, ggd_sort_clear_bytes(passes, ntiles), s));
+  // keys equal to 0xFFFFFFFF (culled Gaussians) are dropped by pass 0; ctl.n_valid (device) = number of kept keys, the
+  // element count of every later pass and of the binning that consumes the order
   // the offsets scan rides on the first three launches as appended workgroups (reduce | block sums | apply)
-  ggd_scan_piggy pg = piggy ? *piggy : ggd_scan_piggy{};
-  const int pnb = piggy ? pg.nb : 0;
-  if (skip_last && !(fold && flag_flat_last)) return ggd_fail(ctx, GGD_E_INVALID, "sort32: skip_last needs the folded front end");
-  if (fold) { pg.n_valid = n_valid; pg.fold_hist = ghist; pg.flat_flag = tickets + RS_MAX_PASSES + 1; pg.spec_flat = skip_last ? 1 : 0; }   // (pass 0 does not read n_valid: its appended workgroup writes it
+  ggd_scan_piggy pg = o.piggy ? *o.piggy : ggd_scan_piggy{};
+  const int pnb = o.piggy ? pg.nb : 0;
+  if (fold) { pg.n_valid = ctl.n_valid; pg.fold_hist = ctl.ghist; pg.flat_flag = ctl.flat; pg.spec_flat = o.skip_last ? 1 : 0; }   // (pass 0 does not read n_valid: its appended workgroup writes it
                                                               // -- and sums the replicas -- for the later passes)
   if (!fold) {
     // (tile size of this launch, measured at 1 M keys: 4 / 16 / 32 / 64 keys per thread = 977 / 245 / 123 / 62 workgroups flushing
     // into the same 1024 words: 50.4 / 19.2 / 19.3 / 29.1 us -- atomic instructions on one 64-byte line serialise, ~43 ns per 16 lanes)
     const int htiles = ntiles;
     hipLaunchKernelGGL((sort_global_hist_kernel<uint32_t, RS32_ITEMS, true>), dim3(htiles + pnb), dim3(RS_THREADS), 0, s,
-                       keys_src, n, passes, ghist, n_valid, clean_ctl ? status : nullptr,
-                       clean_ctl ? status_bytes / sizeof(uint32_t) : (size_t)0, htiles, pg);
+                       keys_src, n, passes, ctl.ghist, ctl.n_valid, o.clean_ctl ? ctl.status : nullptr,
+                       o.clean_ctl ? ggd_sort_status_words(passes, ntiles) : (size_t)0, htiles, pg);
   }
   // every pass copies its pairs out of LDS in digit order (STAGE; measured, sort stage with / without: 1 M Gaussians 69.9 /
   // 71.1 us, 5 M 201 / 235, 5 M shell 252 / 342, 10 M 340 / 390)
   // pass 0: keys_src (read-only, caller's buffer) -> B with identity values; then B -> A -> B -> A ...
   const uint32_t* kin = keys_src;
   const uint32_t* vin = nullptr;
-  for (int p = 0; p < passes - (skip_last ? 1 : 0); ++p) {
+  for (int p = 0; p < passes - (o.skip_last ? 1 : 0); ++p) {
     uint32_t* kout = (p & 1) ? keys_a : keys_b;
     uint32_t* vout = (p & 1) ? vals_a : vals_b;
     if (p == 0)
       hipLaunchKernelGGL((sort_onesweep_kernel<uint32_t, true, RS32_ITEMS, true, true>), dim3(ntiles + (pnb ? 1 : 0)),
-                         dim3(RS_THREADS), 0, s, kin, vin, kout, vout, n, 0, ghist, status, ntiles, gshift, tickets, n_valid,
-                         2, pg, (uint32_t*)nullptr, reps);
+                         dim3(RS_THREADS), 0, s, kin, vin, kout, vout, n, 0, ctl.pass_hist(0), ctl.pass_status(0, ntiles), ntiles,
+                         gshift, ctl.pass_ticket(0), ctl.n_valid, GGD_PASSENGER_SCAN_SUMS, pg, (uint32_t*)nullptr, ctl.reps);
     if (p != 0)
-      hipLaunchKernelGGL((sort_onesweep_kernel<uint32_t, false, RS32_ITEMS, true, true>), dim3(ntiles + ((p == 1 && apply_here) ? pnb : 0)),
-                         dim3(RS_THREADS), 0, s, kin, vin, kout, vout, n, 8 * p, ghist + p * RS_BINS,
-                         status + (size_t)p * pass_words, ntiles, gshift, tickets + p, n_valid, 3, pg,
-                         (flag_flat_last && p == passes - 1) ? tickets + RS_MAX_PASSES + 1 : nullptr, 1);
+      hipLaunchKernelGGL((sort_onesweep_kernel<uint32_t, false, RS32_ITEMS, true, true>), dim3(ntiles + ((p == 1 && o.apply_here) ? pnb : 0)),
+                         dim3(RS_THREADS), 0, s, kin, vin, kout, vout, n, 8 * p, ctl.pass_hist(p), ctl.pass_status(p, ntiles),
+                         ntiles, gshift, ctl.pass_ticket(p), ctl.n_valid, GGD_PASSENGER_SCAN_APPLY, pg,
+                         (o.flag_flat_last && p == passes - 1) ? ctl.flat : nullptr, 1);
     kin = kout; vin = vout;
   }
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }
 
-
-size_t ggd_sort32_msd_table_bytes(int64_t n) {
-  const int64_t ntiles = (n + MSD_TILE - 1) / MSD_TILE;
-  return ggd_align((size_t)(ntiles > 0 ? ntiles : 1) * GGD_MSD_BINS * sizeof(uint32_t));
-}
 bool ggd_sort32_msd_supported(int64_t n) { return n > 0 && (n + MSD_TILE - 1) / MSD_TILE <= GGD_MSD_MAX_TILES; }
 
 // The two-launch form of ggd_launch_sort32_iota (folded front end built with fold.msd; the scan's step 2 rides on launch 1 as
@@ -831,15 +720,15 @@ int ggd_launch_sort32_msd(ggd_ctx* ctx, hipStream_t s, const uint32_t* keys_src,
   if (n <= 0) return GGD_OK;
   if (!fold || !fold->msd || !piggy || !piggy->wg_info || !ggd_sort32_msd_supported(n))
     return ggd_fail(ctx, GGD_E_INVALID, "sort32 (two launches): needs the folded front end in its msd form");
-  const int ntiles = (int)((n + MSD_TILE - 1) / MSD_TILE);
-  uint32_t* tickets = fold->ctl + GGD_FOLD_REPS * GGD_FOLD_REP_STRIDE;
   if (fold->msd_shift < 0 || fold->msd_shift > GGD_MSD_MAX_SHIFT) return ggd_fail(ctx, GGD_E_INVALID, "sort32 (two launches): bucket shift out of range");
+  const int ntiles = (int)((n + MSD_TILE - 1) / MSD_TILE);
+  const ggd_sort_ctl ctl = ggd_sort_ctl::in_fold(fold->ctl);
   ggd_scan_piggy pg = *piggy;
-  pg.n_valid = tickets + RS_MAX_PASSES; pg.fold_hist = fold->ctl; pg.msd = 1; pg.msd_lo = fold->msd_lo; pg.msd_shift = fold->msd_shift;
+  pg.n_valid = ctl.n_valid; pg.fold_hist = ctl.ghist;
   hipLaunchKernelGGL(sort_msd_partition_kernel, dim3(ntiles + 1), dim3(RS_THREADS), 0, s, keys_src, keys_b, vals_b, n, table,
                      ntiles, fold->msd_lo, fold->msd_shift, pg);
   hipLaunchKernelGGL(sort_msd_finish_kernel, dim3(GGD_MSD_BINS), dim3(MSDF_THREADS), 0, s, keys_b, vals_b, keys_a, vals_a,
-                     fold->ctl, table, ntiles, fold->msd_shift);
+                     ctl.ghist, table, ntiles, fold->msd_shift);
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }

@@ -417,8 +417,8 @@ static int geometry_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, c
   }
   {
     StageTimer t(ctx, ST_SCAN, s);
-    rc = ggd_launch_inclusive_scan_ex(ctx, s, g.tiles, g.offsets, prm->P, ctx->d_words, ctx->scratch, ctx->scratch_bytes,
-                                      ctx->h_words_dev);
+    rc = ggd_launch_inclusive_scan(ctx, s, g.tiles, g.offsets, prm->P, ctx->d_words, ctx->scratch, ctx->scratch_bytes,
+                                   ctx->h_words_dev);
     if (rc != GGD_OK) return rc;
   }
   {
@@ -547,23 +547,27 @@ static int sort_depth_and_bin_tiles(ggd_ctx* ctx, hipStream_t s, const ggd_param
     if (msd)
       rc = ggd_launch_sort32_msd(ctx, s, g.depth_keys, ka, va, kb, vb, prm->P,
                                  reinterpret_cast<uint32_t*>(sc + 4 * pairs + sort_tmp + bin_tmp), &pg, &fold);
-    else
-      rc = ggd_launch_sort32_iota(ctx, s, g.depth_keys, ka, va, kb, vb, prm->P, 32, tmp, sort_tmp, folded ? nullptr : clean_ctl,
-                                  riding ? &pg : nullptr, true, false, folded ? &fold : nullptr, fr.three_passes);
+    else {
+      ggd_sort32_opts so;
+      so.clean_ctl = folded ? nullptr : clean_ctl;
+      so.piggy = riding ? &pg : nullptr;
+      so.fold = folded ? &fold : nullptr;
+      so.flag_flat_last = true;
+      so.apply_here = false;             // the offsets are left to the binning's last launch
+      so.skip_last = fr.three_passes;
+      rc = ggd_launch_sort32_iota(ctx, s, g.depth_keys, ka, va, kb, vb, prm->P, 32, tmp, sort_tmp, so);
+    }
     if (rc != GGD_OK) return rc;
     fr.r_pending = riding;
-    if (folded) { n_vis_ptr = ggd_fold_nvalid_ptr(fold.ctl); flat_ptr = ggd_fold_flat_ptr(fold.ctl); }
-    else {
-      const void* ctl = clean_ctl ? static_cast<const void*>(clean_ctl) : tmp;
-      n_vis_ptr = ggd_sort32_nvalid_ptr(ctl); flat_ptr = ggd_sort32_flat_ptr(ctl);
-    }
+    const ggd_sort_ctl sc = ggd_sort_ctl::select(tmp, clean_ctl, folded ? fold.ctl : nullptr);
+    n_vis_ptr = sc.n_valid; flat_ptr = sc.flat;
   }
   StageTimer t(ctx, ST_DUPLICATE, s);
   // the depth sort dropped the culled Gaussians (key 0xFFFFFFFF) and left the number of kept ones on the device
   const bool l1 = folded && (prm->width + 15) / 16 <= 64 && (prm->height + 15) / 16 <= 64;
   return ggd_launch_rowbin(ctx, s, *prm, g.rect, va, n_vis_ptr, list, ranges, capacity, bin_tmp_ptr, bin_tmp, vb,
-                           flat_ptr, riding ? &pg : nullptr, l1 ? fold.ctl + GGD_FOLD_ROWTOT : nullptr,
-                           l1 ? fold.ctl + ggd_fold_l1_offset(prm->P) : nullptr);
+                           flat_ptr, riding ? &pg : nullptr, l1 ? ggd_fold_rowtot(fold.ctl) : nullptr,
+                           l1 ? ggd_fold_l1_status(fold.ctl, prm->P) : nullptr);
 }
 
 // Binning path 2 (GGD_OPT_BINNING = 0, the debug taps, grids beyond 255 x 255 tiles, R = 0): one (tile | depth) key per instance,

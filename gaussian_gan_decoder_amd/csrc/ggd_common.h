@@ -13,6 +13,7 @@
 
 #include "ggd_raster.h"
 #include "ggd_spec.h"
+#include "ggd_binning_layout.h"
 
 #define GGD_WAVE 64
 
@@ -30,8 +31,8 @@ constexpr int GGD_STATS_BWD = 16;            // eight counters of the backward b
 constexpr int GGD_STATS_HEAD = 32;           // first timeline slot (3 words per wave: start, end, listed << 32 | gathered)
 constexpr int GGD_STATS_MAX_WAVES = 1 << 17;
 
-// two-launch depth sort (described at ggd_fold below; the constants the host's policy needs are in ggd_spec.h)
-constexpr int GGD_MSD_BINS = 1024, GGD_MSD_CAP = 12288, GGD_MSD_MAX_TILES = 2048;
+// (two-launch depth sort: described at ggd_fold below; GGD_MSD_BINS / CAP / MAX_TILES are in ggd_binning_layout.h, the constants
+// the host's policy needs in ggd_spec.h)
 
 // The frame in flight: what geometry_enqueue leaves for render_enqueue, and render_enqueue for the collection of num_rendered.
 // A frame begins in geometry_enqueue, which assigns a fresh one (only the tag carries over); nothing else clears these.
@@ -108,21 +109,18 @@ struct ggd_scan_piggy {
   int spec_flat = 0;                        // != 0: only three passes were launched -- set *flat_flag whatever the histogram says
   uint32_t* fold_hist = nullptr;            // the folded front end's histogram replicas: the workgroup that runs step 2 also adds
                                             // replicas 1 .. REPS-1 of passes 1 .. 3 into replica 0 (only pass 0 reads them all)
-  int msd = 0;                              // two-launch sort: fold_hist holds [GGD_MSD_BINS | 256] bins per replica, all summed into replica 0
-  uint32_t msd_lo = 0;                      // ... its key window (ggd_fold)
-  int msd_shift = GGD_MSD_SHIFT;
+  int msd = 0;                              // unused, kept for the kernarg layout
+  uint32_t msd_lo = 0;                      // unused, kept for the kernarg layout
+  int msd_shift = GGD_MSD_SHIFT;            // unused, kept for the kernarg layout
 };
 
 // The depth sort's histogram kernel folded into the preprocess kernel (single-call forward on the tile-binning path): every
 // preprocess workgroup adds the digit counts of its kept depth keys to one of GGD_FOLD_REPS replicas of the four 256-bin
 // histograms and stores {sum of tiles_touched, kept keys} of its 256 points -- the histogram launch (19 us at 1 M points:
 // its 245 workgroups flush into the same 64 lines, and atomic instructions on one line serialise at ~43 ns per 16 lanes) and
-// step 1 of the offsets scan disappear.  Control block (words): [REPS * 1024 histograms | 8 tickets | n_valid | flat | pad
-// to 64 | status words of the 4 passes]; two blocks alternate, each cleared by the preprocess of the frame before its use.
-constexpr int GGD_FOLD_REPS = 16;   // (32 / 16 / 8 replicas: 4114 / 4140 / 4150 frames per second at 1 M / 1024^2; 3907 workgroups over 8 would
-                                    // keep one address busy 80 % of the kernel's time, 16 leaves a margin)
-constexpr int GGD_FOLD_REP_STRIDE = GGD_MSD_BINS + 256;   // ordinary frames: the four byte histograms [p * 256 + digit] in the first
-                                               // 1024 words; two-launch sort: [1024 buckets of the key window | 256 bins of the top byte]
+// step 1 of the offsets scan disappear.  The control block ("fold block": GGD_FOLD_REPS replicas of the histograms, the sort's
+// control words, the row totals, every status word) is laid out in ggd_binning_layout.h; two blocks alternate, each cleared by
+// the preprocess of the frame before its use.
 // Two-launch depth sort (round 5; `msd` in ggd_fold / ggd_scan_piggy; the key WINDOW since round 6).  The kept keys of a frame lie
 // in a narrow range of the 32-bit key space (fp32 bits of depths between, say, 1.8 and 3.6): over a window [lo, lo + 1024 << shift)
 // that contains them they are ordered by ONE most-significant-digit partition and an in-LDS finish instead of three or four
@@ -143,16 +141,10 @@ constexpr int GGD_FOLD_REP_STRIDE = GGD_MSD_BINS + 256;   // ordinary frames: th
 // GGD_FOLD_OUTSIDE == 0; no bucket above GGD_MSD_CAP) and a frame that fails is binned and blended again by the ordinary path (as
 // for the skipped fourth pass); a key outside the window is clamped into the last bucket, so the kernels behind always see a
 // valid permutation.
-// the 64 words behind the histograms: [8 tickets | n_valid | flat | pad | OUTSIDE (word 16, a line of its own): kept keys outside
-// the two-launch sort's window | pad]
-constexpr int GGD_FOLD_OUTSIDE = GGD_FOLD_REPS * GGD_FOLD_REP_STRIDE + 16;
-constexpr int GGD_FOLD_ROWTOT = GGD_FOLD_REPS * GGD_FOLD_REP_STRIDE + 64;   // REPS x 64 words: entries per tile ROW (grids of <= 64
-                                                                           // rows), for the row binning's first level
 // (The kept keys' range of a frame -- what the two-launch sort's window is fitted to -- travels with the per-workgroup sums in
 // wg_info, as plain stores.  Round 6's first forms kept {~min, max} replicas here, updated with atomicMax: 16 replicas packed into
 // two 64-byte lines cost the preprocess kernel + 30 us (atomics on one line serialise at ~11 ns), one line per replica behind a
 // read-and-compare still + 10 us: a device-scope load + atomic at the END of every workgroup adds 2 - 4 us to its ~8 us lifetime.)
-constexpr int GGD_FOLD_HEAD = GGD_FOLD_ROWTOT + GGD_FOLD_REPS * 64;        // words in front of the status words
 struct ggd_fold {
   uint32_t* ctl = nullptr;        // this frame's control block (clean)
   uint32_t* clear = nullptr;      // the other block ...
@@ -163,9 +155,6 @@ struct ggd_fold {
   uint32_t msd_lo = 0;            // bucket of a kept key = min((key - msd_lo) >> msd_shift, 1023); a key for which the unclamped
   int msd_shift = GGD_MSD_SHIFT;  // value exceeds 1023 (below the window: the difference wraps) is counted in GGD_FOLD_OUTSIDE
 };
-// control block: [head | sort status words of the 4 passes | level-1 binning status words]
-size_t ggd_fold_ctl_words(int64_t P);
-size_t ggd_fold_l1_offset(int64_t P);   // first word of the level-1 status words
 
 int ggd_fail(ggd_ctx* ctx, int code, const std::string& msg);
 int ggd_reserve_scratch(ggd_ctx* ctx, size_t bytes, hipStream_t stream);
@@ -193,8 +182,6 @@ struct StageTimer {  // RAII hipEvent pair around one pipeline stage (no-op unle
   }
 };
 
-static inline size_t ggd_align(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-
 // Runtime value -> template argument, for the launchers: calls f(std::integral_constant<int, I>{}) with I = v for
 // 0 <= v < N - 1 and I = N - 1 for every other v (a bool is N = 2).  Kernel templates take their feature flags as trailing
 // defaulted parameters (preprocess_kernel<..., AA>, blend_forward_kernel<..., AUX>, ...): one definition per kernel, the
@@ -216,21 +203,16 @@ int ggd_launch_preprocess(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, co
                           const ggd_fold* fold = nullptr);
 int ggd_launch_mark_visible(ggd_ctx* ctx, hipStream_t s, int P, const float* means3D, const float* view,
                             uint8_t* present);
-// inclusive scan of a uint32 array; total written to *d_total (device)
+// inclusive scan of a uint32 array; total written to *d_total (device) and, if given, to h_total (device view of a pinned
+// host word)
 int ggd_launch_inclusive_scan(ggd_ctx* ctx, hipStream_t s, const uint32_t* in, uint32_t* out, int64_t n,
-                              uint32_t* d_total, void* tmp, size_t tmp_bytes);
+                              uint32_t* d_total, void* tmp, size_t tmp_bytes, uint32_t* h_total = nullptr);
 size_t ggd_scan_tmp_bytes(int64_t n);
-// same, plus: total also written to h_total (device view of a pinned host word)
-int ggd_launch_inclusive_scan_ex(ggd_ctx* ctx, hipStream_t s, const uint32_t* in, uint32_t* out, int64_t n,
-                                 uint32_t* d_total, void* tmp, size_t tmp_bytes, uint32_t* h_total);
 int ggd_scan_blocks(int64_t n);   // workgroups (= block sums) of the scan over n elements
-size_t ggd_sort_ctrl_words();   // words of the depth sort's control block (ggd_launch_sort32_iota's clean_ctl)
 int ggd_launch_duplicate(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const uint2* rect,
                          const uint32_t* depth_keys, const uint32_t* tiles_touched, const uint32_t* offsets,
                          uint64_t* keys, uint32_t* vals);
-size_t ggd_sort_tmp_bytes(int64_t n);
-size_t ggd_sort32_tmp_bytes(int64_t n);
-const uint32_t* ggd_sort32_nvalid_ptr(const void* ctl);  // device word: keys kept by ggd_launch_sort32_iota (ctl = its control block: clean_ctl or tmp)
+// (tmp sizes, the control block and its device words -- kept keys, "flat" -- : ggd_binning_layout.h, ggd_sort_ctl)
 // stable LSD radix sort of (key,val) pairs on key bits [0,nbits); result ends in (keys_a, vals_a); the input must
 // have been placed in the buffer ggd_sort_input_is_alt(nbits) says.
 int ggd_sort_input_is_alt(int nbits);
@@ -238,30 +220,29 @@ int ggd_launch_sort(ggd_ctx* ctx, hipStream_t s, uint64_t* keys_a, uint32_t* val
                     uint32_t* vals_b, int64_t n, int nbits, void* tmp, size_t tmp_bytes);
 // 32-bit-key variant (depth sort of the Gaussians).  keys_src is only read; the result ends in (keys_a, vals_a);
 // values start as the identity permutation.  nbits must be a multiple of 16 (even number of passes).
+struct ggd_sort32_opts {
+  uint32_t* clean_ctl = nullptr;           // a control block (ggd_sort_ctrl_words) an earlier kernel of the frame has cleared: no memset launch
+  const ggd_scan_piggy* piggy = nullptr;   // an offsets scan that rides on the sort's launches
+  const ggd_fold* fold = nullptr;          // histograms, kept-key count and the scan's step 1 come from the preprocess kernel (piggy must
+                                           // carry wg_info); no histogram launch.  The workgroup that runs the scan's step 2 reports "top
+                                           // digit constant" in bit 63 of the tagged num_rendered word and in d_total[2].
+  bool flag_flat_last = false;             // a constant-digit LAST pass copies nothing -- it sets ggd_sort_ctl::flat and the result stays in
+                                           // (keys_b, vals_b)
+  bool apply_here = true;                  // false: the caller runs the riding scan's last step (offsets) elsewhere -- ggd_launch_rowbin(apply = ...)
+  bool skip_last = false;                  // (fold only) the last pass is not launched (the caller expects a constant top digit); the
+                                           // consumers' flat word is set regardless, so that they read the third pass's output (a valid
+                                           // permutation either way)
+};
 int ggd_launch_sort32_iota(ggd_ctx* ctx, hipStream_t s, const uint32_t* keys_src, uint32_t* keys_a, uint32_t* vals_a,
                            uint32_t* keys_b, uint32_t* vals_b, int64_t n, int nbits, void* tmp, size_t tmp_bytes,
-                           uint32_t* clean_ctl = nullptr, const ggd_scan_piggy* piggy = nullptr,
-                           bool flag_flat_last = false, bool apply_here = true, const ggd_fold* fold = nullptr,
-                           bool skip_last = false);
-// flag_flat_last: a constant-digit LAST pass copies nothing -- it sets the word ggd_sort32_flat_ptr(ctl) and the result
-//                 stays in (keys_b, vals_b)
-// apply_here = false: the caller runs the riding scan's last step (offsets) elsewhere -- ggd_launch_rowbin(apply = ...)
-// fold: histograms, kept-key count and the scan's step 1 come from the preprocess kernel (piggy must carry wg_info); no
-//       histogram launch.  The workgroup that runs the scan's step 2 reports "top digit constant" in bit 63 of the tagged
-//       num_rendered word and in d_total[2].
-// skip_last (fold only): the last pass is not launched (the caller expects a constant top digit); the consumers' flat word is
-//       set regardless, so that they read the third pass's output (a valid permutation either way)
-const uint32_t* ggd_sort32_flat_ptr(const void* ctl);
-size_t ggd_sort32_msd_table_bytes(int64_t n);
+                           const ggd_sort32_opts& opts = ggd_sort32_opts());
 bool ggd_sort32_msd_supported(int64_t n);
 int ggd_launch_sort32_msd(ggd_ctx* ctx, hipStream_t s, const uint32_t* keys_src, uint32_t* keys_a, uint32_t* vals_a,
                           uint32_t* keys_b, uint32_t* vals_b, int64_t n, uint32_t* table, const ggd_scan_piggy* piggy,
                           const ggd_fold* fold);
-const uint32_t* ggd_fold_nvalid_ptr(const uint32_t* fold_ctl);   // the same two words of a folded front end's control block
-const uint32_t* ggd_fold_flat_ptr(const uint32_t* fold_ctl);
 // Tile binning (GGD_OPT_BINNING = 1): sorted Gaussian order -> per-tile lists + ranges.
 bool ggd_rowbin_supported(int W, int H);
-size_t ggd_rowbin_tmp_bytes(int P, uint32_t capacity, int W, int H);
+static inline size_t ggd_rowbin_tmp_bytes(int P, uint32_t capacity, int W, int H) { return ggd_rowbin_layout(P, capacity, W, H).total; }
 int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const uint2* rect, const uint32_t* order,
                       const uint32_t* n_vis_ptr, uint32_t* list, uint32_t* ranges, uint32_t capacity, void* tmp,
                       size_t tmp_bytes, const uint32_t* order_alt = nullptr, const uint32_t* use_alt = nullptr,

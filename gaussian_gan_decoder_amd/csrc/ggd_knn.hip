@@ -433,8 +433,7 @@ int knn_run(ggd_ctx* ctx, void* stream, const float* points, int32_t P, float* m
     hipLaunchKernelGGL(knn_codes_kernel, dim3(ngroups), dim3(KNN_T), 0, s, points, P, v.part, nparts, v.codes);
   if (stages & KNN_ST_SORT) {
     // Morton codes are < 2^30, so no key equals the value (~0) that this sort drops; result in (ka, order)
-    const int rc = ggd_launch_sort32_iota(ctx, s, v.codes, v.ka, v.order, v.kb, v.vb, P, 32, v.sort_tmp, v.sort_bytes, nullptr,
-                                          nullptr, false, false, nullptr, false);
+    const int rc = ggd_launch_sort32_iota(ctx, s, v.codes, v.ka, v.order, v.kb, v.vb, P, 32, v.sort_tmp, v.sort_bytes);
     if (rc != GGD_OK) return rc;
   }
   if (stages & KNN_ST_LEAVES)

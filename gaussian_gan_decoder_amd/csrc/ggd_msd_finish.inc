@@ -1,5 +1,5 @@
 // ggd_msd_finish.inc -- the per-bucket half of the two-launch depth sort (GGD_MSD_*, ggd_common.h), included inside the anonymous
-// namespace of ggd_binning.hip (sort_msd_finish_kernel).  Needs ggd_scan.inc (wave_inclusive_scan).  (Kept as an include since
+// namespace of ggd_binning.hip (sort_msd_finish_kernel).  Needs ggd_scan.inc (wave_inclusive_scan); MSD_TILE = the 4096 keys of a tile of launch 1 (ggd_binning_layout.h).  (Kept as an include since
 // round 5's experiment of running level 1 of the binning on the sorted bucket inside the same workgroup -- one launch and one
 // gather chain less, but 48.8 us against 16.5 + 23.0 for the two kernels: profiles/REJECTED.md.)
 //
@@ -8,8 +8,6 @@
 // order; taken in tile order they are in index order throughout, so stable counting passes over the offset's bits 0..7 and
 // 8..shift-1 (shift <= 16; the second pass is skipped for shift <= 8) leave them in the order of a stable sort of the whole
 // key.  1024 threads, <= 12 elements each, all in registers between the passes.
-constexpr int MSD_ITEMS = 16;                       // launch 1: 4096 keys per tile, as the onesweep passes
-constexpr int MSD_TILE = 256 * MSD_ITEMS;
 constexpr int MSDF_THREADS = 1024, MSDF_ITEMS = GGD_MSD_CAP / MSDF_THREADS, MSDF_WAVES = MSDF_THREADS / 64;
 static_assert(MSDF_ITEMS * MSDF_THREADS == GGD_MSD_CAP, "bucket capacity must be a multiple of the workgroup size");
 

@@ -7,50 +7,48 @@
 // intervals, so the expansion is split into two 1-D counting sorts with <= 64 bins each -- one bin per LANE:
 //   level 1 (rows):    Gaussian [y0, y1)  -> one entry {id, x0, x1} in the list of every tile ROW it touches
 //   level 2 (columns): row entry [x0, x1) -> the Gaussian id in the list of every TILE of that row it touches
-// Both levels are stable (items are consumed in order, chunk by chunk), so depth order survives and the final lists
-// equal the radix-sort path's bit for bit.  Per level: count (LDS difference array: +1 at lo, -1 at hi, prefix over
-// lanes), scan (one workgroup: exclusive prefix over chunks per bin, bin starts), scatter.  The scatter is
-// item-serial / bin-parallel: a wave keeps one running destination per lane (= bin); for each item the lanes in
-// [lo, hi) store and advance.  No per-tile LDS tables, no O(T) work per block, entries of one (chunk, bin) are
-// consecutive in memory.
+// Both levels are stable (items are consumed in order, chunk by chunk of 1024), so depth order survives and the final lists
+// equal the radix-sort path's bit for bit.  Per level three launches:
+//   count    per chunk and bin.  An LDS difference array (+1 at lo, -1 at hi, prefix over the lanes): these kernels do
+//            nothing else, and atomics are cheaper than the transposes below (see rb_count2_kernel).
+//   scan     exclusive prefix over the chunks per bin, bin starts: one workgroup at level 1, one per tile row at level 2 (the
+//            rows above are summed from their published totals).
+//   scatter  a wave turns each round of 64 items into the 64 x 64 item / bin bit matrix and transposes it (wave_cols: lane b then
+//            holds the items that cover bin b, in item order, and their popcount is the bin's count); wave_emit walks either
+//            the items (a lane keeps its item and looks up {mask, running destination} of every bin it covers in the wave's
+//            LDS slab) or the bins (a lane drains its bin, payloads come over by shuffle), whichever is shorter for the round.
+//            A chunk's output is staged in LDS in (bin, item) order where it fits and leaves as lane-consecutive runs per bin;
+//            entries of one (chunk, bin) are consecutive in memory either way.
+// Folded front end (the preprocess kernel counted the entries per row): level 1 is ONE launch, rb_level1_kernel -- count from
+// the transposes, two-level look-back over the earlier chunks (ggd_lookback.inc), scatter.
+// Scratch and table layouts: ggd_binning_layout.h (ggd_rowbin_tmp, RB_TAB_* / RBW_TAB_*).
 #include "ggd_common.h"
 
 namespace {
 
 #include "ggd_scan.inc"
+#include "ggd_lookback.inc"
 
-constexpr int RB_THREADS = 256;
 constexpr int RB_WAVES = RB_THREADS / 64;
 constexpr int RB_STAGE = 4096;                     // instances a level-2 workgroup can stage in LDS (16 KB; measured: 4096 / 6144 /
                                                    // 8192 / 12288 -> 3656 / 3640 / 3594 / 3589 frames/s: occupancy beats coverage)
 constexpr int RB_STAGE1 = 4096;                    // row entries a level-1 workgroup can stage (32 KB)
-constexpr int RB_IPL = 4;                          // items per lane (2 and 8 measured slower)
-constexpr int RB_CHUNK = RB_THREADS * RB_IPL;      // 1024 items per workgroup
 constexpr int RB_WCHUNK = 64 * RB_IPL;             // 256 items per wave
 
-// tables (uint32): [0..64] row starts (65 entries, [64] = total entries), [65..129] first level-2 block of each row
-// (+ total), [130 .. 130 + 64*64) start of every (row, column) tile list
-constexpr int RB_TAB_ROWSTART = 0, RB_TAB_ROWBLK = 65, RB_TAB_TILESTART = 130, RB_TAB_ROWINST = 130 + 64 * 64,
-              RB_TAB_FLAG = RB_TAB_ROWINST + 64, RB_TAB_WORDS = RB_TAB_FLAG + 64;
-// [ROWINST + r] instances of row r, [FLAG + r] != 0 once it is published (level-2 scan, one workgroup per row)
-
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_incl_scan_i32(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
+// The tables level 2 reads, from the entries per row (lane = row; inc = their inclusive prefix over the lanes): row starts,
+// first level-2 block of every row, the rows' published flags cleared (consumed by rb_scan2_kernel, a later launch).
+// level-2 blocks cover only the entries that exist in `ent` (ent_cap of them): when a speculative forward
+// under-estimated the capacity the rows are clamped, so that counts2 (sized for ent_cap) is never overrun
+__device__ __forceinline__ void rb_write_row_tables(uint32_t* tab, int lane, uint32_t tot, uint32_t inc, uint32_t ent_cap) {
+  const uint32_t rs = inc - tot;
+  tab[RB_TAB_ROWSTART + lane] = rs;
+  if (lane == 63) tab[RB_TAB_ROWSTART + 64] = inc;
+  const uint32_t have = rs < ent_cap ? min(tot, ent_cap - rs) : 0u;
+  const uint32_t nblk = (have + RB_CHUNK - 1) / RB_CHUNK;
+  const uint32_t binc = wave_inclusive_scan(nblk);
+  tab[RB_TAB_ROWBLK + lane] = binc - nblk;
+  if (lane == 63) tab[RB_TAB_ROWBLK + 64] = binc;
+  tab[RB_TAB_FLAG + lane] = 0u;
 }
 
 // ---- level 1 count: rect of every depth-ordered Gaussian (kept, packed, for the scatter) + per-row counts of the chunk
@@ -82,7 +80,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_count1_kernel(int W, int H, con
     }
   }
   __syncthreads();
-  if (tid < 64) counts1[(size_t)blockIdx.x * 64 + tid] = (uint32_t)wave_incl_scan_i32(diff[tid]);
+  if (tid < 64) counts1[(size_t)blockIdx.x * 64 + tid] = (uint32_t)wave_inclusive_scan(diff[tid]);
 }
 
 // ---- scan over chunks, one workgroup, lane = bin: counts[c][bin] -> exclusive prefix within the bin; totals per bin
@@ -111,20 +109,7 @@ __global__ __launch_bounds__(1024) void rb_scan1_kernel(uint32_t* __restrict__ c
     counts1[idx] = run;
     run += c;
   }
-  if (wv == 0) {
-    const uint32_t inc = wave_incl_scan_u32(tot);
-    tab[RB_TAB_ROWSTART + lane] = inc - tot;
-    if (lane == 63) tab[RB_TAB_ROWSTART + 64] = inc;
-    // level-2 blocks cover only the entries that exist in `ent` (ent_cap of them): when a speculative forward
-    // under-estimated the capacity the rows are clamped, so that counts2 (sized for ent_cap) is never overrun
-    const uint32_t rs = inc - tot;
-    const uint32_t have = rs < ent_cap ? min(tot, ent_cap - rs) : 0u;
-    const uint32_t nblk = (have + RB_CHUNK - 1) / RB_CHUNK;
-    const uint32_t binc = wave_incl_scan_u32(nblk);
-    tab[RB_TAB_ROWBLK + lane] = binc - nblk;
-    if (lane == 63) tab[RB_TAB_ROWBLK + 64] = binc;
-    tab[RB_TAB_FLAG + lane] = 0u;   // consumed by rb_scan2_kernel (next launch on the stream)
-  }
+  if (wv == 0) rb_write_row_tables(tab, lane, tot, wave_inclusive_scan(tot), ent_cap);
 }
 
 // 64 x 64 bit-matrix transpose across the wave: lane i passes row i (bit b = M[i][b]) and gets column `lane`
@@ -264,37 +249,11 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scatter1_kernel(const uint2* __
 }
 
 // ---- level 1 in ONE launch (folded front end: the entries per row were counted by the preprocess kernel, GGD_FOLD_ROWTOT):
-//      count, decoupled look-back over the earlier chunks (lane = row; status words [chunk][64] then [group][64], zero at
-//      launch, bit 30 = published -- the scheme of the depth sort's passes), scatter.  Replaces rb_count1 / rb_scan1 /
+//      count, two-level look-back over the earlier chunks (lane = row; status words [chunk][64] then [group][64], zero at
+//      launch -- lookback_two_level, as the depth sort's passes), scatter.  Replaces rb_count1 / rb_scan1 /
 //      rb_scatter1 and the `packed` round trip between them.  Every workgroup derives the row starts from the 64 x REPS row
 //      totals itself; workgroup 0 also writes the tables level 2 reads.  Workgroups wait only for lower-numbered ones, which
 //      the dispatcher started earlier.
-constexpr uint32_t RB_PUB = 1u << 30;
-constexpr int RB_LB_BATCH = 16;
-__device__ __forceinline__ uint32_t rb_ld(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void rb_st(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// sum of `cnt` published words p[0], p[64], ...: RB_LB_BATCH requests in flight, unpublished ones are polled
-__device__ __forceinline__ uint32_t rb_sum_words(uint32_t* p, int cnt) {
-  uint32_t acc = 0;
-  for (int b0 = 0; b0 < cnt; b0 += RB_LB_BATCH) {
-    uint32_t v[RB_LB_BATCH];
-#pragma unroll
-    for (int i = 0; i < RB_LB_BATCH; ++i) v[i] = (b0 + i < cnt) ? rb_ld(p + (size_t)(b0 + i) * 64) : RB_PUB;
-#pragma unroll
-    for (int i = 0; i < RB_LB_BATCH; ++i) {
-      uint32_t x = v[i];
-      if ((x >> 30) == 0u) {
-        uint32_t* q = p + (size_t)(b0 + i) * 64;
-        do { __builtin_amdgcn_s_sleep(1); x = rb_ld(q); } while ((x >> 30) == 0u);
-      }
-      acc += x & (RB_PUB - 1u);
-    }
-  }
-  return acc;
-}
-
 __global__ __launch_bounds__(RB_THREADS) void rb_level1_kernel(const uint2* __restrict__ rect, const uint32_t* __restrict__ order,
                                                                const uint32_t* __restrict__ n_vis_ptr, int P,
                                                                const uint32_t* __restrict__ rowtot, uint32_t* status,
@@ -314,18 +273,9 @@ __global__ __launch_bounds__(RB_THREADS) void rb_level1_kernel(const uint2* __re
     uint32_t tot = 0;
 #pragma unroll
     for (int r = 0; r < GGD_FOLD_REPS; ++r) tot += rowtot[r * 64 + lane];
-    const uint32_t inc = wave_incl_scan_u32(tot);
+    const uint32_t inc = wave_inclusive_scan(tot);
     rowstart = inc - tot;
-    if (blockIdx.x == 0) {   // the tables of level 2 (as rb_scan1_kernel writes them)
-      tab[RB_TAB_ROWSTART + lane] = rowstart;
-      if (lane == 63) tab[RB_TAB_ROWSTART + 64] = inc;
-      const uint32_t have = rowstart < ent_cap ? min(tot, ent_cap - rowstart) : 0u;
-      const uint32_t nblk = (have + RB_CHUNK - 1) / RB_CHUNK;
-      const uint32_t binc = wave_incl_scan_u32(nblk);
-      tab[RB_TAB_ROWBLK + lane] = binc - nblk;
-      if (lane == 63) tab[RB_TAB_ROWBLK + 64] = binc;
-      tab[RB_TAB_FLAG + lane] = 0u;   // consumed by rb_scan2_kernel
-    }
+    if (blockIdx.x == 0) rb_write_row_tables(tab, lane, tot, inc, ent_cap);
   }
   const uint32_t base = (uint32_t)blockIdx.x * RB_CHUNK;
   if (base >= n_vis) return;
@@ -352,16 +302,8 @@ __global__ __launch_bounds__(RB_THREADS) void rb_level1_kernel(const uint2* __re
     const uint32_t local = wcnt[0][lane] + wcnt[1][lane] + wcnt[2][lane] + wcnt[3][lane];
     const int chunk = (int)blockIdx.x;
     const int live = (int)((n_vis + RB_CHUNK - 1) / RB_CHUNK);   // group size ~ sqrt(live chunks), never above the launch's
-    int gs = 2;
-    while ((1 << (2 * gs)) < live) ++gs;
-    gs = min(gs, gshift_max);
-    const int grp = chunk >> gs, mem = chunk & ((1 << gs) - 1);
-    uint32_t* cw = status + lane;                              // [chunk][64]
-    uint32_t* gw = status + (size_t)chunks_max * 64 + lane;    // [group][64]
-    rb_st(cw + (size_t)chunk * 64, RB_PUB | local);
-    const uint32_t in_group = rb_sum_words(cw + ((size_t)grp << gs) * 64, mem);
-    if (mem == (1 << gs) - 1) rb_st(gw + (size_t)grp * 64, RB_PUB | (in_group + local));
-    s_base[lane] = rowstart + in_group + rb_sum_words(gw, grp);
+    const int gs = min(ggd_group_shift(live), gshift_max);
+    s_base[lane] = lookback_two_level<64>(status, lane, chunks_max, chunk, gs, local, rowstart);
   }
   __syncthreads();
   uint32_t before = 0, rowtot_c = 0;   // lane = row: this chunk's entries of the earlier waves / of the whole chunk
@@ -370,7 +312,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_level1_kernel(const uint2* __re
   // As in rb_scatter2_kernel: the chunk's entries are staged in LDS in (row, item) order and every row's run leaves as
   // lane-consecutive 8-byte stores -- emitted directly every entry was a lone store into one of 64 row lists (the head-like
   // scene writes 3.3 M of them).  Chunks with more entries than the buffer holds keep the direct form.
-  const uint32_t rowend = wave_incl_scan_u32(rowtot_c);          // same in every wave
+  const uint32_t rowend = wave_inclusive_scan(rowtot_c);          // same in every wave
   const uint32_t total = (uint32_t)__shfl((int)rowend, 63, 64);
   const uint32_t rowbeg = rowend - rowtot_c;
   const uint32_t gbase = s_base[lane];
@@ -442,7 +384,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_count2_kernel(const uint2* __re
     if (x1 > x0) { atomicAdd(&diff[x0], 1); atomicAdd(&diff[x1], -1); }
   }
   __syncthreads();
-  if (tid < 64) counts2[(size_t)blockIdx.x * 64 + tid] = (uint32_t)wave_incl_scan_i32(diff[tid]);
+  if (tid < 64) counts2[(size_t)blockIdx.x * 64 + tid] = (uint32_t)wave_inclusive_scan(diff[tid]);
 }
 
 // ---- level-2 scan, one workgroup per tile row: exclusive prefix over the row's chunks (lane = column, 16 waves split
@@ -473,7 +415,7 @@ __global__ __launch_bounds__(1024) void rb_scan2_kernel(uint32_t* __restrict__ c
     run += c;
   }
   if (wv == 0) {
-    const uint32_t inc = wave_incl_scan_u32(tot);
+    const uint32_t inc = wave_inclusive_scan(tot);
     if (lane == 63) {
       tab[RB_TAB_ROWINST + r] = inc;
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -485,7 +427,7 @@ __global__ __launch_bounds__(1024) void rb_scan2_kernel(uint32_t* __restrict__ c
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     if (lane < r) below = __hip_atomic_load(&tab[RB_TAB_ROWINST + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t binc = wave_incl_scan_u32(below);
+    const uint32_t binc = wave_inclusive_scan(below);
     const uint32_t rowbase = (uint32_t)__builtin_amdgcn_readlane((int)binc, 63);
     if (lane < gx) {
       const uint32_t start = rowbase + inc - tot;
@@ -506,7 +448,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scatter2_kernel(const uint2* __
   __shared__ uint32_t wcnt[RB_WAVES][64];
   __shared__ uint32_t stage[RB_STAGE];
   if (blockIdx.x >= main_blocks) {   // appended workgroups: last step of the offsets scan (see ggd_scan_piggy)
-    scan_apply_block<false>(pg.in, pg.out, pg.n, pg.block_sums, (int)(blockIdx.x - main_blocks), stage, pg.sum_stride);
+    scan_apply_block(pg.in, pg.out, pg.n, pg.block_sums, (int)(blockIdx.x - main_blocks), stage, pg.sum_stride);
     return;
   }
   int row; uint32_t chunk, rbeg, rend;
@@ -535,14 +477,13 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scatter2_kernel(const uint2* __
   // The chunk's instances are staged in LDS in (column, item) order and copied out with every column's run as
   // lane-consecutive stores: emitted directly, the list goes out as lone 4-byte words (2.2x write amplification; those
   // stores were 15 of the kernel's 27 us).  Chunks with more instances than the buffer holds keep the direct form.
-  const uint32_t colend = wave_incl_scan_u32(coltot);          // same in every wave
+  const uint32_t colend = wave_inclusive_scan(coltot);          // same in every wave
   const uint32_t total = (uint32_t)__shfl((int)colend, 63, 64);
   const uint32_t colbeg = colend - coltot;
   if (total <= (uint32_t)RB_STAGE) {
     uint32_t ldst = colbeg + before;
     wave_emit<false>(iv, pa, pb, cols, n_items, ldst, slab[wv], [&](uint32_t d, uint32_t id, uint32_t) { stage[d] = id; });
     __syncthreads();
-    // wave w copies columns w, w + 4, ...; the column's (base, count, destination) come from the lane that owns it
 #pragma unroll 4
     for (int c = wv; c < 64; c += RB_WAVES) {
       const uint32_t n = (uint32_t)__shfl((int)coltot, c, 64);
@@ -561,30 +502,12 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scatter2_kernel(const uint2* __
   });
 }
 
-static inline int rb_blocks1(int P) { return (P + RB_CHUNK - 1) / RB_CHUNK; }
-static inline uint32_t rb_blocks2(uint32_t cap) { return (cap + RB_CHUNK - 1) / RB_CHUNK + 64; }
-
 #include "ggd_rowbin_wide.inc"
-
-static inline uint32_t rbw_blocks2(uint32_t cap) { return (cap + RB_CHUNK - 1) / RB_CHUNK + RBW_BINS; }
-static inline bool rb_is_wide(int W, int H) { return (W + 15) / 16 > 64 || (H + 15) / 16 > 64; }
 
 }  // namespace
 
 // grids up to 64 x 64 tiles: the lane-per-bin kernels above; up to 255 x 255: ggd_rowbin_wide.inc
 bool ggd_rowbin_supported(int W, int H) { return W > 0 && H > 0 && (W + 15) / 16 <= 255 && (H + 15) / 16 <= 255; }
-
-size_t ggd_rowbin_tmp_bytes(int P, uint32_t capacity, int W, int H) {
-  if (rb_is_wide(W, H)) {
-    const int nby = 64 * (((H + 15) / 16 + 63) / 64), nbx = 64 * (((W + 15) / 16 + 63) / 64);
-    return ggd_align((size_t)P * sizeof(uint2)) + ggd_align((size_t)rb_blocks1(P) * nby * 4) +
-           ggd_align((size_t)RBW_TAB_WORDS * 4) + ggd_align((size_t)capacity * sizeof(uint2)) +
-           ggd_align((size_t)rbw_blocks2(capacity) * nbx * 4);
-  }
-  return ggd_align((size_t)P * sizeof(uint2)) + ggd_align((size_t)rb_blocks1(P) * 64 * 4) +
-         ggd_align((size_t)RB_TAB_WORDS * 4) + ggd_align((size_t)capacity * sizeof(uint2)) +
-         ggd_align((size_t)rb_blocks2(capacity) * 64 * 4);
-}
 
 // capacity: upper bound on num_rendered (the level-1 entry count is <= num_rendered); order = depth-sorted ids.
 int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const uint2* rect, const uint32_t* order,
@@ -592,18 +515,23 @@ int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const 
                       size_t tmp_bytes, const uint32_t* order_alt, const uint32_t* use_alt, const ggd_scan_piggy* apply,
                       const uint32_t* fold_rowtot, uint32_t* fold_status1) {
   if (!ggd_rowbin_supported(prm.width, prm.height)) return ggd_fail(ctx, GGD_E_INVALID, "tile grid too large for row binning");
-  if (tmp_bytes < ggd_rowbin_tmp_bytes(prm.P, capacity, prm.width, prm.height)) return ggd_fail(ctx, GGD_E_INVALID, "rowbin tmp too small");
+  const ggd_rowbin_tmp lay = ggd_rowbin_layout(prm.P, capacity, prm.width, prm.height);
+  if (tmp_bytes < lay.total) return ggd_fail(ctx, GGD_E_INVALID, "rowbin tmp too small");
   const int gx = (prm.width + 15) / 16, gy = (prm.height + 15) / 16;
+  const bool wide = rb_is_wide(prm.width, prm.height);
   char* p = static_cast<char*>(tmp);
-  if (rb_is_wide(prm.width, prm.height)) {
+  uint2* packed = reinterpret_cast<uint2*>(p + lay.packed);
+  uint32_t* counts1 = reinterpret_cast<uint32_t*>(p + lay.counts1);
+  uint32_t* tab = reinterpret_cast<uint32_t*>(p + lay.tab);
+  uint2* ent = reinterpret_cast<uint2*>(p + lay.ent);
+  uint32_t* counts2 = reinterpret_cast<uint32_t*>(p + lay.counts2);
+  const int nb1 = rb_blocks1(prm.P);
+  const uint32_t nb2 = rb_blocks2(capacity, wide);
+  const uint32_t nb_apply = apply ? (uint32_t)apply->nb : 0u;   // step 3 of a riding scan, appended to the last launch
+  const ggd_scan_piggy pg = apply ? *apply : ggd_scan_piggy{};
+  static_assert(RB_THREADS == SCAN_THREADS, "the appended scan workgroups share the launch's block size");
+  if (wide) {
     const int ngy = (gy + 63) / 64, ngx = (gx + 63) / 64, nby = 64 * ngy, nbx = 64 * ngx;
-    uint2* packed = reinterpret_cast<uint2*>(p); p += ggd_align((size_t)prm.P * sizeof(uint2));
-    uint32_t* counts1 = reinterpret_cast<uint32_t*>(p); p += ggd_align((size_t)rb_blocks1(prm.P) * nby * 4);
-    uint32_t* tab = reinterpret_cast<uint32_t*>(p); p += ggd_align((size_t)RBW_TAB_WORDS * 4);
-    uint2* ent = reinterpret_cast<uint2*>(p); p += ggd_align((size_t)capacity * sizeof(uint2));
-    uint32_t* counts2 = reinterpret_cast<uint32_t*>(p);
-    const int nb1 = rb_blocks1(prm.P);
-    const uint32_t nb2 = rbw_blocks2(capacity);
     hipLaunchKernelGGL(rbw_count1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, rect, order, n_vis_ptr, prm.P, nby, packed,
                        counts1, order_alt, use_alt);
     hipLaunchKernelGGL(rbw_scan1_kernel, dim3(1), dim3(1024), 0, s, counts1, n_vis_ptr, prm.P, ngy, tab, capacity);
@@ -611,23 +539,14 @@ int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const 
                        ent, capacity);
     hipLaunchKernelGGL(rbw_count2_kernel, dim3(nb2), dim3(RB_THREADS), 0, s, ent, capacity, tab, nbx, counts2);
     hipLaunchKernelGGL(rbw_scan2_kernel, dim3(gy), dim3(1024), 0, s, counts2, tab, gx, gy, ngx, ranges);
-    hipLaunchKernelGGL(rbw_scatter2_kernel, dim3(nb2 + (apply ? (uint32_t)apply->nb : 0u)), dim3(RB_THREADS), 0, s, ent,
-                       capacity, tab, ngx, counts2, list, capacity, nb2, apply ? *apply : ggd_scan_piggy{});
+    hipLaunchKernelGGL(rbw_scatter2_kernel, dim3(nb2 + nb_apply), dim3(RB_THREADS), 0, s, ent, capacity, tab, ngx, counts2, list,
+                       capacity, nb2, pg);
     GGD_HIP(hipGetLastError());
     return GGD_OK;
   }
-  uint2* packed = reinterpret_cast<uint2*>(p); p += ggd_align((size_t)prm.P * sizeof(uint2));
-  uint32_t* counts1 = reinterpret_cast<uint32_t*>(p); p += ggd_align((size_t)rb_blocks1(prm.P) * 64 * 4);
-  uint32_t* tab = reinterpret_cast<uint32_t*>(p); p += ggd_align((size_t)RB_TAB_WORDS * 4);
-  uint2* ent = reinterpret_cast<uint2*>(p); p += ggd_align((size_t)capacity * sizeof(uint2));
-  uint32_t* counts2 = reinterpret_cast<uint32_t*>(p);
-  const int nb1 = rb_blocks1(prm.P);
-  const uint32_t nb2 = rb_blocks2(capacity);
-  if (fold_rowtot && fold_status1) {
-    int gsm = 2;
-    while ((1 << (2 * gsm)) < nb1) ++gsm;   // (= rs_gshift(nb1): the group words were laid out for it, ggd_fold_ctl_words)
+  if (fold_rowtot && fold_status1) {   // (the group words were laid out for ggd_group_shift(chunks): ggd_fold_ctl_words)
     hipLaunchKernelGGL(rb_level1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, rect, order, n_vis_ptr, prm.P, fold_rowtot,
-                       fold_status1, nb1, gsm, tab, ent, capacity, order_alt, use_alt);
+                       fold_status1, nb1, ggd_group_shift(nb1), tab, ent, capacity, order_alt, use_alt);
   } else {
     hipLaunchKernelGGL(rb_count1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, prm.width, prm.height, rect, order,
                        n_vis_ptr, prm.P, packed, counts1, order_alt, use_alt);
@@ -637,9 +556,8 @@ int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const 
   }
   hipLaunchKernelGGL(rb_count2_kernel, dim3(nb2), dim3(RB_THREADS), 0, s, ent, capacity, tab, counts2);
   hipLaunchKernelGGL(rb_scan2_kernel, dim3(gy), dim3(1024), 0, s, counts2, tab, gx, gy, ranges);
-  static_assert(RB_THREADS == SCAN_THREADS, "the appended scan workgroups share the launch's block size");
-  hipLaunchKernelGGL(rb_scatter2_kernel, dim3(nb2 + (apply ? (uint32_t)apply->nb : 0u)), dim3(RB_THREADS), 0, s, ent, capacity,
-                     tab, counts2, list, capacity, nb2, apply ? *apply : ggd_scan_piggy{});
+  hipLaunchKernelGGL(rb_scatter2_kernel, dim3(nb2 + nb_apply), dim3(RB_THREADS), 0, s, ent, capacity, tab, counts2, list,
+                     capacity, nb2, pg);
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }

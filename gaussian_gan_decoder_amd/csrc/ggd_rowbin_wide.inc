@@ -7,19 +7,12 @@
 // group into the next, and the emission transposes one 64 x 64 bit matrix per group an item round touches.  Until this
 // path existed a 1080p frame took the single-level tile binning (550 us for 11 M instances) and anything above 8192 tiles
 // the 64-bit radix sort (5.6 ms for the 75 M instances of a 4K frame).
-constexpr int RBW_NG = 4;                 // groups of 64 bins
-constexpr int RBW_BINS = 64 * RBW_NG;     // 256 (bins 0 .. 254 are usable: a rect's exclusive upper bound must fit 8 bits)
-// tables (uint32), strides fixed at RBW_BINS whatever the grid:
-//   [ROWSTART .. +256]  start of every tile row's entry list (+ total)      [ROWBLK .. +256]  first level-2 block of each row (+ total)
-//   [ROWINST + r] instances of row r, [FLAG + r] != 0 once published        [TILESTART + r * 256 + c] start of tile (r, c)'s list
-constexpr int RBW_TAB_ROWSTART = 0, RBW_TAB_ROWBLK = RBW_BINS + 1, RBW_TAB_ROWINST = 2 * (RBW_BINS + 1),
-              RBW_TAB_FLAG = RBW_TAB_ROWINST + RBW_BINS, RBW_TAB_TILESTART = RBW_TAB_FLAG + RBW_BINS,
-              RBW_TAB_WORDS = RBW_TAB_TILESTART + RBW_BINS * RBW_BINS;
+// (RBW_NG = 4 groups of 64 bins, RBW_BINS = 256 and the tables RBW_TAB_*: ggd_binning_layout.h)
 
 // inclusive prefix of an int over the 256 threads of the block (thread = bin); lds4: 4 ints
 __device__ __forceinline__ int block_incl_scan_256_i32(int v, int* lds4) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int inc = wave_incl_scan_i32(v);
+  const int inc = wave_inclusive_scan(v);
   if (lane == 63) lds4[wv] = inc;
   __syncthreads();
   int base = 0;
@@ -91,12 +84,12 @@ __global__ __launch_bounds__(1024) void rbw_scan1_kernel(uint32_t* __restrict__ 
       run += c;
     }
     if (wv == 0) {
-      const uint32_t inc = row_carry + wave_incl_scan_u32(tot);
+      const uint32_t inc = row_carry + wave_inclusive_scan(tot);
       const uint32_t rs = inc - tot;
       tab[RBW_TAB_ROWSTART + bin] = rs;
       const uint32_t have = rs < ent_cap ? min(tot, ent_cap - rs) : 0u;   // see rb_scan1_kernel
       const uint32_t nb2 = (have + RB_CHUNK - 1) / RB_CHUNK;
-      const uint32_t binc = blk_carry + wave_incl_scan_u32(nb2);
+      const uint32_t binc = blk_carry + wave_inclusive_scan(nb2);
       tab[RBW_TAB_ROWBLK + bin] = binc - nb2;
       tab[RBW_TAB_FLAG + bin] = 0u;
       row_carry = (uint32_t)__shfl((int)inc, 63, 64);
@@ -314,7 +307,7 @@ __global__ __launch_bounds__(1024) void rbw_scan2_kernel(uint32_t* __restrict__ 
     uint32_t carry = 0;
 #pragma unroll
     for (int g = 0; g < RBW_NG; ++g) {
-      incs[g] = carry + wave_incl_scan_u32(tots[g]);
+      incs[g] = carry + wave_inclusive_scan(tots[g]);
       carry = (uint32_t)__shfl((int)incs[g], 63, 64);
     }
     if (lane == 63) {   // carry = instances of this row
@@ -328,7 +321,7 @@ __global__ __launch_bounds__(1024) void rbw_scan2_kernel(uint32_t* __restrict__ 
     uint32_t below = 0;
     for (int rr = lane; rr < r; rr += 64)
       below += __hip_atomic_load(&tab[RBW_TAB_ROWINST + rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t binc = wave_incl_scan_u32(below);
+    const uint32_t binc = wave_inclusive_scan(below);
     const uint32_t rowbase = (uint32_t)__builtin_amdgcn_readlane((int)binc, 63);
 #pragma unroll
     for (int g = 0; g < RBW_NG; ++g) {
@@ -357,7 +350,7 @@ __global__ __launch_bounds__(RB_THREADS) void rbw_scatter2_kernel(const uint2* _
   __shared__ uint32_t stage[RB_STAGE];
   __shared__ uint32_t s_n[RBW_BINS], s_b0[RBW_BINS], s_g[RBW_BINS];   // per column: instances, LDS base, list destination
   if (blockIdx.x >= main_blocks) {   // appended workgroups: last step of the offsets scan (see ggd_scan_piggy)
-    scan_apply_block<false>(pg.in, pg.out, pg.n, pg.block_sums, (int)(blockIdx.x - main_blocks), stage, pg.sum_stride);
+    scan_apply_block(pg.in, pg.out, pg.n, pg.block_sums, (int)(blockIdx.x - main_blocks), stage, pg.sum_stride);
     return;
   }
   int row; uint32_t chunk;
@@ -392,7 +385,7 @@ __global__ __launch_bounds__(RB_THREADS) void rbw_scatter2_kernel(const uint2* _
       gbase[g] = tab[RBW_TAB_TILESTART + row * RBW_BINS + col] + prefix2[(size_t)blockIdx.x * nbins + col];
 #pragma unroll
       for (int w = 0; w < RB_WAVES; ++w) { const uint32_t c = wcnt[w][col]; if (w < wv) before[g] += c; coltot[g] += c; }
-      const uint32_t colend = carry + wave_incl_scan_u32(coltot[g]);   // same in every wave
+      const uint32_t colend = carry + wave_inclusive_scan(coltot[g]);   // same in every wave
       colbeg[g] = colend - coltot[g];
       carry = (uint32_t)__shfl((int)colend, 63, 64);
     }

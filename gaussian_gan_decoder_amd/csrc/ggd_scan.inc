@@ -1,16 +1,17 @@
 // ggd_scan.inc -- workgroup-level pieces of the uint32 prefix scan (stage a5), included inside the anonymous namespace of
 // the translation units that run them: ggd_binning.hip (the scan kernels; the depth sort's appended workgroups) and
-// ggd_rowbin.hip (the apply step as appended workgroups of the last binning launch).
+// ggd_rowbin.hip (the apply step as appended workgroups of the last binning launch; the wave scan, for ints too).
 // ------------------------------------------------------------------------------------------------ block scan --
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;                        // per thread
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;  // 2048 per block
 
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
+template <typename T>
+__device__ __forceinline__ T wave_inclusive_scan(T v) {
   const int lane = threadIdx.x & 63;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(v, d, 64);
+    const T o = __shfl_up(v, d, 64);
     if (lane >= d) v += o;
   }
   return v;
@@ -134,7 +135,6 @@ __device__ __forceinline__ uint4 scan_info_block(const uint4* __restrict__ info,
 }
 
 // pstride: block_prefix entries per 2048-element block (1; 8 when the prefixes are per 256-point preprocess workgroup)
-template <bool EXCLUSIVE>
 __device__ __forceinline__ void scan_apply_block(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, int64_t n,
                                                  const uint32_t* __restrict__ block_prefix, int blk, uint32_t* lds4,
                                                  int pstride = 1) {
@@ -157,7 +157,8 @@ __device__ __forceinline__ void scan_apply_block(const uint32_t* __restrict__ in
   uint32_t o[SCAN_ITEMS];
 #pragma unroll
   for (int k = 0; k < SCAN_ITEMS; ++k) {
-    if (EXCLUSIVE) { o[k] = run; run += v[k]; } else { run += v[k]; o[k] = run; }
+    run += v[k];
+    o[k] = run;
   }
   if (full) {
     *reinterpret_cast<uint4*>(out + base) = make_uint4(o[0], o[1], o[2], o[3]);

@@ -427,11 +427,13 @@ int launch_sorted_backward(ggd_ctx* ctx, hipStream_t s, int D, int H, int W, int
   const size_t sort_bytes = ggd_sort32_tmp_bytes(M);
   if (D > 0) hipLaunchKernelGGL((sr_keys_kernel<true>), dim3((N + 255) / 256), dim3(256), 0, s, pos, N, scale, g, axes, keys_src);
   else hipLaunchKernelGGL((sr_keys_kernel<false>), dim3((N + 255) / 256), dim3(256), 0, s, pos, N, scale, g, axes, keys_src);
-  rc = ggd_launch_sort32_iota(ctx, s, keys_src, keys_a, vals_a, keys_b, vals_b, M, 32, sort_tmp, sort_bytes, nullptr, nullptr,
-                              /*flag_flat_last=*/true);
+  ggd_sort32_opts so;
+  so.flag_flat_last = true;
+  rc = ggd_launch_sort32_iota(ctx, s, keys_src, keys_a, vals_a, keys_b, vals_b, M, 32, sort_tmp, sort_bytes, so);
   if (rc != GGD_OK) return rc;
-  const uint32_t* n_valid = ggd_sort32_nvalid_ptr(sort_tmp);
-  const uint32_t* flat = ggd_sort32_flat_ptr(sort_tmp);
+  const ggd_sort_ctl sc = ggd_sort_ctl::in_tmp(sort_tmp);
+  const uint32_t* n_valid = sc.n_valid;
+  const uint32_t* flat = sc.flat;
   const unsigned blocks = (unsigned)((M + 4 * SR_CHUNK - 1) / (4 * SR_CHUNK));
   if (D > 0)
     hipLaunchKernelGGL((sr_accumulate_kernel<C, true>), dim3(blocks), dim3(256), 0, s, keys_a, vals_a, keys_b, vals_b, flat,
