@@ -1,19 +1,46 @@
-"""Minimal Gaussian attribute container for the decoder path.
+"""Gaussian attribute container: the decoder path's getters and the per-scene fitting loop's optimizer and density control.
 
-Mirrors the part of gaussian_splatting/scene/gaussian_model.py the raster hot path touches: the constructor
-(:47-63), the activation getters that form the rasterizer's input prologue (:100-124: exp / normalize / sigmoid /
-pass-through) and get_covariance (:29-33,123-124).  The decoder overwrites `_xyz/_scaling/_rotation/_opacity/
-_features_dc` every step (main/train_pano2gaussian_decoder.py:223-227), so densification, the optimizer set-up
-and the plyfile import of the reference class are intentionally absent.
-create_from_pcd / create_from_pos_col (:126-185) seed a model from a point cloud; their `distCUDA2` is knn.dist_cuda2.
+Mirrors gaussian_splatting/scene/gaussian_model.py: the constructor (:47-63), the activation getters that form the
+rasterizer's input prologue (:100-124: exp / normalize / sigmoid / pass-through), get_covariance (:29-33,123-124),
+create_from_pcd / create_from_pos_col (:126-185; their `distCUDA2` is knn.dist_cuda2), and what the reference's fitting
+loop (gaussian_splatting/train.py:31-132) calls: training_setup / update_learning_rate (:217-246), capture / restore
+(:65-97), reset_opacity (:305-308), add_densification_stats (:544-546), densify_and_prune (:453-542) and prune_points
+(:390-404).  The reference builds the last three from boolean-mask indexing (a `nonzero` and a host wait per mask, four
+copies of every parameter and Adam moment per densification); here they are csrc/ggd_densify.hip: one launch without a
+host wait per iteration (update_densification_stats also keeps max_radii2D), and per densification three small launches,
+one read-back of the new row count and one gather launch that writes every parameter and moment once (DESIGN.md section
+6k).  Those methods need device tensors: there is no CPU fallback.  Absent on purpose: the fork's GUI-only
+manual_densification masks (off by default in the reference), the kill_*_learning_rate helpers, the plyfile import.
 """
 from __future__ import annotations
+
+import ctypes as C
+import math
 
 import numpy as np
 import torch
 from torch import nn
 
 from .sh import RGB2SH
+
+# optimizer group name -> attribute, in the order training_setup registers them (and csrc/ggd_densify.hip gathers them)
+PARAM_GROUPS = (("xyz", "_xyz"), ("f_dc", "_features_dc"), ("f_rest", "_features_rest"), ("opacity", "_opacity"),
+                ("scaling", "_scaling"), ("rotation", "_rotation"))
+
+
+def get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1000000):
+    """step -> learning rate: lr_init at step 0, lr_final from max_steps on, log-linear in between; while step <
+    lr_delay_steps the rate is scaled by a factor that rises from lr_delay_mult to 1 along a quarter sine.  0 for a negative
+    step or when both rates are 0 (reference: utils/general_utils.py:29-62)."""
+    def rate(step):
+        if step < 0 or (lr_init == 0.0 and lr_final == 0.0):
+            return 0.0
+        delay = 1.0
+        if lr_delay_steps > 0:
+            delay = lr_delay_mult + (1.0 - lr_delay_mult) * math.sin(0.5 * math.pi * min(max(step / lr_delay_steps, 0.0), 1.0))
+        t = min(max(step / max_steps, 0.0), 1.0)
+        return delay * math.exp(math.log(lr_init) * (1.0 - t) + math.log(lr_final) * t)
+    return rate
 
 
 def build_rotation(q: torch.Tensor) -> torch.Tensor:
@@ -57,9 +84,16 @@ class GaussianModel:
         self._scaling = torch.empty(0)
         self._rotation = torch.empty(0)
         self._opacity = torch.empty(0)
+        self.max_radii2D = torch.empty(0)
+        self.xyz_gradient_accum = torch.empty(0)
+        self.denom = torch.empty(0)
+        self.optimizer = None
+        self.percent_dense = 0
+        self.spatial_lr_scale = 0
         self.scaling_activation = torch.exp
         self.scaling_inverse_activation = torch.log
         self.opacity_activation = torch.sigmoid
+        self.inverse_opacity_activation = inverse_sigmoid
         self.rotation_activation = torch.nn.functional.normalize
         self.covariance_activation = build_covariance_from_scaling_rotation
 
@@ -153,3 +187,233 @@ class GaussianModel:
     def oneupSHdegree(self):
         if self.active_sh_degree < self.max_sh_degree:
             self.active_sh_degree += 1
+
+    # ---- optimizer (reference: gaussian_model.py:65-97, 217-246) ------------------------------------------------------
+    def training_setup(self, training_args, decoder_params=None):
+        """Adam over the six named groups (lr 0.0 / eps 1e-15 defaults, per-group rates from `training_args`), the position
+        schedule, and zeroed densification statistics on the parameters' device."""
+        self.percent_dense = training_args.percent_dense
+        P, dev = self._xyz.shape[0], self._xyz.device
+        self.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
+        self.denom = torch.zeros((P, 1), device=dev)
+        rates = {"xyz": training_args.position_lr_init * self.spatial_lr_scale, "f_dc": training_args.feature_lr,
+                 "f_rest": training_args.feature_lr / 20.0, "opacity": training_args.opacity_lr,
+                 "scaling": training_args.scaling_lr, "rotation": training_args.rotation_lr}
+        groups = [{"params": [getattr(self, attr)], "lr": rates[name], "name": name} for name, attr in PARAM_GROUPS]
+        if decoder_params is not None:
+            groups += decoder_params
+        self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+        self.xyz_scheduler_args = get_expon_lr_func(lr_init=training_args.position_lr_init * self.spatial_lr_scale,
+                                                    lr_final=training_args.position_lr_final * self.spatial_lr_scale,
+                                                    lr_delay_mult=training_args.position_lr_delay_mult,
+                                                    max_steps=training_args.position_lr_max_steps)
+
+    def update_learning_rate(self, iteration):
+        """Sets and returns the position group's rate for this iteration."""
+        for group in self.optimizer.param_groups:
+            if group["name"] == "xyz":
+                group["lr"] = self.xyz_scheduler_args(iteration)
+                return group["lr"]
+
+    def capture(self):
+        return (self.active_sh_degree, self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation,
+                self._opacity, self.max_radii2D, self.xyz_gradient_accum, self.denom, self.optimizer.state_dict(),
+                self.spatial_lr_scale)
+
+    def restore(self, model_args, training_args):
+        (self.active_sh_degree, self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation,
+         self._opacity, self.max_radii2D, accum, denom, opt_dict, self.spatial_lr_scale) = model_args
+        self.training_setup(training_args)
+        self.xyz_gradient_accum = accum
+        self.denom = denom
+        self.optimizer.load_state_dict(opt_dict)
+
+    def _own_groups(self):
+        """The optimizer's groups of this model's six tensors (decoder groups ride along untouched), or None."""
+        if self.optimizer is None:
+            return None
+        names = {name for name, _ in PARAM_GROUPS}
+        return {g["name"]: g for g in self.optimizer.param_groups if g.get("name") in names}
+
+    def _swap(self, name, attr, tensor, exp_avg=None, exp_avg_sq=None):
+        """`tensor` becomes the group's nn.Parameter; its optimizer state (if any) is re-keyed to it with the given moments,
+        `step` kept (the reference's _prune_optimizer / cat_tensors_to_optimizer / replace_tensor_to_optimizer)."""
+        new = nn.Parameter(tensor.requires_grad_(True))
+        groups = self._own_groups()
+        if groups is not None and name in groups:
+            old = groups[name]["params"][0]
+            state = self.optimizer.state.pop(old, None)
+            groups[name]["params"][0] = new
+            if state is not None:
+                if exp_avg is not None:
+                    state["exp_avg"], state["exp_avg_sq"] = exp_avg, exp_avg_sq
+                self.optimizer.state[new] = state
+        setattr(self, attr, new)
+        return new
+
+    def replace_tensor_to_optimizer(self, tensor, name):
+        """Replaces group `name`'s parameter by `tensor` and zeroes its Adam moments; returns {name: new parameter}."""
+        attr = dict(PARAM_GROUPS)[name]
+        state = self.optimizer.state.get(self._own_groups()[name]["params"][0])
+        zeros = (torch.zeros_like(tensor), torch.zeros_like(tensor)) if state is not None else (None, None)
+        return {name: self._swap(name, attr, tensor, *zeros)}
+
+    def reset_opacity(self):
+        """Opacities above 0.01 drop to 0.01; the group's moments restart at zero."""
+        opacity = self.get_opacity.detach()
+        self.replace_tensor_to_optimizer(inverse_sigmoid(torch.min(opacity, torch.ones_like(opacity) * 0.01)), "opacity")
+
+    # ---- density control (csrc/ggd_densify.hip) -------------------------------------------------------------------------
+    def _device_rows(self, who):
+        if not (isinstance(self._xyz, torch.Tensor) and self._xyz.is_cuda):
+            raise RuntimeError(f"GaussianModel.{who} needs HIP device tensors (there is no CPU fallback)")
+        return int(self._xyz.shape[0])
+
+    def _stats(self, who, viewspace_point_tensor, radii, update_filter):
+        from . import _capi
+        P = self._device_rows(who)
+        grad = viewspace_point_tensor.grad
+        if grad is None:
+            raise ValueError(f"{who}: viewspace_point_tensor has no .grad (call backward first)")
+        for t in (self.xyz_gradient_accum, self.denom):   # updated in place
+            if tuple(t.shape) != (P, 1) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{who}: call training_setup first (contiguous float32 device statistics [{P}, 1] expected)")
+        for t, name, dtypes, shape in ((grad, "viewspace_point_tensor.grad", (torch.float32,), (P, 3)),
+                                       (radii, "radii", (torch.int32,), (P,)),
+                                       (update_filter, "update_filter", (torch.bool, torch.uint8), (P,))):
+            if t is None:
+                continue
+            if not t.is_cuda:
+                raise RuntimeError(f"{who}: {name} must be a HIP device tensor (there is no CPU fallback)")
+            if t.dtype not in dtypes or tuple(t.shape) != shape:
+                raise ValueError(f"{who}: {name} must be {' / '.join(str(d) for d in dtypes)} {list(shape)}")
+        grad = grad.contiguous()
+        radii = radii.contiguous() if radii is not None else None
+        filt = update_filter.contiguous().view(torch.uint8) if update_filter is not None else None
+        max_radii = None
+        if radii is not None:
+            t = self.max_radii2D
+            if tuple(t.shape) != (P,) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{who}: max_radii2D must be a contiguous float32 device tensor [{P}]")
+            max_radii = self.max_radii2D
+        cx, stream = _capi.context_and_stream(grad.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(grad.device):
+            cx.check(cx.lib.ggd_densify_stats(cx.handle, C.c_void_p(stream), P, ptr(grad), ptr(radii), ptr(filt),
+                                              ptr(self.xyz_gradient_accum), ptr(self.denom), ptr(max_radii)))
+
+    def add_densification_stats(self, viewspace_point_tensor, update_filter):
+        """On the rows of the bool filter: xyz_gradient_accum += |grad[:, :2]|, denom += 1.  One launch, no host wait."""
+        self._stats("add_densification_stats", viewspace_point_tensor, None, update_filter)
+
+    def update_densification_stats(self, viewspace_point_tensor, radii):
+        """The loop's two statistics lines in one launch: rows with radii > 0 are visible; on them max_radii2D =
+        max(max_radii2D, radii) and add_densification_stats' update."""
+        self._stats("update_densification_stats", viewspace_point_tensor, radii, None)
+
+    def _regather(self, plan):
+        """plan(context, stream, tmp pointer, tmp bytes, counts) fills the source map and the counts and returns the noise (or
+        None); one launch then writes every parameter and Adam moment at the new size, and the six nn.Parameters and their
+        optimizer state are swapped.  Every tensor is checked BEFORE the plan is launched: the kernels read P rows of the
+        widths below.  Returns (new row count, gather), gather(t) being the rows of another float32 [P, ...] tensor."""
+        from . import _capi
+        P, dev = int(self._xyz.shape[0]), self._xyz.device
+        if self._features_rest.dim() != 3:
+            raise ValueError("density control: _features_rest must be [P, M - 1, 3]")
+        M = 1 + int(self._features_rest.shape[1])
+        if not 1 <= M <= 16:
+            raise ValueError(f"density control: at most 16 SH coefficients per channel (have {M})")
+        shapes = {"xyz": (P, 3), "f_dc": (P, 1, 3), "f_rest": (P, M - 1, 3), "opacity": (P, 1), "scaling": (P, 3), "rotation": (P, 4)}
+        groups = self._own_groups() or {}
+        src = []
+        for name, attr in PARAM_GROUPS:
+            param = getattr(self, attr)
+            state = self.optimizer.state.get(groups[name]["params"][0]) if name in groups else None
+            has = state is not None and "exp_avg" in state
+            ins = [param.detach()] + ([state["exp_avg"], state["exp_avg_sq"]] if has else [])
+            for t in ins:
+                if t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != shapes[name]:
+                    raise ValueError(f"density control: {attr} and its Adam moments must be float32 {list(shapes[name])} on {dev}")
+            src.append([t.contiguous() for t in ins] + ([] if has else [None, None]))
+        cx, stream = _capi.context_and_stream(dev)
+        nbytes = cx.lib.ggd_densify_tmp_bytes(P)
+        if nbytes == 0:
+            raise ValueError(f"density control: at most 2^26 rows (have {P})")
+        tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        counts = (C.c_int64 * 4)()
+        st, tp = C.c_void_p(stream), C.c_void_p(tmp.data_ptr())
+        with torch.cuda.device(dev):
+            noise = plan(cx, st, tp, nbytes, counts)
+            new_P = int(counts[3])
+            out = [[torch.empty((new_P,) + shapes[name][1:], device=dev) if t is not None else None for t in ins]
+                   for (name, _), ins in zip(PARAM_GROUPS, src)]
+            if cx.poison_outputs:                         # tests: an element the launch does not write shows as NaN
+                for t in (t for row in out for t in row if t is not None):
+                    t.fill_(float("nan"))
+            table = lambda rows: (C.c_void_p * 18)(*[t.data_ptr() if t is not None else None for row in rows for t in row])
+            cx.check(cx.lib.ggd_densify_emit(cx.handle, st, P, new_P, M, table(src), table(out),
+                                             C.c_void_p(noise.data_ptr()) if noise is not None else None, tp, nbytes))
+        for (name, attr), (p, m1, m2) in zip(PARAM_GROUPS, out):
+            self._swap(name, attr, p, m1, m2)
+
+        def gather(t, plan_buffer=tmp):                  # (holds the scratch with the source map alive)
+            t = t.contiguous()
+            res = torch.empty((new_P,) + tuple(t.shape[1:]), device=dev)
+            with torch.cuda.device(dev):
+                cx.check(cx.lib.ggd_densify_gather(cx.handle, st, P, new_P, t.numel() // max(P, 1) or 1, C.c_void_p(t.data_ptr()),
+                                                   C.c_void_p(res.data_ptr()), tp, nbytes))
+            return res
+        return new_P, gather
+
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, noise=None):
+        """Clone, split (2 children) and prune in one pass, with the final state of the reference's sequence (see
+        csrc/ggd_densify.hip for the per-row rule).  noise: standard-normal [2, P, 3] device tensor for the children's
+        offsets (drawn here when None).  The statistics restart at zero at the new size."""
+        P = self._device_rows("densify_and_prune")
+        if not max_grad > 0:
+            raise ValueError("densify_and_prune: max_grad must be > 0 (a clone's zero statistic would satisfy the split test)")
+        dev = self._xyz.device
+        for t in (self.xyz_gradient_accum, self.denom):
+            if tuple(t.shape) != (P, 1) or t.dtype != torch.float32 or t.device != dev:
+                raise ValueError(f"densify_and_prune: call training_setup first (float32 statistics [{P}, 1] on {dev} expected)")
+        if noise is None:
+            noise = torch.randn((2, P, 3), device=dev)
+        elif not (isinstance(noise, torch.Tensor) and noise.is_cuda):
+            raise RuntimeError("densify_and_prune: noise must be a HIP device tensor (there is no CPU fallback)")
+        elif noise.dtype != torch.float32 or tuple(noise.shape) != (2, P, 3):
+            raise ValueError(f"densify_and_prune: noise must be float32 [2, {P}, 3]")
+        noise = noise.contiguous()
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        accum, denom = self.xyz_gradient_accum.contiguous(), self.denom.contiguous()
+        scaling, opacity = self._scaling.detach().contiguous(), self._opacity.detach().contiguous()
+
+        def plan(cx, stream, tmp, nbytes, counts):
+            cx.check(cx.lib.ggd_densify_plan(cx.handle, stream, P, ptr(accum), ptr(denom), ptr(scaling), ptr(opacity),
+                                             float(max_grad), float(self.percent_dense * extent), float(min_opacity),
+                                             int(bool(max_screen_size)), float(0.1 * extent), tmp, nbytes, counts))
+            return noise
+        new_P, _ = self._regather(plan)
+        self.xyz_gradient_accum = torch.zeros((new_P, 1), device=dev)
+        self.denom = torch.zeros((new_P, 1), device=dev)
+        self.max_radii2D = torch.zeros((new_P,), device=dev)
+
+    def prune_points(self, mask):
+        """Drops the rows where the bool mask is set, from every parameter, Adam moment and statistic."""
+        P = self._device_rows("prune_points")
+        if not (isinstance(mask, torch.Tensor) and mask.is_cuda):
+            raise RuntimeError("prune_points: mask must be a HIP device tensor (there is no CPU fallback)")
+        if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (P,):
+            raise ValueError(f"prune_points: mask must be bool [{P}]")
+        m8 = mask.contiguous().view(torch.uint8)
+
+        def plan(cx, stream, tmp, nbytes, counts):
+            cx.check(cx.lib.ggd_prune_plan(cx.handle, stream, P, C.c_void_p(m8.data_ptr()), tmp, nbytes, counts))
+            return None
+        stats = [(n, getattr(self, n)) for n in ("xyz_gradient_accum", "denom", "max_radii2D")]
+        stats = [(n, t) for n, t in stats if isinstance(t, torch.Tensor) and t.shape[:1] == (P,)]
+        for n, t in stats:
+            if t.dtype != torch.float32 or t.device != self._xyz.device or t.numel() != P:
+                raise ValueError(f"prune_points: {n} must be float32 with one value per row on {self._xyz.device}")
+        _, gather = self._regather(plan)
+        for n, t in stats:                                # the same source map, one small launch each, no host wait
+            setattr(self, n, gather(t))

@@ -473,6 +473,55 @@ int ggd_knn3(ggd_ctx* ctx, void* stream, const float* points, int32_t P, float* 
 int ggd_knn3_stage(ggd_ctx* ctx, void* stream, const float* points, int32_t P, float* mean_dist2, float* dist2, int32_t* idx,
                    unsigned long long* examined, void* tmp, size_t tmp_bytes, int32_t stage);
 
+/*
+ * Adaptive density control of a fitted scene: the statistics lines and densify_and_prune / prune_points of
+ * gaussian_splatting/scene/gaussian_model.py (:453-546, train.py:115-120) as streaming passes (csrc/ggd_densify.hip).
+ * All arrays are DEVICE float32 unless stated; P <= 2^26.
+ *
+ * ggd_densify_stats: one launch, in place, no host wait.  A row is visible when filter[i] != 0 (filter: uint8 [P]) or, without
+ * a filter, when radii[i] > 0 (radii: int32 [P]); at least one of the two is given.  On visible rows
+ *   accum[i] += sqrt(gx*gx + gy*gy) (grad_means2D: [P][3])    denom[i] += 1    max_radii2D[i] = max(max_radii2D[i], (float)radii[i])
+ * (the last line only when max_radii2D is given, which needs radii); other rows are not touched.
+ *
+ * ggd_densify_plan: per row, g = accum / denom (0/0 = 0), s = exp(scaling [P][3]), smax = max s,
+ *   hot = g >= max_grad   C = hot && smax <= split_threshold   S = hot && smax > split_threshold
+ *   low = sigmoid(opacity) < min_opacity   big(x) = use_world_size && x > world_size
+ *   prune_self = low || big(smax)   prune_child = low || big(exp(log(smax / 1.6)))
+ * and the rows of the result, each segment in source order: originals with !S && !prune_self | raw copies of the rows with
+ * C && !prune_self | first children of the rows with S && !prune_child | their second children -- the final state of the
+ * reference's clone, split, prune sequence (its screen-size test never fires: max_radii2D is zero by then).  max_grad > 0
+ * (GGD_E_INVALID otherwise: a clone's zero statistic would satisfy the split test).  Three launches (classify + reduce, block
+ * sums, source map -- every dependency is a kernel boundary, nothing waits on another workgroup), then ONE read-back, for which
+ * the call waits on `stream`: counts4 (HOST) = {originals kept, clones, split parents kept, new row count}.
+ * ggd_prune_plan: the same with one segment, the rows with mask[i] == 0 (mask: uint8 [P]).
+ * tmp: ggd_densify_tmp_bytes(P) bytes of device scratch, 16-byte aligned (about 9 bytes per row); it carries the plan to
+ * ggd_densify_emit.  No allocation inside.
+ *
+ * ggd_densify_emit: one gather launch, one thread per output float, over the six parameter groups in optimizer order --
+ * xyz [3], f_dc [3], f_rest [3 (M - 1)], opacity [1], scaling [3], rotation [4] floats per row -- and their Adam moments.
+ * in18 / out18: HOST tables of 18 device pointers, [3 g + 0] the group's parameter, [3 g + 1] exp_avg, [3 g + 2] exp_avg_sq
+ * (inputs P rows, outputs new_P rows; a group's four moment pointers may all be NULL: no optimizer state yet; f_rest is
+ * ignored when M == 1).  Originals and clones are copied; a child (c = 0, 1) of row i gets
+ *   xyz = R(rotation_i / |rotation_i|) (s_i * noise[c][i]) + xyz_i     scaling = log(s_i / 1.6)     the rest copied
+ * with noise [2][P][3] standard-normal numbers of the caller (may be NULL for a plan without children).  Moments are copied
+ * for kept originals and zero for every new row.  new_P is counts4[3] of the plan in tmp; new_P == 0 launches nothing.
+ * ggd_densify_gather: out[r] = in[parent row of r] for any other [P][width] float array (1 <= width <= 64) through the same
+ * plan, copies only -- the statistics arrays of prune_points.
+ */
+size_t ggd_densify_tmp_bytes(int32_t P);
+int ggd_densify_stats(ggd_ctx* ctx, void* stream, int32_t P, const float* grad_means2D, const int32_t* radii /* or NULL */,
+                      const uint8_t* filter /* or NULL */, float* accum, float* denom, float* max_radii2D /* or NULL */);
+int ggd_densify_plan(ggd_ctx* ctx, void* stream, int32_t P, const float* accum, const float* denom, const float* scaling,
+                     const float* opacity, float max_grad, float split_threshold, float min_opacity, int32_t use_world_size,
+                     float world_size, void* tmp, size_t tmp_bytes, int64_t* counts4 /* host */);
+int ggd_prune_plan(ggd_ctx* ctx, void* stream, int32_t P, const uint8_t* mask, void* tmp, size_t tmp_bytes,
+                   int64_t* counts4 /* host */);
+int ggd_densify_emit(ggd_ctx* ctx, void* stream, int32_t P, int32_t new_P, int32_t M, const float* const* in18,
+                     float* const* out18, const float* noise /* [2][P][3] or NULL */, const void* tmp, size_t tmp_bytes);
+
+int ggd_densify_gather(ggd_ctx* ctx, void* stream, int32_t P, int32_t new_P, int32_t width, const float* in, float* out,
+                       const void* tmp, size_t tmp_bytes);
+
 /* ggd_decoder_backward + ggd_decoder_wgrad over point chunks of `chunk` points (<= 0: one chunk), each chunk's weight-
  * gradient kernel launched right behind its backward kernel so that it reads dz / z from the Infinity Cache. */
 int ggd_decoder_backward_wgrad(ggd_ctx* ctx, void* stream, int32_t N, int32_t chunk, const void* packed_t,
