@@ -522,8 +522,13 @@ int ggd_densify_emit(ggd_ctx* ctx, void* stream, int32_t P, int32_t new_P, int32
 int ggd_densify_gather(ggd_ctx* ctx, void* stream, int32_t P, int32_t new_P, int32_t width, const float* in, float* out,
                        const void* tmp, size_t tmp_bytes);
 
-/* ggd_decoder_backward + ggd_decoder_wgrad over point chunks of `chunk` points (<= 0: one chunk), each chunk's weight-
- * gradient kernel launched right behind its backward kernel so that it reads dz / z from the Infinity Cache. */
+/* ggd_decoder_backward + ggd_decoder_wgrad over point chunks of `chunk` points, each chunk's weight-gradient kernel launched
+ * right behind its backward kernel so that it reads dz / z from the Infinity Cache.  chunk <= 0 or chunk > N: one chunk;
+ * otherwise `chunk` is ROUNDED UP to a multiple of 256 points (one batch of a backward workgroup = four weight-gradient
+ * stages), so that every chunk but the last starts and ends on the boundaries of the 16-point blocks of zbuf / dzbuf, of
+ * the 32-point slabs and of the 64-point stages: chunk = 1 runs 256 points per launch pair, chunk = 300 runs 512.  dfeat,
+ * dinfo, dout and dzbuf do not depend on `chunk` (bit for bit); wgrad is summed by float atomics in either form.
+ * ggd_decoder_backward_wgrad_hl rounds `chunk` the same way. */
 int ggd_decoder_backward_wgrad(ggd_ctx* ctx, void* stream, int32_t N, int32_t chunk, const void* packed_t,
                                const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf, float* dout,
                                float* dfeat, float* dinfo, const float* feat, const float* pos, float* wgrad);
@@ -534,9 +539,9 @@ int ggd_decoder_backward_wgrad(ggd_ctx* ctx, void* stream, int32_t N, int32_t ch
  * every product evaluated as W_hi x_hi + W_hi x_lo + W_lo x_hi with fp32 accumulation (csrc/ggd_mlp_hl.inc), in the forward,
  * the backward and the weight gradients (outputs within 1e-5 of an fp32 evaluation).
  * The weight images have their own format (hi and lo image per layer): ggd_decoder_pack_hl builds both from the 40
- * parameter tensors (see ggd_decoder_pack).  zbuf: ggd_decoder_zbuf_bytes(N) as in the bf16 form, but holding fp16; dzbuf:
- * TWO bf16 planes (hi | lo), ggd_decoder_dzbuf_hl_bytes(N) = 2 x ggd_decoder_zbuf_bytes(N); dout / dfeat / dinfo / wgrad as
- * in the bf16 entry points (ggd_decoder_forward_hl with zbuf == NULL is the inference form).
+ * parameter tensors (see ggd_decoder_pack).  zbuf: ggd_decoder_zbuf_bytes(N) as in the bf16 form (fp16 values in both); dzbuf:
+ * ONE fp16 plane, every (head, 32-point slab) scaled by its own power of two, ggd_decoder_dzbuf_hl_bytes(N) =
+ * ggd_decoder_zbuf_bytes(N); dout / dfeat / dinfo / wgrad as in the bf16 entry points (ggd_decoder_forward_hl with zbuf == NULL is the inference form).
  */
 size_t ggd_decoder_packed_hl_bytes(void);
 size_t ggd_decoder_dzbuf_hl_bytes(int32_t N);
