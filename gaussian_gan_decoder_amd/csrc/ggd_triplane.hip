@@ -17,6 +17,16 @@ namespace {
 
 struct Tap { int idx[4]; float w[4]; };  // up to 4 texels (idx < 0: outside -> zero padding)
 
+// Is the tap at floor(i) + o (o = 0 / 1) inside [0, size)?  Tested on the FLOAT floor: for a coordinate beyond the int range
+// (+-1e30, +-inf) (int)floorf() saturates and x0 + 1 overflows, which the compiler may treat -- and for `x1 >= 0 && x1 < W`
+// did treat -- as inside.  The same decision as the integer test for every coordinate that fits an int; false for NaN.
+// Where this is false for such a coordinate the integers x0, x0 + 1 .. the callers derive are MEANINGLESS (the conversion and
+// the increment are undefined there, not merely saturated): use them only under this test, never in a range test of their own.
+__device__ __forceinline__ bool tap_inside(float f, int o, int size) {
+  const float t = f + (float)o;
+  return t >= 0.0f && t <= (float)(size - 1);
+}
+
 __device__ __forceinline__ Tap bilinear_taps(float u, float v, int H, int W) {
   // grid_sample, align_corners = False: pixel = ((g + 1) * size - 1) / 2
   const float ix = ((u + 1.0f) * (float)W - 1.0f) * 0.5f;
@@ -26,7 +36,7 @@ __device__ __forceinline__ Tap bilinear_taps(float u, float v, int H, int W) {
   const float ax = ix - fx, ay = iy - fy;
   Tap t;
   t.w[0] = (1.0f - ax) * (1.0f - ay); t.w[1] = ax * (1.0f - ay); t.w[2] = (1.0f - ax) * ay; t.w[3] = ax * ay;
-  const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W, vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
+  const bool vx0 = tap_inside(fx, 0, W), vx1 = tap_inside(fx, 1, W), vy0 = tap_inside(fy, 0, H), vy1 = tap_inside(fy, 1, H);
   t.idx[0] = (vx0 && vy0) ? y0 * W + x0 : -1;
   t.idx[1] = (vx1 && vy0) ? y0 * W + x1 : -1;
   t.idx[2] = (vx0 && vy1) ? y1 * W + x0 : -1;
@@ -111,7 +121,7 @@ __global__ __launch_bounds__(256) void trigrid_kernel(const float* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int xx = x0 + (k & 1), yy = y0 + ((k >> 1) & 1), zz = z0 + (k >> 2);
-      if (xx >= 0 && xx < W && yy >= 0 && yy < H && zz >= 0 && zz < D) {
+      if (tap_inside(fx, k & 1, W) && tap_inside(fy, (k >> 1) & 1, H) && tap_inside(fz, k >> 2, D)) {
         // weights in grid_sampler_3d's order: (x) * (y) * (z)
         const float wgt = ((k & 1) ? ax : 1.0f - ax) * ((k & 2) ? ay : 1.0f - ay) * ((k & 4) ? az : 1.0f - az);
         const size_t off = p * grid_stride + (((size_t)zz * H + yy) * W + xx) * C + c;
@@ -164,7 +174,7 @@ __global__ __launch_bounds__(256) void gather4_kernel(const float* __restrict__ 
 #pragma unroll
     for (int k = 0; k < (G3 ? 8 : 4); ++k) {
       const int xx = x0 + (k & 1), yy = y0 + ((k >> 1) & 1), zz = G3 ? z0 + (k >> 2) : 0;
-      const bool in = xx >= 0 && xx < W && yy >= 0 && yy < H && zz >= 0 && zz < Dd;
+      const bool in = tap_inside(fx, k & 1, W) && tap_inside(fy, (k >> 1) & 1, H) && (!G3 || tap_inside(fz, k >> 2, Dd));
       // weights in grid_sampler's order: (x) * (y) [* (z)]
       float wk = ((k & 1) ? ax : 1.0f - ax) * ((k & 2) ? ay : 1.0f - ay);
       if (G3) wk = wk * ((k & 4) ? az : 1.0f - az);
@@ -478,13 +488,16 @@ extern "C" int ggd_planes_scatter(ggd_ctx* ctx, void* stream, int32_t C, int32_t
                                   const float* mod, const float* pos, int32_t N, float box_warp, const float* dout,
                                   float* dgrids_cl, int32_t accumulate) {
   if (!ctx) return GGD_E_INVALID;
-  if (!dgrids_cl || H <= 0 || W <= 0 || C <= 0 || D < 0 || axes < 0 || axes > 1 || (D == 0 && axes != 0))
+  if (!dgrids_cl || H <= 0 || W <= 0 || D < 0 || axes < 0 || axes > 1 || (D == 0 && axes != 0))
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_planes_scatter: bad argument");
+  if (C <= 0 || C > 64 || (C & (C - 1)) != 0)
+    return ggd_fail(ctx, GGD_E_INVALID, "ggd_planes_scatter: channel count must be a power of two <= 64");
+  // every refusal comes before the clear: a refused call leaves the caller's gradient buffer as it was
+  if (N > 0 && (!pos || !dout || box_warp == 0.0f)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_planes_scatter: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int Dd = D > 0 ? D : 1;
   if (!accumulate) GGD_HIP(hipMemsetAsync(dgrids_cl, 0, (size_t)3 * Dd * H * W * C * sizeof(float), s));
   if (N <= 0) return GGD_OK;
-  if (!pos || !dout || box_warp == 0.0f) return ggd_fail(ctx, GGD_E_INVALID, "ggd_planes_scatter: bad argument");
   // many points per cell: sort the (point, plane) items by cell and sum runs in registers; few: plain scatter-add
   if (sr_supported(C, D, H, W, N)) return sorted_backward(ctx, s, C, D, H, W, axes, pos, N, box_warp, dout, mod, dgrids_cl);
   if (D == 0) return launch<true>(ctx, s, nullptr, dgrids_cl, C, H, W, pos, N, box_warp, dout, nullptr, mod);
