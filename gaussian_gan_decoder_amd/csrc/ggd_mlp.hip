@@ -23,16 +23,28 @@ namespace {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));   // 8 x f16: forward operands, the z planes, the scaled dz plane
 
 constexpr int HID = 128;
 constexpr int NHEAD = 5;
-// LDS image of one head (bytes); rows are K bf16 + 8 bf16 of padding
-// Weight rows are K bf16 with NO padding; the 16-byte slots of a row are XOR-swizzled by the row index so that a
+// THE HEAD CHAIN, stated once (SequentialDecoderReverse: colour -> opacity -> rotation -> scale -> xyz).  Head h writes
+// head_od(h) values at attrs slot head_a0(h), and sees, behind the 32 plane features and the position, the head_a0(h) attrs
+// slots the earlier heads wrote (its n_extra): its first layer has head_in(h) = 35 + head_a0(h) inputs.
+// (a macro underneath: the forward kernels expand it in place -- through a call, even a force-inlined one, they compile to other
+// code with more scratch in decoder_forward_hl_kernel<true>)
+#define GGD_HEAD_A0(h) ((h) == 0 ? 0 : ((h) == 1 ? 3 : ((h) == 2 ? 4 : ((h) == 3 ? 8 : 11))))
+__host__ __device__ constexpr int head_a0(int h) { return GGD_HEAD_A0(h); }
+__host__ __device__ constexpr int head_od(int h) { return h == 1 ? 1 : (h == 2 ? 4 : 3); }
+__host__ __device__ constexpr int head_in(int h) { return 32 + 3 + head_a0(h); }
+static_assert(head_a0(0) == 0 && head_a0(1) == head_a0(0) + head_od(0) && head_a0(2) == head_a0(1) + head_od(1) &&
+              head_a0(3) == head_a0(2) + head_od(2) && head_a0(4) == head_a0(3) + head_od(3) && head_a0(4) + head_od(4) == 14,
+              "every head starts where the one before it ends; attrs slots 14, 15 are unused");
+// LDS image of one head (bytes).  Weight rows are K 16-bit values with NO padding; the 16-byte slots of a row are XOR-swizzled by the row index so that a
 // ds_read_b128 of one k-slot of 16 consecutive rows by the four lane groups of a wave (rows i = lane & 15, slot g + 4 s) is
 // bank-conflict free: the LDS services a b128 read in four 16-lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ... over a
 // 256-byte bank row; with padded rows (stride 272 B) two lanes of every group met on one 16-byte slot (47 % of the LDS
-// cycles of these kernels were bank conflicts).  wslot() is the one place that knows the mapping; the pack kernels
-// (ggd_mlp_pack.inc, ggd_mlp_hl.inc) and fused_decoder.pack_weights write through the same formula.
+// cycles of these kernels were bank conflicts).  wslot() is the one place on the reading side that knows the mapping; the pack
+// kernel (ggd_mlp_pack.inc: pack_phys) and fused_decoder._swizzle_rows write through the same formula.
 constexpr int ROW1 = 64 * 2;     // layer 1: K = 64 (32 plane features + 32 info slots): two rows per 256-byte bank row
 constexpr int ROW2 = 128 * 2;    // layers 2..4: K = 128: one row per bank row
 template <int ROW>
@@ -101,7 +113,6 @@ __device__ __forceinline__ bf16x8 pack8(const f4& lo, const f4& hi) {
 }
 
 // ---- forward operands: f16 (weights and activations), v_mfma_f32_16x16x32_f16
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 
 // Four GELU pairs in packed f16, in lock step.  The hidden layers' weights and biases are HALVED in the forward image (an exact
@@ -148,8 +159,12 @@ __device__ __forceinline__ void gelu_h2x4(h2v (&y)[4]) {
   for (int i = 0; i < 4; ++i) y[i] = __builtin_elementwise_fma(a[i], p[i], y[i]);
 }
 __device__ __forceinline__ h2v cvt_h2(float a, float b) { return __builtin_convertvector((f2v){a, b}, h2v); }   // v_cvt_pk_f16_f32
-// the kernel's inputs (plane features, positions, earlier heads' outputs) are clamped to the f16 range
+// fp32 -> f16, saturating: THE clamp of everything that enters an f16 format from outside an accumulator -- the forward's inputs
+// (plane features, positions, earlier heads' outputs), the packed weights, the z and scaled dz planes of the reference-precision
+// tier (a conversion past 65504 gives inf, and inf * 0 = NaN would reach the weight gradients).  h16: one value; pack8h: eight,
+// through the packed conversion.
 __device__ __forceinline__ float clamp_h(float v) { return __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f); }
+__device__ __forceinline__ _Float16 h16(float v) { return (_Float16)clamp_h(v); }
 __device__ __forceinline__ h16x8 pack8h(const f4& lo, const f4& hi) {
   const h2v p0 = cvt_h2(clamp_h(lo[0]), clamp_h(lo[1])), p1 = cvt_h2(clamp_h(lo[2]), clamp_h(lo[3]));
   const h2v p2 = cvt_h2(clamp_h(hi[0]), clamp_h(hi[1])), p3 = cvt_h2(clamp_h(hi[2]), clamp_h(hi[3]));
@@ -262,7 +277,7 @@ __global__ __launch_bounds__(FWD_THREADS, FWD_WAVES / 4) void decoder_forward_ke
   const int64_t cend = min((int64_t)N, cbeg + per);
 
   for (int head = 0; head < NHEAD; ++head) {
-    const int n_extra = head == 0 ? 0 : (head == 1 ? 3 : (head == 2 ? 4 : (head == 3 ? 8 : 11)));
+    const int n_extra = GGD_HEAD_A0(head);   // = head_a0(head), expanded in place
     __syncthreads();  // everyone is done with the previous head's weights (and its attrs stores are issued)
     {
       const uint4* src = reinterpret_cast<const uint4*>(packed + (size_t)head * HEAD_BYTES);
@@ -360,26 +375,62 @@ __global__ __launch_bounds__(FWD_THREADS, FWD_WAVES / 4) void decoder_forward_ke
 
 #include "ggd_mlp_bwd.inc"
 #include "ggd_mlp_wgrad.inc"
-#include "ggd_mlp_pack.inc"
 #include "ggd_mlp_hl.inc"
+#include "ggd_mlp_pack.inc"
 
 }  // namespace
 
+// ---- host side: the launch geometry and the per-context set-up, each stated once ---------------------------------------------
+// workgroups of `waves` waves for n points: at least one 32-point slab per wave, at most 256 workgroups
+static int slab_grid(int n, int waves) {
+  const int grid = (n + waves * SLAB - 1) / (waves * SLAB);
+  return grid > 256 ? 256 : grid < 1 ? 1 : grid;
+}
+// split-K of the weight gradients over up to 128 point chunks x 20 (head, layer) problems (measured: 32 -> 4.6 ms, 64 -> 3.9,
+// 128 -> 3.7, 256 -> 3.9); at least 4 stages per workgroup
+static int wgrad_chunks(int n) {
+  const int chunks = (n + 4 * WG_K - 1) / (4 * WG_K);
+  return chunks > 128 ? 128 : chunks < 1 ? 1 : chunks;
+}
+// the kernels' dynamic-LDS limits, raised once per context (`bit` of ctx->attr_mask remembers it)
+struct lds_kernel { const void* fn; int bytes; };
+static int lds_once(ggd_ctx* ctx, uint32_t bit, std::initializer_list<lds_kernel> kernels) {
+  if (ctx->attr_mask & bit) return GGD_OK;
+  for (const lds_kernel& k : kernels) GGD_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes));
+  ctx->attr_mask |= bit;
+  return GGD_OK;
+}
+// Backward + weight gradients in point CHUNKS [first, last): the backward kernel of a chunk is followed immediately by the
+// weight-gradient kernel of the same chunk, so that the dz / z rows it reads are still in the 256 MB Infinity Cache instead of
+// coming back from HBM.  chunk <= 0: one chunk; otherwise rounded up to a multiple of 256 points.
+template <typename F>
+static void chunk_walk(int32_t N, int32_t chunk, F&& launch_both) {
+  if (chunk <= 0 || chunk > N) chunk = N;
+  chunk = (chunk + 255) / 256 * 256;
+  for (int32_t first = 0; first < N; first += chunk) launch_both(first, first + chunk < N ? first + chunk : N);
+}
+
 extern "C" size_t ggd_decoder_packed_bytes(void) { return (size_t)NHEAD * HEAD_BYTES; }
 
-extern "C" int ggd_decoder_pack(ggd_ctx* ctx, void* stream, const float* const* params40, void* packed, void* packed_t) {
+template <bool HL>
+static int decoder_pack_impl(ggd_ctx* ctx, void* stream, const float* const* params40, void* packed, void* packed_t,
+                             const char* entry) {
   if (!ctx) return GGD_E_INVALID;
-  if (!params40 || !packed) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_pack: NULL pointer");
+  if (!params40 || !packed) return ggd_fail(ctx, GGD_E_INVALID, std::string(entry) + ": NULL pointer");
   ggd_pack_ptrs ptrs;
   for (int i = 0; i < NHEAD * 8; ++i) {
-    if (!params40[i]) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_pack: NULL parameter pointer");
+    if (!params40[i]) return ggd_fail(ctx, GGD_E_INVALID, std::string(entry) + ": NULL parameter pointer");
     ptrs.p[i] = params40[i];
   }
-  const int total = NHEAD * PACK_PER_HEAD;
-  hipLaunchKernelGGL(decoder_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), ptrs,
+  const int total = NHEAD * (HL ? 2 : 1) * (pack_elems(0) + pack_elems(1)) + NHEAD * PACK_BIAS;   // one thread per element
+  hipLaunchKernelGGL(decoder_pack_kernel<HL>, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), ptrs,
                      static_cast<unsigned char*>(packed), static_cast<unsigned char*>(packed_t));
   GGD_HIP(hipGetLastError());
   return GGD_OK;
+}
+
+extern "C" int ggd_decoder_pack(ggd_ctx* ctx, void* stream, const float* const* params40, void* packed, void* packed_t) {
+  return decoder_pack_impl<false>(ctx, stream, params40, packed, packed_t, "ggd_decoder_pack");
 }
 
 // the GELU / GELU' tables (ggd_mlp_gelu.inc), built once per context in double precision
@@ -399,16 +450,10 @@ static int decoder_forward_impl(ggd_ctx* ctx, void* stream, const float* feat, c
   if (N == 0) return GGD_OK;
   if (!feat || !pos || !packed_weights || !attrs) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_forward: NULL pointer");
   const size_t lds = HEAD_BYTES;
-  if (!(ctx->attr_mask & GGD_ATTR_MLP_FWD)) {
-    GGD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decoder_forward_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GGD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decoder_forward_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ctx->attr_mask |= GGD_ATTR_MLP_FWD;
-  }
-  int grid = (N + FWD_WAVES * SLAB - 1) / (FWD_WAVES * SLAB);  // at least one slab per wave
-  if (grid > 256) grid = 256;
-  if (grid < 1) grid = 1;
+  const int rc = lds_once(ctx, GGD_ATTR_MLP_FWD, {{reinterpret_cast<const void*>(decoder_forward_kernel<false>), HEAD_BYTES},
+                                                  {reinterpret_cast<const void*>(decoder_forward_kernel<true>), HEAD_BYTES}});
+  if (rc != GGD_OK) return rc;
+  const int grid = slab_grid(N, FWD_WAVES);
   if (zbuf)
     hipLaunchKernelGGL(decoder_forward_kernel<true>, dim3(grid), dim3(FWD_THREADS), lds, static_cast<hipStream_t>(stream),
                        feat, pos, N, static_cast<const unsigned char*>(packed_weights), attrs, static_cast<_Float16*>(zbuf));
@@ -477,6 +522,26 @@ extern "C" int ggd_decoder_forward(ggd_ctx* ctx, void* stream, const float* feat
 
 extern "C" size_t ggd_decoder_packed_t_bytes(void) { return (size_t)NHEAD * HEADT_BYTES; }
 
+// the two launches of the 16-bit tier's backward over the points [first, last) of N
+static int launch_backward(ggd_ctx* ctx, hipStream_t s, int32_t N, int32_t first, int32_t last, const void* packed_t,
+                           const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf, float* dout, float* dfeat,
+                           float* dinfo) {
+  const int rc = lds_once(ctx, GGD_ATTR_MLP_BWD, {{reinterpret_cast<const void*>(decoder_backward_kernel), HEADT_BYTES}});
+  if (rc != GGD_OK) return rc;
+  hipLaunchKernelGGL(decoder_backward_kernel, dim3(slab_grid(last - first, MLP_WAVES)), dim3(MLP_THREADS), HEADT_BYTES, s, N,
+                     first, last, static_cast<const unsigned char*>(packed_t), attrs, dattrs, static_cast<const _Float16*>(zbuf),
+                     static_cast<__bf16*>(dzbuf), dout, dfeat, dinfo);
+  return GGD_OK;
+}
+static int launch_wgrad(ggd_ctx* ctx, hipStream_t s, int32_t N, int32_t first, int32_t last, const void* zbuf, const void* dzbuf,
+                        const float* dout, const float* feat, const float* pos, const float* attrs, float* wgrad) {
+  const int rc = lds_once(ctx, GGD_ATTR_MLP_WGRAD, {{reinterpret_cast<const void*>(decoder_wgrad_kernel), WG_LDS}});
+  if (rc != GGD_OK) return rc;
+  hipLaunchKernelGGL(decoder_wgrad_kernel, dim3(wgrad_chunks(last - first), NHEAD * 4), dim3(WG_THREADS), WG_LDS, s, N, first,
+                     last, static_cast<const __bf16*>(zbuf), static_cast<const __bf16*>(dzbuf), dout, feat, pos, attrs, wgrad);
+  return GGD_OK;
+}
+
 extern "C" int ggd_decoder_backward(ggd_ctx* ctx, void* stream, int32_t N, const void* packed_t, const float* attrs,
                                     const float* dattrs, const void* zbuf, void* dzbuf, float* dout, float* dfeat,
                                     float* dinfo) {
@@ -485,16 +550,9 @@ extern "C" int ggd_decoder_backward(ggd_ctx* ctx, void* stream, int32_t N, const
   if (N == 0) return GGD_OK;
   if (!packed_t || !attrs || !dattrs || !zbuf || !dzbuf || !dout || !dfeat || !dinfo)
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_backward: NULL pointer");
-  if (!(ctx->attr_mask & GGD_ATTR_MLP_BWD)) {
-    GGD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decoder_backward_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEADT_BYTES));
-    ctx->attr_mask |= GGD_ATTR_MLP_BWD;
-  }
-  int grid = (N + MLP_WAVES * SLAB - 1) / (MLP_WAVES * SLAB);
-  if (grid > 256) grid = 256;
-  hipLaunchKernelGGL(decoder_backward_kernel, dim3(grid), dim3(MLP_THREADS), HEADT_BYTES, static_cast<hipStream_t>(stream),
-                     N, 0, N, static_cast<const unsigned char*>(packed_t), attrs, dattrs, static_cast<const _Float16*>(zbuf),
-                     static_cast<__bf16*>(dzbuf), dout, dfeat, dinfo);
+  const int rc = launch_backward(ctx, static_cast<hipStream_t>(stream), N, 0, N, packed_t, attrs, dattrs, zbuf, dzbuf, dout, dfeat,
+                                 dinfo);
+  if (rc != GGD_OK) return rc;
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }
@@ -519,25 +577,13 @@ extern "C" int ggd_decoder_wgrad(ggd_ctx* ctx, void* stream, int32_t N, const vo
   if (N == 0) return GGD_OK;
   if (!zbuf || !dzbuf || !dout || !feat || !pos || !attrs || !wgrad)
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_wgrad: NULL pointer");
-  if (!(ctx->attr_mask & GGD_ATTR_MLP_WGRAD)) {
-    GGD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decoder_wgrad_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS));
-    ctx->attr_mask |= GGD_ATTR_MLP_WGRAD;
-  }
-  // split-K over up to 128 point chunks x 20 (head, layer) problems (measured: 32 -> 4.6 ms, 64 -> 3.9, 128 -> 3.7, 256 -> 3.9); at least 4 stages per workgroup
-  int chunks = (N + 4 * WG_K - 1) / (4 * WG_K);
-  if (chunks > 128) chunks = 128;
-  if (chunks < 1) chunks = 1;
-  hipLaunchKernelGGL(decoder_wgrad_kernel, dim3(chunks, NHEAD * 4), dim3(WG_THREADS), WG_LDS,
-                     static_cast<hipStream_t>(stream), N, 0, N, static_cast<const __bf16*>(zbuf),
-                     static_cast<const __bf16*>(dzbuf), dout, feat, pos, attrs, wgrad);
+  const int rc = launch_wgrad(ctx, static_cast<hipStream_t>(stream), N, 0, N, zbuf, dzbuf, dout, feat, pos, attrs, wgrad);
+  if (rc != GGD_OK) return rc;
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }
 
-// Backward + weight gradients in point CHUNKS: the backward kernel of a chunk is followed immediately by the weight-
-// gradient kernel of the same chunk, so that the dz / z rows it reads are still in the 256 MB Infinity Cache instead of
-// coming back from HBM.  chunk <= 0: one chunk (= ggd_decoder_backward followed by ggd_decoder_wgrad).
+// chunk <= 0: one chunk (= ggd_decoder_backward followed by ggd_decoder_wgrad); see chunk_walk
 extern "C" int ggd_decoder_backward_wgrad(ggd_ctx* ctx, void* stream, int32_t N, int32_t chunk, const void* packed_t,
                                           const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf,
                                           float* dout, float* dfeat, float* dinfo, const float* feat, const float* pos,
@@ -547,30 +593,13 @@ extern "C" int ggd_decoder_backward_wgrad(ggd_ctx* ctx, void* stream, int32_t N,
   if (N == 0) return GGD_OK;
   if (!packed_t || !attrs || !dattrs || !zbuf || !dzbuf || !dout || !dfeat || !dinfo || !feat || !pos || !wgrad)
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_backward_wgrad: NULL pointer");
-  if ((ctx->attr_mask & (GGD_ATTR_MLP_BWD | GGD_ATTR_MLP_WGRAD)) != (GGD_ATTR_MLP_BWD | GGD_ATTR_MLP_WGRAD)) {
-    GGD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decoder_backward_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEADT_BYTES));
-    GGD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decoder_wgrad_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS));
-    ctx->attr_mask |= GGD_ATTR_MLP_BWD | GGD_ATTR_MLP_WGRAD;
-  }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (chunk <= 0 || chunk > N) chunk = N;
-  chunk = (chunk + 255) / 256 * 256;
-  for (int32_t first = 0; first < N; first += chunk) {
-    const int32_t last = first + chunk < N ? first + chunk : N;
-    const int32_t n = last - first;
-    int grid = (n + MLP_WAVES * SLAB - 1) / (MLP_WAVES * SLAB);
-    if (grid > 256) grid = 256;
-    hipLaunchKernelGGL(decoder_backward_kernel, dim3(grid), dim3(MLP_THREADS), HEADT_BYTES, s, N, first, last,
-                       static_cast<const unsigned char*>(packed_t), attrs, dattrs, static_cast<const _Float16*>(zbuf),
-                       static_cast<__bf16*>(dzbuf), dout, dfeat, dinfo);
-    int chunks = (n + 4 * WG_K - 1) / (4 * WG_K);
-    if (chunks > 128) chunks = 128;
-    if (chunks < 1) chunks = 1;
-    hipLaunchKernelGGL(decoder_wgrad_kernel, dim3(chunks, NHEAD * 4), dim3(WG_THREADS), WG_LDS, s, N, first, last,
-                       static_cast<const __bf16*>(zbuf), static_cast<const __bf16*>(dzbuf), dout, feat, pos, attrs, wgrad);
-  }
+  int rc = GGD_OK;
+  chunk_walk(N, chunk, [&](int32_t first, int32_t last) {
+    if (rc == GGD_OK) rc = launch_backward(ctx, s, N, first, last, packed_t, attrs, dattrs, zbuf, dzbuf, dout, dfeat, dinfo);
+    if (rc == GGD_OK) rc = launch_wgrad(ctx, s, N, first, last, zbuf, dzbuf, dout, feat, pos, attrs, wgrad);
+  });
+  if (rc != GGD_OK) return rc;
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }
@@ -582,33 +611,16 @@ extern "C" size_t ggd_decoder_packed_t_hl_bytes(void) { return (size_t)NHEAD * H
 
 extern "C" int ggd_decoder_pack_hl(ggd_ctx* ctx, void* stream, const float* const* params40, void* packed_hl,
                                    void* packed_t_hl) {
-  if (!ctx) return GGD_E_INVALID;
-  if (!params40 || !packed_hl) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_pack_hl: NULL pointer");
-  ggd_pack_ptrs ptrs;
-  for (int i = 0; i < NHEAD * 8; ++i) {
-    if (!params40[i]) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_pack_hl: NULL parameter pointer");
-    ptrs.p[i] = params40[i];
-  }
-  const int total = NHEAD * HLPK_PER_HEAD;
-  hipLaunchKernelGGL(decoder_pack_hl_kernel, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), ptrs,
-                     static_cast<unsigned char*>(packed_hl), static_cast<unsigned char*>(packed_t_hl));
-  GGD_HIP(hipGetLastError());
-  return GGD_OK;
+  return decoder_pack_impl<true>(ctx, stream, params40, packed_hl, packed_t_hl, "ggd_decoder_pack_hl");
 }
 
-static int hl_attributes(ggd_ctx* ctx) {
-  if (ctx->attr_mask & GGD_ATTR_MLP_HL) return GGD_OK;
-  { const int rt = gelu_tables(ctx); if (rt != GGD_OK) return rt; }
-  GGD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decoder_forward_hl_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)HL_LDS_FWD));
-  GGD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decoder_forward_hl_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)HL_LDS_FWD));
-  GGD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decoder_backward_hl_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)HL_LDS_BWD));
-  GGD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decoder_wgrad_hl_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)WGH_LDS));
-  ctx->attr_mask |= GGD_ATTR_MLP_HL;
-  return GGD_OK;
+static int hl_attributes(ggd_ctx* ctx) {   // the GELU tables and the four kernels' LDS limits
+  const int rt = gelu_tables(ctx);
+  if (rt != GGD_OK) return rt;
+  return lds_once(ctx, GGD_ATTR_MLP_HL, {{reinterpret_cast<const void*>(decoder_forward_hl_kernel<false>), HL_LDS_FWD},
+                                         {reinterpret_cast<const void*>(decoder_forward_hl_kernel<true>), HL_LDS_FWD},
+                                         {reinterpret_cast<const void*>(decoder_backward_hl_kernel), HL_LDS_BWD},
+                                         {reinterpret_cast<const void*>(decoder_wgrad_hl_kernel), WGH_LDS}});
 }
 
 extern "C" int ggd_decoder_forward_hl(ggd_ctx* ctx, void* stream, const float* feat, const float* pos, int32_t N,
@@ -619,8 +631,7 @@ extern "C" int ggd_decoder_forward_hl(ggd_ctx* ctx, void* stream, const float* f
   if (!feat || !pos || !packed_hl || !attrs) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_forward_hl: NULL pointer");
   const int rc = hl_attributes(ctx);
   if (rc != GGD_OK) return rc;
-  int grid = (N + FWD_WAVES * SLAB - 1) / (FWD_WAVES * SLAB);
-  if (grid > 256) grid = 256;
+  const int grid = slab_grid(N, FWD_WAVES);
   if (zbuf)
     hipLaunchKernelGGL(decoder_forward_hl_kernel<true>, dim3(grid), dim3(FWD_THREADS), HL_LDS_FWD,
                        static_cast<hipStream_t>(stream), feat, pos, N, static_cast<const unsigned char*>(packed_hl), attrs,
@@ -654,24 +665,15 @@ extern "C" int ggd_decoder_backward_wgrad_hl(ggd_ctx* ctx, void* stream, int32_t
   int* karr = static_cast<int*>(ctx->scratch);
   int* kref = reinterpret_cast<int*>(static_cast<char*>(ctx->scratch) + ggd_align((size_t)NHEAD * nslab * sizeof(int)));
   GGD_HIP(hipMemsetAsync(kref, 0x80, 64, s));     // every byte 0x80: far below any exponent (atomicMax target); < HL_KNONE is never stored
-  if (chunk <= 0 || chunk > N) chunk = N;
-  chunk = (chunk + 255) / 256 * 256;
-  for (int32_t first = 0; first < N; first += chunk) {
-    const int32_t last = first + chunk < N ? first + chunk : N;
-    const int32_t n = last - first;
-    int grid = (n + MLP_WAVES * SLAB - 1) / (MLP_WAVES * SLAB);
-    if (grid > 256) grid = 256;
-    hipLaunchKernelGGL(decoder_backward_hl_kernel, dim3(grid), dim3(MLP_THREADS), HL_LDS_BWD, s, N, first, last,
-                       static_cast<const unsigned char*>(packed_t_hl), attrs, dattrs, static_cast<const __bf16*>(zbuf),
-                       static_cast<__bf16*>(dzbuf), dout, dfeat, dinfo, karr, kref,
+  chunk_walk(N, chunk, [&](int32_t first, int32_t last) {
+    hipLaunchKernelGGL(decoder_backward_hl_kernel, dim3(slab_grid(last - first, MLP_WAVES)), dim3(MLP_THREADS), HL_LDS_BWD, s, N,
+                       first, last, static_cast<const unsigned char*>(packed_t_hl), attrs, dattrs,
+                       static_cast<const __bf16*>(zbuf), static_cast<__bf16*>(dzbuf), dout, dfeat, dinfo, karr, kref,
                        static_cast<const unsigned char*>(ctx->gelu_tables));
-    int chunks = (n + 4 * WG_K - 1) / (4 * WG_K);
-    if (chunks > 128) chunks = 128;
-    if (chunks < 1) chunks = 1;
-    hipLaunchKernelGGL(decoder_wgrad_hl_kernel, dim3(chunks, NHEAD * 4), dim3(WG_THREADS), WGH_LDS, s, N, first, last,
-                       static_cast<const __bf16*>(zbuf), static_cast<const __bf16*>(dzbuf), dout, feat, pos, attrs, wgrad, karr, kref,
-                       static_cast<const unsigned char*>(ctx->gelu_tables));
-  }
+    hipLaunchKernelGGL(decoder_wgrad_hl_kernel, dim3(wgrad_chunks(last - first), NHEAD * 4), dim3(WG_THREADS), WGH_LDS, s, N,
+                       first, last, static_cast<const __bf16*>(zbuf), static_cast<const __bf16*>(dzbuf), dout, feat, pos, attrs,
+                       wgrad, karr, kref, static_cast<const unsigned char*>(ctx->gelu_tables));
+  });
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }

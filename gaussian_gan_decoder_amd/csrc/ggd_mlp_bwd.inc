@@ -2,8 +2,9 @@
 //
 // dL/d(activations) of the 5 heads, last head first.  Same transposed chain as the forward with the TRANSPOSED weights
 // (dh_{l-1}^T = W_l^T . dz_l^T, dz_l = dh_l * gelu'(z_l)); z_l comes from the forward's zbuf.  The kernel writes
-//   dzbuf[head][layer][point][128] (bf16), dout[head][point][4] (fp32, gradient at the head's raw 4-wide output),
-// from which the weight / bias gradients are plain [out,N]x[N,in] reductions (done by the caller as split-K GEMMs),
+//   dzbuf[head][layer][16-point block][4 KB] (bf16, the blocked Z layout of zbuf: ggd_mlp.hip), dout[head][point][4] (fp32,
+//   gradient at the head's raw 4-wide output),
+// from which decoder_wgrad_kernel (ggd_mlp_wgrad.inc) forms the weight / bias gradients as [out,N]x[N,in] split-K reductions,
 // accumulates dL/d(plane features) into dfeat[point][32] and carries dL/d(info) between heads in dinfo[point][16].
 constexpr int ROW4T = (32 + 8) * 2;
 constexpr int OFFT_W4 = 0;
@@ -29,25 +30,10 @@ __device__ __forceinline__ void layer_mfma_t(const unsigned char* __restrict__ w
   }
 }
 
-// gelu'(x) = Phi(x) + x phi(x) for two values: 0.5 + xc * P7(xc^2) with xc = clamp(x, -4, 4) (least-squares fit on
-// Chebyshev nodes, max |error| 3.1e-4 over all x in fp32 Horner form -- a tenth of the bf16 rounding of dz).  11 packed
-// VALU ops per pair and no transcendental; the erf-polynomial + exp form it replaces cost 24 and made the kernel
-// VALU-bound at 3.7x its MFMA time.
-__device__ __forceinline__ f2v gelu_grad2(f2v x) {
-  const f2v xc = {__builtin_amdgcn_fmed3f(x.x, -4.0f, 4.0f), __builtin_amdgcn_fmed3f(x.y, -4.0f, 4.0f)};
-  const f2v s2 = xc * xc;
-  f2v p = {-1.557768258e-08f, -1.557768258e-08f};
-  p = __builtin_elementwise_fma(p, s2, (f2v){1.163350639e-06f, 1.163350639e-06f});
-  p = __builtin_elementwise_fma(p, s2, (f2v){-3.725065996e-05f, -3.725065996e-05f});
-  p = __builtin_elementwise_fma(p, s2, (f2v){6.728997635e-04f, 6.728997635e-04f});
-  p = __builtin_elementwise_fma(p, s2, (f2v){-7.591166539e-03f, -7.591166539e-03f});
-  p = __builtin_elementwise_fma(p, s2, (f2v){5.559237280e-02f, 5.559237280e-02f});
-  p = __builtin_elementwise_fma(p, s2, (f2v){-2.615541427e-01f, -2.615541427e-01f});
-  p = __builtin_elementwise_fma(p, s2, (f2v){7.965189430e-01f, 7.965189430e-01f});
-  return __builtin_elementwise_fma(xc, p, (f2v){0.5f, 0.5f});
-}
-
-// four pairs in lock step (see gelu2x4: no wait states between dependent packed ops)
+// gelu'(x) = Phi(x) + x phi(x): 0.5 + xc * P7(xc^2) with xc = clamp(x, -4, 4) (least-squares fit on Chebyshev nodes, max
+// |error| 3.1e-4 over all x in fp32 Horner form -- a tenth of the bf16 rounding of dz).  11 packed VALU ops per pair and no
+// transcendental; the erf-polynomial + exp form it replaces cost 24 and made the kernel VALU-bound at 3.7x its MFMA time.
+// Four pairs in lock step (see gelu2x4: no wait states between dependent packed ops).
 __device__ __forceinline__ void gelu_grad2x4(f2v (&x)[4]) {
   f2v xc[4], s2[4], p[4];
 #pragma unroll
@@ -85,7 +71,8 @@ __device__ __forceinline__ void load_z_tiles(const T* __restrict__ zl, int64_t p
   }
 }
 
-// dz = dh * gelu'(z) for the wave's tiles; stores dz (bf16, row-major) and packs it as the next B operand.
+// dz = dh * gelu'(z) for the wave's tiles, packed as the next B operand; the same 16-byte pieces are stored as dz (bf16, blocked
+// Z layout).
 __device__ __forceinline__ void gelu_bwd_pack(const f4 (&dh)[2][8], const h16x8 (&zv)[2][4],
                                               __bf16* __restrict__ dzl, int64_t p0, int64_t cend, int lane,
                                               bf16x8 (&bout)[2][4]) {
@@ -115,6 +102,57 @@ __device__ __forceinline__ void gelu_bwd_pack(const f4 (&dh)[2][8], const h16x8 
   }
 }
 
+// dx = W1^T dz1 of the wave's tiles -> the gradients of the head's inputs: rows 0..31 (feature tiles 0, 1) are the plane features,
+// rows 32..47 (tile 2) the info slots (position + earlier heads' outputs).  The last head (the first one the backward visits)
+// writes dfeat / dinfo, every other head adds to them.
+__device__ __forceinline__ void add_input_grads(const f4 (&acc)[2][8], int head, int64_t p0, int64_t cend, int lane,
+                                                float* dfeat, float* dinfo) {
+  const int j = lane & 15, g = lane >> 4;
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int64_t pt = p0 + 16 * c + j;
+    if (pt >= cend) continue;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+      f4* dst = reinterpret_cast<f4*>(dfeat + pt * 32 + 16 * mt + 4 * g);
+      f4 v = acc[c][mt];
+      if (head != NHEAD - 1) { const f4 o = *dst; v = v + o; }
+      *dst = v;
+    }
+    f4* di = reinterpret_cast<f4*>(dinfo + pt * 16 + 4 * g);
+    f4 v = acc[c][2];
+    if (head != NHEAD - 1) { const f4 o = *di; v = v + o; }
+    *di = v;
+  }
+}
+
+// Gradient at head `head`'s raw output for one point (the lane of group 0 that owns its output rows 0..3): dattrs of the head's
+// slots, plus what the later heads sent back through `info`, through the derivative of the head's activation; stored to dout
+// [head][point][4] (the weight-gradient kernel's layer-4 operand) and returned.
+__device__ __forceinline__ f4 head_out_grad(int head, int64_t pt, int N, const float* __restrict__ attrs,
+                                            const float* __restrict__ dattrs, const float* dinfo, float* __restrict__ dout) {
+  const int a0 = head_a0(head), od = head_od(head);   // first attrs slot, output width
+  f4 d = {0, 0, 0, 0};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (e < od) {
+      float v = dattrs[pt * 16 + a0 + e];
+      if (head == 4) {
+        v *= 0.01f;                                   // xyz = head * 0.01 + position
+      } else {
+        v += dinfo[pt * 16 + 3 + a0 + e];             // + what the later heads sent back through `info`
+        if (head == 3) {                              // scale = -softplus(s + 5) - 2.5
+          const float sp = -attrs[pt * 16 + a0 + e] - 2.5f;
+          v *= -(1.0f - expf(-sp));                   // -sigmoid(s + 5) = -(1 - exp(-softplus))
+        }
+      }
+      d[e] = v;
+    }
+  }
+  *reinterpret_cast<f4*>(dout + ((size_t)head * N + pt) * 4) = d;
+  return d;
+}
+
 __global__ __launch_bounds__(MLP_THREADS, MLP_THREADS / 256) void decoder_backward_kernel(
     int N, int first, int last, const unsigned char* __restrict__ packed_t, const float* __restrict__ attrs,
     const float* __restrict__ dattrs, const _Float16* __restrict__ zbuf, __bf16* __restrict__ dzbuf,
@@ -129,8 +167,6 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_THREADS / 256) void decoder_backwa
   const int64_t cend = min((int64_t)last, cbeg + per);
 
   for (int head = NHEAD - 1; head >= 0; --head) {
-    const int a0 = head == 0 ? 0 : (head == 1 ? 3 : (head == 2 ? 4 : (head == 3 ? 8 : 11)));  // first attrs slot
-    const int od = head == 1 ? 1 : (head == 2 ? 4 : 3);                                          // output width
     __syncthreads();
     {
       const uint4* src = reinterpret_cast<const uint4*>(packed_t + (size_t)head * HEADT_BYTES);
@@ -153,25 +189,7 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_THREADS / 256) void decoder_backwa
       for (int c = 0; c < 2; ++c) {
         const int64_t pt = p0 + 16 * c + j;
         f4 d = {0, 0, 0, 0};
-        if (g == 0 && pt < cend) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            if (e < od) {
-              float v = dattrs[pt * 16 + a0 + e];
-              if (head == 4) {
-                v *= 0.01f;                                   // xyz = head * 0.01 + position
-              } else {
-                v += dinfo[pt * 16 + 3 + a0 + e];             // + what the later heads sent back through `info`
-                if (head == 3) {                              // scale = -softplus(s + 5) - 2.5
-                  const float sp = -attrs[pt * 16 + a0 + e] - 2.5f;
-                  v *= -(1.0f - expf(-sp));                   // -sigmoid(s + 5) = -(1 - exp(-softplus))
-                }
-              }
-              d[e] = v;
-            }
-          }
-          *reinterpret_cast<f4*>(dout + ((size_t)head * N + pt) * 4) = d;
-        }
+        if (g == 0 && pt < cend) d = head_out_grad(head, pt, N, attrs, dattrs, dinfo, dout);
         const f4 z = {0, 0, 0, 0};
         bin[c][0] = pack8(d, z);
         bin[c][1] = bin[c][0]; bin[c][2] = bin[c][0]; bin[c][3] = bin[c][0];  // unused k blocks
@@ -189,23 +207,7 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_THREADS / 256) void decoder_backwa
       layer_mfma_t<8, 4, ROW2>(wl + OFFT_W2, bh, acc, lane);         // dh1 = W2^T dz2
       gelu_bwd_pack(acc, zv, dz1, p0, cend, lane, bh);
       layer_mfma_t<4, 4, ROW2>(wl + OFFT_W1, bh, acc, lane);         // dx (64 input rows) = W1^T dz1
-      // rows 0..31 -> plane features, rows 32..47 -> info slots (position + earlier heads' outputs)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const int64_t pt = p0 + 16 * c + j;
-        if (pt >= cend) continue;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-          f4* dst = reinterpret_cast<f4*>(dfeat + pt * 32 + 16 * mt + 4 * g);
-          f4 v = acc[c][mt];
-          if (head != NHEAD - 1) { const f4 o = *dst; v = v + o; }
-          *dst = v;
-        }
-        f4* di = reinterpret_cast<f4*>(dinfo + pt * 16 + 4 * g);
-        f4 v = acc[c][2];
-        if (head != NHEAD - 1) { const f4 o = *di; v = v + o; }
-        *di = v;
-      }
+      add_input_grads(acc, head, p0, cend, lane, dfeat, dinfo);
     }
   }
 }

@@ -16,9 +16,6 @@ constexpr int GT_OFF_FWD = 0, GT_OFF_BWD = gt_bytes(GT_N_FWD), GT_OFF_WG = GT_OF
 constexpr int GT_BYTES = GT_OFF_WG + gt_bytes(GT_N_WG);
 template <int N>
 __device__ __forceinline__ float gt_lin(const float2* __restrict__ tbl, float x) {
-#ifdef GGD_HL_NOGELU   // timing experiments only (wrong results)
-  return x;
-#endif
   float t = __builtin_fmaf(x, (float)N / 12.0f, 0.5f * (float)N);      // (x + 6) * N / 12
   t = __builtin_amdgcn_fmed3f(t, 0.0f, (float)N - 0.001f);             // NaN -> 0
   const float fl = __builtin_floorf(t);
@@ -30,9 +27,6 @@ __device__ __forceinline__ float gt_lin(const float2* __restrict__ tbl, float x)
 // 23.5 ms).  Here the block's 16 temporaries live for its 30 instructions and are dead outside.  x -> f(x) in place.
 // tbl: LDS byte address of the table (wave-uniform); sc, hf, hi: N / 12, N / 2, N - 0.001 held in VGPRs by the caller.
 __device__ __forceinline__ void gt_lin4(uint32_t tbl, float sc, float hf, float hi, float& x0, float& x1, float& x2, float& x3) {
-#ifdef GGD_HL_NOGELU   // timing experiments only (wrong results)
-  return;
-#endif
   // (round 5: one ds_read_b64 per value instead of two ds_read_b32 -- the {f, df} pair is one aligned 8-byte word; per-lane
   // addresses over a 16 - 32 KB table collide in the 32 banks either way, but half the LDS instructions halve the conflict
   // cycles: 58 - 63 % of the LDS pipe's active cycles in these kernels were bank conflicts, profiles/r04/pmc_summary_decoder_fp32.txt.

@@ -1,5 +1,5 @@
 // ggd_mlp_hl.inc -- the fused decoder at REFERENCE PRECISION on the bf16 matrix cores (included inside ggd_mlp.hip's
-// anonymous namespace, after ggd_mlp_bwd.inc).
+// anonymous namespace, after ggd_mlp_wgrad.inc; its weight images are built by ggd_mlp_pack.inc).
 //
 // The reference trains its decoder in fp32 (main/decoder_models/base_decoder.py:8-27).  The plain bf16 kernels round every
 // weight to 8 mantissa bits -- the SAME perturbation for every point, i.e. a systematic error of the function being
@@ -63,9 +63,6 @@ static_assert((2 * HL_P1) % 1024 == 0 && (2 * HL_P2) % 1024 == 0 && (2 * HL_P4) 
 // being computed (it cannot tell the two weight buffers apart inside one dynamic LDS array and would wait for every
 // LDS-direct load before the next ds_read); the consumer side waits explicitly, see hl_step_begin.
 __device__ __forceinline__ void hl_dma16(const void* gptr, uint32_t lds_off) {
-#ifdef GGD_HL_NOSTREAM   // timing experiments only (wrong results)
-  return;
-#endif
   asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(lds_off), "v"(gptr) : "memory");
 }
 // the workgroup's NW waves stream `bytes` (a multiple of 1024) from src to LDS offset dst
@@ -78,34 +75,8 @@ __device__ __forceinline__ void hl_stream(const unsigned char* __restrict__ src,
 // workgroup barrier: every wave's share of the layer's weights is in LDS, and every wave has finished reading the OTHER
 // buffer, which the caller now refills.
 __device__ __forceinline__ void hl_step_begin() {
-#ifndef GGD_HL_NOSTREAM
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#ifndef GGD_HL_NOBARRIER   // timing experiments only (wrong results)
   __syncthreads();
-#endif
-}
-
-// GELU at fp32 accuracy: x Phi(x), Phi(-|x|) = erfc(|x| / sqrt2) / 2 = 2^(P9(u)) / 2 with u = min(|x| / sqrt2, 4.3)
-// (P9: least-squares fit of log2 erfc on Chebyshev nodes of [0, 4.3]; beyond, Phi is 0 / 1 to 1e-9).  max |error| 6e-7.
-__device__ __forceinline__ float gelu_acc(float x) {
-#ifdef GGD_HL_NOGELU   // timing experiments only (wrong results)
-  return x;
-#endif
-  const float u = fminf(fabsf(x) * 0.70710678118654752f, 4.3f);
-  float p = 9.437868584e-07f;
-  p = __builtin_fmaf(p, u, -1.822167542e-05f);
-  p = __builtin_fmaf(p, u, 1.253326191e-04f);
-  p = __builtin_fmaf(p, u, -1.361948816e-04f);
-  p = __builtin_fmaf(p, u, -3.693860956e-03f);
-  p = __builtin_fmaf(p, u, 3.174497187e-02f);
-  p = __builtin_fmaf(p, u, -1.507675201e-01f);
-  p = __builtin_fmaf(p, u, -9.176738262e-01f);
-  p = __builtin_fmaf(p, u, -1.628001332e+00f);
-  p = __builtin_fmaf(p, u, 1.916012707e-06f);
-  const float h = 0.5f * __builtin_amdgcn_exp2f(p);     // Phi(-|x|)
-  const float phi = x < 0.0f ? h : 1.0f - h;
-  return x * phi;
 }
 
 // 8 fp32 values -> their bf16 hi and lo parts (the B-operand pieces of the next layer)
@@ -116,15 +87,17 @@ __device__ __forceinline__ void split8(const f4& a, const f4& b, bf16x8& hi, bf1
   lo = pack8(ra, rb);
 }
 
-// One hidden layer on split operands: acc[c][mt] = bias + W_lo x_hi + W_hi x_lo + W_hi x_hi for the wave's two 16-point
-// column tiles.  w: the layer's hi image, the lo image PART bytes behind it.
-template <int KB, int ROW, int PART>
+// One layer on split operands for the wave's two 16-point column tiles, MT feature tiles of 16 rows:
+//   acc[c][mt] = (BIAS ? bias : 0) + W_lo x_hi + W_hi x_lo + W_hi x_hi       (three MFMAs per fragment pair, small terms first)
+// forward: x = the activations, W a hidden layer (MT = 8, BIAS); backward: x = dz, W a transposed layer (dh = W^T dz, no bias).
+// w: the layer's hi image, the lo image PART bytes behind it.
+template <int MT, int KB, int ROW, int PART, bool BIAS>
 __device__ __forceinline__ void layer_mfma_hl(const unsigned char* __restrict__ w, const float* __restrict__ bias,
                                               const bf16x8 (&bhi)[2][4], const bf16x8 (&blo)[2][4], f4 (&acc)[2][8],
                                               int lane) {
   const int i = lane & 15, g = lane >> 4;
 #pragma unroll
-  for (int mt = 0; mt < 8; ++mt) {
+  for (int mt = 0; mt < MT; ++mt) {
     // (no look-ahead on the weight fragments here: hi + lo fragments of two tiles would not fit the 256 registers a wave
     // has at two waves per SIMD; the six MFMAs per fragment pair and the SIMD's other wave cover the LDS latency)
     bf16x8 ah[KB], al[KB];
@@ -134,10 +107,11 @@ __device__ __forceinline__ void layer_mfma_hl(const unsigned char* __restrict__ 
       ah[s] = *reinterpret_cast<const bf16x8*>(w + o);
       al[s] = *reinterpret_cast<const bf16x8*>(w + PART + o);
     }
-    const f4 bb = *reinterpret_cast<const f4*>(bias + 16 * mt + 4 * g);
+    f4 bb = {0, 0, 0, 0};
+    if (BIAS) bb = *reinterpret_cast<const f4*>(bias + 16 * mt + 4 * g);
     acc[0][mt] = bb; acc[1][mt] = bb;
 #pragma unroll
-    for (int s = 0; s < KB; ++s) {   // small terms first
+    for (int s = 0; s < KB; ++s) {
       acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[s], bhi[0][s], acc[0][mt], 0, 0, 0);
       acc[1][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[s], bhi[1][s], acc[1][mt], 0, 0, 0);
       acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], blo[0][s], acc[0][mt], 0, 0, 0);
@@ -152,26 +126,22 @@ __device__ __forceinline__ void layer_mfma_hl(const unsigned char* __restrict__ 
   }
 }
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-// fp32 -> fp16, saturating (a conversion past 65504 gives inf, and inf * 0 = NaN would reach the weight gradients)
-__device__ __forceinline__ _Float16 h16(float v) { return (_Float16)__builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f); }
-
-// z of the wave's tiles as fp16 pieces (blocked Z layout, see store_z: same positions, same 16-byte pieces).  The stores are
+// z of the wave's tiles as fp16 pieces (blocked Z layout, zpiece: the positions and 16-byte pieces of gelu_pack's stores).  The stores are
 // DEFERRED to the top of the next layer step: a step begins by waiting for everything the wave has outstanding (that is how
 // the LDS-direct weight loads are awaited: loads and stores share one counter and complete out of order with respect to each
 // other), and stores issued at the end of the previous step would put an HBM write round trip on that wait (measured: 23 k
 // cycles per step with them, against ~8 k of MFMA + GELU work).  Issued right after the wait they have a whole step to land.
-__device__ __forceinline__ void pack_z16(const f4 (&acc)[2][8], f16x8 (&zr)[2][4]) {
+__device__ __forceinline__ void pack_z16(const f4 (&acc)[2][8], h16x8 (&zr)[2][4]) {
 #pragma unroll
   for (int c = 0; c < 2; ++c)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const f4& a0 = acc[c][2 * k];
       const f4& a1 = acc[c][2 * k + 1];
-      zr[c][k] = (f16x8){h16(a0[0]), h16(a0[1]), h16(a0[2]), h16(a0[3]), h16(a1[0]), h16(a1[1]), h16(a1[2]), h16(a1[3])};
+      zr[c][k] = (h16x8){h16(a0[0]), h16(a0[1]), h16(a0[2]), h16(a0[3]), h16(a1[0]), h16(a1[1]), h16(a1[2]), h16(a1[3])};
     }
 }
-__device__ __forceinline__ void flush_z16(_Float16* __restrict__ zl, const f16x8 (&zr)[2][4], int64_t p0, int64_t cend,
+__device__ __forceinline__ void flush_z16(_Float16* __restrict__ zl, const h16x8 (&zr)[2][4], int64_t p0, int64_t cend,
                                           int lane) {
   const int j = lane & 15, g = lane >> 4;
 #pragma unroll
@@ -179,7 +149,7 @@ __device__ __forceinline__ void flush_z16(_Float16* __restrict__ zl, const f16x8
     const int64_t pt = p0 + 16 * c + j;
     if (pt >= cend) continue;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) *reinterpret_cast<f16x8*>(zl + zpiece(pt, k, g)) = zr[c][k];
+    for (int k = 0; k < 4; ++k) *reinterpret_cast<h16x8*>(zl + zpiece(pt, k, g)) = zr[c][k];
   }
 }
 
@@ -239,7 +209,7 @@ __global__ __launch_bounds__(FWD_THREADS) void decoder_forward_hl_kernel(const f
   for (int b = 0; b < nbatch; ++b) {
     const int64_t p0 = cbeg + (int64_t)b * BATCH + (int64_t)wv * SLAB;
     for (int head = 0; head < NHEAD; ++head) {
-      const int n_extra = head == 0 ? 0 : (head == 1 ? 3 : (head == 2 ? 4 : (head == 3 ? 8 : 11)));
+      const int n_extra = GGD_HEAD_A0(head);   // = head_a0(head), expanded in place
       const unsigned char* hw = packed + (size_t)head * HLF_HEAD;
       const float* b1 = biases + head * HL_NBIAS;
       const float* b2 = b1 + HID;
@@ -270,26 +240,26 @@ __global__ __launch_bounds__(FWD_THREADS) void decoder_forward_hl_kernel(const f
         bhi[c][2] = bhi[c][1]; bhi[c][3] = bhi[c][1]; blo[c][2] = blo[c][1]; blo[c][3] = blo[c][1];   // unused k blocks
       }
       f4 acc[2][8];
-      f16x8 zr[2][4];      // the layer's z as fp16, stored at the top of the NEXT step (see pack_z16)
+      h16x8 zr[2][4];      // the layer's z as fp16, stored at the top of the NEXT step (see pack_z16)
       _Float16* zh = reinterpret_cast<_Float16*>(zbuf) + (size_t)(head * 3) * zlayer_elems(N);
       // ---- layer 1 (buffer 0); layer 2 streams into buffer 1
       hl_step_begin();
       hl_stream<FWD_WAVES>(hw + HLF_L2, lds1, 2 * HL_P2, wv, lane);
-      layer_mfma_hl<2, ROW1, HL_P1>(buf0, b1, bhi, blo, acc, lane);
+      layer_mfma_hl<8, 2, ROW1, HL_P1, true>(buf0, b1, bhi, blo, acc, lane);
       if (STORE_Z) pack_z16(acc, zr);
       gelu_split(acc, bhi, blo, phi_tbl);
       // ---- layer 2 (buffer 1); layer 3 streams into buffer 0
       hl_step_begin();
       hl_stream<FWD_WAVES>(hw + HLF_L3, lds0, 2 * HL_P2, wv, lane);
       if (STORE_Z) flush_z16(zh, zr, p0, cend, lane);
-      layer_mfma_hl<4, ROW2, HL_P2>(buf1, b2, bhi, blo, acc, lane);
+      layer_mfma_hl<8, 4, ROW2, HL_P2, true>(buf1, b2, bhi, blo, acc, lane);
       if (STORE_Z) pack_z16(acc, zr);
       gelu_split(acc, bhi, blo, phi_tbl);
       // ---- layer 3 (buffer 0); layer 4 streams into buffer 1
       hl_step_begin();
       hl_stream<FWD_WAVES>(hw + HLF_L4, lds1, 2 * HL_P4, wv, lane);
       if (STORE_Z) flush_z16(zh + zlayer_elems(N), zr, p0, cend, lane);
-      layer_mfma_hl<4, ROW2, HL_P2>(buf0, b3, bhi, blo, acc, lane);
+      layer_mfma_hl<8, 4, ROW2, HL_P2, true>(buf0, b3, bhi, blo, acc, lane);
       if (STORE_Z) pack_z16(acc, zr);
       gelu_split(acc, bhi, blo, phi_tbl);
       // ---- output layer (buffer 1): one feature tile; the next step's layer 1 (next head, or head 0 of the next batch)
@@ -349,62 +319,11 @@ __global__ __launch_bounds__(FWD_THREADS) void decoder_forward_hl_kernel(const f
   }
 }
 
-// gelu'(x) = Phi(x) + x phi(x) at fp32 accuracy.  Both terms share ONE exponential: with E = exp(-x^2 / 2),
-// phi = E / sqrt(2 pi) and Phi(-|x|) = erfc(|x| / sqrt2) / 2 = E * (a1 t + ... + a5 t^5) / 2, t = 1 / (1 + p |x| / sqrt2)
-// (Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7 on erfc): one v_rcp_f32, one v_exp_f32 and a degree-5 Horner instead of
-// the two exponentials and the degree-9 polynomial of gelu_acc's form (22 issue units instead of 27).  max |error| 3e-7.
-__device__ __forceinline__ float gelu_grad_acc(float x) {
-#ifdef GGD_HL_NOGELU   // timing experiments only (wrong results)
-  return x;
-#endif
-  const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(fabsf(x), 0.3275911f * 0.70710678118654752f, 1.0f));
-  const float E = __builtin_amdgcn_exp2f((x * x) * -0.72134752044448170f);
-  float q = 0.5f * 1.061405429f;
-  q = __builtin_fmaf(q, t, 0.5f * -1.453152027f);
-  q = __builtin_fmaf(q, t, 0.5f * 1.421413741f);
-  q = __builtin_fmaf(q, t, 0.5f * -0.284496736f);
-  q = __builtin_fmaf(q, t, 0.5f * 0.254829592f);
-  const float h = (q * t) * E;                          // Phi(-|x|)
-  const float Phi = x < 0.0f ? h : 1.0f - h;
-  return __builtin_fmaf(x * 0.3989422804014327f, E, Phi);
-}
-
-// dh = (W_hi + W_lo)^T (dz_hi + dz_lo) for the wave's tiles: three MFMAs per fragment pair
-template <int MT, int KB, int ROW, int PART>
-__device__ __forceinline__ void layer_mfma_t_hl(const unsigned char* __restrict__ w, const bf16x8 (&bhi)[2][4],
-                                                const bf16x8 (&blo)[2][4], f4 (&acc)[2][8], int lane) {
-  const int i = lane & 15, g = lane >> 4;
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    acc[0][mt] = (f4){0, 0, 0, 0}; acc[1][mt] = (f4){0, 0, 0, 0};
-    bf16x8 ah[KB], al[KB];
-#pragma unroll
-    for (int s = 0; s < KB; ++s) {
-      const int o = wslot<ROW>(16 * mt + i, g + 4 * s);
-      ah[s] = *reinterpret_cast<const bf16x8*>(w + o);
-      al[s] = *reinterpret_cast<const bf16x8*>(w + PART + o);
-    }
-#pragma unroll
-    for (int s = 0; s < KB; ++s) {
-      acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[s], bhi[0][s], acc[0][mt], 0, 0, 0);
-      acc[1][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[s], bhi[1][s], acc[1][mt], 0, 0, 0);
-      acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], blo[0][s], acc[0][mt], 0, 0, 0);
-      acc[1][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], blo[1][s], acc[1][mt], 0, 0, 0);
-    }
-#pragma unroll
-    for (int s = 0; s < KB; ++s) {
-      acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], bhi[0][s], acc[0][mt], 0, 0, 0);
-      acc[1][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[s], bhi[1][s], acc[1][mt], 0, 0, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
 // dz = dh * gelu'(z) for the wave's tiles at fp32 accuracy (z: the fp16 plane, raw 16-byte pieces as load_z_tiles returns
-// them), split: its hi / lo parts are the next layer's B operands AND the two 16-byte Z-layout pieces of dz, which
-// store_dz_hl writes at the top of the next step (deferred like the forward's z stores; no extra registers here).
+// them), split into hi / lo parts, the next layer's B operands; and dz * S as ONE fp16 plane (dzs), which flush_z16
+// writes at the top of the next step (deferred like the forward's z stores).
 __device__ __forceinline__ void gelu_bwd_split(const f4 (&dh)[2][8], const bf16x8 (&zraw)[2][4],
-                                               bf16x8 (&ohi)[2][4], bf16x8 (&olo)[2][4], f16x8 (&dzs)[2][4], float S,
+                                               bf16x8 (&ohi)[2][4], bf16x8 (&olo)[2][4], h16x8 (&dzs)[2][4], float S,
                                                uint32_t dg_lds) {
   float sc = (float)GT_N_BWD / 12.0f, hf = 0.5f * (float)GT_N_BWD, hi = (float)GT_N_BWD - 0.001f;
   asm volatile("" : "+v"(sc), "+v"(hf), "+v"(hi));
@@ -412,7 +331,7 @@ __device__ __forceinline__ void gelu_bwd_split(const f4 (&dh)[2][8], const bf16x
   for (int c = 0; c < 2; ++c) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      const f16x8 z8 = __builtin_bit_cast(f16x8, zraw[c][s]);
+      const h16x8 z8 = __builtin_bit_cast(h16x8, zraw[c][s]);
       f4 out2[2];
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2) {
@@ -422,22 +341,10 @@ __device__ __forceinline__ void gelu_bwd_split(const f4 (&dh)[2][8], const bf16x
         out2[h2] = (f4){d[0] * q0, d[1] * q1, d[2] * q2, d[3] * q3};
       }
       split8(out2[0], out2[1], ohi[c][s], olo[c][s]);
-      dzs[c][s] = (f16x8){h16(out2[0][0] * S), h16(out2[0][1] * S), h16(out2[0][2] * S), h16(out2[0][3] * S),
+      dzs[c][s] = (h16x8){h16(out2[0][0] * S), h16(out2[0][1] * S), h16(out2[0][2] * S), h16(out2[0][3] * S),
                           h16(out2[1][0] * S), h16(out2[1][1] * S), h16(out2[1][2] * S), h16(out2[1][3] * S)};
       __builtin_amdgcn_sched_barrier(0);
     }
-  }
-}
-// dz * S of the wave's tiles as ONE fp16 plane (blocked Z layout), stored at the top of the next step like the forward's z
-__device__ __forceinline__ void store_dz_hl(_Float16* __restrict__ dzp, const f16x8 (&dzs)[2][4], int64_t p0, int64_t cend,
-                                            int lane) {
-  const int j = lane & 15, g = lane >> 4;
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const int64_t pt = p0 + 16 * c + j;
-    if (pt >= cend) continue;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) *reinterpret_cast<f16x8*>(dzp + zpiece(pt, s, g)) = dzs[c][s];
   }
 }
 
@@ -471,8 +378,6 @@ __global__ __launch_bounds__(MLP_THREADS) void decoder_backward_hl_kernel(
   for (int b = 0; b < nbatch; ++b) {
     const int64_t p0 = cbeg + (int64_t)b * BATCH + (int64_t)wv * SLAB;
     for (int head = NHEAD - 1; head >= 0; --head) {
-      const int a0 = head == 0 ? 0 : (head == 1 ? 3 : (head == 2 ? 4 : (head == 3 ? 8 : 11)));  // first attrs slot
-      const int od = head == 1 ? 1 : (head == 2 ? 4 : 3);                                          // output width
       const unsigned char* hw = packed_t + (size_t)head * HLT_HEAD;
       const __bf16* z1 = zbuf + (size_t)(head * 3 + 0) * LS;
       const __bf16* z2 = zbuf + (size_t)(head * 3 + 1) * LS;
@@ -487,25 +392,7 @@ __global__ __launch_bounds__(MLP_THREADS) void decoder_backward_hl_kernel(
       for (int c = 0; c < 2; ++c) {
         const int64_t pt = p0 + 16 * c + j;
         f4 d = {0, 0, 0, 0};
-        if (g == 0 && pt < cend) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            if (e < od) {
-              float v = dattrs[pt * 16 + a0 + e];
-              if (head == 4) {
-                v *= 0.01f;                                   // xyz = head * 0.01 + position
-              } else {
-                v += dinfo[pt * 16 + 3 + a0 + e];             // + what the later heads sent back through `info`
-                if (head == 3) {                              // scale = -softplus(s + 5) - 2.5
-                  const float sp = -attrs[pt * 16 + a0 + e] - 2.5f;
-                  v *= -(1.0f - expf(-sp));                   // -sigmoid(s + 5) = -(1 - exp(-softplus))
-                }
-              }
-              d[e] = v;
-            }
-          }
-          *reinterpret_cast<f4*>(dout + ((size_t)head * N + pt) * 4) = d;
-        }
+        if (g == 0 && pt < cend) d = head_out_grad(head, pt, N, attrs, dattrs, dinfo, dout);
         const f4 z = {0, 0, 0, 0};
         split8(d, z, bhi[c][0], blo[c][0]);
         bhi[c][1] = bhi[c][0]; bhi[c][2] = bhi[c][0]; bhi[c][3] = bhi[c][0];  // unused k blocks
@@ -524,54 +411,38 @@ __global__ __launch_bounds__(MLP_THREADS) void decoder_backward_hl_kernel(
       }
       f4 acc[2][8];
       bf16x8 zv[2][4];   // raw 16-byte pieces of the fp16 z plane
-      f16x8 dzs[2][4];   // the layer's dz * S as fp16, stored at the top of the NEXT step
+      h16x8 dzs[2][4];   // the layer's dz * S as fp16, stored at the top of the NEXT step
       // ---- dh3 = W4^T dz4 (buffer 0); W3^T streams into buffer 1
       hl_step_begin();
       hl_stream<MLP_WAVES>(hw + HLT_L3, lds1, 2 * HL_P2, wv, lane);
       load_z_tiles(z3, p0, cend, lane, zv);
-      layer_mfma_t_hl<8, 1, ROW4T, HL_PT4>(buf0, bhi, blo, acc, lane);
+      layer_mfma_hl<8, 1, ROW4T, HL_PT4, false>(buf0, nullptr, bhi, blo, acc, lane);
       gelu_bwd_split(acc, zv, bhi, blo, dzs, S, dg_tbl);
       // ---- dh2 = W3^T dz3 (buffer 1); W2^T -> buffer 0
       hl_step_begin();
       hl_stream<MLP_WAVES>(hw + HLT_L2, lds0, 2 * HL_P2, wv, lane);
-      store_dz_hl(dz3, dzs, p0, cend, lane);
+      flush_z16(dz3, dzs, p0, cend, lane);
       load_z_tiles(z2, p0, cend, lane, zv);
-      layer_mfma_t_hl<8, 4, ROW2, HL_P2>(buf1, bhi, blo, acc, lane);
+      layer_mfma_hl<8, 4, ROW2, HL_P2, false>(buf1, nullptr, bhi, blo, acc, lane);
       gelu_bwd_split(acc, zv, bhi, blo, dzs, S, dg_tbl);
       // ---- dh1 = W2^T dz2 (buffer 0); W1^T -> buffer 1
       hl_step_begin();
       hl_stream<MLP_WAVES>(hw + HLT_L1, lds1, 2 * HL_PT1, wv, lane);
-      store_dz_hl(dz2, dzs, p0, cend, lane);
+      flush_z16(dz2, dzs, p0, cend, lane);
       load_z_tiles(z1, p0, cend, lane, zv);
-      layer_mfma_t_hl<8, 4, ROW2, HL_P2>(buf0, bhi, blo, acc, lane);
+      layer_mfma_hl<8, 4, ROW2, HL_P2, false>(buf0, nullptr, bhi, blo, acc, lane);
       gelu_bwd_split(acc, zv, bhi, blo, dzs, S, dg_tbl);
       // ---- dx (64 input rows) = W1^T dz1 (buffer 1); the next step's W4^T (head - 1, or the last head of the next batch)
       //      streams into buffer 0
       hl_step_begin();
-      store_dz_hl(dz1, dzs, p0, cend, lane);
+      flush_z16(dz1, dzs, p0, cend, lane);
       {
         const int nh = head > 0 ? head - 1 : NHEAD - 1;
         if (head > 0 || b + 1 < nbatch)
           hl_stream<MLP_WAVES>(packed_t + (size_t)nh * HLT_HEAD + HLT_L4, lds0, 2 * HL_PT4, wv, lane);
       }
-      layer_mfma_t_hl<4, 4, ROW2, HL_PT1>(buf1, bhi, blo, acc, lane);
-      // rows 0..31 -> plane features, rows 32..47 -> info slots (position + earlier heads' outputs)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const int64_t pt = p0 + 16 * c + j;
-        if (pt >= cend) continue;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-          f4* dst = reinterpret_cast<f4*>(dfeat + pt * 32 + 16 * mt + 4 * g);
-          f4 v = acc[c][mt];
-          if (head != NHEAD - 1) { const f4 o = *dst; v = v + o; }
-          *dst = v;
-        }
-        f4* di = reinterpret_cast<f4*>(dinfo + pt * 16 + 4 * g);
-        f4 v = acc[c][2];
-        if (head != NHEAD - 1) { const f4 o = *di; v = v + o; }
-        *di = v;
-      }
+      layer_mfma_hl<4, 4, ROW2, HL_PT1, false>(buf1, nullptr, bhi, blo, acc, lane);
+      add_input_grads(acc, head, p0, cend, lane, dfeat, dinfo);
     }
   }
 }
@@ -611,98 +482,4 @@ __global__ __launch_bounds__(WG_THREADS, 4) void decoder_wgrad_hl_kernel(
     case 3: wgrad_layer<3, true>(smem, N, pbeg, pend, dz + 2 * LS, z + LS, nullptr, nullptr, nullptr, nullptr, out + WG_OFF_W3, out + WG_OFF_B3, ks, km, phi_lin); break;
     default: wgrad_layer<4, true>(smem, N, pbeg, pend, nullptr, z + 2 * LS, dout_h, nullptr, nullptr, nullptr, out + WG_OFF_W4, out + WG_OFF_B4, ks, km, phi_lin); break;
   }
-}
-
-// ---- weight images of the split form, built on the device (see ggd_mlp_pack.inc for the row format) -----------------------
-// forward : per head [L1 hi | L1 lo | L2 hi | L2 lo | L3 hi | L3 lo | L4 hi | L4 lo | biases]
-// backward: per head [W4^T hi | lo | W3^T hi | lo | W2^T hi | lo | W1^T hi | lo]
-constexpr int HLPK_FWD = HLF_B / 2;        // bf16 elements of one head's forward image
-constexpr int HLPK_T = HLT_HEAD / 2;
-constexpr int HLPK_PER_HEAD = HLPK_FWD + HL_NBIAS + HLPK_T;
-
-__device__ __forceinline__ __bf16 hl_part(float v, bool lo) {
-  const __bf16 h = (__bf16)v;
-  return lo ? (__bf16)(v - (float)h) : h;
-}
-
-__global__ __launch_bounds__(256) void decoder_pack_hl_kernel(ggd_pack_ptrs ptrs, unsigned char* __restrict__ packed,
-                                                              unsigned char* __restrict__ packed_t) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= NHEAD * HLPK_PER_HEAD) return;
-  const int head = t / HLPK_PER_HEAD;
-  int e = t - head * HLPK_PER_HEAD;
-  const int in_dim = 35 + (head == 0 ? 0 : (head == 1 ? 3 : (head == 2 ? 4 : (head == 3 ? 8 : 11))));
-  const int out_dim = head == 0 ? 3 : (head == 1 ? 1 : (head == 2 ? 4 : 3));
-  const float* const* P = ptrs.p + head * 8;
-  const float *W1 = P[0], *W2 = P[2], *W3 = P[4], *W4 = P[6];
-  // e enumerates LOGICAL elements (part, row, position); the destination is the swizzled slot of that row
-  if (e < HLPK_FWD) {
-    __bf16* img = reinterpret_cast<__bf16*>(packed + (size_t)head * HLF_HEAD);
-    float v = 0.0f;
-    bool lo = false;
-    int dst;
-    if (e < HLF_L2 / 2) {                                   // layer 1: two parts of [128][64]
-      lo = e >= HL_P1 / 2;
-      const int q = e - (lo ? HL_P1 / 2 : 0);
-      const int r = q / 64, c = q - 64 * r;
-      const int k = pack_perm_col(c);
-      if (k < in_dim) v = W1[r * in_dim + k];
-      dst = HLF_L1 / 2 + (lo ? HL_P1 / 2 : 0) + pack_phys(r, c, 64);
-    } else if (e < HLF_L4 / 2) {                            // layers 2, 3: two parts of [128][128] each
-      const bool third = e >= HLF_L3 / 2;
-      int q = e - (third ? HLF_L3 : HLF_L2) / 2;
-      lo = q >= HL_P2 / 2;
-      q -= lo ? HL_P2 / 2 : 0;
-      const int r = q / 128, c = q - 128 * r;
-      v = (third ? W3 : W2)[r * HID + pack_perm_col(c)];
-      dst = (third ? HLF_L3 : HLF_L2) / 2 + (lo ? HL_P2 / 2 : 0) + pack_phys(r, c, 128);
-    } else {                                                // layer 4: two parts of [16][128]
-      int q = e - HLF_L4 / 2;
-      lo = q >= HL_P4 / 2;
-      q -= lo ? HL_P4 / 2 : 0;
-      const int r = q / 128, c = q - 128 * r;
-      if (r < out_dim) v = W4[r * HID + pack_perm_col(c)];
-      dst = HLF_L4 / 2 + (lo ? HL_P4 / 2 : 0) + pack_phys(r, c, 128);
-    }
-    img[dst] = hl_part(v, lo);
-    return;
-  }
-  e -= HLPK_FWD;
-  if (e < HL_NBIAS) {
-    float* dst = reinterpret_cast<float*>(packed + (size_t)head * HLF_HEAD + HLF_B) + e;
-    float v = 0.0f;
-    if (e < 3 * HID) v = P[1 + 2 * (e / HID)][e % HID];
-    else if (e - 3 * HID < out_dim) v = P[7][e - 3 * HID];
-    *dst = v;
-    return;
-  }
-  e -= HL_NBIAS;
-  if (!packed_t) return;
-  __bf16* img = reinterpret_cast<__bf16*>(packed_t + (size_t)head * HLT_HEAD);
-  float v = 0.0f;
-  bool lo = false;
-  int dst;
-  if (e < HLT_L3 / 2) {                                     // W4^T: two parts of [128][40] (padded rows, not swizzled)
-    lo = e >= HL_PT4 / 2;
-    const int q = e - (lo ? HL_PT4 / 2 : 0);
-    const int r = q / 40, c = q - 40 * r;
-    if (c < 32) { const int k = pack_perm_col(c); if (k < out_dim) v = W4[k * HID + r]; }
-    dst = e;
-  } else if (e < HLT_L1 / 2) {                              // W3^T, W2^T: two parts of [128][128] each
-    const bool second = e >= HLT_L2 / 2;
-    int q = e - (second ? HLT_L2 : HLT_L3) / 2;
-    lo = q >= HL_P2 / 2;
-    q -= lo ? HL_P2 / 2 : 0;
-    const int r = q / 128, c = q - 128 * r;
-    v = (second ? W2 : W3)[pack_perm_col(c) * HID + r];
-    dst = (second ? HLT_L2 : HLT_L3) / 2 + (lo ? HL_P2 / 2 : 0) + pack_phys(r, c, 128);
-  } else {                                                  // W1^T: two parts of [64][128]
-    int q = e - HLT_L1 / 2;
-    lo = q >= HL_PT1 / 2;
-    q -= lo ? HL_PT1 / 2 : 0;
-    const int r = q / 128, c = q - 128 * r;
-    if (r < in_dim) v = W1[pack_perm_col(c) * in_dim + r];
-    dst = HLT_L1 / 2 + (lo ? HL_PT1 / 2 : 0) + pack_phys(r, c, 128);
-  }
-  img[dst] = hl_part(v, lo);
 }

@@ -56,11 +56,9 @@ __device__ __forceinline__ uint4 gelu_bf16x8(uint4 raw) {
 // z the fp16 plane, a = gelu(z) evaluated at fp32 accuracy, times 2^(ks[slab] - km), rounded to fp16; products on
 // v_mfma_f32_16x16x32_f16; sums scaled by 2^(km - 4).
 constexpr int HL_KNONE = -(1 << 30);   // "this slab has no gradient at this head" / "no slab has"
-typedef _Float16 wg_f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ _Float16 wg_h16(float v) { return (_Float16)__builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f); }
-__device__ __forceinline__ wg_f16x8 wg_pack8h(const f4& a, const f4& b, float k) {
-  return (wg_f16x8){wg_h16(a[0] * k), wg_h16(a[1] * k), wg_h16(a[2] * k), wg_h16(a[3] * k),
-                    wg_h16(b[0] * k), wg_h16(b[1] * k), wg_h16(b[2] * k), wg_h16(b[3] * k)};
+__device__ __forceinline__ h16x8 wg_pack8h(const f4& a, const f4& b, float k) {
+  return (h16x8){h16(a[0] * k), h16(a[1] * k), h16(a[2] * k), h16(a[3] * k),
+                    h16(b[0] * k), h16(b[1] * k), h16(b[2] * k), h16(b[3] * k)};
 }
 template <int LAYER, bool F16 = false>
 __device__ __forceinline__ void wgrad_layer(unsigned char* smem, int N, int64_t pbeg, int64_t pend,
@@ -97,7 +95,7 @@ __device__ __forceinline__ void wgrad_layer(unsigned char* smem, int N, int64_t 
   for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
   auto mma = [&](const bf16x8& a, const bf16x8& b, const f4& c) {
     if constexpr (F16)
-      return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wg_f16x8, a), __builtin_bit_cast(wg_f16x8, b), c, 0, 0, 0);
+      return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
     else
       return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
   };
@@ -179,11 +177,11 @@ __device__ __forceinline__ void wgrad_layer(unsigned char* smem, int N, int64_t 
           if constexpr (F16) v = __builtin_bit_cast(uint4, wg_pack8h(rf[t][0], rf[t][1], fB(rk[t])));
           else v = __builtin_bit_cast(uint4, pack8(rf[t][0], rf[t][1]));
         } else if constexpr (F16) {
-          const wg_f16x8 z = __builtin_bit_cast(wg_f16x8, rb[t]);
-          wg_f16x8 a;
+          const h16x8 z = __builtin_bit_cast(h16x8, rb[t]);
+          h16x8 a;
           const float fk = fB(rk[t]);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) { const float x = (float)z[e]; a[e] = wg_h16((x * gt_lin<GT_N_WG>(phi_lin, x)) * fk); }
+          for (int e = 0; e < 8; ++e) { const float x = (float)z[e]; a[e] = h16((x * gt_lin<GT_N_WG>(phi_lin, x)) * fk); }
           v = __builtin_bit_cast(uint4, a);
         } else {
           v = gelu_bf16x8(rb[t]);
@@ -220,7 +218,7 @@ __device__ __forceinline__ void wgrad_layer(unsigned char* smem, int N, int64_t 
       bf16x8 fone = ones;
       if constexpr (F16) {
         const _Float16 f1 = (_Float16)fB(kcur[kb]);
-        wg_f16x8 o;
+        h16x8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = f1;
         fone = __builtin_bit_cast(bf16x8, o);

@@ -1,8 +1,9 @@
-"""Inference-time fused decoder: tri-plane gather + the 5 chained MLP heads as ONE MFMA kernel with 16-bit operands
+"""Fused decoder: tri-plane gather + the 5 chained MLP heads as ONE MFMA kernel with 16-bit operands
 (csrc/ggd_mlp.hip; SURVEY.md section 8f row 1, BASELINE config 3).
 
-`FusedDecoder(decoder)` wraps a `SequentialDecoderReverse` (same parameters; call `.repack()` after they change) and
-returns the same namespace (xyz, scale, rotation, opacity, color).  No autograd: training keeps the PyTorch modules.
+`FusedDecoder(decoder)` (inference, no autograd) wraps a `SequentialDecoderReverse` (same parameters; call `.repack()` after
+they change) and returns the same namespace (xyz, scale, rotation, opacity, color).  `FusedTrainDecoder` is the training
+front-end: the same forward with the pre-activations kept, and `FusedDecoderFn`'s backward and weight-gradient kernels.
 Numerics of the forward: weights and activations are rounded to f16 (11 significant bits; inputs and weights clamped to
 +-65504) at every layer input, accumulation and bias in fp32, GELU as a degree-6 polynomial in packed f16 (<= 1.7e-3, mean
 5e-5: scripts/gelu_f16_fit.py).  The training tier named "bf16" runs this forward; its backward kernels keep bf16 operands
@@ -30,7 +31,13 @@ def _permute_blocks(w: torch.Tensor) -> torch.Tensor:
     return w[:, idx]
 
 
-_IN_FEATURES = (35, 38, 39, 43, 46)   # colour, opacity, rotation, scale, xyz: 32 plane channels + xyz + the earlier heads
+# THE HEAD CHAIN (csrc/ggd_mlp.hip: head_a0 / head_od): colour, opacity, rotation, scale, xyz; head h writes _OUT_DIM[h] values at
+# attrs column _N_EXTRA[h] and sees the _N_EXTRA[h] columns in front of it behind the 32 plane channels and the position
+_HEADS = ("color_decoder", "opacity_decoder", "rotation_decoder", "scale_decoder", "xyz_decoder")
+_OUT_DIM = (3, 1, 4, 3, 3)
+_N_EXTRA = tuple(sum(_OUT_DIM[:h]) for h in range(5))   # 0, 3, 4, 8, 11: chained inputs of each head (outputs of the earlier heads)
+_IN_FEATURES = tuple(32 + 3 + n for n in _N_EXTRA)      # 35, 38, 39, 43, 46
+ROW4T = 32 + 8
 
 
 def _check_decoder(decoder) -> None:
@@ -43,8 +50,7 @@ def _check_decoder(decoder) -> None:
                         "use the PyTorch module for the other decoder types")
     if getattr(decoder, "use_xyz_embedding", False):
         raise ValueError("the fused decoder kernels do not implement use_xyz_embedding; use the PyTorch module")
-    got = tuple(getattr(decoder, n).backbone[0].in_features for n in
-                ("color_decoder", "opacity_decoder", "rotation_decoder", "scale_decoder", "xyz_decoder"))
+    got = tuple(getattr(decoder, n).backbone[0].in_features for n in _HEADS)
     if got != _IN_FEATURES:
         raise ValueError(f"fused decoder: first-layer widths {got} are not SequentialDecoderReverse's {_IN_FEATURES} "
                          "(32 plane channels, 3-D positions)")
@@ -63,45 +69,6 @@ def _swizzle_rows(wp: torch.Tensor) -> torch.Tensor:
     return out.view(rows, K)
 
 
-def pack_weights(decoder: SequentialDecoderReverse) -> torch.Tensor:
-    """-> uint8 tensor of ggd_decoder_packed_bytes(): per head [W1 128x64 | W2 128x128 | W3 128x128 | W4 16x128] f16 (clamped
-    to +-65504, slots swizzled), then b1 b2 b3 [128] and b4 [16] fp32; W1 .. W3 and b1 .. b3 halved."""
-    _check_decoder(decoder)
-    dev = next(decoder.parameters()).device
-    chunks = []
-    for head in (decoder.color_decoder, decoder.opacity_decoder, decoder.rotation_decoder, decoder.scale_decoder,
-                 decoder.xyz_decoder):
-        l1, l2, l3, l4 = head.backbone[0], head.backbone[2], head.backbone[4], head.backbone[6]
-        if l1.out_features != HID or l1.in_features < 35 or l1.in_features > 32 + 16 or l4.out_features > 16:
-            raise ValueError("fused decoder supports hidden_dim 128, 32 plane channels, <= 13 chained inputs")
-        w1 = torch.zeros(HID, 64, device=dev)
-        w1[:, :l1.in_features] = l1.weight.detach().float()        # cols 0..31 planes, 32.. = info slots
-        w4 = torch.zeros(16, HID, device=dev)
-        w4[:l4.out_features] = l4.weight.detach().float()
-        b4 = torch.zeros(16, device=dev)
-        b4[:l4.out_features] = l4.bias.detach().float()
-        rows = []
-        # the hidden layers are halved (exact): the forward's accumulators hold z / 2, the form its f16 GELU starts from
-        for w, row in ((0.5 * w1, ROW1), (0.5 * l2.weight.detach().float(), ROW2), (0.5 * l3.weight.detach().float(), ROW2),
-                       (w4, ROW2)):
-            assert row == w.shape[1]
-            wp = _swizzle_rows(_permute_blocks(w))
-            rows.append(wp.clamp(-65504.0, 65504.0).to(torch.float16).contiguous().view(torch.uint8).reshape(-1))
-        biases = torch.cat([0.5 * l1.bias.detach().float(), 0.5 * l2.bias.detach().float(), 0.5 * l3.bias.detach().float(), b4])
-        chunks += rows + [biases.contiguous().view(torch.uint8).reshape(-1)]
-    packed = torch.cat(chunks).contiguous()
-    expect = _capi.load().ggd_decoder_packed_bytes()
-    if packed.numel() != expect:
-        raise RuntimeError(f"packed decoder image is {packed.numel()} bytes, library expects {expect}")
-    return packed
-
-
-_HEADS = ("color_decoder", "opacity_decoder", "rotation_decoder", "scale_decoder", "xyz_decoder")
-_N_EXTRA = (0, 3, 4, 8, 11)   # chained inputs of each head (outputs of the earlier heads)
-_OUT_DIM = (3, 1, 4, 3, 3)
-ROW4T = 32 + 8
-
-
 def _head_tensors(decoder):
     """[(W1,b1,W2,b2,W3,b3,W4,b4)] * 5 in head order."""
     _check_decoder(decoder)
@@ -110,6 +77,30 @@ def _head_tensors(decoder):
         bb = getattr(decoder, name).backbone
         out.append(tuple(t for k in (0, 2, 4, 6) for t in (bb[k].weight, bb[k].bias)))
     return out
+
+
+def pack_weights(decoder: SequentialDecoderReverse) -> torch.Tensor:
+    """-> uint8 tensor of ggd_decoder_packed_bytes(): per head [W1 128x64 | W2 128x128 | W3 128x128 | W4 16x128] f16 (clamped
+    to +-65504, slots swizzled), then b1 b2 b3 [128] and b4 [16] fp32; W1 .. W3 and b1 .. b3 halved."""
+    dev = next(decoder.parameters()).device
+    chunks = []
+    for (w1, b1, w2, b2, w3, b3, w4, b4) in _head_tensors(decoder):
+        if w1.shape[0] != HID:
+            raise ValueError("fused decoder supports hidden_dim 128")
+        w1f = torch.zeros(HID, 64, device=dev); w1f[:, :w1.shape[1]] = w1.detach().float()    # cols 0..31 planes, 32.. = info slots
+        w4f = torch.zeros(16, HID, device=dev); w4f[:w4.shape[0]] = w4.detach().float()
+        b4f = torch.zeros(16, device=dev); b4f[:b4.shape[0]] = b4.detach().float()
+        # the hidden layers are halved (exact): the forward's accumulators hold z / 2, the form its f16 GELU starts from
+        for w in (0.5 * w1f, 0.5 * w2.detach().float(), 0.5 * w3.detach().float(), w4f):
+            wp = _swizzle_rows(_permute_blocks(w))
+            chunks.append(wp.clamp(-65504.0, 65504.0).to(torch.float16).contiguous().view(torch.uint8).reshape(-1))
+        biases = torch.cat([0.5 * b1.detach().float(), 0.5 * b2.detach().float(), 0.5 * b3.detach().float(), b4f])
+        chunks.append(biases.contiguous().view(torch.uint8).reshape(-1))
+    packed = torch.cat(chunks).contiguous()
+    expect = _capi.load().ggd_decoder_packed_bytes()
+    if packed.numel() != expect:
+        raise RuntimeError(f"packed decoder image is {packed.numel()} bytes, library expects {expect}")
+    return packed
 
 
 def pack_weights_t(decoder: SequentialDecoderReverse) -> torch.Tensor:
@@ -134,20 +125,6 @@ def pack_weights_t(decoder: SequentialDecoderReverse) -> torch.Tensor:
     if packed.numel() != expect:
         raise RuntimeError(f"packed transposed image is {packed.numel()} bytes, library expects {expect}")
     return packed
-
-
-def _splitk_dw(dy: torch.Tensor, x: torch.Tensor, chunk: int = 4096) -> torch.Tensor:
-    """dW = dy^T x over N points ([N,out], [N,in] bf16) as a batched split-K product (keeps all CUs busy)."""
-    n = dy.shape[0]
-    main = (n // chunk) * chunk
-    dw = None
-    if main:
-        dw = torch.bmm(dy[:main].view(-1, chunk, dy.shape[1]).transpose(1, 2),
-                       x[:main].view(-1, chunk, x.shape[1])).float().sum(0)
-    if main < n:
-        tail = (dy[main:].t() @ x[main:]).float()
-        dw = tail if dw is None else dw + tail
-    return dw
 
 
 PRECISIONS = ("bf16", "fp32")

@@ -93,11 +93,17 @@ def r_f16(x):
     return _via(x.clamp(-65504.0, 65504.0), torch.float16)
 
 
-def r_hl(x):
-    """hi + lo bf16 (hl_part / split8 in ggd_mlp_hl.inc): hi = bf16(x), lo = bf16(x - hi), both from the fp32 value"""
+def split_hl(x):
+    """fp32 -> its (hi, lo) bf16 parts (split8 in ggd_mlp_hl.inc, the pack kernel's bf16 hi / lo formats): hi = bf16(x),
+    lo = bf16(x - hi), both from the fp32 value"""
     x32 = x.float()
-    hi = x32.bfloat16().float()
-    lo = (x32 - hi).bfloat16().float()
+    hi = x32.bfloat16()
+    return hi, (x32 - hi.float()).bfloat16()
+
+
+def r_hl(x):
+    """hi + lo bf16 (split_hl), summed"""
+    hi, lo = split_hl(x)
     return (hi.double() + lo.double()).to(x.dtype)
 
 
@@ -292,3 +298,33 @@ def colour_only(dattrs):
     d = torch.zeros_like(dattrs)
     d[:, 0:3] = dattrs[:, 0:3]
     return d
+
+
+# ---- the reference-precision tier's weight images (the 16-bit tier's host statement is fused_decoder.pack_weights / _t) ----------
+def pack_hl_host(mod):
+    """TEST-ONLY host statement of what ggd_decoder_pack_hl writes: (packed_hl, packed_t_hl) as uint8 tensors.  Rows are
+    permuted and swizzled exactly like the 16-bit images (fused_decoder._permute_blocks / _swizzle_rows); every matrix is two
+    bf16 images, hi then lo (split_hl).
+      forward, per head   : [L1 hi | L1 lo | L2 hi | L2 lo | L3 hi | L3 lo | L4 hi | L4 lo | b1 b2 b3 b4(16) fp32], nothing halved
+                            (L1 = W1 [128][64], K padded with zeros; L4 = W4 [16][128], rows padded with zeros)
+      transposed, per head: [W4^T hi | lo | W3^T hi | lo | W2^T hi | lo | W1^T hi | lo], W4^T [128][32 + 8] padded and not
+                            swizzled, W1^T [64][128]"""
+    from gaussian_gan_decoder_amd import fused_decoder as FD
+    p = module_params(mod, dtype=torch.float32)
+    dev = p[0].device
+    as_bytes = lambda t: t.contiguous().view(torch.uint8).reshape(-1)
+    fwd, bwd = [], []
+    for h in range(5):
+        w1, b1, w2, b2, w3, b3, w4, b4 = p[8 * h:8 * h + 8]
+        w1f = torch.zeros(128, 64, device=dev); w1f[:, :w1.shape[1]] = w1
+        w4f = torch.zeros(16, 128, device=dev); w4f[:w4.shape[0]] = w4
+        b4f = torch.zeros(16, device=dev); b4f[:b4.shape[0]] = b4
+        for w in (w1f, w2, w3, w4f):
+            fwd += [as_bytes(part) for part in split_hl(FD._swizzle_rows(FD._permute_blocks(w)))]
+        fwd.append(as_bytes(torch.cat([b1, b2, b3, b4f])))
+        w4t = torch.zeros(32, 128, device=dev); w4t[:w4.shape[0]] = w4
+        w4p = torch.zeros(128, FD.ROW4T, device=dev); w4p[:, :32] = FD._permute_blocks(w4t.t().contiguous())
+        bwd += [as_bytes(part) for part in split_hl(w4p)]
+        for w in (w3, w2, w1f):
+            bwd += [as_bytes(part) for part in split_hl(FD._swizzle_rows(FD._permute_blocks(w.t().contiguous())))]
+    return torch.cat(fwd), torch.cat(bwd)

@@ -269,6 +269,22 @@ def test_device_pack_matches_the_host_statement_of_the_format(native_lib):
     assert torch.equal(packed_t, pack_weights_t(dec))
 
 
+def test_device_pack_hl_matches_the_host_statement(native_lib):
+    """ggd_decoder_pack_hl == tests/_decoder_ref.pack_hl_host (torch ops: the host-side statement of the split hi / lo image
+    formats of the reference-precision tier), byte for byte."""
+    import _decoder_ref as R
+    from gaussian_gan_decoder_amd.fused_decoder import device_pack
+    dev = torch.device("cuda:0")
+    torch.manual_seed(5)
+    dec = SequentialDecoderReverse().to(dev)
+    for p in dec.parameters():
+        p.data = torch.randn_like(p) * 0.7
+    packed, packed_t = device_pack(dec, hl=True)
+    ref, ref_t = R.pack_hl_host(dec)
+    assert torch.equal(packed, ref)
+    assert torch.equal(packed_t, ref_t)
+
+
 def test_fused_train_decoder_follows_an_optimizer_step(native_lib):
     """torch's fused Adam updates parameters without bumping Tensor._version; the fused decoder must still decode with
     the new weights (it used to cache its weight images on the version counters and train a frozen decoder)."""
