@@ -12,20 +12,11 @@
 // scatter-add is one line-wide group of float atomics per texel (torch's NCHW grid_sampler_2d_backward issues one
 // scattered atomic per (point, channel): 9.6 ms per 5e5 points measured on MI355X; this kernel is HBM/L2 bound).
 #include "ggd_common.h"
+#include "ggd_planes.h"
 
 namespace {
 
 struct Tap { int idx[4]; float w[4]; };  // up to 4 texels (idx < 0: outside -> zero padding)
-
-// Is the tap at floor(i) + o (o = 0 / 1) inside [0, size)?  Tested on the FLOAT floor: for a coordinate beyond the int range
-// (+-1e30, +-inf) (int)floorf() saturates and x0 + 1 overflows, which the compiler may treat -- and for `x1 >= 0 && x1 < W`
-// did treat -- as inside.  The same decision as the integer test for every coordinate that fits an int; false for NaN.
-// Where this is false for such a coordinate the integers x0, x0 + 1 .. the callers derive are MEANINGLESS (the conversion and
-// the increment are undefined there, not merely saturated): use them only under this test, never in a range test of their own.
-__device__ __forceinline__ bool tap_inside(float f, int o, int size) {
-  const float t = f + (float)o;
-  return t >= 0.0f && t <= (float)(size - 1);
-}
 
 __device__ __forceinline__ Tap bilinear_taps(float u, float v, int H, int W) {
   // grid_sample, align_corners = False: pixel = ((g + 1) * size - 1) / 2
@@ -42,10 +33,6 @@ __device__ __forceinline__ Tap bilinear_taps(float u, float v, int H, int W) {
   t.idx[2] = (vx0 && vy1) ? y1 * W + x0 : -1;
   t.idx[3] = (vx1 && vy1) ? y1 * W + x1 : -1;
   return t;
-}
-
-__device__ __forceinline__ void plane_uv(int p, float x, float y, float z, float& u, float& v) {
-  if (p == 0) { u = x; v = y; } else if (p == 1) { u = x; v = z; } else { u = z; v = x; }
 }
 
 template <int C, bool BACKWARD>
@@ -86,13 +73,7 @@ __global__ __launch_bounds__(256) void triplane_kernel(const float* __restrict__
 // renderer.py:47-58; selected at main/decoder_models/sequential_decoder_reverse.py:42-50).  (u, v, w) index (W, H, D).
 // axes: 0 = EG3D plane axes (plane 2 -> (z, x, y)), 1 = PanoHead (plane 2 -> (y, z, x)); plane 0 -> (x, y, z),
 // plane 1 -> (x, z, y) in both.  Grids are channel-last [3][D][H][W][C]: lane = channel, one coalesced line per texel.
-__device__ __forceinline__ void grid_uvw(int axes, int p, float x, float y, float z, float& u, float& v, float& w) {
-  if (p == 0) { u = x; v = y; w = z; }
-  else if (p == 1) { u = x; v = z; w = y; }
-  else if (axes == 0) { u = z; v = x; w = y; }
-  else { u = y; v = z; w = x; }
-}
-
+// (grid_uvw: ggd_planes.h)
 template <int C, bool BACKWARD>
 __global__ __launch_bounds__(256) void trigrid_kernel(const float* __restrict__ grids_cl, float* __restrict__ dgrids_cl,
                                                       int D, int H, int W, int axes, const float* __restrict__ pos, int N,

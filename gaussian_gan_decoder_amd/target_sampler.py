@@ -40,3 +40,14 @@ def sample_surface_points(sigmas: torch.Tensor, level: float = 10.0, num_points:
                                            C.c_void_p(pos.data_ptr()) if num_points else None, C.c_void_p(nf.data_ptr()),
                                            C.c_void_p(tmp.data_ptr()), nbytes))
     return pos, nf
+
+
+def sample_target_points(planes_cl: torch.Tensor, weights, n: int = 128, level: float = 10.0, num_points: int = 500_000,
+                         surface_thickness: float = 0.1, seed: int = 0, cube_length=None, box_warp: float = 1.0,
+                         plane_axes: str = "eg3d", triplane_depth=None, lattice: str = "reference"):
+    """Feature planes -> surface points without leaving the device: density.density_grid (the teacher's sigma on the
+    reference's n^3 lattice, target_dataloader.py:134-169) -> sample_surface_points (:96-118,172-176).  planes_cl, weights,
+    cube_length .. lattice as density_grid takes them; returns what sample_surface_points returns."""
+    from .density import density_grid
+    sigmas = density_grid(planes_cl, weights, n, cube_length, box_warp, plane_axes, triplane_depth, lattice)
+    return sample_surface_points(sigmas, level, num_points, surface_thickness, seed)

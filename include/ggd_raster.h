@@ -553,6 +553,40 @@ int ggd_decoder_backward_wgrad_hl(ggd_ctx* ctx, void* stream, int32_t N, int32_t
                                   const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf, float* dout,
                                   float* dfeat, float* dinfo, const float* feat, const float* pos, float* wgrad);
 
+/*
+ * The teacher's density field sampled on the device: what G.sample_mixed evaluates every iteration of the reference's
+ * target loader (main/decoder_utils/target_dataloader.py:134-169) -- sample_from_planes, then OSGDecoder (mean over the
+ * three planes, 32 -> 64 softplus -> 1 + 32; eg3d / PanoHead training/triplane.py) -- in ONE launch and with no intermediate
+ * tensor (csrc/ggd_density.hip).  Per point:
+ *   f = the 32 features of ggd_planes_gather (same planes, C, D, H, W, axes, box_warp; no modulation)
+ *   h = softplus(w1 f + b1)            softplus(z) = z > 20 ? z : log1p(exp(z))
+ *   sigma = w2[0] . h + b2[0];   rgb = act(w2[1:33] h + b2[1:33])
+ * w1 [64][32], b1 [64], w2 [33][64], b2 [33]: the EFFECTIVE fp32 weights (FullyConnectedLayer's weight * weight_gain and
+ * bias * bias_gain already applied).  rgb_act: 0 sigmoid(x) * 1.002 - 0.001 (EG3D, PanoHead "sigmoid"), 1 leaky_relu(x, 0.2)
+ * * sqrt(2) (PanoHead "lrelu"), 2 none.  rgb [N][32], or NULL: sigma only -- the 32 rgb rows are then never read or computed,
+ * and sigma is bit-identical to that of a call with rgb.  C must be 32 (64 hidden units and 32 rgb channels are fixed):
+ * anything else is GGD_E_INVALID.  All arithmetic is fp32; no atomics: results are bit-identical from run to run.  A point
+ * with a non-finite coordinate has no taps on the planes that coordinate reaches (zero features there).
+ *
+ * ggd_density_points: explicit coordinates pos [N][3].
+ * ggd_density_grid:   the n^3 samples of the reference's lattice (main/marching_cube/sample.py:5-26, create_samples), generated
+ *   in registers; sigma [n^3] comes out flat in sample order = [x][y][z], z fastest -- what ggd_surface_sample reads.
+ *   lattice 0: the reference's arithmetic, op for op in fp32: t_z = i mod n, t_y = fmod(float(i) / n, n), t_x = fmod((float(i)
+ *   / n) / n, n) (un-floored: the y and x indices carry fractional parts and x, y reach past the box), coordinate =
+ *   fl(fl(t * voxel) + origin) with voxel = (float)(cube_length / (n - 1)) and origin = (float)(-cube_length / 2), both formed
+ *   in DOUBLE (hence the double argument).  lattice 1: the regular lattice (floored indices).  2 <= n <= 1024.
+ * ggd_density_lattice: the coordinates themselves, pos [n^3][3] (the reference's use_marching_cubes = False branch keeps
+ *   samples[sigmas > 10]); bit-identical to what ggd_density_grid samples.
+ */
+int ggd_density_points(ggd_ctx* ctx, void* stream, const float* grids_cl, int32_t C, int32_t D, int32_t H, int32_t W,
+                       int32_t axes, float box_warp, const float* w1, const float* b1, const float* w2, const float* b2,
+                       int32_t rgb_act, const float* pos, int32_t N, float* sigma, float* rgb /* NULL = skip */);
+int ggd_density_grid(ggd_ctx* ctx, void* stream, const float* grids_cl, int32_t C, int32_t D, int32_t H, int32_t W,
+                     int32_t axes, float box_warp, const float* w1, const float* b1, const float* w2, const float* b2,
+                     int32_t rgb_act, int32_t n, double cube_length, int32_t lattice, float* sigma,
+                     float* rgb /* NULL = skip */);
+int ggd_density_lattice(ggd_ctx* ctx, void* stream, int32_t n, double cube_length, int32_t lattice, float* pos);
+
 /* Per-stage device time (ms, hipEvent pairs on `stream`) of the most recent forward_geometry / forward_render /
  * backward call when profiling is on.  Stage names: ggd_stage_name(i), i in [0, ggd_stage_count()). */
 int ggd_set_profiling(ggd_ctx* ctx, int enabled);
