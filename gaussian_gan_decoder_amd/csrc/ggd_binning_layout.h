@@ -69,7 +69,8 @@ static inline size_t ggd_sort32_msd_table_bytes(int64_t n) {   // table[tile][bu
 
 // Fold block (words; described at ggd_fold, ggd_common.h):
 //   [REPS replicas of REP_STRIDE histogram words | 8 tickets | n_valid | flat | pad | OUTSIDE (word 16 behind the histograms, a
-//    line of its own) | pad to 64 | ROWTOT: REPS x 64 entries per tile row | status words of the 4 passes | level-1 status words]
+//    line of its own) | pad to 64 | ROWTOT: REPS x 64 entries per tile row | status words of the 4 passes | level-1 status words |
+//    ROWINST: REPS x 64 instances per tile row]
 constexpr int GGD_FOLD_REPS = 16;   // (32 / 16 / 8 replicas: 4114 / 4140 / 4150 frames per second at 1 M / 1024^2; 3907 workgroups over 8 would
                                     // keep one address busy 80 % of the kernel's time, 16 leaves a margin)
 constexpr int GGD_FOLD_REP_STRIDE = GGD_MSD_BINS + 256;   // ordinary frames: the four byte histograms [p * 256 + digit] in the first
@@ -85,7 +86,13 @@ static inline size_t ggd_fold_ctl_words(int64_t P) {   // + level-1 binning: one
   const int64_t chunks = (P + 1023) / 1024;
   return ggd_fold_l1_offset(P) + (size_t)(chunks + ((int64_t)1 << ggd_group_shift(chunks > 0 ? chunks : 1)) + 2) * 64;
 }
+// REPS x 64 words behind the level-1 status words: INSTANCES per tile row (the row's entries weighted by their width in tiles) --
+// the only cross-row quantity of the row binning's second level, which then needs no scan launch (rb_scatter2_kernel<true>).
+// Appended, so that every offset above keeps its value; ggd_fold_block_words is what a fold block holds in all.
+static inline size_t ggd_fold_rowinst_offset(int64_t P) { return ggd_fold_ctl_words(P); }
+static inline size_t ggd_fold_block_words(int64_t P) { return ggd_fold_rowinst_offset(P) + (size_t)GGD_FOLD_REPS * 64; }
 static inline uint32_t* ggd_fold_rowtot(uint32_t* fold_ctl) { return fold_ctl + GGD_FOLD_ROWTOT; }
+static inline uint32_t* ggd_fold_rowinst(uint32_t* fold_ctl, int64_t P) { return fold_ctl + ggd_fold_rowinst_offset(P); }
 static inline uint32_t* ggd_fold_l1_status(uint32_t* fold_ctl, int64_t P) { return fold_ctl + ggd_fold_l1_offset(P); }
 
 // The sort's control block in its three forms.  n_valid: kept keys (the element count of every pass after the first and of the
@@ -147,6 +154,13 @@ constexpr int RBW_TAB_ROWSTART = 0, RBW_TAB_ROWBLK = RBW_BINS + 1, RBW_TAB_ROWIN
 
 static inline bool rb_is_wide(int W, int H) { return (W + 15) / 16 > 64 || (H + 15) / 16 > 64; }
 static inline int rb_blocks1(int P) { return (P + RB_CHUNK - 1) / RB_CHUNK; }                      // level-1 workgroups
+// The scan-in-scatter form of level 2 (rb_scatter2_kernel<true>) has every workgroup of a tile row read the count rows of all of
+// the row's blocks: 256 bytes x (blocks of the row)^2 per row, a device-side figure.  The host only knows the launched blocks (one
+// per 1024 instances of CAPACITY; the live ones cover the row entries: 1200 of 5857 on the 1 M cube, 3200 of 16449 on the shell),
+// so the form is taken for capacities up to 2^24 instances -- what the 1 M shell needs (2^24 + 1) and no more.  Worst case
+// admitted: 2^24 one-tile-wide entries in ONE tile row, 16384 blocks, 16384^2 rows of 256 bytes = 69 GB of cache reads (reasoned, not
+// timed: DESIGN.md 6o); spread over the 64 rows, 1/64 of that.  Larger frames keep rb_scan2_kernel.
+constexpr uint32_t RB_SCAN_IN_SCATTER_MAX_BLOCKS = (1u << 24) / RB_CHUNK + 128;
 static inline uint32_t rb_blocks2(uint32_t cap, bool wide) {                                       // level-2 workgroups: a ragged
   return (cap + RB_CHUNK - 1) / RB_CHUNK + (wide ? (uint32_t)RBW_BINS : 64u);                      // last chunk per tile row
 }

@@ -1,9 +1,9 @@
 // ggd_capi.hip -- the C ABI declared in include/ggd_raster.h (host side: ctx, workspace, stage sequencing).
 //
 // A single-call frame on the tile-binning path (ggd_forward, ggd_forward_enqueue) is enqueued whole before the host knows
-// num_rendered -- binning_buf's capacity stands in for it -- in eight launches when the two-launch sort is planned:
+// num_rendered -- binning_buf's capacity stands in for it -- in seven launches when the two-launch sort is planned:
 //   geometry_enqueue  preprocess; with GGD_OPT_FOLD it also builds the depth sort's histograms (which ones: this frame's plan,
-//                     ggd_spec.h), step 1 of the offsets scan and the binning's per-row counts (ggd_fold)
+//                     ggd_spec.h), step 1 of the offsets scan and the binning's entries and instances per tile row (ggd_fold)
 //   render_enqueue    depth sort (two launches over the planned key window, or three / four onesweep passes), row / column binning,
 //                     blend; steps 2 and 3 of the scan ride on the sort's first and the binning's last launch
 //   collect           the ONE host wait: geometry_finish polls the pinned word (flags | tag | num_rendered) that scan step 2 stores
@@ -259,6 +259,7 @@ extern "C" int ggd_get_option(ggd_ctx* ctx, int option) {
   if (ctx && option == GGD_STAT_FLAT_STREAK) return ctx->spec.flat_streak;
   if (ctx && option == GGD_STAT_SORT_RERUNS) return (int)(ctx->spec.reruns & 0x7fffffffull);
   if (ctx && option == GGD_STAT_MSD_FRAMES) return (int)(ctx->spec.msd_frames & 0x7fffffffull);
+  if (ctx && option == GGD_STAT_SCAN_IN_SCATTER_FRAMES) return (int)(ctx->scan_in_scatter_frames & 0x7fffffffull);
   if (!ctx || option < 0 || option >= GGD_OPT_COUNT) return GGD_E_INVALID;
   return ctx->opt[option];
 }
@@ -331,7 +332,7 @@ static int fold_prepare(ggd_ctx* ctx, hipStream_t s, const ggd_params* prm, ggd_
   int rc = grow_buffers(ctx, {{(void**)&ctx->scan_sums, sizeof(uint32_t)}}, &ctx->scan_sums_cap, 5 * (size_t)nwg + 64,
                         5 * (size_t)(nwg + nwg / 2) + 64);
   if (rc != GGD_OK) return rc;
-  const size_t need = ggd_fold_ctl_words(prm->P);
+  const size_t need = ggd_fold_block_words(prm->P);   // (status words and the instances per tile row behind them included)
   const bool fresh = ctx->foldctl_cap < need;   // (grow-only; both blocks start clean)
   rc = grow_buffers(ctx, {{(void**)&ctx->foldctl[0], sizeof(uint32_t)}, {(void**)&ctx->foldctl[1], sizeof(uint32_t)}},
                     &ctx->foldctl_cap, need, need + need / 2, &s);
@@ -350,6 +351,7 @@ static int fold_prepare(ggd_ctx* ctx, hipStream_t s, const ggd_params* prm, ggd_
   fold->clear_words = (uint32_t)ctx->foldctl_dirty[oth];
   fold->wg_info = reinterpret_cast<uint4*>(ctx->scan_sums + (((size_t)nwg + 3) & ~(size_t)3));
   fold->rows = ((prm->width + 15) / 16 <= 64 && (prm->height + 15) / 16 <= 64) ? 1 : 0;
+  fold->rowinst = ggd_fold_rowinst(fold->ctl, prm->P);
   // the two-launch depth sort is decided HERE because it selects the histograms this launch builds
   const ggd_spec_plan plan = ctx->spec.plan(ctx->opt[GGD_OPT_FOLD], ctx->opt[GGD_OPT_MSD_SORT], ggd_sort32_msd_supported(prm->P));
   fold->msd = plan.msd ? 1 : 0;
@@ -565,9 +567,13 @@ static int sort_depth_and_bin_tiles(ggd_ctx* ctx, hipStream_t s, const ggd_param
   StageTimer t(ctx, ST_DUPLICATE, s);
   // the depth sort dropped the culled Gaussians (key 0xFFFFFFFF) and left the number of kept ones on the device
   const bool l1 = folded && (prm->width + 15) / 16 <= 64 && (prm->height + 15) / 16 <= 64;
-  return ggd_launch_rowbin(ctx, s, *prm, g.rect, va, n_vis_ptr, list, ranges, capacity, bin_tmp_ptr, bin_tmp, vb,
-                           flat_ptr, riding ? &pg : nullptr, l1 ? ggd_fold_rowtot(fold.ctl) : nullptr,
-                           l1 ? ggd_fold_l1_status(fold.ctl, prm->P) : nullptr);
+  bool scan_in_scatter = false;
+  rc = ggd_launch_rowbin(ctx, s, *prm, g.rect, va, n_vis_ptr, list, ranges, capacity, bin_tmp_ptr, bin_tmp, vb,
+                         flat_ptr, riding ? &pg : nullptr, l1 ? ggd_fold_rowtot(fold.ctl) : nullptr,
+                         l1 ? ggd_fold_l1_status(fold.ctl, prm->P) : nullptr, l1 ? ggd_fold_rowinst(fold.ctl, prm->P) : nullptr,
+                         &scan_in_scatter);
+  if (scan_in_scatter) ++ctx->scan_in_scatter_frames;
+  return rc;
 }
 
 // Binning path 2 (GGD_OPT_BINNING = 0, the debug taps, grids beyond 255 x 255 tiles, R = 0): one (tile | depth) key per instance,

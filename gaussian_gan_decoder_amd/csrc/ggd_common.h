@@ -68,6 +68,7 @@ struct ggd_ctx {
   size_t foldctl_dirty[2] = {0, 0}; // words of each block its last user may have written (what the next clear must cover)
   int fold_cur = 0;                 // block the next folding preprocess accumulates into (cleared by the previous one)
   bool fold_poisoned = false;       // a folding launch failed: nothing is known about the blocks -- clear both before the next use
+  unsigned long long scan_in_scatter_frames = 0;   // GGD_STAT_SCAN_IN_SCATTER_FRAMES
   ggd_spec spec;                    // cross-frame speculation policy: three sort passes / the two-launch sort (ggd_spec.h)
   ggd_frame frame;                  // the one frame in flight
   // ggd_forward_enqueue ... ggd_forward_collect: the frame whose num_rendered has not been collected yet
@@ -151,6 +152,7 @@ struct ggd_fold {
   uint32_t clear_words = 0;       // ... and how much of it the preprocess clears for the next frame
   uint4* wg_info = nullptr;       // [ceil(P / 256)] {sum of tiles_touched, kept keys, ~min kept key, max kept key}
   int rows = 0;                   // != 0: also count the Gaussians per tile row (the grid has <= 64 rows)
+  uint32_t* rowinst = nullptr;    // ... and the instances per tile row, in REPS x 64 words of ctl (ggd_fold_rowinst)
   int msd = 0;                    // != 0: histograms of the two-launch sort (1024 buckets of the key window, top byte) instead of the four bytes
   uint32_t msd_lo = 0;            // bucket of a kept key = min((key - msd_lo) >> msd_shift, 1023); a key for which the unclamped
   int msd_shift = GGD_MSD_SHIFT;  // value exceeds 1023 (below the window: the difference wraps) is counted in GGD_FOLD_OUTSIDE
@@ -246,11 +248,14 @@ static inline size_t ggd_rowbin_tmp_bytes(int P, uint32_t capacity, int W, int H
 int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const uint2* rect, const uint32_t* order,
                       const uint32_t* n_vis_ptr, uint32_t* list, uint32_t* ranges, uint32_t capacity, void* tmp,
                       size_t tmp_bytes, const uint32_t* order_alt = nullptr, const uint32_t* use_alt = nullptr,
-                      const ggd_scan_piggy* apply = nullptr, const uint32_t* fold_rowtot = nullptr, uint32_t* fold_status1 = nullptr);   // apply: step 3 of a riding scan, as appended workgroups of the
+                      const ggd_scan_piggy* apply = nullptr, const uint32_t* fold_rowtot = nullptr, uint32_t* fold_status1 = nullptr,
+                      const uint32_t* fold_rowinst = nullptr, bool* scan_in_scatter = nullptr);   // apply: step 3 of a riding scan, as appended workgroups of the
                                                                  // last (longest) binning launch
                       // *use_alt != 0 (device): the depth order is in order_alt (see ggd_launch_sort32_iota)
                       // fold_rowtot / fold_status1 (folded front end, grids of <= 64 x 64 tiles): the entries per tile row were
                       // counted by the preprocess kernel -- level 1 is ONE launch (count, look-back over the chunks, scatter)
+                      // fold_rowinst (with them): so were the instances per tile row -- level 2 is count + scatter, the scatter
+                      // workgroups form their tile starts themselves (no scan launch); *scan_in_scatter reports that this form ran
 int ggd_launch_ranges(ggd_ctx* ctx, hipStream_t s, const uint64_t* keys, int64_t n, uint32_t* ranges, int T);
 // out_depth / out_alpha non-null (both): the depth / alpha extension (blend_forward_kernel<..., AUX>), which also reads
 // depth_keys (the geometry buffer's: the fp32 bits of each Gaussian's view-space depth)

@@ -36,10 +36,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
   __shared__ uint32_t s_hist[FOLD ? GGD_FOLD_REP_STRIDE : 1];
   __shared__ uint32_t s_red[FOLD ? 17 : 1];   // per wave: sum of tiles, kept keys, ~min key, max key; [16]: keys outside the window
   __shared__ int s_rowdiff[FOLD ? 65 : 1];
+  __shared__ int s_rowwdiff[FOLD ? 65 : 1];   // the same difference array weighted by the rect's width: instances per tile row
   if constexpr (FOLD) {
     for (uint32_t z = blockIdx.x * 256 + threadIdx.x; z < fold.clear_words; z += gridDim.x * 256) fold.clear[z] = 0u;
     for (int b = threadIdx.x; b < GGD_FOLD_REP_STRIDE; b += 256) s_hist[b] = 0u;
-    if (threadIdx.x < 65) s_rowdiff[threadIdx.x] = 0;
+    if (threadIdx.x < 65) { s_rowdiff[threadIdx.x] = 0; s_rowwdiff[threadIdx.x] = 0; }
     if (threadIdx.x == 0) s_red[16] = 0u;
     __syncthreads();
   } else {
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
   const bool in_range = i < P;
   if (!FOLD && !in_range) return;
   int irad = 0;
-  uint32_t ntiles = 0, rect_rows = 0;   // rect_rows = miny | maxy << 16 of a visible Gaussian
+  uint32_t ntiles = 0, rect_rows = 0, rect_cols = 0;   // rect_rows = miny | maxy << 16, rect_cols = minx | maxx << 16 of a visible Gaussian
   bool visible = false;
   float depth = 0.0f;
   if (in_range) {
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
   tiles_touched[i] = ntiles;
   depth_keys[i] = visible ? __float_as_uint(t[2]) : 0xFFFFFFFFu;
   rect[i] = rect_out;
-  rect_rows = rect_out.y;
+  rect_rows = rect_out.y; rect_cols = rect_out.x;
   if (clamped) clamped[i] = (uint8_t)clamp_bits;
   if (visible) {
     float4* dst = reinterpret_cast<float4*>(splat + i);
@@ -265,10 +266,15 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
       }
     }
     // (d) grids of <= 64 tile rows: entries per row for the row binning's first level -- difference array over the rows the
-    //     Gaussian's rect covers, prefix over the lanes after the barrier
+    //     Gaussian's rect covers, prefix over the lanes after the barrier; and the INSTANCES per row (each entry weighted by the
+    //     rect's width) for its second level.  visible <=> rect area > 0 <=> level 1 emits the Gaussian's entries: the tile
+    //     starts behind a Gaussian counted here and not binned there would all shift.
     if (fold.rows && visible) {
+      const int w = (int)(rect_cols >> 16) - (int)(rect_cols & 0xffffu);
       atomicAdd(&s_rowdiff[rect_rows & 0xffffu], 1);
       atomicAdd(&s_rowdiff[rect_rows >> 16], -1);
+      atomicAdd(&s_rowwdiff[rect_rows & 0xffffu], w);
+      atomicAdd(&s_rowwdiff[rect_rows >> 16], -w);
     }
     uint32_t tsum = ntiles;
     // kept-key range of the frame (for the NEXT frames' two-launch-sort window): ~min and max, so that both reduce -- and
@@ -289,10 +295,16 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
       if (c) atomicAdd(&hist[b], c);
     }
     if (fold.rows && threadIdx.x < 64) {
-      int c = s_rowdiff[lane];
+      int c = s_rowdiff[lane], cw = s_rowwdiff[lane];
 #pragma unroll
-      for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(c, d, 64); if (lane >= d) c += o; }
-      if (c) atomicAdd(&fold.ctl[GGD_FOLD_ROWTOT + (blockIdx.x % GGD_FOLD_REPS) * 64 + lane], (uint32_t)c);
+      for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(c, d, 64), ow = __shfl_up(cw, d, 64);
+        if (lane >= d) { c += o; cw += ow; }
+      }
+      if (c) {   // (a row without entries has no instances)
+        atomicAdd(&fold.ctl[GGD_FOLD_ROWTOT + (blockIdx.x % GGD_FOLD_REPS) * 64 + lane], (uint32_t)c);
+        atomicAdd(&fold.rowinst[(blockIdx.x % GGD_FOLD_REPS) * 64 + lane], (uint32_t)cw);
+      }
     }
     if (threadIdx.x == 0) {
       const uint32_t kept = s_red[4] + s_red[5] + s_red[6] + s_red[7];

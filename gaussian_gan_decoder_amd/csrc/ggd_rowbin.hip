@@ -20,7 +20,9 @@
 //            A chunk's output is staged in LDS in (bin, item) order where it fits and leaves as lane-consecutive runs per bin;
 //            entries of one (chunk, bin) are consecutive in memory either way.
 // Folded front end (the preprocess kernel counted the entries per row): level 1 is ONE launch, rb_level1_kernel -- count from
-// the transposes, two-level look-back over the earlier chunks (ggd_lookback.inc), scatter.
+// the transposes, two-level look-back over the earlier chunks (ggd_lookback.inc), scatter.  It counted the instances per row too,
+// the only cross-row quantity of level 2: level 2 is then TWO launches, count and scatter -- every scatter workgroup sums the
+// count rows of its tile row's blocks itself (rb_scatter2_kernel<true>; no scan launch, no hand-off between workgroups).
 // Scratch and table layouts: ggd_binning_layout.h (ggd_rowbin_tmp, RB_TAB_* / RBW_TAB_*).
 #include "ggd_common.h"
 
@@ -260,7 +262,8 @@ __global__ __launch_bounds__(RB_THREADS) void rb_level1_kernel(const uint2* __re
                                                                int chunks_max, int gshift_max, uint32_t* __restrict__ tab,
                                                                uint2* __restrict__ ent, uint32_t ent_cap,
                                                                const uint32_t* __restrict__ order_alt,
-                                                               const uint32_t* __restrict__ use_alt) {
+                                                               const uint32_t* __restrict__ use_alt,
+                                                               const uint32_t* __restrict__ rowinst) {
   __shared__ uint4 slab[RB_WAVES][64];
   __shared__ uint32_t wcnt[RB_WAVES][64];
   __shared__ uint32_t s_base[64];
@@ -275,7 +278,15 @@ __global__ __launch_bounds__(RB_THREADS) void rb_level1_kernel(const uint2* __re
     for (int r = 0; r < GGD_FOLD_REPS; ++r) tot += rowtot[r * 64 + lane];
     const uint32_t inc = wave_inclusive_scan(tot);
     rowstart = inc - tot;
-    if (blockIdx.x == 0) rb_write_row_tables(tab, lane, tot, inc, ent_cap);
+    if (blockIdx.x == 0) {
+      rb_write_row_tables(tab, lane, tot, inc, ent_cap);
+      if (rowinst) {   // the instances per row, for rb_scatter2_kernel<true> (plain stores: the next launch reads them)
+        uint32_t inst = 0;
+#pragma unroll
+        for (int r = 0; r < GGD_FOLD_REPS; ++r) inst += rowinst[r * 64 + lane];
+        tab[RB_TAB_ROWINST + lane] = inst;
+      }
+    }
   }
   const uint32_t base = (uint32_t)blockIdx.x * RB_CHUNK;
   if (base >= n_vis) return;
@@ -439,38 +450,123 @@ __global__ __launch_bounds__(1024) void rb_scan2_kernel(uint32_t* __restrict__ c
   }
 }
 
+// SCAN (folded front end; no rb_scan2_kernel in front): counts2 holds rb_count2_kernel's RAW counts and tab[RB_TAB_ROWINST] the
+// instances per row as the preprocess kernel counted them.  The workgroup of block (row r, chunk c) forms its tile starts itself:
+//   start(r, col) = instances of the rows above r + exclusive prefix over the columns of total[col] + before[col],
+//   total / before = sum of counts2[b][col] over all blocks b of row r / over the blocks in front of chunk c
+// -- the count rows of the row's blocks (16 lanes a row of four columns each, rows dealt to the four waves, 8 independent 16-byte
+// loads a lane) are requested in the same round trip as the entries, and the waves' partial sums meet at the barrier behind
+// wave_cols.  Nothing is handed from one workgroup to another (the two forms that did, profiles/REJECTED.md round 5, doubled
+// rb_count2_kernel).
+// Chunk 0 of a row writes the row's ranges; a row without blocks has no workgroup, so workgroup z < gy writes the zero ranges of
+// row z when that row has none.  The reads grow with the square of a row's blocks: RB_SCAN_IN_SCATTER_MAX_BLOCKS.
+template <bool SCAN>
 __global__ __launch_bounds__(RB_THREADS) void rb_scatter2_kernel(const uint2* __restrict__ ent, uint32_t ent_cap,
                                                                  const uint32_t* __restrict__ tab,
                                                                  const uint32_t* __restrict__ prefix2,
                                                                  uint32_t* __restrict__ list, uint32_t capacity,
-                                                                 uint32_t main_blocks, ggd_scan_piggy pg) {
+                                                                 uint32_t main_blocks, ggd_scan_piggy pg, int gx, int gy,
+                                                                 uint32_t* __restrict__ ranges) {
   __shared__ uint4 slab[RB_WAVES][64];
   __shared__ uint32_t wcnt[RB_WAVES][64];
+  __shared__ __attribute__((aligned(16))) uint32_t wsum[SCAN ? 2 * RB_WAVES : 1][64];   // SCAN: the waves' partial {before, total} per column
   __shared__ uint32_t stage[RB_STAGE];
   if (blockIdx.x >= main_blocks) {   // appended workgroups: last step of the offsets scan (see ggd_scan_piggy)
     scan_apply_block(pg.in, pg.out, pg.n, pg.block_sums, (int)(blockIdx.x - main_blocks), stage, pg.sum_stride);
     return;
   }
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  uint32_t rowinst = 0, rowblks = 0;   // lane = row: its instances, its level-2 blocks
+  if constexpr (SCAN) {   // (first round trip, with rb_block_row_range's four loads)
+    rowinst = tab[RB_TAB_ROWINST + lane];
+    rowblks = tab[RB_TAB_ROWBLK + lane + 1] - tab[RB_TAB_ROWBLK + lane];
+    if ((int)blockIdx.x < gy && wv == 0) {
+      const uint32_t nb_z = (uint32_t)__shfl((int)rowblks, (int)blockIdx.x, 64);
+      if (nb_z == 0u && lane < gx) {
+        const int t = (int)blockIdx.x * gx + lane;
+        ranges[2 * t] = 0u;
+        ranges[2 * t + 1] = 0u;
+      }
+    }
+  }
   int row; uint32_t chunk, rbeg, rend;
   if (!rb_block_row_range(tab, blockIdx.x, ent_cap, row, chunk, rbeg, rend)) return;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const uint32_t wbeg = rbeg + chunk * RB_CHUNK + (uint32_t)wv * RB_WCHUNK;
   const int n_items = (int)min((uint32_t)RB_WCHUNK, rend > wbeg ? rend - wbeg : 0u);
   uint32_t iv[RB_IPL], pa[RB_IPL], pb[RB_IPL];
-  // second (and last) round trip: the entries, the tile starts and the chunk's prefixes, all requested before anything waits
+  // second (and last) round trip: the entries, the tile starts and the chunk's prefixes (SCAN: the count rows of the row's blocks),
+  // all requested before anything waits.  (A lane without an item reads the block's first entry, which exists: behind
+  // `if (i < n_items)` every one of the four loads was followed by its own wait -- four round trips instead of one.)
+  const uint32_t blkbeg = rbeg + chunk * RB_CHUNK;
+  uint2 raw[RB_IPL];
 #pragma unroll
   for (int q = 0; q < RB_IPL; ++q) {
     const int i = q * 64 + lane;
-    uint2 it = make_uint2(0, 0);
-    if (i < n_items) it = ent[wbeg + i];
-    pa[q] = it.x; pb[q] = 0;
-    iv[q] = it.y & 0xffffu;   // x0 | x1 << 8
+    raw[q] = ent[i < n_items ? wbeg + (uint32_t)i : blkbeg];
   }
-  const uint32_t gbase = tab[RB_TAB_TILESTART + row * 64 + lane] + prefix2[(size_t)blockIdx.x * 64 + lane];
+  uint32_t gbase = 0;
+  if constexpr (SCAN) {
+    const uint32_t blk0 = blockIdx.x - chunk;                                        // first block of the row
+    const uint32_t nblk_row = (uint32_t)__shfl((int)rowblks, row, 64);               // >= chunk + 1
+    // a lane takes four columns of a count row (one 16-byte load), a wave four rows per load instruction, the workgroup
+    // 16 x BATCH rows per round trip: the cube's 19 blocks a row, the shell's 50 - 130 are one batch
+    constexpr int BATCH = 8;
+    const uint32_t sub = (uint32_t)lane >> 4, c4 = ((uint32_t)lane & 15u) * 4u;
+    uint4 bef4 = make_uint4(0, 0, 0, 0), tot4 = make_uint4(0, 0, 0, 0);
+    for (uint32_t k0 = (uint32_t)wv * 4u; k0 < nblk_row; k0 += 4u * RB_WAVES * BATCH) {
+      uint4 v[BATCH];
+#pragma unroll
+      for (int j = 0; j < BATCH; ++j) {
+        const uint32_t k = k0 + sub + (uint32_t)(4 * RB_WAVES * j);
+        v[j] = make_uint4(0, 0, 0, 0);
+        if (k < nblk_row) v[j] = *reinterpret_cast<const uint4*>(prefix2 + (size_t)(blk0 + k) * 64 + c4);
+      }
+#pragma unroll
+      for (int j = 0; j < BATCH; ++j) {
+        const uint32_t k = k0 + sub + (uint32_t)(4 * RB_WAVES * j);
+        tot4.x += v[j].x; tot4.y += v[j].y; tot4.z += v[j].z; tot4.w += v[j].w;
+        const uint32_t m = k < chunk ? 0xffffffffu : 0u;
+        bef4.x += v[j].x & m; bef4.y += v[j].y & m; bef4.z += v[j].z & m; bef4.w += v[j].w & m;
+      }
+    }
+#pragma unroll
+    for (int d = 16; d <= 32; d <<= 1) {   // the wave's four row groups hold the same columns
+      tot4.x += (uint32_t)__shfl_xor((int)tot4.x, d, 64); tot4.y += (uint32_t)__shfl_xor((int)tot4.y, d, 64);
+      tot4.z += (uint32_t)__shfl_xor((int)tot4.z, d, 64); tot4.w += (uint32_t)__shfl_xor((int)tot4.w, d, 64);
+      bef4.x += (uint32_t)__shfl_xor((int)bef4.x, d, 64); bef4.y += (uint32_t)__shfl_xor((int)bef4.y, d, 64);
+      bef4.z += (uint32_t)__shfl_xor((int)bef4.z, d, 64); bef4.w += (uint32_t)__shfl_xor((int)bef4.w, d, 64);
+    }
+    if (lane < 16) {
+      *reinterpret_cast<uint4*>(&wsum[wv][c4]) = bef4;
+      *reinterpret_cast<uint4*>(&wsum[RB_WAVES + wv][c4]) = tot4;
+    }
+  } else {
+    gbase = tab[RB_TAB_TILESTART + row * 64 + lane] + prefix2[(size_t)blockIdx.x * 64 + lane];
+  }
+#pragma unroll
+  for (int q = 0; q < RB_IPL; ++q) {   // (the entries are looked at only here, behind the other requests)
+    const bool have = q * 64 + lane < n_items;
+    pa[q] = have ? raw[q].x : 0u; pb[q] = 0;
+    iv[q] = have ? raw[q].y & 0xffffu : 0u;   // x0 | x1 << 8
+  }
   uint64_t cols[RB_IPL];
   const uint32_t mine = wave_cols(iv, n_items, cols);
   wcnt[wv][lane] = mine;
   __syncthreads();
+  if constexpr (SCAN) {
+    uint32_t bef = 0, tot = 0;   // lane = column: instances of the row's earlier blocks / of the whole row
+#pragma unroll
+    for (int w = 0; w < RB_WAVES; ++w) { bef += wsum[w][lane]; tot += wsum[RB_WAVES + w][lane]; }
+    const uint32_t rinc = wave_inclusive_scan(rowinst);
+    const uint32_t rowbase = (uint32_t)__shfl((int)(rinc - rowinst), row, 64);       // instances of the rows above
+    const uint32_t start = rowbase + wave_inclusive_scan(tot) - tot;
+    gbase = start + bef;
+    if (chunk == 0u && wv == 0 && lane < gx) {
+      const int t = row * gx + lane;
+      ranges[2 * t] = tot ? start : 0u;
+      ranges[2 * t + 1] = tot ? start + tot : 0u;
+    }
+  }
   uint32_t before = 0, coltot = 0;   // lane = column: instances of the earlier waves / of the whole chunk
 #pragma unroll
   for (int w = 0; w < RB_WAVES; ++w) { const uint32_t c = wcnt[w][lane]; if (w < wv) before += c; coltot += c; }
@@ -513,7 +609,8 @@ bool ggd_rowbin_supported(int W, int H) { return W > 0 && H > 0 && (W + 15) / 16
 int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const uint2* rect, const uint32_t* order,
                       const uint32_t* n_vis_ptr, uint32_t* list, uint32_t* ranges, uint32_t capacity, void* tmp,
                       size_t tmp_bytes, const uint32_t* order_alt, const uint32_t* use_alt, const ggd_scan_piggy* apply,
-                      const uint32_t* fold_rowtot, uint32_t* fold_status1) {
+                      const uint32_t* fold_rowtot, uint32_t* fold_status1, const uint32_t* fold_rowinst, bool* scan_in_scatter) {
+  if (scan_in_scatter) *scan_in_scatter = false;
   if (!ggd_rowbin_supported(prm.width, prm.height)) return ggd_fail(ctx, GGD_E_INVALID, "tile grid too large for row binning");
   const ggd_rowbin_tmp lay = ggd_rowbin_layout(prm.P, capacity, prm.width, prm.height);
   if (tmp_bytes < lay.total) return ggd_fail(ctx, GGD_E_INVALID, "rowbin tmp too small");
@@ -544,9 +641,13 @@ int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const 
     GGD_HIP(hipGetLastError());
     return GGD_OK;
   }
+  // the front end counted the instances per row as well: level 2 needs no scan launch (up to the block count the quadratic
+  // reads of rb_scatter2_kernel<true> are admitted for)
+  const bool fused2 = fold_rowtot && fold_status1 && fold_rowinst && nb2 <= RB_SCAN_IN_SCATTER_MAX_BLOCKS;
   if (fold_rowtot && fold_status1) {   // (the group words were laid out for ggd_group_shift(chunks): ggd_fold_ctl_words)
     hipLaunchKernelGGL(rb_level1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, rect, order, n_vis_ptr, prm.P, fold_rowtot,
-                       fold_status1, nb1, ggd_group_shift(nb1), tab, ent, capacity, order_alt, use_alt);
+                       fold_status1, nb1, ggd_group_shift(nb1), tab, ent, capacity, order_alt, use_alt,
+                       fused2 ? fold_rowinst : nullptr);
   } else {
     hipLaunchKernelGGL(rb_count1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, prm.width, prm.height, rect, order,
                        n_vis_ptr, prm.P, packed, counts1, order_alt, use_alt);
@@ -555,9 +656,15 @@ int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const 
                        ent, capacity);
   }
   hipLaunchKernelGGL(rb_count2_kernel, dim3(nb2), dim3(RB_THREADS), 0, s, ent, capacity, tab, counts2);
-  hipLaunchKernelGGL(rb_scan2_kernel, dim3(gy), dim3(1024), 0, s, counts2, tab, gx, gy, ranges);
-  hipLaunchKernelGGL(rb_scatter2_kernel, dim3(nb2 + nb_apply), dim3(RB_THREADS), 0, s, ent, capacity, tab, counts2, list,
-                     capacity, nb2, pg);
+  if (fused2) {
+    hipLaunchKernelGGL(rb_scatter2_kernel<true>, dim3(nb2 + nb_apply), dim3(RB_THREADS), 0, s, ent, capacity, tab, counts2, list,
+                       capacity, nb2, pg, gx, gy, ranges);
+    if (scan_in_scatter) *scan_in_scatter = true;
+  } else {
+    hipLaunchKernelGGL(rb_scan2_kernel, dim3(gy), dim3(1024), 0, s, counts2, tab, gx, gy, ranges);
+    hipLaunchKernelGGL(rb_scatter2_kernel<false>, dim3(nb2 + nb_apply), dim3(RB_THREADS), 0, s, ent, capacity, tab, counts2, list,
+                       capacity, nb2, pg, gx, gy, ranges);
+  }
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }

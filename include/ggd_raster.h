@@ -302,7 +302,9 @@ int ggd_get_option(ggd_ctx* ctx, int option);
 enum {
   GGD_STAT_FLAT_STREAK = 100,   /* consecutive frames whose top depth digit was constant */
   GGD_STAT_SORT_RERUNS = 101,   /* frames re-rendered because the speculated short form of the depth sort did not hold */
-  GGD_STAT_MSD_FRAMES = 102     /* frames whose depth sort ran as two launches (GGD_OPT_MSD_SORT) */
+  GGD_STAT_MSD_FRAMES = 102,    /* frames whose depth sort ran as two launches (GGD_OPT_MSD_SORT) */
+  GGD_STAT_SCAN_IN_SCATTER_FRAMES = 103   /* frames (binning passes) whose row binning ran without its level-2 scan launch: the per-Gaussian
+                                             kernel counted the instances per tile row, the scatter workgroups form their tile starts */
 };
 
 /*

@@ -87,15 +87,17 @@ for sub, workload, out in (("pmc", "1M_1024_cube", "traffic.json"), ("pmc_shell"
                          "(MI355X_MICROARCH.md, HBM section; calibrated in round 1 on kernels of known traffic: scan_apply reads 3906 KiB "
                          "and reports 1988, preprocess reads 54688 KiB and reports 27359); WRITE_SIZE unscaled",
            "kernels": kern,
-           # one STEADY-STATE forward frame: with the two-launch depth sort its eight kernels, once each (the traced run's first
-           # frames go through the two-call form and the three-pass sort; their kernels stay in `kernels`)
+           # one STEADY-STATE forward frame: with the two-launch depth sort its seven kernels, once each (the traced run's first
+           # frames go through the two-call form and the three-pass sort; their kernels -- rb_scan2_kernel and
+           # rb_scatter2_kernel<false> among them -- stay in `kernels`)
            "forward_kernels": ({k: 1.0 for k in kern if any(k.startswith(p) for p in (
-               "preprocess_kernel<false, true>", "sort_msd_", "rb_level1", "rb_count2", "rb_scan2", "rb_scatter2", "blend_forward"))}
+               "preprocess_kernel<false, true", "sort_msd_", "rb_level1", "rb_count2", "rb_scatter2_kernel<true>", "blend_forward"))}
                                if any(k.startswith("sort_msd_finish") for k in kern)
                                else {k: kern[k]["launches_per_frame"] or 1 for k in fwd}),
            "stage_to_kernel": {"blend": next((k for k in kern if k.startswith("blend_forward")), ""), "blend_bwd": bwd_blend,
                                "preprocess": "preprocess_kernel",
-                               "duplicate": next((k for k in kern if k.startswith("rb_scatter2")), ""),
+                               "duplicate": next((k for k in kern if k.startswith("rb_scatter2_kernel<true>")),
+                                                 next((k for k in kern if k.startswith("rb_scatter2")), "")),
                                "sort": next((k for k in kern if k.startswith("sort_msd_finish")),
                                             next((k for k in kern if k.startswith("sort_onesweep")), ""))}}
     json.dump(doc, open(os.path.join(dst, out), "w"), indent=1)
