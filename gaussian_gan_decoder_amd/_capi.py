@@ -23,7 +23,7 @@ EXPORTS = [
     "ggd_decoder_forward_train", "ggd_decoder_backward", "ggd_decoder_wgrad_floats", "ggd_decoder_wgrad", "ggd_decoder_backward_wgrad", "ggd_decoder_packed_hl_bytes", "ggd_decoder_packed_t_hl_bytes", "ggd_decoder_dzbuf_hl_bytes", "ggd_decoder_pack_hl", "ggd_decoder_forward_hl", "ggd_decoder_backward_wgrad_hl", "ggd_image_loss_tmp_bytes", "ggd_image_loss", "ggd_image_loss_masked", "ggd_mask_composite", "ggd_set_option", "ggd_get_option", "ggd_blend_stats", "ggd_blend_backward_stats", "ggd_blend_timeline", "ggd_set_profiling", "ggd_stage_count", "ggd_stage_name", "ggd_stage_times",
     "ggd_knn_tmp_bytes", "ggd_knn_leaf_size", "ggd_knn_max_points", "ggd_knn3", "ggd_knn3_stage",
     "ggd_densify_tmp_bytes", "ggd_densify_stats", "ggd_densify_plan", "ggd_prune_plan", "ggd_densify_emit", "ggd_densify_gather",
-    "ggd_density_points", "ggd_density_grid", "ggd_density_lattice",
+    "ggd_density_points", "ggd_density_grid", "ggd_density_lattice", "ggd_teacher_render",
 ]
 
 
@@ -145,6 +145,8 @@ def load():
         lib.ggd_density_points.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp, i32, vp, vp]
         lib.ggd_density_grid.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, i32, C.c_double, i32, vp, vp]
         lib.ggd_density_lattice.argtypes = [vp, vp, i32, C.c_double, i32, vp]
+        lib.ggd_teacher_render.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp, vp, i32, C.c_double, C.c_double,
+                                           vp, i32, i32, vp, vp, i32, C.c_double, i32, vp, vp, vp, vp]
         _lib = lib
         return lib
 

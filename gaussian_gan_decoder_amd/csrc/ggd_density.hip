@@ -32,6 +32,7 @@
 // Coordinates come from pos[N][3] or are generated in registers (DnSrc): the reference's lattice, op for op in fp32, or the
 // regular one.
 #include "ggd_common.h"
+#include "ggd_density_launch.h"
 #include "ggd_planes.h"
 
 namespace {
@@ -275,6 +276,13 @@ int launch_density(ggd_ctx* ctx, hipStream_t s, const char* who, const float* gr
 }
 
 }  // namespace
+
+int ggd_launch_density_points(ggd_ctx* ctx, hipStream_t s, const char* who, const float* grids_cl, int C, int D, int H, int W,
+                              int axes, float box_warp, const float* w1, const float* b1, const float* w2, const float* b2, int act,
+                              const float* pos, int64_t N, float* sigma, float* rgb) {
+  const DnSrc src{pos, 0, 0, 0.0f, 0.0f};
+  return launch_density(ctx, s, who, grids_cl, C, D, H, W, axes, box_warp, w1, b1, w2, b2, act, src, N, sigma, rgb);
+}
 
 extern "C" int ggd_density_points(ggd_ctx* ctx, void* stream, const float* grids_cl, int32_t C, int32_t D, int32_t H, int32_t W,
                                   int32_t axes, float box_warp, const float* w1, const float* b1, const float* w2,

@@ -5,6 +5,10 @@ density grid [n, n, n] -> iso-surface at level 10 -> 500 000 random surface poin
 barycentric weights rand(3) / sum -> scaled by clip(1 + surface_thickness * N(0,1), 0, 1).  The reference does this with
 skimage + trimesh on the CPU (a D2H copy of the grid and an H2D copy of the mesh every step); here it is three HIP launches
 (csrc/ggd_surface.hip: marching tetrahedra, see there) and no host sync.
+
+The other half of the reference's targets -- the teacher's rendered features, depth and mask (`G.synthesis`, target_dataloader.py:
+91) -- comes from teacher.render_teacher(planes_cl, weights, *teacher.camera_rays(cam2world, intrinsics, resolution)) on the same
+planes and weights: .images(resolution) gives the feature image, image_depth and image_mask.
 """
 from __future__ import annotations
 

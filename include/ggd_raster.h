@@ -589,6 +589,39 @@ int ggd_density_grid(ggd_ctx* ctx, void* stream, const float* grids_cl, int32_t 
                      float* rgb /* NULL = skip */);
 int ggd_density_lattice(ggd_ctx* ctx, void* stream, int32_t n, double cube_length, int32_t lattice, float* pos);
 
+/*
+ * The teacher's feature, depth and weight maps (csrc/ggd_teacher.hip): what ImportanceRenderer.forward and MipRayMarcher2 compute
+ * per ray (PanoHead training/volumetric_rendering/renderer.py:100-323, ray_marcher.py:27-57; eg3d .../renderer.py:88-140) --
+ * stratified coarse depths, the field above at the coarse samples, the march, importance resampling, the field at the fine
+ * samples, the union ordered by depth, the second march -- in six launches, no host wait, scratch in the context's workspace.
+ * Planes, weights and rgb_act as in ggd_density_points.  origins, dirs [M][3] (device).  Per ray, all fp32:
+ *   coarse depth k   fl(coarse_table[k] + fl(u_coarse[k] * delta)),  delta = (float)((ray_end - ray_start) / (Nc - 1)) formed in
+ *                    DOUBLE (hence the double arguments);  coarse_table: HOST pointer to the Nc values of
+ *                    torch.linspace(ray_start, ray_end, Nc), copied into the launch's arguments
+ *   coordinate       fl(o + fl(depth * d));   field: ggd_density_points at that coordinate, bit for bit
+ *   crop (use_crop)  sigma = -1e3 where !(|x| <= lim && |z| <= lim),  lim = (float)crop_limit  (box_warp / 2 - triplane_crop,
+ *                    formed by the caller in double)
+ *   march            midpoints of depth, sigma and rgb; softplus(sigma_mid - 1); alpha = 1 - exp(-sigma_mid * width);
+ *                    w = alpha * exclusive cumprod(1 - alpha + 1e-10)
+ *   importance       max_pool1d(2, 1, pad 1), avg_pool1d(2, 1), + 0.01, both ends dropped, + 1e-5, normalised, cumulative sum with
+ *                    a leading 0, searchsorted(right) of u_fine, the denom < 1e-5 -> 1 rule, linear interpolation in the mid-depths
+ *   composite        features = sum w rgb_mid (+ 1 - sum w with white_back), weights = sum w, depth = sum(w depth_mid) / sum w,
+ *                    NaN -> +inf, clamped to the minimum and maximum over every sample depth of the call (all rays)
+ * The scans and sums along a ray accumulate in double in one fixed order and round once; no atomics: bit-identical from run to
+ * run.  u_coarse [M][Nc], u_fine [M][Ni] (NULL with Ni = 0): the reference's two rand draws, in [0, 1).  4 <= Nc <= 64,
+ * 0 <= Ni <= 64 (0: the coarse-only branch), finite ray_start < ray_end, M * (Nc + Ni) < 2^31; anything else, and anything
+ * ggd_density_points refuses, is GGD_E_INVALID before anything is launched.
+ * Outputs: features [M][32], depth [M], weights [M].  samples: NULL, or a 16-byte aligned block of M * (Nc + Ni) * 37 floats that
+ * receives every stage's values, in this order: rgb coarse [M][Nc][32], rgb fine [M][Ni][32], sigma coarse [M][Nc], sigma fine
+ * [M][Ni] (both after the crop), depths coarse [M][Nc], depths fine [M][Ni], coordinates coarse [M][Nc][3], fine [M][Ni][3].
+ */
+int ggd_teacher_render(ggd_ctx* ctx, void* stream, const float* grids_cl, int32_t C, int32_t D, int32_t H, int32_t W,
+                       int32_t axes, float box_warp, const float* w1, const float* b1, const float* w2, const float* b2,
+                       int32_t rgb_act, const float* origins, const float* dirs, int32_t M, double ray_start, double ray_end,
+                       const float* coarse_table /* host */, int32_t Nc, int32_t Ni, const float* u_coarse, const float* u_fine,
+                       int32_t use_crop, double crop_limit, int32_t white_back, float* features, float* depth, float* weights,
+                       float* samples /* NULL = workspace */);
+
 /* Per-stage device time (ms, hipEvent pairs on `stream`) of the most recent forward_geometry / forward_render /
  * backward call when profiling is on.  Stage names: ggd_stage_name(i), i in [0, ggd_stage_count()). */
 int ggd_set_profiling(ggd_ctx* ctx, int enabled);
