@@ -47,7 +47,7 @@ class ImgView(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in ("ranges", "final_T", "n_contrib", "total")]
 
 
-OPT_EXP_MODE, OPT_BLEND_CULL, OPT_BINNING, OPT_BLEND_SPLIT, OPT_FOLD, OPT_MSD_SORT = 0, 1, 2, 3, 4, 5
+OPT_EXP_MODE, OPT_BLEND_CULL, OPT_BINNING, OPT_BLEND_SPLIT, OPT_FOLD, OPT_MSD_SORT, OPT_PREPROCESS_WGS = 0, 1, 2, 3, 4, 5, 6
 STAT_FLAT_STREAK, STAT_SORT_RERUNS, STAT_MSD_FRAMES, STAT_SCAN_IN_SCATTER_FRAMES = 100, 101, 102, 103   # read-only, through get_option
 SPLAT_BYTES = 48
 SPLAT_FIELDS = ("x", "y", "hA", "nB", "hC", "thr", "opacity", "r", "g", "b", "ex", "ey")

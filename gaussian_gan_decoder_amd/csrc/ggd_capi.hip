@@ -163,6 +163,7 @@ extern "C" ggd_ctx* ggd_create(int device) {
   if (const char* e = getenv("GGD_BLEND_CULL")) ctx->opt[GGD_OPT_BLEND_CULL] = atoi(e) != 0;
   if (const char* e = getenv("GGD_FOLD")) ctx->opt[GGD_OPT_FOLD] = atoi(e) != 0;
   if (const char* e = getenv("GGD_MSD_SORT")) ctx->opt[GGD_OPT_MSD_SORT] = atoi(e) != 0;
+  if (const char* e = getenv("GGD_PREPROCESS_WGS")) { const int v = atoi(e); if (v >= 0 && v <= GGD_PREPROCESS_WGS_MAX) ctx->opt[GGD_OPT_PREPROCESS_WGS] = v; }
   if (const char* e = getenv("GGD_MSD_BUCKETS")) { const int v = atoi(e); if (v >= 16 && v <= GGD_MSD_BINS) ctx->spec.msd_buckets = v; }   // timing experiments
   int prev = 0;
   (void)hipGetDevice(&prev);
@@ -171,7 +172,8 @@ extern "C" ggd_ctx* ggd_create(int device) {
             // coherent (fine-grained) pinned memory: the tagged num_rendered word must become visible to the polling host
             // while the kernel that stored it is still running, whatever HIP_HOST_COHERENT says
             hipHostMalloc((void**)&ctx->h_words, 64, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess &&
-            hipMemset(ctx->d_words, 0, 256) == hipSuccess;
+            hipMemset(ctx->d_words, 0, 256) == hipSuccess &&
+            hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ctx->cus > 0;
   // stale pinned memory (e.g. of a destroyed context) must never match a tag: r_tag restarts at 1 for every context
   if (ok) memset(ctx->h_words, 0, 64);
   for (int i = 0; ok && i < 2 * ST_COUNT; ++i) ok = hipEventCreate(&ctx->ev[i]) == hipSuccess;
@@ -211,7 +213,7 @@ extern "C" const char* ggd_last_error(ggd_ctx* ctx) { return ctx ? ctx->err.c_st
 
 extern "C" int ggd_set_option(ggd_ctx* ctx, int option, int value) {
   if (!ctx) return GGD_E_INVALID;
-  static const int kMax[GGD_OPT_COUNT] = {3, 1, 3, 4, 1, 1};
+  static const int kMax[GGD_OPT_COUNT] = {3, 1, 3, 4, 1, 1, GGD_PREPROCESS_WGS_MAX};
   if (option < 0 || option >= GGD_OPT_COUNT || value < 0 || value > kMax[option])
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_set_option: unknown option or value");
   ctx->opt[option] = value;

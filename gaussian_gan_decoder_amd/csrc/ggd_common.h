@@ -53,6 +53,7 @@ struct ggd_frame {
 
 struct ggd_ctx {
   int device = 0;
+  int cus = 0;                  // compute units of the device (sizes the persistent preprocess grid)
   void* scratch = nullptr;      // grow-only device workspace (sort histograms, scan block sums, dL_dconic, ...)
   size_t scratch_bytes = 0;
   uint32_t attr_mask = 0;       // GGD_ATTR_* bits: kernels whose dynamic-LDS limit was raised on this ctx's device
@@ -77,7 +78,7 @@ struct ggd_ctx {
   void* gelu_tables = nullptr;      // GELU / GELU' interpolation tables of the reference-precision decoder kernels (built on first use)
   void *dbg_keys = nullptr, *dbg_vals = nullptr;   // debug copy of the unsorted list
   size_t dbg_cap = 0;
-  int opt[GGD_OPT_COUNT] = {3, 1, 1, 1, 1, 1};  // exp: bare v_exp_f32 in the forward blend, compensated 2^x (1-2 ulp) in the backward
+  int opt[GGD_OPT_COUNT] = {3, 1, 1, 1, 1, 1, 0};  // exp: bare v_exp_f32 in the forward blend, compensated 2^x (1-2 ulp) in the backward
   unsigned long long* blend_stats = nullptr;  // debug: device counters filled by the forward blend when non-null
   unsigned long long* stats_buf = nullptr;    // its storage: [0..5] counters, [GGD_STATS_MODE] 1 = per-wave timeline, slots from GGD_STATS_HEAD
   bool profiling = false;
@@ -102,7 +103,7 @@ struct ggd_scan_piggy {
   uint32_t tag = 0;                         // polls it instead of waiting on an event (an event record between two kernels
                                             // costs the GPU a ~6 us bubble)
   // folded front end (ggd_fold): step 1 was done by the preprocess workgroups (256 points each) -- step 2 scans their sums
-  const uint4* wg_info = nullptr;           // [n_info] {sum of tiles_touched, kept depth keys, ~min kept key, max kept key} per preprocess workgroup
+  const uint4* wg_info = nullptr;           // [n_info] {sum of tiles_touched, kept depth keys, ~min kept key, max kept key} per 256-Gaussian tile of the preprocess
   int n_info = 0;
   uint32_t* n_valid = nullptr;              // receives the number of kept keys (sum of wg_info[].y)
   int sum_stride = 1;                       // block_sums entries per scan block of step 3 (8 with wg_info: 2048 / 256)
@@ -150,7 +151,7 @@ struct ggd_fold {
   uint32_t* ctl = nullptr;        // this frame's control block (clean)
   uint32_t* clear = nullptr;      // the other block ...
   uint32_t clear_words = 0;       // ... and how much of it the preprocess clears for the next frame
-  uint4* wg_info = nullptr;       // [ceil(P / 256)] {sum of tiles_touched, kept keys, ~min kept key, max kept key}
+  uint4* wg_info = nullptr;       // [ceil(P / 256)] {sum of tiles_touched, kept keys, ~min kept key, max kept key} per 256-Gaussian tile
   int rows = 0;                   // != 0: also count the Gaussians per tile row (the grid has <= 64 rows)
   uint32_t* rowinst = nullptr;    // ... and the instances per tile row, in REPS x 64 words of ctl (ggd_fold_rowinst)
   int msd = 0;                    // != 0: histograms of the two-launch sort (1024 buckets of the key window, top byte) instead of the four bytes

@@ -2,7 +2,8 @@
 //
 // Replaces the per-Gaussian half of `_C.rasterize_gaussians` that the reference reaches through
 // gaussian_splatting/gaussian_renderer/__init__.py:167-175 (source not in the reference tree; algorithm restated
-// in SURVEY.md section 9.2).  One lane per Gaussian, 256-lane workgroups; every input array is read exactly once
+// in SURVEY.md section 9.2).  One lane per Gaussian, 256-lane workgroups that each walk several 256-Gaussian tiles (a persistent
+// grid); every input array is read exactly once
 // with per-lane vector loads over contiguous addresses (a wave covers 64 consecutive Gaussians = one contiguous
 // 768 B / 1 KiB span per array), and the outputs the blend needs are packed into ONE 48-byte record per Gaussian
 // (ggd_splat) so that the per-tile gather later touches a single 64 B-aligned-ish record instead of four arrays.
@@ -17,80 +18,155 @@ using namespace ggdm;
 // instruction touches 64 different rows whatever its width (1 M Gaussians, M = 16: preprocess 76 -> see DESIGN.md).
 // FOLD (ggd_fold, single-call forward on the tile-binning path): the workgroup also (a) clears its share of the OTHER
 // control block for the next frame, (b) adds the four digit counts of its kept depth keys to replica blockIdx % REPS of the
-// depth sort's histograms (LDS histogram first; bins that stayed empty cost nothing), (c) stores {sum of tiles_touched, kept
-// keys} of its 256 points for the offsets scan -- the sort's histogram launch and the scan's first step disappear.
+// depth sort's histograms (LDS histogram over all its tiles first, one flush; bins that stayed empty cost nothing), (c) stores
+// {sum of tiles_touched, kept keys} of each tile's 256 points for the offsets scan -- the sort's histogram launch and the scan's
+// first step disappear.
 // AA (ggd_params.antialiasing): the opacity-compensated 2D filter.  The record's opacity -- and with it thr, ex, ey -- is
 // o_eff = o h, h = sqrt(max(2.5e-5, det0 / det1)), det0 / det1 the determinants of the EWA 2D covariance before / after the
 // 0.3 px^2 dilation (Mip-Splatting).  The conic, radius, rect, tiles_touched and depth key come from the dilated covariance
 // either way.
+// Workgroups per compute unit of the persistent grid: 6 and 7 measured alike (the kernel holds 7 waves per SIMD), 4 and 2 slower
+// (DESIGN.md section 6q).
+constexpr int GGD_PREPROCESS_WGS_PER_CU = 6;
+
+// What the kernel reads of every Gaussian whatever becomes of it: position, scale, rotation, colour (or SH band 0), opacity.
+typedef float f3v __attribute__((ext_vector_type(3)));
+typedef float f4v __attribute__((ext_vector_type(4)));
+struct pre_inputs { f3v p, s, c; f4v q; float o; };
+
+// The kernel's one argument.  The kernel walks many tiles, and forty arguments held in registers around that loop -- with
+// everything the compiler derives from them once -- cost it 16 scalar registers spilled and two waves per SIMD.  So each tile
+// reads what it needs from the kernel-argument segment again, as a one-tile kernel does (tile_args()), in front of the wait
+// for its inputs.
+struct pre_args {
+  int P, M, deg, W, H;
+  float tanfovx, tanfovy, fx, fy, mod;
+  int prefiltered, raw;
+  const float *view, *proj, *campos, *means3D, *shs, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp;
+  ggd_splat* splat;
+  uint32_t* tiles_touched;
+  uint8_t* clamped;
+  int32_t* radii;
+  uint32_t* depth_keys;
+  uint2* rect;
+  uint32_t* trap_flag;
+  uint32_t* zero_ptr;
+  int zero_words;
+  ggd_fold fold;
+};
+typedef const __attribute__((address_space(4))) pre_args* pre_args_ptr;
+
+// The argument segment (pre_args is the kernel's first and only explicit argument: offset 0) as a pointer the compiler cannot
+// trace from one tile to the next: no load through it is hoisted out of the tile loop.
+__device__ __forceinline__ pre_args_ptr tile_args() {
+  pre_args_ptr a = (pre_args_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(a));
+  return a;
+}
+// A pointer read through tile_args() is a generic one to the compiler; every one of them points to device memory.
+template <typename T>
+__device__ __forceinline__ T* as_global(T* p) {
+  return (T*)(__attribute__((address_space(1))) T*)p;
+}
+
+// Requests a tile's inputs and does NOT wait for them: `in` is not to be read, copied or passed on before landed(in) has
+// returned.  Inline asm, because the compiler sinks plain loads behind the culling tests (their only uses).  An array this call
+// does not have is replaced by the 64-byte view matrix, so that no load sits behind a branch; the lanes behind P of the last tile
+// read Gaussian P - 1 and use nothing of it.
+__device__ __forceinline__ void request_inputs(pre_inputs& in, int tile) {
+  const pre_args_ptr a = tile_args();
+  const int i = min(tile * 256 + (int)threadIdx.x, a->P - 1);
+  const float* view = as_global(a->view);
+  const float* colors_precomp = as_global(a->colors_precomp);
+  const float* shs = as_global(a->shs);
+  const bool cov = a->cov3D_precomp != nullptr;
+  const float* pp = as_global(a->means3D) + 3 * (size_t)i;
+  const float* sp = cov ? view : as_global(a->scales) + 3 * (size_t)i;
+  const float* qp = cov ? view : as_global(a->rotations) + 4 * (size_t)i;
+  const float* cp = colors_precomp ? colors_precomp + 3 * (size_t)i : (shs ? shs + (size_t)i * a->M * 3 : view);   // colour, or SH band 0
+  const float* op = as_global(a->opacities) + i;
+  asm volatile("global_load_dwordx3 %0, %5, off\n\t"
+               "global_load_dwordx3 %1, %6, off\n\t"
+               "global_load_dwordx4 %2, %7, off\n\t"
+               "global_load_dwordx3 %3, %8, off\n\t"
+               "global_load_dword %4, %9, off"
+               : "=&v"(in.p), "=&v"(in.s), "=&v"(in.q), "=&v"(in.c), "=&v"(in.o)
+               : "v"(pp), "v"(sp), "v"(qp), "v"(cp), "v"(op)
+               : "memory");
+}
+// The hardware completes loads in order, but stores issued earlier (the control-block clear, the tile before) share the counter:
+// one wait for everything.  Then every register of `in` passes through an empty statement: nothing that reads one can be
+// scheduled ahead of the wait, and a copy the compiler makes for the statement's sake sits behind the wait too.
+__device__ __forceinline__ void landed(pre_inputs& in) {
+  asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+  asm volatile("" : "+v"(in.p), "+v"(in.s), "+v"(in.q), "+v"(in.c), "+v"(in.o) : : "memory");
+}
+
 template <bool SHVEC, bool FOLD, bool AA = false>
-__global__ __launch_bounds__(256) void preprocess_kernel(
-    int P, int M, int deg, int W, int H, float tanfovx, float tanfovy, float fx, float fy, float mod, int prefiltered, int raw,
-    const float* __restrict__ view, const float* __restrict__ proj, const float* __restrict__ campos_p,
-    const float* __restrict__ means3D, const float* __restrict__ shs, const float* __restrict__ colors_precomp,
-    const float* __restrict__ opacities, const float* __restrict__ scales, const float* __restrict__ rotations,
-    const float* __restrict__ cov3D_precomp, ggd_splat* __restrict__ splat, uint32_t* __restrict__ tiles_touched,
-    uint8_t* __restrict__ clamped, int32_t* __restrict__ radii, uint32_t* __restrict__ depth_keys,
-    uint2* __restrict__ rect, uint32_t* __restrict__ trap_flag, uint32_t* __restrict__ zero_ptr, int zero_words,
-    ggd_fold fold) {
+__global__ __launch_bounds__(256) void preprocess_kernel(pre_args args) {
   __shared__ uint32_t s_hist[FOLD ? GGD_FOLD_REP_STRIDE : 1];
-  __shared__ uint32_t s_red[FOLD ? 17 : 1];   // per wave: sum of tiles, kept keys, ~min key, max key; [16]: keys outside the window
+  // two buffers of 16 (tile parity), per wave: sum of tiles, kept keys, ~min key, max key; [32]: keys outside the window
+  __shared__ uint32_t s_red[FOLD ? 33 : 1];
   __shared__ int s_rowdiff[FOLD ? 65 : 1];
   __shared__ int s_rowwdiff[FOLD ? 65 : 1];   // the same difference array weighted by the rect's width: instances per tile row
+  // Persistent grid: the workgroup takes the 256-Gaussian tiles blockIdx.x, blockIdx.x + gridDim.x, ...  What is keyed by the
+  // tile (the per-Gaussian stores, fold.wg_info[tile]) is written per tile, what is a sum (the histograms, the row arrays, the
+  // outside count) stays in LDS until the workgroup ends: one flush per workgroup, not per tile.
+  const Mat16 V = load_mat(args.view);   // (ahead of every store: scalar loads)
+  const Mat16 PV = load_mat(args.proj);
+  const int tiles = (args.P + 255) >> 8;
+  int tile = blockIdx.x;
+  int parity = 0;
+  pre_inputs in;
+  request_inputs(in, tile);   // in flight under the clears and the barrier below
   if constexpr (FOLD) {
-    for (uint32_t z = blockIdx.x * 256 + threadIdx.x; z < fold.clear_words; z += gridDim.x * 256) fold.clear[z] = 0u;
+    for (uint32_t z = blockIdx.x * 256 + threadIdx.x; z < args.fold.clear_words; z += gridDim.x * 256) args.fold.clear[z] = 0u;
     for (int b = threadIdx.x; b < GGD_FOLD_REP_STRIDE; b += 256) s_hist[b] = 0u;
     if (threadIdx.x < 65) { s_rowdiff[threadIdx.x] = 0; s_rowwdiff[threadIdx.x] = 0; }
-    if (threadIdx.x == 0) s_red[16] = 0u;
+    if (threadIdx.x == 0) s_red[32] = 0u;
     __syncthreads();
   } else {
     // first kernel of a frame: its first workgroups also clear the depth sort's control block (no memset launch there)
     const int zb = min(8, (int)gridDim.x);
     if ((int)blockIdx.x < zb)
-      for (int z = blockIdx.x * 256 + threadIdx.x; z < zero_words; z += zb * 256) zero_ptr[z] = 0u;
+      for (int z = blockIdx.x * 256 + threadIdx.x; z < args.zero_words; z += zb * 256) args.zero_ptr[z] = 0u;
   }
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  auto do_tile = [&](pre_inputs& cur, const int tile, const int parity) __attribute__((always_inline)) {
+  const pre_args_ptr a = tile_args();
+  const int P = a->P, M = a->M, deg = a->deg, W = a->W, H = a->H, prefiltered = a->prefiltered, raw = a->raw;
+  const float tanfovx = a->tanfovx, tanfovy = a->tanfovy, fx = a->fx, fy = a->fy, mod = a->mod;
+  const float* campos_p = as_global(a->campos);
+  const float* shs = as_global(a->shs);
+  const float* colors_precomp = as_global(a->colors_precomp);
+  const float* cov3D_precomp = as_global(a->cov3D_precomp);
+  ggd_splat* splat = as_global(a->splat);
+  uint32_t* tiles_touched = as_global(a->tiles_touched);
+  uint8_t* clamped = as_global(a->clamped);
+  int32_t* radii = as_global(a->radii);
+  uint32_t* depth_keys = as_global(a->depth_keys);
+  uint2* rect = as_global(a->rect);
+  uint32_t* trap_flag = as_global(a->trap_flag);
+  // The arguments arrive while the tile's inputs are still on their way: read behind the wait, "at the point of use", they
+  // are three dependent scalar round trips on the tile's critical path (+ 1.4 us on a 391-workgroup launch).
+  asm volatile("" : : "s"(P), "s"(M), "s"(deg), "s"(W), "s"(H), "s"(prefiltered), "s"(raw), "s"(tanfovx), "s"(tanfovy), "s"(fx),
+               "s"(fy), "s"(mod), "s"(shs), "s"(colors_precomp), "s"(cov3D_precomp));
+  asm volatile("" : : "s"(splat), "s"(tiles_touched), "s"(clamped), "s"(radii), "s"(depth_keys), "s"(rect), "s"(trap_flag));
+  landed(cur);
+  const int i = tile * 256 + threadIdx.x;
   const bool in_range = i < P;
-  if (!FOLD && !in_range) return;
+  // Every per-Gaussian input was requested in one go, whatever the culling tests below decide: behind the tests
+  // (position -> depth test -> scale / rotation -> rect test -> colour -> opacity) a wave paid four dependent trips to memory
+  // and lived 10 us, 60 % of it waiting.  The price is 16 B of colour + opacity for a Gaussian whose rect turns out empty.
   int irad = 0;
   uint32_t ntiles = 0, rect_rows = 0, rect_cols = 0;   // rect_rows = miny | maxy << 16, rect_cols = minx | maxx << 16 of a visible Gaussian
   bool visible = false;
   float depth = 0.0f;
   if (in_range) {
-  const Mat16 V = load_mat(view);
-  const Mat16 PV = load_mat(proj);
-
-  // Every per-Gaussian input is requested HERE, in one go, whatever the culling tests below decide: behind the tests (position
-  // -> depth test -> scale / rotation -> rect test -> colour -> opacity) a wave paid four dependent trips to memory and lived
-  // 10 us, 60 % of it waiting.  The price is 16 B of colour + opacity for a Gaussian whose rect turns out empty.  Inline asm,
-  // because the compiler sinks plain loads back behind the tests (their only uses); an array this call does not have is
-  // replaced by the 64-byte view matrix so that no load sits behind a branch.  The hardware completes loads in order, but
-  // stores issued earlier (the control-block clear) share the counter: one wait for everything.
-  typedef float f3v __attribute__((ext_vector_type(3)));
-  typedef float f4v __attribute__((ext_vector_type(4)));
-  f3v p_v, s_v, c_v;
-  f4v q_v;
-  float opac_in;
-  {
-    const float* pp = means3D + 3 * (size_t)i;
-    const float* sp = cov3D_precomp ? view : scales + 3 * (size_t)i;
-    const float* qp = cov3D_precomp ? view : rotations + 4 * (size_t)i;
-    const float* cp = colors_precomp ? colors_precomp + 3 * (size_t)i : (shs ? shs + (size_t)i * M * 3 : view);   // colour, or SH band 0
-    const float* op = opacities + i;
-    asm volatile("global_load_dwordx3 %0, %5, off\n\t"
-                 "global_load_dwordx3 %1, %6, off\n\t"
-                 "global_load_dwordx4 %2, %7, off\n\t"
-                 "global_load_dwordx3 %3, %8, off\n\t"
-                 "global_load_dword %4, %9, off\n\t"
-                 "s_waitcnt vmcnt(0)"
-                 : "=&v"(p_v), "=&v"(s_v), "=&v"(q_v), "=&v"(c_v), "=&v"(opac_in)
-                 : "v"(pp), "v"(sp), "v"(qp), "v"(cp), "v"(op)
-                 : "memory");
-  }
-  const float p[3] = {p_v.x, p_v.y, p_v.z};
-  float s3[3] = {s_v.x, s_v.y, s_v.z};
-  float4 q = make_float4(q_v.x, q_v.y, q_v.z, q_v.w);
-  const float rgb_in[3] = {c_v.x, c_v.y, c_v.z};
+  const float opac_in = cur.o;
+  const float p[3] = {cur.p.x, cur.p.y, cur.p.z};
+  float s3[3] = {cur.s.x, cur.s.y, cur.s.z};
+  float4 q = make_float4(cur.q.x, cur.q.y, cur.q.z, cur.q.w);
+  const float rgb_in[3] = {cur.c.x, cur.c.y, cur.c.z};
   float t[3];
   t[0] = V.m[0] * p[0] + V.m[4] * p[1] + V.m[8] * p[2] + V.m[12];
   t[1] = V.m[1] * p[0] + V.m[5] * p[1] + V.m[9] * p[2] + V.m[13];
@@ -236,11 +312,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
       // (as sort_global_hist_kernel: the two high bytes -- sign / exponent / leading mantissa bits of a depth -- are usually
       // shared by the whole wave: one lane adds the count instead of 64 conflicting LDS atomics)
       const int leader = __builtin_ctzll(act);
-      if (fold.msd) {   // two-launch sort: the bucket inside the key window (never shared by a wave) and the top byte (almost always)
+      if (a->fold.msd) {   // two-launch sort: the bucket inside the key window (never shared by a wave) and the top byte (almost always)
         if (visible) {
-          const uint32_t bkt = (key - fold.msd_lo) >> fold.msd_shift;     // (a key below the window wraps to a huge value)
+          const uint32_t bkt = (key - a->fold.msd_lo) >> a->fold.msd_shift;     // (a key below the window wraps to a huge value)
           atomicAdd(&s_hist[min(bkt, (uint32_t)(GGD_MSD_BINS - 1))], 1u);
-          if (bkt > (uint32_t)(GGD_MSD_BINS - 1)) atomicAdd(&s_red[16], 1u);   // outside: the frame will be rendered again
+          if (bkt > (uint32_t)(GGD_MSD_BINS - 1)) atomicAdd(&s_red[32], 1u);   // outside: the frame will be rendered again
         }
         const uint32_t d = key >> 24;
         const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)d, leader);
@@ -269,7 +345,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
     //     Gaussian's rect covers, prefix over the lanes after the barrier; and the INSTANCES per row (each entry weighted by the
     //     rect's width) for its second level.  visible <=> rect area > 0 <=> level 1 emits the Gaussian's entries: the tile
     //     starts behind a Gaussian counted here and not binned there would all shift.
-    if (fold.rows && visible) {
+    if (a->fold.rows && visible) {
       const int w = (int)(rect_cols >> 16) - (int)(rect_cols & 0xffffu);
       atomicAdd(&s_rowdiff[rect_rows & 0xffffu], 1);
       atomicAdd(&s_rowdiff[rect_rows >> 16], -1);
@@ -286,15 +362,35 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
       nmin = max(nmin, (uint32_t)__shfl_xor((int)nmin, sh, 64));
       kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, sh, 64));
     }
-    if (lane == 0) { s_red[wv] = tsum; s_red[4 + wv] = (uint32_t)__popcll(act); s_red[8 + wv] = nmin; s_red[12 + wv] = kmax; }
+    // (the tile after this one writes the other buffer, and nobody writes this one again before thread 0 has passed the next
+    // tile's barrier: one barrier per tile)
+    uint32_t* red = s_red + 16 * parity;
+    if (lane == 0) { red[wv] = tsum; red[4 + wv] = (uint32_t)__popcll(act); red[8 + wv] = nmin; red[12 + wv] = kmax; }
     __syncthreads();
-    uint32_t* hist = fold.ctl + (blockIdx.x % GGD_FOLD_REPS) * GGD_FOLD_REP_STRIDE;
-    const int used = fold.msd ? GGD_FOLD_REP_STRIDE : 4 * 256;
+    if (threadIdx.x == 0)
+      as_global(a->fold.wg_info)[tile] = make_uint4(red[0] + red[1] + red[2] + red[3], red[4] + red[5] + red[6] + red[7],
+                                      max(max(red[8], red[9]), max(red[10], red[11])),
+                                      max(max(red[12], red[13]), max(red[14], red[15])));
+  }
+  };  // do_tile
+  for (;;) {
+    do_tile(in, tile, parity);
+    tile += gridDim.x;
+    if (tile >= tiles) break;
+    parity ^= 1;
+    request_inputs(in, tile);
+  }
+  if constexpr (FOLD) {   // (behind the last tile's barrier: every LDS sum is complete)
+    const int lane = threadIdx.x & 63;
+    const pre_args_ptr a = tile_args();
+    uint32_t* ctl = as_global(a->fold.ctl);
+    uint32_t* hist = ctl + (blockIdx.x % GGD_FOLD_REPS) * GGD_FOLD_REP_STRIDE;
+    const int used = a->fold.msd ? GGD_FOLD_REP_STRIDE : 4 * 256;
     for (int b = threadIdx.x; b < used; b += 256) {
       const uint32_t c = s_hist[b];
       if (c) atomicAdd(&hist[b], c);
     }
-    if (fold.rows && threadIdx.x < 64) {
+    if (a->fold.rows && threadIdx.x < 64) {
       int c = s_rowdiff[lane], cw = s_rowwdiff[lane];
 #pragma unroll
       for (int d = 1; d < 64; d <<= 1) {
@@ -302,17 +398,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
         if (lane >= d) { c += o; cw += ow; }
       }
       if (c) {   // (a row without entries has no instances)
-        atomicAdd(&fold.ctl[GGD_FOLD_ROWTOT + (blockIdx.x % GGD_FOLD_REPS) * 64 + lane], (uint32_t)c);
-        atomicAdd(&fold.rowinst[(blockIdx.x % GGD_FOLD_REPS) * 64 + lane], (uint32_t)cw);
+        atomicAdd(&ctl[GGD_FOLD_ROWTOT + (blockIdx.x % GGD_FOLD_REPS) * 64 + lane], (uint32_t)c);
+        atomicAdd(&as_global(a->fold.rowinst)[(blockIdx.x % GGD_FOLD_REPS) * 64 + lane], (uint32_t)cw);
       }
     }
-    if (threadIdx.x == 0) {
-      const uint32_t kept = s_red[4] + s_red[5] + s_red[6] + s_red[7];
-      fold.wg_info[blockIdx.x] = make_uint4(s_red[0] + s_red[1] + s_red[2] + s_red[3], kept,
-                                            max(max(s_red[8], s_red[9]), max(s_red[10], s_red[11])),
-                                            max(max(s_red[12], s_red[13]), max(s_red[14], s_red[15])));
-      if (s_red[16]) atomicAdd(&fold.ctl[GGD_FOLD_OUTSIDE], s_red[16]);
-    }
+    if (threadIdx.x == 0 && s_red[32]) atomicAdd(&ctl[GGD_FOLD_OUTSIDE], s_red[32]);
   }
 }
 
@@ -335,20 +425,30 @@ int ggd_launch_preprocess(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, co
                           uint32_t* depth_keys, uint2* rect, uint32_t* trap_flag, uint32_t* zero_ptr, int zero_words,
                           const ggd_fold* fold) {
   if (prm.P == 0) return GGD_OK;
-  const int grid = (prm.P + 255) / 256;
+  // persistent grid: GGD_PREPROCESS_WGS_PER_CU workgroups per compute unit stride over the 256-Gaussian
+  // tiles; GGD_OPT_PREPROCESS_WGS = n > 0 asks for exactly min(n, tiles) workgroups
+  const int tiles = (prm.P + 255) / 256;
+  const int want = ctx->opt[GGD_OPT_PREPROCESS_WGS] > 0 ? ctx->opt[GGD_OPT_PREPROCESS_WGS] : GGD_PREPROCESS_WGS_PER_CU * ctx->cus;
+  const int grid = min(tiles, max(want, 1));
   const bool shvec = !colors_precomp && prm.M > 1 && prm.M <= 16 && ((3 * prm.M) & 3) == 0;
   const ggd_fold f = fold ? *fold : ggd_fold{};
   // focal lengths: wave-uniform correctly rounded divisions, done once here (same fp32 expression, same result)
   const float fx = (float)prm.width / (2.0f * prm.tanfovx), fy = (float)prm.height / (2.0f * prm.tanfovy);
+  pre_args a{};
+  a.P = prm.P; a.M = prm.M; a.deg = prm.sh_degree; a.W = prm.width; a.H = prm.height;
+  a.tanfovx = prm.tanfovx; a.tanfovy = prm.tanfovy; a.fx = fx; a.fy = fy; a.mod = prm.scale_modifier;
+  a.prefiltered = prm.prefiltered; a.raw = prm.raw_attributes;
+  a.view = prm.viewmatrix; a.proj = prm.projmatrix; a.campos = prm.campos;
+  a.means3D = means3D; a.shs = shs; a.colors_precomp = colors_precomp; a.opacities = opacities; a.scales = scales;
+  a.rotations = rotations; a.cov3D_precomp = cov3D_precomp;
+  a.splat = splat; a.tiles_touched = tiles_touched; a.clamped = clamped; a.radii = radii; a.depth_keys = depth_keys; a.rect = rect;
+  a.trap_flag = trap_flag; a.zero_ptr = zero_ptr; a.zero_words = zero_ptr ? zero_words : 0;
+  a.fold = f;
   ggd_dispatch<2>(shvec, [&](auto sv) {
     ggd_dispatch<2>(fold != nullptr, [&](auto fo) {
       ggd_dispatch<2>(prm.antialiasing != 0, [&](auto aa) {
         hipLaunchKernelGGL((preprocess_kernel<decltype(sv)::value != 0, decltype(fo)::value != 0, decltype(aa)::value != 0>),
-                           dim3(grid), dim3(256), 0, s, prm.P, prm.M, prm.sh_degree, prm.width, prm.height, prm.tanfovx,
-                           prm.tanfovy, fx, fy, prm.scale_modifier, prm.prefiltered, prm.raw_attributes, prm.viewmatrix,
-                           prm.projmatrix, prm.campos, means3D, shs, colors_precomp, opacities, scales, rotations,
-                           cov3D_precomp, splat, tiles_touched, clamped, radii, depth_keys, rect, trap_flag, zero_ptr,
-                           zero_ptr ? zero_words : 0, f);
+                           dim3(grid), dim3(256), 0, s, a);
       });
     });
   });

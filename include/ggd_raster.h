@@ -276,8 +276,12 @@ enum {
                              kept key outside the window, no bucket above the finish kernel's capacity), a frame it does not hold
                              for is re-rendered by the ordinary path and its range joins the window.  0 = never.  Results are
                              identical.  Setting this option or GGD_OPT_FOLD (to any value) restarts the speculation state. */
+  GGD_OPT_PREPROCESS_WGS = 6, /* workgroups of the per-Gaussian forward kernel, each of which strides over the 256-Gaussian tiles:
+                             0 (default) = automatic (a fixed number per compute unit), n > 0 = exactly min(n, tiles).  Results are
+                             identical; for timing experiments, and so that a small input can put many tiles on one workgroup. */
   GGD_OPT_COUNT
 };
+#define GGD_PREPROCESS_WGS_MAX (1 << 20)
 int ggd_set_option(ggd_ctx* ctx, int option, int value);
 /* Debug: blend work counters of the NEXT forward calls: out[0]=records visited, [1]=records culled by the wave-level
  * test, [2]=lanes with a candidate pixel (summed over visited records), [3]=candidate pixels, [4]=sum of list lengths,
