@@ -20,7 +20,10 @@ EXPORTS = [
     "ggd_forward_geometry", "ggd_forward_render", "ggd_forward", "ggd_forward_enqueue", "ggd_forward_collect", "ggd_forward_can_speculate", "ggd_backward",
     "ggd_forward_aux", "ggd_forward_render_aux", "ggd_backward_aux", "ggd_mark_visible", "ggd_debug_unsorted",
     "ggd_triplane_forward", "ggd_triplane_backward", "ggd_trigrid_forward", "ggd_trigrid_backward", "ggd_planes_gather", "ggd_planes_scatter", "ggd_surface_tmp_bytes", "ggd_surface_sample", "ggd_attrs_split", "ggd_attrs_merge", "ggd_decoder_packed_bytes", "ggd_decoder_pack", "ggd_decoder_forward", "ggd_decoder_zbuf_bytes", "ggd_decoder_packed_t_bytes",
-    "ggd_decoder_forward_train", "ggd_decoder_backward", "ggd_decoder_wgrad_floats", "ggd_decoder_wgrad", "ggd_decoder_backward_wgrad", "ggd_decoder_packed_hl_bytes", "ggd_decoder_packed_t_hl_bytes", "ggd_decoder_dzbuf_hl_bytes", "ggd_decoder_pack_hl", "ggd_decoder_forward_hl", "ggd_decoder_backward_wgrad_hl", "ggd_image_loss_tmp_bytes", "ggd_image_loss", "ggd_image_loss_masked", "ggd_mask_composite", "ggd_set_option", "ggd_get_option", "ggd_blend_stats", "ggd_blend_backward_stats", "ggd_blend_timeline", "ggd_set_profiling", "ggd_stage_count", "ggd_stage_name", "ggd_stage_times",
+    "ggd_decoder_forward_train", "ggd_decoder_backward", "ggd_decoder_wgrad_floats", "ggd_decoder_wgrad", "ggd_decoder_backward_wgrad", "ggd_decoder_packed_hl_bytes", "ggd_decoder_packed_t_hl_bytes", "ggd_decoder_dzbuf_hl_bytes", "ggd_decoder_pack_hl", "ggd_decoder_forward_hl", "ggd_decoder_backward_wgrad_hl",
+    "ggd_decoder_pack_chain", "ggd_decoder_forward_chain", "ggd_decoder_forward_train_chain", "ggd_decoder_backward_chain", "ggd_decoder_wgrad_chain",
+    "ggd_decoder_backward_wgrad_chain", "ggd_decoder_pack_hl_chain", "ggd_decoder_forward_hl_chain", "ggd_decoder_backward_wgrad_hl_chain",
+    "ggd_image_loss_tmp_bytes", "ggd_image_loss", "ggd_image_loss_masked", "ggd_mask_composite", "ggd_set_option", "ggd_get_option", "ggd_blend_stats", "ggd_blend_backward_stats", "ggd_blend_timeline", "ggd_set_profiling", "ggd_stage_count", "ggd_stage_name", "ggd_stage_times",
     "ggd_knn_tmp_bytes", "ggd_knn_leaf_size", "ggd_knn_max_points", "ggd_knn3", "ggd_knn3_stage",
     "ggd_densify_tmp_bytes", "ggd_densify_stats", "ggd_densify_plan", "ggd_prune_plan", "ggd_densify_emit", "ggd_densify_gather",
     "ggd_density_points", "ggd_density_grid", "ggd_density_lattice", "ggd_teacher_render",
@@ -118,6 +121,11 @@ def load():
         lib.ggd_decoder_pack_hl.argtypes = [vp, vp, C.POINTER(C.c_void_p), vp, vp]
         lib.ggd_decoder_forward_hl.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
         lib.ggd_decoder_backward_wgrad_hl.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        # the *_chain forms: the chain (ggd_decoder_chain) behind `stream`, then the arguments of the form without it
+        for name in ("pack", "forward", "forward_train", "backward", "wgrad", "backward_wgrad", "pack_hl", "forward_hl",
+                     "backward_wgrad_hl"):
+            base = getattr(lib, "ggd_decoder_" + name).argtypes
+            getattr(lib, "ggd_decoder_" + name + "_chain").argtypes = list(base[:2]) + [i32] + list(base[2:])
         lib.ggd_image_loss_tmp_bytes.restype = sz; lib.ggd_image_loss_tmp_bytes.argtypes = [i32, i32]
         lib.ggd_image_loss.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz]
         lib.ggd_image_loss_masked.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz]

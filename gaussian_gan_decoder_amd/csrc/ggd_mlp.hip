@@ -4,7 +4,9 @@
 // Replaces, for inference, the 5 x `Decoder` calls of main/decoder_models/sequential_decoder_reverse.py:68-85
 // (each: concat -> Linear+GELU x3 -> Linear, main/decoder_models/base_decoder.py:8-27):
 //   color(3) -> opacity(1) -> rotation(4) -> scale(3, -softplus(s+5)-2.5) -> xyz(3, *0.01 + position),
-// every head seeing [plane_mean(32), position(3), outputs of the earlier heads].
+// every head seeing [plane_mean(32), position(3), outputs of the earlier heads].  The reference's other two decoder types
+// (sequential_decoder.py: xyz first; parallel_decoder.py: no chaining) are further compile-time instances of the same kernels:
+// THE THREE CHAINS below.
 //
 // Formulation: TRANSPOSED GEMMs, Y^T[feature][point] = W[feature][k] . X^T[k][point], with
 // v_mfma_f32_16x16x32_f16 (fp32 accumulate; f16 operands in the forward since round 4 -- 11 significant bits instead of
@@ -39,6 +41,45 @@ __host__ __device__ constexpr int head_in(int h) { return 32 + 3 + head_a0(h); }
 static_assert(head_a0(0) == 0 && head_a0(1) == head_a0(0) + head_od(0) && head_a0(2) == head_a0(1) + head_od(1) &&
               head_a0(3) == head_a0(2) + head_od(2) && head_a0(4) == head_a0(3) + head_od(3) && head_a0(4) + head_od(4) == 14,
               "every head starts where the one before it ends; attrs slots 14, 15 are unused");
+// THE THREE CHAINS (ggd_decoder_chain).  The five ATTRIBUTES keep their public attrs columns whatever the
+// chain: attribute a (0 colour, 1 opacity, 2 rotation, 3 scale, 4 xyz) is head_od(a) columns at head_a0(a), and carries its
+// activation with it (3: -softplus(s + 5) - chain_scale_c, 4: * 0.01 + position).  A chain is the ORDER in which the attributes
+// are decoded and what each decoded head sees; everywhere below, `head` is an EXECUTION POSITION (params40, dout, the image
+// slots, the z planes and the weight-gradient blocks are indexed by it):
+//   GGD_CHAIN_ATTR(C, h)   the attribute decoded at position h      chain 0: h (colour first); chains 1, 2: 4 - h (xyz first)
+//   GGD_CHAIN_NX(C, h)     its n_extra: the info slots 3 .. 3 + n_extra hold the outputs of the positions before it, in
+//                          execution order (the reference's torch.concat order: W1 needs no column permutation)
+//                          chain 0: 0 3 4 8 11; chain 1: 0 3 6 10 11; chain 2 (parallel): 0 everywhere
+//   GGD_CHAIN_COL(C, k)    the public attrs column info slot 3 + k reads          chain 0: k; chain 1: 11 12 13 | 8 9 10 | 4 5 6 7 | 3
+// A sequential chain's position h writes what the later positions read at info slots 3 + GGD_CHAIN_NX(C, h) ..; the backward
+// adds dinfo there to dattrs unless no later position reads it (chain_reads_back).
+#define GGD_CHAIN_ATTR(C, h) ((C) == 0 ? (h) : 4 - (h))
+#define GGD_CHAIN_NX(C, h) \
+  ((C) == 0 ? GGD_HEAD_A0(h) : ((C) == 2 ? 0 : ((h) == 0 ? 0 : ((h) == 1 ? 3 : ((h) == 2 ? 6 : ((h) == 3 ? 10 : 11))))))
+#define GGD_CHAIN_COL(C, k) \
+  ((C) == 1 ? (int)(((k) < 8 ? 0x54a98dcbu >> (4 * (k)) : 0x376u >> (4 * ((k) - 8))) & 15u) : (k))   /* a nibble per slot */
+constexpr int NCHAIN = 3;
+__host__ __device__ constexpr int chain_attr(int c, int h) { return GGD_CHAIN_ATTR(c, h); }
+__host__ __device__ constexpr int chain_nx(int c, int h) { return GGD_CHAIN_NX(c, h); }
+__host__ __device__ constexpr int chain_col(int c, int k) { return GGD_CHAIN_COL(c, k); }
+__host__ __device__ constexpr int chain_od(int c, int h) { return head_od(chain_attr(c, h)); }
+__host__ __device__ constexpr int chain_in(int c, int h) { return 32 + 3 + chain_nx(c, h); }
+__host__ __device__ constexpr bool chain_reads_back(int c, int h) { return c != 2 && h != NHEAD - 1; }
+__host__ __device__ constexpr float chain_scale_c(int c) { return c == 0 ? 2.5f : 2.0f; }
+constexpr bool chain_consistent(int c) {   // n_extra = the widths before it; slot 3 + nx(h) + e reads column a0(attr(h)) + e
+  int nx = 0;
+  for (int h = 0; h < NHEAD; ++h) {
+    if (c != 2 && chain_nx(c, h) != nx) return false;
+    if (c == 2 && chain_nx(c, h) != 0) return false;
+    if (c != 2 && h != NHEAD - 1)
+      for (int e = 0; e < chain_od(c, h); ++e)
+        if (chain_col(c, nx + e) != head_a0(chain_attr(c, h)) + e) return false;
+    nx += chain_od(c, h);
+  }
+  return nx == 14;
+}
+static_assert(chain_consistent(0) && chain_consistent(1) && chain_consistent(2), "the chain table");
+static_assert(chain_in(0, 0) == head_in(0) && chain_in(0, 4) == head_in(4) && chain_in(1, 2) == 41 && chain_in(1, 3) == 45, "widths");
 // LDS image of one head (bytes).  Weight rows are K 16-bit values with NO padding; the 16-byte slots of a row are XOR-swizzled by the row index so that a
 // ds_read_b128 of one k-slot of 16 consecutive rows by the four lane groups of a wave (rows i = lane & 15, slot g + 4 s) is
 // bank-conflict free: the LDS services a b128 read in four 16-lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ... over a
@@ -260,7 +301,7 @@ __device__ __forceinline__ void gelu_pack(const f4 (&acc)[2][8], h16x8 (&bout)[2
 // vector a head sees is [position(3), attrs[0 .. n_extra)] with n_extra = 0, 3, 4, 8, 11.
 // STORE_Z (training): the pre-activations of the three hidden layers are kept (rounded to f16) for the backward,
 // zbuf[head][layer][16-point block][4 KB] (blocked Z layout above).
-template <bool STORE_Z>
+template <int CHAIN, bool STORE_Z>
 __global__ __launch_bounds__(FWD_THREADS, FWD_WAVES / 4) void decoder_forward_kernel(const float* __restrict__ feat,
                                                                          const float* __restrict__ pos, int N,
                                                                          const unsigned char* __restrict__ packed,
@@ -277,7 +318,7 @@ __global__ __launch_bounds__(FWD_THREADS, FWD_WAVES / 4) void decoder_forward_ke
   const int64_t cend = min((int64_t)N, cbeg + per);
 
   for (int head = 0; head < NHEAD; ++head) {
-    const int n_extra = GGD_HEAD_A0(head);   // = head_a0(head), expanded in place
+    const int n_extra = GGD_CHAIN_NX(CHAIN, head);   // = chain_nx(CHAIN, head), expanded in place
     __syncthreads();  // everyone is done with the previous head's weights (and its attrs stores are issued)
     {
       const uint4* src = reinterpret_cast<const uint4*>(packed + (size_t)head * HEAD_BYTES);
@@ -309,7 +350,14 @@ __global__ __launch_bounds__(FWD_THREADS, FWD_WAVES / 4) void decoder_forward_ke
             const int q = 4 * g + e;  // info slot
             float v = 0.0f;
             if (q < 3) v = pos[pt * 3 + q];
-            else if (q - 3 < n_extra) v = attrs[pt * 16 + (q - 3)];
+            else if (q - 3 < n_extra) {
+              int col = GGD_CHAIN_COL(CHAIN, q - 3);
+              // (chain 1's four columns are four addresses per point tile, the same for every head: left alone they are
+              // hoisted out of the head loop and spilled -- 18 VGPRs in decoder_forward_hl_kernel<1, true>; opaque, they are
+              // formed again from the row's address where they are used)
+              if (CHAIN == 1) asm volatile("" : "+v"(col));
+              v = attrs[pt * 16 + col];
+            }
             inf[e] = v;
           }
         }
@@ -339,6 +387,7 @@ __global__ __launch_bounds__(FWD_THREADS, FWD_WAVES / 4) void decoder_forward_ke
         }
       }
       // lane group 0 holds output features 0..3 of point j (D rows 0..3)
+      const int attr = GGD_CHAIN_ATTR(CHAIN, head);   // which attribute this position decodes: it names the columns and the activation
       if (g == 0) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -346,13 +395,13 @@ __global__ __launch_bounds__(FWD_THREADS, FWD_WAVES / 4) void decoder_forward_ke
           if (pt >= cend) continue;
           float* arow = attrs + pt * 16;
           const f4 o = out[c];
-          if (head == 0) {
+          if (attr == 0) {
             arow[0] = o[0]; arow[1] = o[1]; arow[2] = o[2];
-          } else if (head == 1) {
+          } else if (attr == 1) {
             arow[3] = o[0];
-          } else if (head == 2) {
+          } else if (attr == 2) {
             arow[4] = o[0]; arow[5] = o[1]; arow[6] = o[2]; arow[7] = o[3];
-          } else if (head == 3) {  // -softplus(s + 5) - 2.5   (torch.nn.Softplus: beta 1, threshold 20)
+          } else if (attr == 3) {  // -softplus(s + 5) - 2.5, or - 2 (chain_scale_c)   (torch.nn.Softplus: beta 1, threshold 20)
             // v_exp_f32 / v_log_f32 forms: |error| <= 2e-7 absolute (1 + e rounds, the hardware log2 is good to an ulp) against
             // this tier's 2e-3; libm's expf + log1pf were ~800 instructions per slab on this head -- 9 % of the kernel's issue
             // slots averaged over the heads (0.660 -> 0.633 ms at 1 M points).  The reference-precision kernel (bar 1e-4) does the same.
@@ -360,7 +409,7 @@ __global__ __launch_bounds__(FWD_THREADS, FWD_WAVES / 4) void decoder_forward_ke
             for (int q = 0; q < 3; ++q) {
               const float v = o[q] + 5.0f;
               const float sp = v > 20.0f ? v : __logf(1.0f + __expf(v));
-              arow[8 + q] = -sp - 2.5f;
+              arow[8 + q] = -sp - chain_scale_c(CHAIN);
             }
           } else {                 // xyz = head * 0.01 + position
             arow[11] = o[0] * 0.01f + pos[pt * 3]; arow[12] = o[1] * 0.01f + pos[pt * 3 + 1];
@@ -410,12 +459,27 @@ static void chunk_walk(int32_t N, int32_t chunk, F&& launch_both) {
   for (int32_t first = 0; first < N; first += chunk) launch_both(first, first + chunk < N ? first + chunk : N);
 }
 
+// The chain of an entry point -> the kernels' compile-time parameter: launch(std::integral_constant<int, CHAIN>) for a known
+// chain, GGD_E_INVALID otherwise.
+template <typename F>
+static int with_chain(ggd_ctx* ctx, int32_t chain, const char* entry, F&& launch) {
+  switch (chain) {
+    case GGD_CHAIN_SEQUENTIAL_REVERSED: return launch(std::integral_constant<int, 0>{});
+    case GGD_CHAIN_SEQUENTIAL: return launch(std::integral_constant<int, 1>{});
+    case GGD_CHAIN_PARALLEL: return launch(std::integral_constant<int, 2>{});
+    default: return ggd_fail(ctx, GGD_E_INVALID, std::string(entry) + ": unknown decoder chain " + std::to_string(chain));
+  }
+}
+static_assert(GGD_CHAIN_PARALLEL + 1 == NCHAIN, "ggd_decoder_chain");
+static bool chain_known(int32_t chain) { return chain >= 0 && chain < NCHAIN; }
+
 extern "C" size_t ggd_decoder_packed_bytes(void) { return (size_t)NHEAD * HEAD_BYTES; }
 
 template <bool HL>
-static int decoder_pack_impl(ggd_ctx* ctx, void* stream, const float* const* params40, void* packed, void* packed_t,
-                             const char* entry) {
+static int decoder_pack_impl(ggd_ctx* ctx, void* stream, int32_t chain, const float* const* params40, void* packed,
+                             void* packed_t, const char* entry) {
   if (!ctx) return GGD_E_INVALID;
+  if (!chain_known(chain)) return ggd_fail(ctx, GGD_E_INVALID, std::string(entry) + ": unknown decoder chain " + std::to_string(chain));
   if (!params40 || !packed) return ggd_fail(ctx, GGD_E_INVALID, std::string(entry) + ": NULL pointer");
   ggd_pack_ptrs ptrs;
   for (int i = 0; i < NHEAD * 8; ++i) {
@@ -424,13 +488,17 @@ static int decoder_pack_impl(ggd_ctx* ctx, void* stream, const float* const* par
   }
   const int total = NHEAD * (HL ? 2 : 1) * (pack_elems(0) + pack_elems(1)) + NHEAD * PACK_BIAS;   // one thread per element
   hipLaunchKernelGGL(decoder_pack_kernel<HL>, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), ptrs,
-                     static_cast<unsigned char*>(packed), static_cast<unsigned char*>(packed_t));
+                     (int)chain, static_cast<unsigned char*>(packed), static_cast<unsigned char*>(packed_t));
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }
 
+extern "C" int ggd_decoder_pack_chain(ggd_ctx* ctx, void* stream, int32_t chain, const float* const* params40, void* packed,
+                                      void* packed_t) {
+  return decoder_pack_impl<false>(ctx, stream, chain, params40, packed, packed_t, "ggd_decoder_pack");
+}
 extern "C" int ggd_decoder_pack(ggd_ctx* ctx, void* stream, const float* const* params40, void* packed, void* packed_t) {
-  return decoder_pack_impl<false>(ctx, stream, params40, packed, packed_t, "ggd_decoder_pack");
+  return ggd_decoder_pack_chain(ctx, stream, GGD_CHAIN_SEQUENTIAL_REVERSED, params40, packed, packed_t);
 }
 
 // the GELU / GELU' tables (ggd_mlp_gelu.inc), built once per context in double precision
@@ -443,23 +511,36 @@ static int gelu_tables(ggd_ctx* ctx) {
   return GGD_OK;
 }
 
-static int decoder_forward_impl(ggd_ctx* ctx, void* stream, const float* feat, const float* pos, int32_t N,
+// every chain's instance of a kernel template with one int parameter (K<0>, K<1>, K<2>) at `bytes` of dynamic LDS
+#define GGD_CHAIN_LDS(K, bytes) \
+  {reinterpret_cast<const void*>(K<0>), bytes}, {reinterpret_cast<const void*>(K<1>), bytes}, {reinterpret_cast<const void*>(K<2>), bytes}
+#define GGD_CHAIN_LDS_Z(K, bytes) \
+  {reinterpret_cast<const void*>(K<0, false>), bytes}, {reinterpret_cast<const void*>(K<0, true>), bytes}, \
+  {reinterpret_cast<const void*>(K<1, false>), bytes}, {reinterpret_cast<const void*>(K<1, true>), bytes}, \
+  {reinterpret_cast<const void*>(K<2, false>), bytes}, {reinterpret_cast<const void*>(K<2, true>), bytes}
+
+static int decoder_forward_impl(ggd_ctx* ctx, void* stream, int32_t chain, const float* feat, const float* pos, int32_t N,
                                 const void* packed_weights, float* attrs, void* zbuf) {
   if (!ctx) return GGD_E_INVALID;
+  if (!chain_known(chain)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_forward: unknown decoder chain " + std::to_string(chain));
   if (N < 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_forward: N < 0");
   if (N == 0) return GGD_OK;
   if (!feat || !pos || !packed_weights || !attrs) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_forward: NULL pointer");
   const size_t lds = HEAD_BYTES;
-  const int rc = lds_once(ctx, GGD_ATTR_MLP_FWD, {{reinterpret_cast<const void*>(decoder_forward_kernel<false>), HEAD_BYTES},
-                                                  {reinterpret_cast<const void*>(decoder_forward_kernel<true>), HEAD_BYTES}});
+  const int rc = lds_once(ctx, GGD_ATTR_MLP_FWD, {GGD_CHAIN_LDS_Z(decoder_forward_kernel, HEAD_BYTES)});
   if (rc != GGD_OK) return rc;
   const int grid = slab_grid(N, FWD_WAVES);
-  if (zbuf)
-    hipLaunchKernelGGL(decoder_forward_kernel<true>, dim3(grid), dim3(FWD_THREADS), lds, static_cast<hipStream_t>(stream),
-                       feat, pos, N, static_cast<const unsigned char*>(packed_weights), attrs, static_cast<_Float16*>(zbuf));
-  else
-    hipLaunchKernelGGL(decoder_forward_kernel<false>, dim3(grid), dim3(FWD_THREADS), lds, static_cast<hipStream_t>(stream),
-                       feat, pos, N, static_cast<const unsigned char*>(packed_weights), attrs, (_Float16*)nullptr);
+  const int rl = with_chain(ctx, chain, "ggd_decoder_forward", [&](auto c) {
+    constexpr int CH = decltype(c)::value;
+    if (zbuf)
+      hipLaunchKernelGGL((decoder_forward_kernel<CH, true>), dim3(grid), dim3(FWD_THREADS), lds, static_cast<hipStream_t>(stream),
+                         feat, pos, N, static_cast<const unsigned char*>(packed_weights), attrs, static_cast<_Float16*>(zbuf));
+    else
+      hipLaunchKernelGGL((decoder_forward_kernel<CH, false>), dim3(grid), dim3(FWD_THREADS), lds, static_cast<hipStream_t>(stream),
+                         feat, pos, N, static_cast<const unsigned char*>(packed_weights), attrs, (_Float16*)nullptr);
+    return GGD_OK;
+  });
+  if (rl != GGD_OK) return rl;
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }
@@ -515,80 +596,109 @@ extern "C" int ggd_attrs_merge(ggd_ctx* ctx, void* stream, int64_t N, const floa
   return GGD_OK;
 }
 
+extern "C" int ggd_decoder_forward_chain(ggd_ctx* ctx, void* stream, int32_t chain, const float* feat, const float* pos,
+                                         int32_t N, const void* packed_weights, float* attrs) {
+  return decoder_forward_impl(ctx, stream, chain, feat, pos, N, packed_weights, attrs, nullptr);
+}
 extern "C" int ggd_decoder_forward(ggd_ctx* ctx, void* stream, const float* feat, const float* pos, int32_t N,
                                    const void* packed_weights, float* attrs) {
-  return decoder_forward_impl(ctx, stream, feat, pos, N, packed_weights, attrs, nullptr);
+  return ggd_decoder_forward_chain(ctx, stream, GGD_CHAIN_SEQUENTIAL_REVERSED, feat, pos, N, packed_weights, attrs);
 }
 
 extern "C" size_t ggd_decoder_packed_t_bytes(void) { return (size_t)NHEAD * HEADT_BYTES; }
 
 // the two launches of the 16-bit tier's backward over the points [first, last) of N
-static int launch_backward(ggd_ctx* ctx, hipStream_t s, int32_t N, int32_t first, int32_t last, const void* packed_t,
-                           const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf, float* dout, float* dfeat,
-                           float* dinfo) {
-  const int rc = lds_once(ctx, GGD_ATTR_MLP_BWD, {{reinterpret_cast<const void*>(decoder_backward_kernel), HEADT_BYTES}});
+static int launch_backward(ggd_ctx* ctx, hipStream_t s, int32_t chain, int32_t N, int32_t first, int32_t last,
+                           const void* packed_t, const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf,
+                           float* dout, float* dfeat, float* dinfo) {
+  const int rc = lds_once(ctx, GGD_ATTR_MLP_BWD, {GGD_CHAIN_LDS(decoder_backward_kernel, HEADT_BYTES)});
   if (rc != GGD_OK) return rc;
-  hipLaunchKernelGGL(decoder_backward_kernel, dim3(slab_grid(last - first, MLP_WAVES)), dim3(MLP_THREADS), HEADT_BYTES, s, N,
-                     first, last, static_cast<const unsigned char*>(packed_t), attrs, dattrs, static_cast<const _Float16*>(zbuf),
-                     static_cast<__bf16*>(dzbuf), dout, dfeat, dinfo);
-  return GGD_OK;
+  return with_chain(ctx, chain, "ggd_decoder_backward", [&](auto c) {
+    hipLaunchKernelGGL(decoder_backward_kernel<decltype(c)::value>, dim3(slab_grid(last - first, MLP_WAVES)), dim3(MLP_THREADS),
+                       HEADT_BYTES, s, N, first, last, static_cast<const unsigned char*>(packed_t), attrs, dattrs,
+                       static_cast<const _Float16*>(zbuf), static_cast<__bf16*>(dzbuf), dout, dfeat, dinfo);
+    return GGD_OK;
+  });
 }
-static int launch_wgrad(ggd_ctx* ctx, hipStream_t s, int32_t N, int32_t first, int32_t last, const void* zbuf, const void* dzbuf,
-                        const float* dout, const float* feat, const float* pos, const float* attrs, float* wgrad) {
-  const int rc = lds_once(ctx, GGD_ATTR_MLP_WGRAD, {{reinterpret_cast<const void*>(decoder_wgrad_kernel), WG_LDS}});
+static int launch_wgrad(ggd_ctx* ctx, hipStream_t s, int32_t chain, int32_t N, int32_t first, int32_t last, const void* zbuf,
+                        const void* dzbuf, const float* dout, const float* feat, const float* pos, const float* attrs,
+                        float* wgrad) {
+  const int rc = lds_once(ctx, GGD_ATTR_MLP_WGRAD, {GGD_CHAIN_LDS(decoder_wgrad_kernel, WG_LDS)});
   if (rc != GGD_OK) return rc;
-  hipLaunchKernelGGL(decoder_wgrad_kernel, dim3(wgrad_chunks(last - first), NHEAD * 4), dim3(WG_THREADS), WG_LDS, s, N, first,
-                     last, static_cast<const __bf16*>(zbuf), static_cast<const __bf16*>(dzbuf), dout, feat, pos, attrs, wgrad);
-  return GGD_OK;
+  return with_chain(ctx, chain, "ggd_decoder_wgrad", [&](auto c) {
+    hipLaunchKernelGGL(decoder_wgrad_kernel<decltype(c)::value>, dim3(wgrad_chunks(last - first), NHEAD * 4), dim3(WG_THREADS),
+                       WG_LDS, s, N, first, last, static_cast<const __bf16*>(zbuf), static_cast<const __bf16*>(dzbuf), dout, feat,
+                       pos, attrs, wgrad);
+    return GGD_OK;
+  });
 }
 
-extern "C" int ggd_decoder_backward(ggd_ctx* ctx, void* stream, int32_t N, const void* packed_t, const float* attrs,
-                                    const float* dattrs, const void* zbuf, void* dzbuf, float* dout, float* dfeat,
-                                    float* dinfo) {
+extern "C" int ggd_decoder_backward_chain(ggd_ctx* ctx, void* stream, int32_t chain, int32_t N, const void* packed_t,
+                                          const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf, float* dout,
+                                          float* dfeat, float* dinfo) {
   if (!ctx) return GGD_E_INVALID;
+  if (!chain_known(chain)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_backward: unknown decoder chain " + std::to_string(chain));
   if (N < 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_backward: N < 0");
   if (N == 0) return GGD_OK;
   if (!packed_t || !attrs || !dattrs || !zbuf || !dzbuf || !dout || !dfeat || !dinfo)
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_backward: NULL pointer");
-  const int rc = launch_backward(ctx, static_cast<hipStream_t>(stream), N, 0, N, packed_t, attrs, dattrs, zbuf, dzbuf, dout, dfeat,
-                                 dinfo);
+  const int rc = launch_backward(ctx, static_cast<hipStream_t>(stream), chain, N, 0, N, packed_t, attrs, dattrs, zbuf, dzbuf, dout,
+                                 dfeat, dinfo);
   if (rc != GGD_OK) return rc;
   GGD_HIP(hipGetLastError());
   return GGD_OK;
+}
+extern "C" int ggd_decoder_backward(ggd_ctx* ctx, void* stream, int32_t N, const void* packed_t, const float* attrs,
+                                    const float* dattrs, const void* zbuf, void* dzbuf, float* dout, float* dfeat,
+                                    float* dinfo) {
+  return ggd_decoder_backward_chain(ctx, stream, GGD_CHAIN_SEQUENTIAL_REVERSED, N, packed_t, attrs, dattrs, zbuf, dzbuf, dout, dfeat,
+                                    dinfo);
 }
 
 extern "C" size_t ggd_decoder_zbuf_bytes(int32_t N) {   // 16-point blocks: N rounded up to a multiple of 16
   return (size_t)NHEAD * 3 * (size_t)(N > 0 ? ((N + 15) & ~15) : 0) * HID * 2;
 }
 
+extern "C" int ggd_decoder_forward_train_chain(ggd_ctx* ctx, void* stream, int32_t chain, const float* feat, const float* pos,
+                                               int32_t N, const void* packed_weights, float* attrs, void* zbuf) {
+  if (ctx && N > 0 && !zbuf) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_forward_train: zbuf is NULL");
+  return decoder_forward_impl(ctx, stream, chain, feat, pos, N, packed_weights, attrs, zbuf);
+}
 extern "C" int ggd_decoder_forward_train(ggd_ctx* ctx, void* stream, const float* feat, const float* pos, int32_t N,
                                          const void* packed_weights, float* attrs, void* zbuf) {
-  if (ctx && N > 0 && !zbuf) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_forward_train: zbuf is NULL");
-  return decoder_forward_impl(ctx, stream, feat, pos, N, packed_weights, attrs, zbuf);
+  return ggd_decoder_forward_train_chain(ctx, stream, GGD_CHAIN_SEQUENTIAL_REVERSED, feat, pos, N, packed_weights, attrs, zbuf);
 }
 
 extern "C" size_t ggd_decoder_wgrad_floats(void) { return (size_t)NHEAD * WG_HEAD_FLOATS; }
 
-extern "C" int ggd_decoder_wgrad(ggd_ctx* ctx, void* stream, int32_t N, const void* zbuf, const void* dzbuf,
-                                 const float* dout, const float* feat, const float* pos, const float* attrs,
-                                 float* wgrad) {
+extern "C" int ggd_decoder_wgrad_chain(ggd_ctx* ctx, void* stream, int32_t chain, int32_t N, const void* zbuf,
+                                       const void* dzbuf, const float* dout, const float* feat, const float* pos,
+                                       const float* attrs, float* wgrad) {
   if (!ctx) return GGD_E_INVALID;
+  if (!chain_known(chain)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_wgrad: unknown decoder chain " + std::to_string(chain));
   if (N < 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_wgrad: N < 0");
   if (N == 0) return GGD_OK;
   if (!zbuf || !dzbuf || !dout || !feat || !pos || !attrs || !wgrad)
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_wgrad: NULL pointer");
-  const int rc = launch_wgrad(ctx, static_cast<hipStream_t>(stream), N, 0, N, zbuf, dzbuf, dout, feat, pos, attrs, wgrad);
+  const int rc = launch_wgrad(ctx, static_cast<hipStream_t>(stream), chain, N, 0, N, zbuf, dzbuf, dout, feat, pos, attrs, wgrad);
   if (rc != GGD_OK) return rc;
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }
+extern "C" int ggd_decoder_wgrad(ggd_ctx* ctx, void* stream, int32_t N, const void* zbuf, const void* dzbuf,
+                                 const float* dout, const float* feat, const float* pos, const float* attrs,
+                                 float* wgrad) {
+  return ggd_decoder_wgrad_chain(ctx, stream, GGD_CHAIN_SEQUENTIAL_REVERSED, N, zbuf, dzbuf, dout, feat, pos, attrs, wgrad);
+}
 
 // chunk <= 0: one chunk (= ggd_decoder_backward followed by ggd_decoder_wgrad); see chunk_walk
-extern "C" int ggd_decoder_backward_wgrad(ggd_ctx* ctx, void* stream, int32_t N, int32_t chunk, const void* packed_t,
-                                          const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf,
-                                          float* dout, float* dfeat, float* dinfo, const float* feat, const float* pos,
-                                          float* wgrad) {
+extern "C" int ggd_decoder_backward_wgrad_chain(ggd_ctx* ctx, void* stream, int32_t chain, int32_t N, int32_t chunk,
+                                                const void* packed_t, const float* attrs, const float* dattrs, const void* zbuf,
+                                                void* dzbuf, float* dout, float* dfeat, float* dinfo, const float* feat,
+                                                const float* pos, float* wgrad) {
   if (!ctx) return GGD_E_INVALID;
+  if (!chain_known(chain))
+    return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_backward_wgrad: unknown decoder chain " + std::to_string(chain));
   if (N < 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_backward_wgrad: N < 0");
   if (N == 0) return GGD_OK;
   if (!packed_t || !attrs || !dattrs || !zbuf || !dzbuf || !dout || !dfeat || !dinfo || !feat || !pos || !wgrad)
@@ -596,12 +706,19 @@ extern "C" int ggd_decoder_backward_wgrad(ggd_ctx* ctx, void* stream, int32_t N,
   hipStream_t s = static_cast<hipStream_t>(stream);
   int rc = GGD_OK;
   chunk_walk(N, chunk, [&](int32_t first, int32_t last) {
-    if (rc == GGD_OK) rc = launch_backward(ctx, s, N, first, last, packed_t, attrs, dattrs, zbuf, dzbuf, dout, dfeat, dinfo);
-    if (rc == GGD_OK) rc = launch_wgrad(ctx, s, N, first, last, zbuf, dzbuf, dout, feat, pos, attrs, wgrad);
+    if (rc == GGD_OK) rc = launch_backward(ctx, s, chain, N, first, last, packed_t, attrs, dattrs, zbuf, dzbuf, dout, dfeat, dinfo);
+    if (rc == GGD_OK) rc = launch_wgrad(ctx, s, chain, N, first, last, zbuf, dzbuf, dout, feat, pos, attrs, wgrad);
   });
   if (rc != GGD_OK) return rc;
   GGD_HIP(hipGetLastError());
   return GGD_OK;
+}
+extern "C" int ggd_decoder_backward_wgrad(ggd_ctx* ctx, void* stream, int32_t N, int32_t chunk, const void* packed_t,
+                                          const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf,
+                                          float* dout, float* dfeat, float* dinfo, const float* feat, const float* pos,
+                                          float* wgrad) {
+  return ggd_decoder_backward_wgrad_chain(ctx, stream, GGD_CHAIN_SEQUENTIAL_REVERSED, N, chunk, packed_t, attrs, dattrs, zbuf, dzbuf,
+                                          dout, dfeat, dinfo, feat, pos, wgrad);
 }
 
 // ---- the decoder at reference precision (split bf16 operands, csrc/ggd_mlp_hl.inc) -------------------------------------------
@@ -609,46 +726,61 @@ extern "C" size_t ggd_decoder_packed_hl_bytes(void) { return (size_t)NHEAD * HLF
 extern "C" size_t ggd_decoder_dzbuf_hl_bytes(int32_t N) { return ggd_decoder_zbuf_bytes(N); }   // dz: one loss-scaled fp16 plane (z: one fp16 plane, ggd_decoder_zbuf_bytes)
 extern "C" size_t ggd_decoder_packed_t_hl_bytes(void) { return (size_t)NHEAD * HLT_HEAD; }
 
+extern "C" int ggd_decoder_pack_hl_chain(ggd_ctx* ctx, void* stream, int32_t chain, const float* const* params40,
+                                         void* packed_hl, void* packed_t_hl) {
+  return decoder_pack_impl<true>(ctx, stream, chain, params40, packed_hl, packed_t_hl, "ggd_decoder_pack_hl");
+}
 extern "C" int ggd_decoder_pack_hl(ggd_ctx* ctx, void* stream, const float* const* params40, void* packed_hl,
                                    void* packed_t_hl) {
-  return decoder_pack_impl<true>(ctx, stream, params40, packed_hl, packed_t_hl, "ggd_decoder_pack_hl");
+  return ggd_decoder_pack_hl_chain(ctx, stream, GGD_CHAIN_SEQUENTIAL_REVERSED, params40, packed_hl, packed_t_hl);
 }
 
 static int hl_attributes(ggd_ctx* ctx) {   // the GELU tables and the four kernels' LDS limits
   const int rt = gelu_tables(ctx);
   if (rt != GGD_OK) return rt;
-  return lds_once(ctx, GGD_ATTR_MLP_HL, {{reinterpret_cast<const void*>(decoder_forward_hl_kernel<false>), HL_LDS_FWD},
-                                         {reinterpret_cast<const void*>(decoder_forward_hl_kernel<true>), HL_LDS_FWD},
-                                         {reinterpret_cast<const void*>(decoder_backward_hl_kernel), HL_LDS_BWD},
-                                         {reinterpret_cast<const void*>(decoder_wgrad_hl_kernel), WGH_LDS}});
+  return lds_once(ctx, GGD_ATTR_MLP_HL, {GGD_CHAIN_LDS_Z(decoder_forward_hl_kernel, HL_LDS_FWD),
+                                         GGD_CHAIN_LDS(decoder_backward_hl_kernel, HL_LDS_BWD),
+                                         GGD_CHAIN_LDS(decoder_wgrad_hl_kernel, WGH_LDS)});
 }
 
-extern "C" int ggd_decoder_forward_hl(ggd_ctx* ctx, void* stream, const float* feat, const float* pos, int32_t N,
-                                      const void* packed_hl, float* attrs, void* zbuf) {
+extern "C" int ggd_decoder_forward_hl_chain(ggd_ctx* ctx, void* stream, int32_t chain, const float* feat, const float* pos,
+                                            int32_t N, const void* packed_hl, float* attrs, void* zbuf) {
   if (!ctx) return GGD_E_INVALID;
+  if (!chain_known(chain)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_forward_hl: unknown decoder chain " + std::to_string(chain));
   if (N < 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_forward_hl: N < 0");
   if (N == 0) return GGD_OK;
   if (!feat || !pos || !packed_hl || !attrs) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_forward_hl: NULL pointer");
   const int rc = hl_attributes(ctx);
   if (rc != GGD_OK) return rc;
   const int grid = slab_grid(N, FWD_WAVES);
-  if (zbuf)
-    hipLaunchKernelGGL(decoder_forward_hl_kernel<true>, dim3(grid), dim3(FWD_THREADS), HL_LDS_FWD,
-                       static_cast<hipStream_t>(stream), feat, pos, N, static_cast<const unsigned char*>(packed_hl), attrs,
-                       static_cast<__bf16*>(zbuf), static_cast<const unsigned char*>(ctx->gelu_tables));
-  else
-    hipLaunchKernelGGL(decoder_forward_hl_kernel<false>, dim3(grid), dim3(FWD_THREADS), HL_LDS_FWD,
-                       static_cast<hipStream_t>(stream), feat, pos, N, static_cast<const unsigned char*>(packed_hl), attrs,
-                       (__bf16*)nullptr, static_cast<const unsigned char*>(ctx->gelu_tables));
+  const int rl = with_chain(ctx, chain, "ggd_decoder_forward_hl", [&](auto c) {
+    constexpr int CH = decltype(c)::value;
+    if (zbuf)
+      hipLaunchKernelGGL((decoder_forward_hl_kernel<CH, true>), dim3(grid), dim3(FWD_THREADS), HL_LDS_FWD,
+                         static_cast<hipStream_t>(stream), feat, pos, N, static_cast<const unsigned char*>(packed_hl), attrs,
+                         static_cast<__bf16*>(zbuf), static_cast<const unsigned char*>(ctx->gelu_tables));
+    else
+      hipLaunchKernelGGL((decoder_forward_hl_kernel<CH, false>), dim3(grid), dim3(FWD_THREADS), HL_LDS_FWD,
+                         static_cast<hipStream_t>(stream), feat, pos, N, static_cast<const unsigned char*>(packed_hl), attrs,
+                         (__bf16*)nullptr, static_cast<const unsigned char*>(ctx->gelu_tables));
+    return GGD_OK;
+  });
+  if (rl != GGD_OK) return rl;
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }
+extern "C" int ggd_decoder_forward_hl(ggd_ctx* ctx, void* stream, const float* feat, const float* pos, int32_t N,
+                                      const void* packed_hl, float* attrs, void* zbuf) {
+  return ggd_decoder_forward_hl_chain(ctx, stream, GGD_CHAIN_SEQUENTIAL_REVERSED, feat, pos, N, packed_hl, attrs, zbuf);
+}
 
-extern "C" int ggd_decoder_backward_wgrad_hl(ggd_ctx* ctx, void* stream, int32_t N, int32_t chunk, const void* packed_t_hl,
-                                             const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf,
-                                             float* dout, float* dfeat, float* dinfo, const float* feat, const float* pos,
-                                             float* wgrad) {
+extern "C" int ggd_decoder_backward_wgrad_hl_chain(ggd_ctx* ctx, void* stream, int32_t chain, int32_t N, int32_t chunk,
+                                                   const void* packed_t_hl, const float* attrs, const float* dattrs,
+                                                   const void* zbuf, void* dzbuf, float* dout, float* dfeat, float* dinfo,
+                                                   const float* feat, const float* pos, float* wgrad) {
   if (!ctx) return GGD_E_INVALID;
+  if (!chain_known(chain))
+    return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_backward_wgrad_hl: unknown decoder chain " + std::to_string(chain));
   if (N < 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_decoder_backward_wgrad_hl: N < 0");
   if (N == 0) return GGD_OK;
   if (!packed_t_hl || !attrs || !dattrs || !zbuf || !dzbuf || !dout || !dfeat || !dinfo || !feat || !pos || !wgrad)
@@ -665,15 +797,27 @@ extern "C" int ggd_decoder_backward_wgrad_hl(ggd_ctx* ctx, void* stream, int32_t
   int* karr = static_cast<int*>(ctx->scratch);
   int* kref = reinterpret_cast<int*>(static_cast<char*>(ctx->scratch) + ggd_align((size_t)NHEAD * nslab * sizeof(int)));
   GGD_HIP(hipMemsetAsync(kref, 0x80, 64, s));     // every byte 0x80: far below any exponent (atomicMax target); < HL_KNONE is never stored
-  chunk_walk(N, chunk, [&](int32_t first, int32_t last) {
-    hipLaunchKernelGGL(decoder_backward_hl_kernel, dim3(slab_grid(last - first, MLP_WAVES)), dim3(MLP_THREADS), HL_LDS_BWD, s, N,
-                       first, last, static_cast<const unsigned char*>(packed_t_hl), attrs, dattrs,
-                       static_cast<const __bf16*>(zbuf), static_cast<__bf16*>(dzbuf), dout, dfeat, dinfo, karr, kref,
-                       static_cast<const unsigned char*>(ctx->gelu_tables));
-    hipLaunchKernelGGL(decoder_wgrad_hl_kernel, dim3(wgrad_chunks(last - first), NHEAD * 4), dim3(WG_THREADS), WGH_LDS, s, N,
-                       first, last, static_cast<const __bf16*>(zbuf), static_cast<const __bf16*>(dzbuf), dout, feat, pos, attrs,
-                       wgrad, karr, kref, static_cast<const unsigned char*>(ctx->gelu_tables));
+  const int rl = with_chain(ctx, chain, "ggd_decoder_backward_wgrad_hl", [&](auto c) {
+    constexpr int CH = decltype(c)::value;
+    chunk_walk(N, chunk, [&](int32_t first, int32_t last) {
+      hipLaunchKernelGGL(decoder_backward_hl_kernel<CH>, dim3(slab_grid(last - first, MLP_WAVES)), dim3(MLP_THREADS), HL_LDS_BWD, s,
+                         N, first, last, static_cast<const unsigned char*>(packed_t_hl), attrs, dattrs,
+                         static_cast<const __bf16*>(zbuf), static_cast<__bf16*>(dzbuf), dout, dfeat, dinfo, karr, kref,
+                         static_cast<const unsigned char*>(ctx->gelu_tables));
+      hipLaunchKernelGGL(decoder_wgrad_hl_kernel<CH>, dim3(wgrad_chunks(last - first), NHEAD * 4), dim3(WG_THREADS), WGH_LDS, s, N,
+                         first, last, static_cast<const __bf16*>(zbuf), static_cast<const __bf16*>(dzbuf), dout, feat, pos, attrs,
+                         wgrad, karr, kref, static_cast<const unsigned char*>(ctx->gelu_tables));
+    });
+    return GGD_OK;
   });
+  if (rl != GGD_OK) return rl;
   GGD_HIP(hipGetLastError());
   return GGD_OK;
+}
+extern "C" int ggd_decoder_backward_wgrad_hl(ggd_ctx* ctx, void* stream, int32_t N, int32_t chunk, const void* packed_t_hl,
+                                             const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf,
+                                             float* dout, float* dfeat, float* dinfo, const float* feat, const float* pos,
+                                             float* wgrad) {
+  return ggd_decoder_backward_wgrad_hl_chain(ctx, stream, GGD_CHAIN_SEQUENTIAL_REVERSED, N, chunk, packed_t_hl, attrs, dattrs, zbuf,
+                                             dzbuf, dout, dfeat, dinfo, feat, pos, wgrad);
 }

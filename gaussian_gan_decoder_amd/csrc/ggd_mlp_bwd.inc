@@ -127,23 +127,32 @@ __device__ __forceinline__ void add_input_grads(const f4 (&acc)[2][8], int head,
 }
 
 // Gradient at head `head`'s raw output for one point (the lane of group 0 that owns its output rows 0..3): dattrs of the head's
-// slots, plus what the later heads sent back through `info`, through the derivative of the head's activation; stored to dout
+// slots, plus what the later heads sent back through `info` (if the chain has a later head that reads them: chain_reads_back),
+// through the derivative of the head's activation; stored to dout
 // [head][point][4] (the weight-gradient kernel's layer-4 operand) and returned.
+template <int CHAIN>
 __device__ __forceinline__ f4 head_out_grad(int head, int64_t pt, int N, const float* __restrict__ attrs,
                                             const float* __restrict__ dattrs, const float* dinfo, float* __restrict__ dout) {
-  const int a0 = head_a0(head), od = head_od(head);   // first attrs slot, output width
+  const int attr = chain_attr(CHAIN, head);          // the attribute decoded at this position: its columns, its activation
+  const int a0 = head_a0(attr), od = head_od(attr);   // first attrs slot, output width
+  // where the later positions read this one's outputs: info slot 3 + its n_extra -- in chain 0 that IS a0 (said so: computed as
+  // a second select chain, the chain-0 kernels come out as other code)
+  const int slot = 3 + (CHAIN == 0 ? a0 : chain_nx(CHAIN, head));
+  const bool back = chain_reads_back(CHAIN, head);    // does a later position read them at all?
   f4 d = {0, 0, 0, 0};
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     if (e < od) {
       float v = dattrs[pt * 16 + a0 + e];
-      if (head == 4) {
+      if (!back && attr == 4) {
         v *= 0.01f;                                   // xyz = head * 0.01 + position
       } else {
-        v += dinfo[pt * 16 + 3 + a0 + e];             // + what the later heads sent back through `info`
-        if (head == 3) {                              // scale = -softplus(s + 5) - 2.5
-          const float sp = -attrs[pt * 16 + a0 + e] - 2.5f;
+        if (back) v += dinfo[pt * 16 + slot + e];     // + what the later heads sent back through `info`
+        if (attr == 3) {                              // scale = -softplus(s + 5) - 2.5 (chains 1, 2: - 2)
+          const float sp = -attrs[pt * 16 + a0 + e] - chain_scale_c(CHAIN);
           v *= -(1.0f - expf(-sp));                   // -sigmoid(s + 5) = -(1 - exp(-softplus))
+        } else if (attr == 4) {
+          v *= 0.01f;                                 // xyz as the FIRST head (chain 1): 0.01 (dattrs + dinfo)
         }
       }
       d[e] = v;
@@ -153,6 +162,7 @@ __device__ __forceinline__ f4 head_out_grad(int head, int64_t pt, int N, const f
   return d;
 }
 
+template <int CHAIN>
 __global__ __launch_bounds__(MLP_THREADS, MLP_THREADS / 256) void decoder_backward_kernel(
     int N, int first, int last, const unsigned char* __restrict__ packed_t, const float* __restrict__ attrs,
     const float* __restrict__ dattrs, const _Float16* __restrict__ zbuf, __bf16* __restrict__ dzbuf,
@@ -189,7 +199,7 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_THREADS / 256) void decoder_backwa
       for (int c = 0; c < 2; ++c) {
         const int64_t pt = p0 + 16 * c + j;
         f4 d = {0, 0, 0, 0};
-        if (g == 0 && pt < cend) d = head_out_grad(head, pt, N, attrs, dattrs, dinfo, dout);
+        if (g == 0 && pt < cend) d = head_out_grad<CHAIN>(head, pt, N, attrs, dattrs, dinfo, dout);
         const f4 z = {0, 0, 0, 0};
         bin[c][0] = pack8(d, z);
         bin[c][1] = bin[c][0]; bin[c][2] = bin[c][0]; bin[c][3] = bin[c][0];  // unused k blocks

@@ -176,7 +176,7 @@ __device__ __forceinline__ void gelu_split(const f4 (&acc)[2][8], bf16x8 (&ohi)[
 // Forward.  Same point / wave / register mapping as decoder_forward_kernel (32-point slabs, D layout of a layer == B
 // layout of the next); the loop nest is batch (256 points per workgroup) -> head -> layer, with the layer's weights in
 // buffer (layer - 1) % 2 and the next step's weights streaming into the other one.
-template <bool STORE_Z>
+template <int CHAIN, bool STORE_Z>
 __global__ __launch_bounds__(FWD_THREADS) void decoder_forward_hl_kernel(const float* __restrict__ feat,
                                                                          const float* __restrict__ pos, int N,
                                                                          const unsigned char* __restrict__ packed,
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(FWD_THREADS) void decoder_forward_hl_kernel(const f
   for (int b = 0; b < nbatch; ++b) {
     const int64_t p0 = cbeg + (int64_t)b * BATCH + (int64_t)wv * SLAB;
     for (int head = 0; head < NHEAD; ++head) {
-      const int n_extra = GGD_HEAD_A0(head);   // = head_a0(head), expanded in place
+      const int n_extra = GGD_CHAIN_NX(CHAIN, head);   // = chain_nx(CHAIN, head), expanded in place
       const unsigned char* hw = packed + (size_t)head * HLF_HEAD;
       const float* b1 = biases + head * HL_NBIAS;
       const float* b2 = b1 + HID;
@@ -230,7 +230,14 @@ __global__ __launch_bounds__(FWD_THREADS) void decoder_forward_hl_kernel(const f
             const int q = 4 * g + e;  // info slot
             float v = 0.0f;
             if (q < 3) v = pos[pt * 3 + q];
-            else if (q - 3 < n_extra) v = attrs[pt * 16 + (q - 3)];
+            else if (q - 3 < n_extra) {
+              int col = GGD_CHAIN_COL(CHAIN, q - 3);
+              // (chain 1's four columns are four addresses per point tile, the same for every head: left alone they are
+              // hoisted out of the head loop and spilled -- 18 VGPRs in decoder_forward_hl_kernel<1, true>; opaque, they are
+              // formed again from the row's address where they are used)
+              if (CHAIN == 1) asm volatile("" : "+v"(col));
+              v = attrs[pt * 16 + col];
+            }
             inf[e] = v;
           }
         }
@@ -288,6 +295,7 @@ __global__ __launch_bounds__(FWD_THREADS) void decoder_forward_hl_kernel(const f
           out[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bhi[1][s], out[1], 0, 0, 0);
         }
       }
+      const int attr = GGD_CHAIN_ATTR(CHAIN, head);   // the attribute this position decodes (see decoder_forward_kernel)
       if (g == 0) {   // lane group 0 holds output features 0..3 of point j (D rows 0..3)
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -295,18 +303,18 @@ __global__ __launch_bounds__(FWD_THREADS) void decoder_forward_hl_kernel(const f
           if (pt >= cend) continue;
           float* arow = attrs + pt * 16;
           const f4 o = out[c];
-          if (head == 0) {
+          if (attr == 0) {
             arow[0] = o[0]; arow[1] = o[1]; arow[2] = o[2];
-          } else if (head == 1) {
+          } else if (attr == 1) {
             arow[3] = o[0];
-          } else if (head == 2) {
+          } else if (attr == 2) {
             arow[4] = o[0]; arow[5] = o[1]; arow[6] = o[2]; arow[7] = o[3];
-          } else if (head == 3) {  // -softplus(s + 5) - 2.5   (torch.nn.Softplus: beta 1, threshold 20)
+          } else if (attr == 3) {  // -softplus(s + 5) - 2.5, or - 2 (chain_scale_c)   (torch.nn.Softplus: beta 1, threshold 20)
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
               const float v = o[q] + 5.0f;
               const float sp = v > 20.0f ? v : __logf(1.0f + __expf(v));   // <= 2e-7 absolute (see decoder_forward_kernel); this tier's bar is 1e-4
-              arow[8 + q] = -sp - 2.5f;
+              arow[8 + q] = -sp - chain_scale_c(CHAIN);
             }
           } else {                 // xyz = head * 0.01 + position
             arow[11] = o[0] * 0.01f + pos[pt * 3]; arow[12] = o[1] * 0.01f + pos[pt * 3 + 1];
@@ -350,6 +358,7 @@ __device__ __forceinline__ void gelu_bwd_split(const f4 (&dh)[2][8], const bf16x
 
 // Backward on split operands: the loop nest of decoder_backward_kernel turned batch -> head (last first) -> layer (last
 // first), weights cycled as in the forward: W4^T -> buffer 0, W3^T -> 1, W2^T -> 0, W1^T -> 1.
+template <int CHAIN>
 __global__ __launch_bounds__(MLP_THREADS) void decoder_backward_hl_kernel(
     int N, int first, int last, const unsigned char* __restrict__ packed_t, const float* __restrict__ attrs,
     const float* __restrict__ dattrs, const __bf16* __restrict__ zbuf, __bf16* __restrict__ dzbuf,
@@ -392,7 +401,7 @@ __global__ __launch_bounds__(MLP_THREADS) void decoder_backward_hl_kernel(
       for (int c = 0; c < 2; ++c) {
         const int64_t pt = p0 + 16 * c + j;
         f4 d = {0, 0, 0, 0};
-        if (g == 0 && pt < cend) d = head_out_grad(head, pt, N, attrs, dattrs, dinfo, dout);
+        if (g == 0 && pt < cend) d = head_out_grad<CHAIN>(head, pt, N, attrs, dattrs, dinfo, dout);
         const f4 z = {0, 0, 0, 0};
         split8(d, z, bhi[c][0], blo[c][0]);
         bhi[c][1] = bhi[c][0]; bhi[c][2] = bhi[c][0]; bhi[c][3] = bhi[c][0];  // unused k blocks
@@ -452,6 +461,7 @@ __global__ __launch_bounds__(MLP_THREADS) void decoder_backward_hl_kernel(
 // LDS untouched (layer 4: dout * 2^(4 - e)); B = gelu(z) at fp32 accuracy from the fp16 z plane, times the slab's 2^(e - e_max),
 // rounded to fp16 (layer 1: the fp32 decoder inputs); one v_mfma_f32_16x16x32_f16 per product, 2^(e_max - 4) applied to the
 // sums in the epilogue.
+template <int CHAIN>
 __global__ __launch_bounds__(WG_THREADS, 4) void decoder_wgrad_hl_kernel(
     int N, int first, int last, const __bf16* __restrict__ zbuf, const __bf16* __restrict__ dzbuf, const float* __restrict__ dout,
     const float* __restrict__ feat, const float* __restrict__ pos, const float* __restrict__ attrs,
@@ -477,7 +487,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void decoder_wgrad_hl_kernel(
   const float* dout_h = dout + (size_t)head * N * 4;
   const int* ks = karr + (size_t)head * (((int64_t)N + SLAB - 1) / SLAB);
   switch (layer) {
-    case 1: wgrad_layer<1, true>(smem, N, pbeg, pend, dz, nullptr, nullptr, feat, pos, attrs, out + WG_OFF_W1, out + WG_OFF_B1, ks, km, phi_lin); break;
+    case 1: wgrad_layer<1, true, CHAIN>(smem, N, pbeg, pend, dz, nullptr, nullptr, feat, pos, attrs, out + WG_OFF_W1, out + WG_OFF_B1, ks, km, phi_lin); break;
     case 2: wgrad_layer<2, true>(smem, N, pbeg, pend, dz + LS, z, nullptr, nullptr, nullptr, nullptr, out + WG_OFF_W2, out + WG_OFF_B2, ks, km, phi_lin); break;
     case 3: wgrad_layer<3, true>(smem, N, pbeg, pend, dz + 2 * LS, z + LS, nullptr, nullptr, nullptr, nullptr, out + WG_OFF_W3, out + WG_OFF_B3, ks, km, phi_lin); break;
     default: wgrad_layer<4, true>(smem, N, pbeg, pend, nullptr, z + 2 * LS, dout_h, nullptr, nullptr, nullptr, out + WG_OFF_W4, out + WG_OFF_B4, ks, km, phi_lin); break;

@@ -1,6 +1,7 @@
 // ggd_mlp_pack.inc -- builds the decoder's weight images on the device (included by ggd_mlp.hip, after ggd_mlp_hl.inc).
 //
-// One launch turns the 40 parameter tensors of a SequentialDecoderReverse (per head W1 b1 W2 b2 W3 b3 W4 b4, fp32,
+// One launch turns the 40 parameter tensors of a decoder module (per head, in the EXECUTION ORDER of its chain -- ggd_mlp.hip:
+// THE THREE CHAINS; `chain` is a run-time argument here, it only sets the tensors' widths -- W1 b1 W2 b2 W3 b3 W4 b4, fp32,
 // row-major [out][in] as torch.nn.Linear stores them) into the forward image (ggd_decoder_packed_bytes) and the
 // transposed image the backward kernel reads (ggd_decoder_packed_t_bytes).  Training repacks after EVERY optimizer
 // step; done with torch ops (pad / permute / cast / concatenate) that was ~400 tiny launches per step.
@@ -72,7 +73,7 @@ __device__ __forceinline__ void pack_store(unsigned char* img, int dst, float v,
 
 // One thread per LOGICAL element of a head: [forward image: PARTS x 4 matrices | biases | transposed image: PARTS x 4 matrices]
 template <bool HL>
-__global__ __launch_bounds__(256) void decoder_pack_kernel(ggd_pack_ptrs ptrs, unsigned char* __restrict__ packed,
+__global__ __launch_bounds__(256) void decoder_pack_kernel(ggd_pack_ptrs ptrs, int chain, unsigned char* __restrict__ packed,
                                                            unsigned char* __restrict__ packed_t) {
   constexpr int PARTS = HL ? 2 : 1;
   constexpr int FWD = PARTS * pack_elems(0), T = PARTS * pack_elems(1), PER_HEAD = FWD + PACK_BIAS + T;
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(256) void decoder_pack_kernel(ggd_pack_ptrs ptrs, u
     e -= FWD;
     float v = 0.0f;
     if (e < 3 * HID) v = (HL ? 1.0f : 0.5f) * P[1 + 2 * (e / HID)][e % HID];
-    else if (e - 3 * HID < head_od(head)) v = P[7][e - 3 * HID];
+    else if (e - 3 * HID < chain_od(chain, head)) v = P[7][e - 3 * HID];
     reinterpret_cast<float*>(fwd + 2 * FWD)[e] = v;
     return;
   }
@@ -108,7 +109,7 @@ __global__ __launch_bounds__(256) void decoder_pack_kernel(ggd_pack_ptrs ptrs, u
       float v = 0.0f;
       if (c < M.K) {
         const int k = pack_perm_col(c);
-        const int out_n = M.src == 6 ? head_od(head) : HID, in_n = M.src == 0 ? head_in(head) : HID;   // the tensor is [out_n][in_n]
+        const int out_n = M.src == 6 ? chain_od(chain, head) : HID, in_n = M.src == 0 ? chain_in(chain, head) : HID;   // the tensor is [out_n][in_n]
         const int o = image ? k : r, i = image ? r : k;
         if (o < out_n && i < in_n) v = P[M.src][o * in_n + i];
       }

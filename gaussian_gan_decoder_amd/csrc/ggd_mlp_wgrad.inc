@@ -60,7 +60,7 @@ __device__ __forceinline__ h16x8 wg_pack8h(const f4& a, const f4& b, float k) {
   return (h16x8){h16(a[0] * k), h16(a[1] * k), h16(a[2] * k), h16(a[3] * k),
                     h16(b[0] * k), h16(b[1] * k), h16(b[2] * k), h16(b[3] * k)};
 }
-template <int LAYER, bool F16 = false>
+template <int LAYER, bool F16 = false, int CHAIN = 0 /* read by LAYER 1 only: its input columns */>
 __device__ __forceinline__ void wgrad_layer(unsigned char* smem, int N, int64_t pbeg, int64_t pend,
                                             const __bf16* __restrict__ dz, const __bf16* __restrict__ zprev,
                                             const float* __restrict__ dout, const float* __restrict__ feat,
@@ -143,15 +143,26 @@ __device__ __forceinline__ void wgrad_layer(unsigned char* smem, int N, int64_t 
           if (q < 4) {
             rf[t][0] = *reinterpret_cast<const f4*>(feat + p * 32 + 8 * q);
             rf[t][1] = *reinterpret_cast<const f4*>(feat + p * 32 + 8 * q + 4);
-          } else if (q == 4) {   // columns 32..39: position, attrs[0..4]
+          } else if (CHAIN == 0 && q == 4) {   // columns 32..39: position, attrs[0..4]
             const f4 a0 = *reinterpret_cast<const f4*>(attrs + p * 16);
             rf[t][0] = (f4){pos[p * 3], pos[p * 3 + 1], pos[p * 3 + 2], a0[0]};
             rf[t][1] = (f4){a0[1], a0[2], a0[3], attrs[p * 16 + 4]};
-          } else if (q == 5) {   // columns 40..47: attrs[5..10]
+          } else if (CHAIN == 0 && q == 5) {   // columns 40..47: attrs[5..10]
             const f4 a1 = *reinterpret_cast<const f4*>(attrs + p * 16 + 4);
             const f4 a2 = *reinterpret_cast<const f4*>(attrs + p * 16 + 8);
             rf[t][0] = (f4){a1[1], a1[2], a1[3], a2[0]};
             rf[t][1] = (f4){a2[1], a2[2], 0.f, 0.f};
+          } else if (CHAIN == 1 && q == 4) {   // chain 1, columns 32..39: position, attrs[11 12 13 | 8 9] (GGD_CHAIN_COL)
+            const f4 a2 = *reinterpret_cast<const f4*>(attrs + p * 16 + 8);
+            const f4 a3 = *reinterpret_cast<const f4*>(attrs + p * 16 + 12);
+            rf[t][0] = (f4){pos[p * 3], pos[p * 3 + 1], pos[p * 3 + 2], a2[3]};
+            rf[t][1] = (f4){a3[0], a3[1], a2[0], a2[1]};
+          } else if (CHAIN == 1 && q == 5) {   // chain 1, columns 40..47: attrs[10 | 4 5 6 7 | 3]
+            const f4 a1 = *reinterpret_cast<const f4*>(attrs + p * 16 + 4);
+            rf[t][0] = (f4){attrs[p * 16 + 10], a1[0], a1[1], a1[2]};
+            rf[t][1] = (f4){a1[3], attrs[p * 16 + 3], 0.f, 0.f};
+          } else if (CHAIN == 2 && q == 4) {   // parallel: the position is every head's whole info vector
+            rf[t][0] = (f4){pos[p * 3], pos[p * 3 + 1], pos[p * 3 + 2], 0.f};
           }
         }
       } else {
@@ -262,6 +273,7 @@ __device__ __forceinline__ void wgrad_layer(unsigned char* smem, int N, int64_t 
   }
 }
 
+template <int CHAIN>
 __global__ __launch_bounds__(WG_THREADS, 4) void decoder_wgrad_kernel(
     int N, int first, int last, const __bf16* __restrict__ zbuf, const __bf16* __restrict__ dzbuf, const float* __restrict__ dout,
     const float* __restrict__ feat, const float* __restrict__ pos, const float* __restrict__ attrs,
@@ -278,7 +290,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void decoder_wgrad_kernel(
   const __bf16* dz = dzbuf + (size_t)head * 3 * LS;
   const float* dout_h = dout + (size_t)head * N * 4;
   switch (layer) {
-    case 1: wgrad_layer<1>(smem, N, pbeg, pend, dz, nullptr, nullptr, feat, pos, attrs, out + WG_OFF_W1, out + WG_OFF_B1); break;
+    case 1: wgrad_layer<1, false, CHAIN>(smem, N, pbeg, pend, dz, nullptr, nullptr, feat, pos, attrs, out + WG_OFF_W1, out + WG_OFF_B1); break;
     case 2: wgrad_layer<2>(smem, N, pbeg, pend, dz + LS, z, nullptr, nullptr, nullptr, nullptr, out + WG_OFF_W2, out + WG_OFF_B2); break;
     case 3: wgrad_layer<3>(smem, N, pbeg, pend, dz + 2 * LS, z + LS, nullptr, nullptr, nullptr, nullptr, out + WG_OFF_W3, out + WG_OFF_B3); break;
     default: wgrad_layer<4>(smem, N, pbeg, pend, nullptr, z + 2 * LS, dout_h, nullptr, nullptr, nullptr, out + WG_OFF_W4, out + WG_OFF_B4); break;

@@ -233,7 +233,7 @@ class SequentialDecoderReverse(nn.Module):
         "panohead", D: PanoHead tri-grids [3, 32 * D, H, W] (G.rendering_kwargs["triplane_depth"],
         sequential_decoder_reverse.py:42-50).  use_xyz_embedding: the reference's optional positional encoding of the
         positions (sequential_decoder_reverse.py:21-22,63-66; off by default in main/train_pano2gaussian_decoder.py:46);
-        PyTorch modules only -- the fused MFMA decoder takes the 3-vector form."""
+        PyTorch modules only -- the fused MFMA decoder (all three decoder types) takes the 3-vector form."""
         super().__init__()
         self.use_xyz_embedding = bool(use_xyz_embedding)
         f = plane_channels + _info_dim(position_dim, self.use_xyz_embedding)
@@ -297,8 +297,10 @@ class SequentialDecoder(nn.Module):
     def activate_scale(self, scale):
         return -self.scale_activation(scale + 5) - 2
 
-    def forward(self, feature_planes, init_position):
-        pf = triplane_mean(feature_planes, init_position, self.box_warp, self.plane_axes, self.triplane_depth)
+    def forward(self, feature_planes, init_position, features=None):
+        """features: as in SequentialDecoderReverse.forward (the plane-mean features [N, C], gathered already)"""
+        pf = features if features is not None else \
+            triplane_mean(feature_planes, init_position, self.box_warp, self.plane_axes, self.triplane_depth)
         info = embed_positions(init_position) if self.use_xyz_embedding else init_position
         xyz = self.xyz_decoder(pf, info) * 0.01 + init_position
         info = torch.concat([info, xyz], dim=-1)
@@ -334,8 +336,10 @@ class ParallelDecoder(nn.Module):
     def activate_scale(self, scale):
         return -self.scale_activation(scale + 5) - 2
 
-    def forward(self, feature_planes, init_position):
-        pf = triplane_mean(feature_planes, init_position, self.box_warp, self.plane_axes, self.triplane_depth)
+    def forward(self, feature_planes, init_position, features=None):
+        """features: as in SequentialDecoderReverse.forward (the plane-mean features [N, C], gathered already)"""
+        pf = features if features is not None else \
+            triplane_mean(feature_planes, init_position, self.box_warp, self.plane_axes, self.triplane_depth)
         pos = embed_positions(init_position) if self.use_xyz_embedding else init_position
         return SimpleNamespace(xyz=self.xyz_decoder(pf, pos) * 0.01 + init_position,
                                scale=self.activate_scale(self.scale_decoder(pf, pos)),
@@ -343,3 +347,7 @@ class ParallelDecoder(nn.Module):
                                color=self.color_decoder(pf, pos))
 
     get_params_custom = SequentialDecoderReverse.get_params_custom
+
+
+# the reference's --decoder_type option (main/train_pano2gaussian_decoder.py:45,170-192) -> the module
+DECODER_TYPES = {"sequential_reversed": SequentialDecoderReverse, "sequential": SequentialDecoder, "parallel": ParallelDecoder}

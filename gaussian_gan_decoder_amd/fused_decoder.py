@@ -1,8 +1,9 @@
 """Fused decoder: tri-plane gather + the 5 chained MLP heads as ONE MFMA kernel with 16-bit operands
 (csrc/ggd_mlp.hip; SURVEY.md section 8f row 1, BASELINE config 3).
 
-`FusedDecoder(decoder)` (inference, no autograd) wraps a `SequentialDecoderReverse` (same parameters; call `.repack()` after
-they change) and returns the same namespace (xyz, scale, rotation, opacity, color).  `FusedTrainDecoder` is the training
+`FusedDecoder(decoder)` (inference, no autograd) wraps a `SequentialDecoderReverse`, `SequentialDecoder` or `ParallelDecoder`
+(the reference's three decoder types: one set of kernels, one compile-time chain each -- _CHAINS below; same parameters; call
+`.repack()` after they change) and returns the same namespace (xyz, scale, rotation, opacity, color).  `FusedTrainDecoder` is the training
 front-end: the same forward with the pre-activations kept, and `FusedDecoderFn`'s backward and weight-gradient kernels.
 Numerics of the forward: weights and activations are rounded to f16 (11 significant bits; inputs and weights clamped to
 +-65504) at every layer input, accumulation and bias in fp32, GELU as a degree-6 polynomial in packed f16 (<= 1.7e-3, mean
@@ -16,7 +17,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _capi
-from .decoder import SequentialDecoderReverse, triplane_mean
+from .decoder import ParallelDecoder, SequentialDecoder, SequentialDecoderReverse, triplane_mean
 
 HID = 128
 ROW1, ROW2 = 64, 128                # 16-bit elements per weight row (no padding; 16-byte slots swizzled, see _swizzle_rows)
@@ -31,29 +32,63 @@ def _permute_blocks(w: torch.Tensor) -> torch.Tensor:
     return w[:, idx]
 
 
-# THE HEAD CHAIN (csrc/ggd_mlp.hip: head_a0 / head_od): colour, opacity, rotation, scale, xyz; head h writes _OUT_DIM[h] values at
-# attrs column _N_EXTRA[h] and sees the _N_EXTRA[h] columns in front of it behind the 32 plane channels and the position
-_HEADS = ("color_decoder", "opacity_decoder", "rotation_decoder", "scale_decoder", "xyz_decoder")
-_OUT_DIM = (3, 1, 4, 3, 3)
-_N_EXTRA = tuple(sum(_OUT_DIM[:h]) for h in range(5))   # 0, 3, 4, 8, 11: chained inputs of each head (outputs of the earlier heads)
-_IN_FEATURES = tuple(32 + 3 + n for n in _N_EXTRA)      # 35, 38, 39, 43, 46
+# THE CHAINS (csrc/ggd_mlp.hip: THE THREE CHAINS; include/ggd_raster.h: ggd_decoder_chain).  The five ATTRIBUTES keep their public
+# attrs columns whatever the chain: colour 0..2, opacity 3, rotation 4..7, scale 8..10, xyz 11..13.  A chain is the order in which
+# they are decoded and what each head sees behind the 32 plane channels and the position: the outputs of the heads executed before
+# it, in execution order (the module's own torch.concat order).  Everything per head -- the 40 tensors handed to the pack kernel,
+# the weight-gradient blocks -- is in EXECUTION order.
+_ATTRS = ("color_decoder", "opacity_decoder", "rotation_decoder", "scale_decoder", "xyz_decoder")
+_ATTR_OD = (3, 1, 4, 3, 3)
+_ATTR_A0 = (0, 3, 4, 8, 11)
+
+
+class _Chain:
+    """id: ggd_decoder_chain; order: the attributes in execution order; chained: does a head see the earlier heads' outputs"""
+
+    def __init__(self, cid: int, name: str, order, chained: bool):
+        self.id, self.name, self.order = cid, name, tuple(order)
+        self.heads = tuple(_ATTRS[a] for a in self.order)
+        self.out_dim = tuple(_ATTR_OD[a] for a in self.order)
+        seen = tuple(sum(self.out_dim[:h]) for h in range(5))
+        self.n_extra = seen if chained else (0,) * 5          # chained inputs of each head
+        self.in_features = tuple(32 + 3 + n for n in self.n_extra)
+        # info slot 3 + k -> the public attrs column it reads
+        self.cols = tuple(_ATTR_A0[a] + e for a in self.order[:4] for e in range(_ATTR_OD[a])) if chained else ()
+
+
+_CHAINS = {
+    SequentialDecoderReverse: _Chain(0, "sequential_reversed", (0, 1, 2, 3, 4), True),   # colour, opacity, rotation, scale, xyz
+    SequentialDecoder: _Chain(1, "sequential", (4, 3, 2, 1, 0), True),                   # xyz, scale, rotation, opacity, colour
+    ParallelDecoder: _Chain(2, "parallel", (4, 3, 2, 1, 0), False),
+}
+_CHAIN_BY_ID = {c.id: c for c in _CHAINS.values()}
+# chain 0 under its earlier names
+_HEADS = _CHAINS[SequentialDecoderReverse].heads
+_OUT_DIM = _CHAINS[SequentialDecoderReverse].out_dim            # 3, 1, 4, 3, 3
+_N_EXTRA = _CHAINS[SequentialDecoderReverse].n_extra            # 0, 3, 4, 8, 11
+_IN_FEATURES = _CHAINS[SequentialDecoderReverse].in_features    # 35, 38, 39, 43, 46
 ROW4T = 32 + 8
 
 
-def _check_decoder(decoder) -> None:
-    """The kernels hard-code SequentialDecoderReverse's chain (colour -> opacity -> rotation -> scale -> xyz, each head fed
-    the earlier heads' outputs) and its scale activation -softplus(s + 5) - 2.5: anything else -- SequentialDecoder (xyz
-    first, -2), ParallelDecoder (no chaining), the positional-encoding option -- would pack without complaint (same head
-    names, first-layer widths inside 35..48) and then decode silently wrong attributes and gradients."""
-    if not isinstance(decoder, SequentialDecoderReverse):
-        raise TypeError(f"the fused decoder kernels implement SequentialDecoderReverse only (got {type(decoder).__name__}); "
-                        "use the PyTorch module for the other decoder types")
+def _check_decoder(decoder) -> _Chain:
+    """The module's chain (by its exact type: the three chains differ in the order of the heads, in what a head sees and in the
+    constant of the scale activation, none of which the parameters show), after checking what the kernels build in: 3-vector
+    positions (use_xyz_embedding has 63 position columns, which do not fit layer 1's K = 64 image), hidden_dim 128, and that
+    type's first-layer widths -- anything else would pack without complaint and decode silently wrong attributes."""
+    chain = _CHAINS.get(type(decoder))
+    if chain is None:
+        raise TypeError("the fused decoder kernels implement SequentialDecoderReverse, SequentialDecoder and ParallelDecoder "
+                        f"(got {type(decoder).__name__}); use the PyTorch module for anything else")
     if getattr(decoder, "use_xyz_embedding", False):
         raise ValueError("the fused decoder kernels do not implement use_xyz_embedding; use the PyTorch module")
-    got = tuple(getattr(decoder, n).backbone[0].in_features for n in _HEADS)
-    if got != _IN_FEATURES:
-        raise ValueError(f"fused decoder: first-layer widths {got} are not SequentialDecoderReverse's {_IN_FEATURES} "
+    hidden = tuple(getattr(decoder, n).backbone[0].out_features for n in chain.heads)
+    if hidden != (HID,) * 5:
+        raise ValueError(f"the fused decoder kernels implement hidden_dim {HID} (got {hidden[0]}); use the PyTorch module")
+    got = tuple(getattr(decoder, n).backbone[0].in_features for n in chain.heads)
+    if got != chain.in_features:
+        raise ValueError(f"fused decoder: first-layer widths {got} are not {type(decoder).__name__}'s {chain.in_features} "
                          "(32 plane channels, 3-D positions)")
+    return chain
 
 
 def _swizzle_rows(wp: torch.Tensor) -> torch.Tensor:
@@ -70,18 +105,19 @@ def _swizzle_rows(wp: torch.Tensor) -> torch.Tensor:
 
 
 def _head_tensors(decoder):
-    """[(W1,b1,W2,b2,W3,b3,W4,b4)] * 5 in head order."""
-    _check_decoder(decoder)
+    """[(W1,b1,W2,b2,W3,b3,W4,b4)] * 5 in the execution order of the decoder's chain."""
+    chain = _check_decoder(decoder)
     out = []
-    for name in _HEADS:
+    for name in chain.heads:
         bb = getattr(decoder, name).backbone
         out.append(tuple(t for k in (0, 2, 4, 6) for t in (bb[k].weight, bb[k].bias)))
     return out
 
 
-def pack_weights(decoder: SequentialDecoderReverse) -> torch.Tensor:
+def pack_weights(decoder) -> torch.Tensor:
     """-> uint8 tensor of ggd_decoder_packed_bytes(): per head [W1 128x64 | W2 128x128 | W3 128x128 | W4 16x128] f16 (clamped
-    to +-65504, slots swizzled), then b1 b2 b3 [128] and b4 [16] fp32; W1 .. W3 and b1 .. b3 halved."""
+    to +-65504, slots swizzled), then b1 b2 b3 [128] and b4 [16] fp32; W1 .. W3 and b1 .. b3 halved.  Heads in the execution
+    order of the decoder's chain; W1's columns as the module has them (info slots in its own concat order)."""
     dev = next(decoder.parameters()).device
     chunks = []
     for (w1, b1, w2, b2, w3, b3, w4, b4) in _head_tensors(decoder):
@@ -103,7 +139,7 @@ def pack_weights(decoder: SequentialDecoderReverse) -> torch.Tensor:
     return packed
 
 
-def pack_weights_t(decoder: SequentialDecoderReverse) -> torch.Tensor:
+def pack_weights_t(decoder) -> torch.Tensor:
     """Transposed weight image for ggd_decoder_backward: per head [W4^T 128x40 | W3^T 128x128 | W2^T 128x128 |
     W1^T 64x128] bf16, every row's K (= the layer's OUTPUT features) permuted like the forward image; the K = 128 rows
     swizzled like the forward image, W4^T rows padded (32 + 8) and not swizzled."""
@@ -137,10 +173,12 @@ def _check_precision(precision: str) -> bool:
 
 
 def device_pack(decoder, params=None, buffers=None, hl: bool = False):
-    """(packed, packed_t) built by the library's pack kernel from the decoder's 40 parameter tensors (head order colour,
-    opacity, rotation, scale, xyz; W1 b1 .. W4 b4).  hl=False: the bf16 images -- same bytes as pack_weights /
+    """(packed, packed_t) built by the library's pack kernel from the decoder's 40 parameter tensors (heads in the execution
+    order of its chain -- colour, opacity, rotation, scale, xyz for SequentialDecoderReverse, the reverse for the other two;
+    W1 b1 .. W4 b4).  hl=False: the bf16 images -- same bytes as pack_weights /
     pack_weights_t, which stay the host-side statement of that format; hl=True: the split (hi + lo) images of the
     reference-precision kernels (csrc/ggd_mlp_hl.inc).  `buffers`: a previous result to overwrite in place."""
+    chain = _check_decoder(decoder)
     if params is None:
         params = [t for head in _head_tensors(decoder) for t in head]
     dev = params[0].device
@@ -155,9 +193,9 @@ def device_pack(decoder, params=None, buffers=None, hl: bool = False):
         buffers = (torch.empty((sizes[0],), dtype=torch.uint8, device=dev),
                    torch.empty((sizes[1],), dtype=torch.uint8, device=dev))
     table = (C.c_void_p * 40)(*[p.data_ptr() for p in ps])
-    fn = cx.lib.ggd_decoder_pack_hl if hl else cx.lib.ggd_decoder_pack
+    fn = cx.lib.ggd_decoder_pack_hl_chain if hl else cx.lib.ggd_decoder_pack_chain
     with torch.cuda.device(dev):
-        cx.check(fn(cx.handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), table,
+        cx.check(fn(cx.handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), chain.id, table,
                     C.c_void_p(buffers[0].data_ptr()), C.c_void_p(buffers[1].data_ptr())))
     return buffers
 
@@ -169,12 +207,12 @@ WGRAD_CHUNK = int(_os.environ.get("GGD_WGRAD_CHUNK", "0"))
 
 
 class FusedDecoderFn(torch.autograd.Function):
-    """attrs[N,16] = fused 5-head decoder(feats[N,32], pos[N,3]; 40 weight/bias tensors), differentiable w.r.t. feats
-    and the parameters.  Forward and activation-backward are the bf16-MFMA kernels; the weight gradients are split-K
+    """attrs[N,16] = fused 5-head decoder(feats[N,32], pos[N,3]; 40 weight/bias tensors in the execution order of chain
+    `chain_id`), differentiable w.r.t. feats and the parameters.  Forward and activation-backward are the bf16-MFMA kernels; the weight gradients are split-K
     GEMMs over the kept pre-activations (bf16)."""
 
     @staticmethod
-    def forward(ctx, feats, pos, packed, packed_t, hl, *params):
+    def forward(ctx, feats, pos, packed, packed_t, hl, chain_id, *params):
         dev = feats.device
         feats = feats.contiguous().float()
         pos = pos.contiguous().float()
@@ -183,9 +221,9 @@ class FusedDecoderFn(torch.autograd.Function):
         attrs = torch.empty((n, 16), dtype=torch.float32, device=dev)
         # 16-point blocks (ggd_decoder_zbuf_bytes); f16 values in both tiers (opaque here)
         zbuf = torch.empty((5, 3, (n + 15) // 16 * 16, HID), dtype=torch.bfloat16, device=dev)
-        fwd = cx.lib.ggd_decoder_forward_hl if hl else cx.lib.ggd_decoder_forward_train
+        fwd = cx.lib.ggd_decoder_forward_hl_chain if hl else cx.lib.ggd_decoder_forward_train_chain
         with torch.cuda.device(dev):
-            cx.check(fwd(cx.handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(feats.data_ptr()),
+            cx.check(fwd(cx.handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), int(chain_id), C.c_void_p(feats.data_ptr()),
                          C.c_void_p(pos.data_ptr()), n, C.c_void_p(packed.data_ptr()), C.c_void_p(attrs.data_ptr()),
                          C.c_void_p(zbuf.data_ptr())))
         # packed_t is rebuilt IN PLACE by the next forward (FusedTrainDecoder._images), through raw pointers autograd cannot
@@ -194,6 +232,7 @@ class FusedDecoderFn(torch.autograd.Function):
         ctx.save_for_backward(feats, pos, attrs, zbuf, packed_t.clone())
         ctx.param_shapes = [tuple(p.shape) for p in params]
         ctx.hl = bool(hl)
+        ctx.chain = _CHAIN_BY_ID[int(chain_id)]
         return attrs
 
     @staticmethod
@@ -213,17 +252,17 @@ class FusedDecoderFn(torch.autograd.Function):
         wg = torch.zeros((5, per_head), dtype=torch.float32, device=dev)
         # activation backward + weight gradients, chunk by chunk (WGRAD_CHUNK points): a chunk's dz / z rows are consumed by
         # the weight-gradient kernel while they are still in the Infinity Cache
-        bwd = cx.lib.ggd_decoder_backward_wgrad_hl if ctx.hl else cx.lib.ggd_decoder_backward_wgrad
+        bwd = cx.lib.ggd_decoder_backward_wgrad_hl_chain if ctx.hl else cx.lib.ggd_decoder_backward_wgrad_chain
         with torch.cuda.device(dev):
             cx.check(bwd(
-                cx.handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), n, int(WGRAD_CHUNK),
+                cx.handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), ctx.chain.id, n, int(WGRAD_CHUNK),
                 C.c_void_p(packed_t.data_ptr()), C.c_void_p(attrs.data_ptr()), C.c_void_p(dattrs.data_ptr()),
                 C.c_void_p(zbuf.data_ptr()), C.c_void_p(dzbuf.data_ptr()), C.c_void_p(dout.data_ptr()),
                 C.c_void_p(dfeat.data_ptr()), C.c_void_p(dinfo.data_ptr()), C.c_void_p(feats.data_ptr()),
                 C.c_void_p(pos.data_ptr()), C.c_void_p(wg.data_ptr())))
         grads = []
-        for h in range(5):
-            in_dim, od = 35 + _N_EXTRA[h], _OUT_DIM[h]
+        for h in range(5):   # execution order, like `params`
+            in_dim, od = ctx.chain.in_features[h], ctx.chain.out_dim[h]
             o = 0
             for rows, cols, r_used, c_used in ((HID, 64, HID, in_dim), (HID, HID, HID, HID), (HID, HID, HID, HID),
                                                (16, HID, od, HID)):
@@ -231,7 +270,7 @@ class FusedDecoderFn(torch.autograd.Function):
                 o += rows * cols
                 grads += [w, wg[h, o:o + rows][:r_used]]
                 o += rows
-        return (dfeat, None, None, None, None, *grads)
+        return (dfeat, None, None, None, None, None, *grads)
 
 
 class _SplitAttrs(torch.autograd.Function):
@@ -290,17 +329,18 @@ def split_attrs(attrs: torch.Tensor):
 
 
 class FusedTrainDecoder(torch.nn.Module):
-    """Training front-end with the `SequentialDecoderReverse` call signature: tri-plane gather (HIP) + the fused
-    bf16-MFMA decoder with autograd.  Wraps (and shares the parameters of) a SequentialDecoderReverse."""
+    """Training front-end with the decoder modules' call signature: tri-plane gather (HIP) + the fused bf16-MFMA decoder
+    with autograd.  Wraps (and shares the parameters of) a SequentialDecoderReverse, SequentialDecoder or ParallelDecoder;
+    the chain is taken from the module's type."""
 
-    def __init__(self, decoder: SequentialDecoderReverse, precision: str = "bf16"):
+    def __init__(self, decoder, precision: str = "bf16"):
         """precision: "bf16" = 16-bit operands: f16 forward, bf16 backward (outputs within 2e-3, measured 4e-4; parameter gradients
         within 1.5 % relative L2 of fp32, measured 0.6 %);
         "fp32" = the reference's training precision on the same matrix cores: split bf16 operands, three MFMAs per product
         (outputs within 1e-4, parameter gradients within 1e-3 relative L2 of the fp32 module)."""
         super().__init__()
         self.decoder = decoder
-        _check_decoder(decoder)
+        self.chain = _check_decoder(decoder)
         self.precision = precision
         self._hl = _check_precision(precision)
         self._image_bufs = None
@@ -326,7 +366,7 @@ class FusedTrainDecoder(torch.nn.Module):
                                              self.decoder.triplane_depth) for b in range(B)], dim=0)
         params = [t for head in _head_tensors(self.decoder) for t in head]
         packed, packed_t = self._images(params)
-        a = FusedDecoderFn.apply(feats, positions.reshape(B * N, 3), packed, packed_t, self._hl, *params)
+        a = FusedDecoderFn.apply(feats, positions.reshape(B * N, 3), packed, packed_t, self._hl, self.chain.id, *params)
         return a.view(B, N, 16)
 
     def forward(self, feature_planes, init_position, features=None):
@@ -335,15 +375,16 @@ class FusedTrainDecoder(torch.nn.Module):
                           self.decoder.triplane_depth)
         params = [t for head in _head_tensors(self.decoder) for t in head]
         packed, packed_t = self._images(params)
-        a = FusedDecoderFn.apply(feats, init_position, packed, packed_t, self._hl, *params)
+        a = FusedDecoderFn.apply(feats, init_position, packed, packed_t, self._hl, self.chain.id, *params)
         return SimpleNamespace(color=a[:, 0:3], opacity=a[:, 3:4], rotation=a[:, 4:8], scale=a[:, 8:11], xyz=a[:, 11:14])
 
 
 class FusedDecoder:
-    def __init__(self, decoder: SequentialDecoderReverse, precision: str = "bf16"):
+    def __init__(self, decoder, precision: str = "bf16"):
         self.precision = precision
         self._hl = _check_precision(precision)
         self.decoder = decoder
+        self.chain = _check_decoder(decoder)
         self.box_warp = decoder.box_warp
         self.plane_axes, self.triplane_depth = decoder.plane_axes, decoder.triplane_depth
         self.repack()
@@ -371,11 +412,11 @@ class FusedDecoder:
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         with torch.cuda.device(dev):
             if self._hl:
-                cx.check(cx.lib.ggd_decoder_forward_hl(cx.handle, stream, C.c_void_p(feats.data_ptr()),
+                cx.check(cx.lib.ggd_decoder_forward_hl_chain(cx.handle, stream, self.chain.id, C.c_void_p(feats.data_ptr()),
                                                        C.c_void_p(positions.data_ptr()), n,
                                                        C.c_void_p(self.packed.data_ptr()), C.c_void_p(attrs.data_ptr()), None))
             else:
-                cx.check(cx.lib.ggd_decoder_forward(cx.handle, stream, C.c_void_p(feats.data_ptr()),
+                cx.check(cx.lib.ggd_decoder_forward_chain(cx.handle, stream, self.chain.id, C.c_void_p(feats.data_ptr()),
                                                     C.c_void_p(positions.data_ptr()), n,
                                                     C.c_void_p(self.packed.data_ptr()), C.c_void_p(attrs.data_ptr())))
         return attrs

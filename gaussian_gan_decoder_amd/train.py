@@ -33,7 +33,7 @@ from typing import Optional
 import torch
 
 from .cameras import CustomCam, look_at_cam2world
-from .decoder import SequentialDecoderReverse
+from .decoder import DECODER_TYPES
 from .losses import composite_mask, fused_image_loss, PerceptualStandIn
 from .gaussian_model import GaussianModel
 
@@ -94,7 +94,7 @@ class DecoderTrainer:
                  backbone_params: int = 0, perceptual_weight: float = 0.0, perceptual_width_div: int = 1,
                  scene_streams: bool = False, decoder_precision: str = "bf16", plane_axes: str = "eg3d",
                  triplane_depth=None, fused_planes=None, force_comm=None, antialiasing: bool = False,
-                 apply_mask_to_rendering: bool = False):
+                 apply_mask_to_rendering: bool = False, decoder_type: str = "sequential_reversed"):
         """plane_axes / triplane_depth: the generator whose planes are decoded -- ("eg3d", None): tri-planes
         [3, C, res, res]; ("panohead", 3): PanoHead's tri-grids [3, C * 3, res, res] sampled with a 3-D grid_sample
         (the reference's default generator: main/train_pano2gaussian_decoder.py:43, PanoHead/train.py:230,318,
@@ -110,7 +110,10 @@ class DecoderTrainer:
         apply_mask_to_rendering: the reference's option of that name (main/train_pano2gaussian_decoder.py:52,237-241): the
         batch's mask, upsampled bilinearly, composites the rendered image and the target onto white before every loss
         term -- `mask=` of loss_fn (passed only when set), composite_mask for the perceptual term; a batch without a mask
-        is an error."""
+        is an error.
+        decoder_type: the reference's option of that name (main/train_pano2gaussian_decoder.py:45,170-192):
+        "sequential_reversed" (SequentialDecoderReverse, the default), "sequential" (SequentialDecoder) or "parallel"
+        (ParallelDecoder); fused_decoder=True runs any of them on the MFMA kernels."""
         import os
         import torch.distributed as dist
         self.force_comm = bool(int(os.environ.get("GGD_FORCE_COMM", "0"))) if force_comm is None else bool(force_comm)
@@ -126,8 +129,11 @@ class DecoderTrainer:
         torch.manual_seed(seed)
         self.plane_axes, self.triplane_depth = plane_axes, (None if triplane_depth is None else int(triplane_depth))
         depth = self.triplane_depth or 1
-        self.decoder = SequentialDecoderReverse(plane_channels, hidden_dim, plane_axes=plane_axes,
-                                                triplane_depth=self.triplane_depth).to(self.device)
+        if decoder_type not in DECODER_TYPES:
+            raise ValueError(f"decoder_type must be one of {tuple(DECODER_TYPES)} (got {decoder_type!r})")
+        self.decoder_type = decoder_type
+        self.decoder = DECODER_TYPES[decoder_type](plane_channels, hidden_dim, plane_axes=plane_axes,
+                                                   triplane_depth=self.triplane_depth).to(self.device)
         # stand-in for the finetuned GAN backbone (shared, replicated, all-reduced like the reference's G): ONE learnable
         # tri-plane, modulated per scene by a fixed per-scene channel code (the "latent" z of that scene)
         g = torch.Generator().manual_seed(seed + 17)

@@ -367,11 +367,11 @@ int ggd_surface_sample(ggd_ctx* ctx, void* stream, const float* sigma, int32_t n
 
 /*
  * Fused per-point decoder, inference (bf16 MFMA, fp32 accumulate): the 5 chained `Decoder` MLPs of
- * main/decoder_models/sequential_decoder_reverse.py:68-85 in ONE launch.
+ * main/decoder_models/sequential_decoder_reverse.py:68-85 in ONE launch (the other two decoder types: THE DECODER CHAINS below).
  *   feat  [N,32]  mean-of-planes features (ggd_triplane_forward)      pos [N,3] positions
  *   packed_weights : ggd_decoder_packed_bytes() bytes, the LDS image of the 5 heads (bf16 weight rows pre-permuted to
  *                    the MFMA operand order + fp32 biases; built by gaussian_gan_decoder_amd.fused_decoder.pack_weights)
- *   attrs [N,16]  out: [0..2] color, [3] opacity, [4..7] rotation, [8..10] scale (= -softplus(s+5)-2.5),
+ *   attrs [N,16]  out: [0..2] color, [3] opacity, [4..7] rotation, [8..10] scale (= -softplus(s+5)-2.5; - 2 in chains 1, 2),
  *                      [11..13] xyz (= head*0.01 + pos), [14..15] zero
  */
 size_t ggd_decoder_packed_bytes(void);
@@ -388,6 +388,39 @@ int ggd_attrs_merge(ggd_ctx* ctx, void* stream, int64_t N, const float* dxyz, co
                     const float* dopacity, const float* dcolor, float* dattrs);
 int ggd_decoder_forward(ggd_ctx* ctx, void* stream, const float* feat, const float* pos, int32_t N,
                         const void* packed_weights, float* attrs);
+
+/*
+ * THE DECODER CHAINS.  The reference selects one of three decoders (main/train_pano2gaussian_decoder.py:45,170-192); the
+ * same kernels run all three, as compile-time instances.  A chain is the ORDER in which the five attributes are decoded and
+ * what each head sees behind the 32 plane features and the position (its "info" slots 3 .. 3 + n_extra: the outputs of the
+ * heads executed before it, in execution order -- the reference's own torch.concat order, so W1 is taken as it is):
+ *   chain                            execution order                          n_extra          first-layer widths   scale
+ *   GGD_CHAIN_SEQUENTIAL_REVERSED    colour, opacity, rotation, scale, xyz    0, 3, 4, 8, 11   35, 38, 39, 43, 46   -softplus(s+5) - 2.5
+ *   GGD_CHAIN_SEQUENTIAL             xyz, scale, rotation, opacity, colour    0, 3, 6, 10, 11  35, 38, 41, 45, 46   -softplus(s+5) - 2
+ *   GGD_CHAIN_PARALLEL               xyz, scale, rotation, opacity, colour    0, 0, 0, 0, 0    35 x 5               -softplus(s+5) - 2
+ * (main/decoder_models/sequential_decoder_reverse.py, sequential_decoder.py:27-84, parallel_decoder.py:27-80).
+ * The attrs[N,16] row is THE SAME for every chain (colour 0..2, opacity 3, rotation 4..7, activated scale 8..10, xyz 11..13,
+ * 14..15 zero): an attribute keeps its columns and its activation wherever it executes.  In GGD_CHAIN_SEQUENTIAL info slots
+ * 3..5 read columns 11..13, 6..8 read 8..10, 9..12 read 4..7 and 13 reads column 3.
+ * EVERYTHING PER HEAD IS INDEXED BY EXECUTION POSITION: params40 is passed in the chain's execution order (for chains 1 and 2:
+ * xyz, scale, rotation, opacity, colour), and so are the head slots of the weight images, of zbuf / dzbuf, of dout[h] and of
+ * the weight-gradient blocks; dinfo[N,16] is in the chain's slot order (slots 0..2 position, 3 + k the k-th chained input).
+ * Backward: a head adds dinfo at its own info slots to dattrs only if a later-executed head can read them -- the last
+ * executed head never does, no head of GGD_CHAIN_PARALLEL does; the first head of GGD_CHAIN_SEQUENTIAL (xyz) receives
+ * 0.01 * (dattrs + dinfo).
+ * Every ggd_decoder_* entry point has a *_chain form that takes the chain behind `stream`; the form without it is the
+ * GGD_CHAIN_SEQUENTIAL_REVERSED call.  An unknown chain value returns GGD_E_INVALID.  The image sizes, ggd_decoder_zbuf_bytes
+ * and ggd_decoder_wgrad_floats do not depend on the chain.
+ */
+typedef enum ggd_decoder_chain {
+  GGD_CHAIN_SEQUENTIAL_REVERSED = 0,
+  GGD_CHAIN_SEQUENTIAL = 1,
+  GGD_CHAIN_PARALLEL = 2
+} ggd_decoder_chain;
+int ggd_decoder_pack_chain(ggd_ctx* ctx, void* stream, int32_t chain, const float* const* params40, void* packed,
+                           void* packed_t);
+int ggd_decoder_forward_chain(ggd_ctx* ctx, void* stream, int32_t chain, const float* feat, const float* pos, int32_t N,
+                              const void* packed_weights, float* attrs);
 
 /*
  * Fused decoder, TRAINING.  ggd_decoder_forward_train == ggd_decoder_forward that also keeps the hidden layers'
@@ -409,6 +442,10 @@ int ggd_decoder_forward_train(ggd_ctx* ctx, void* stream, const float* feat, con
                               const void* packed_weights, float* attrs, void* zbuf);
 int ggd_decoder_backward(ggd_ctx* ctx, void* stream, int32_t N, const void* packed_t, const float* attrs,
                          const float* dattrs, const void* zbuf, void* dzbuf, float* dout, float* dfeat, float* dinfo);
+int ggd_decoder_forward_train_chain(ggd_ctx* ctx, void* stream, int32_t chain, const float* feat, const float* pos, int32_t N,
+                                    const void* packed_weights, float* attrs, void* zbuf);
+int ggd_decoder_backward_chain(ggd_ctx* ctx, void* stream, int32_t chain, int32_t N, const void* packed_t, const float* attrs,
+                               const float* dattrs, const void* zbuf, void* dzbuf, float* dout, float* dfeat, float* dinfo);
 
 /*
  * Weight / bias gradients of the fused decoder: split-K MFMA GEMMs over the points, operands transposed through LDS
@@ -422,6 +459,8 @@ int ggd_decoder_backward(ggd_ctx* ctx, void* stream, int32_t N, const void* pack
 size_t ggd_decoder_wgrad_floats(void);
 int ggd_decoder_wgrad(ggd_ctx* ctx, void* stream, int32_t N, const void* zbuf, const void* dzbuf, const float* dout,
                       const float* feat, const float* pos, const float* attrs, float* wgrad);
+int ggd_decoder_wgrad_chain(ggd_ctx* ctx, void* stream, int32_t chain, int32_t N, const void* zbuf, const void* dzbuf,
+                            const float* dout, const float* feat, const float* pos, const float* attrs, float* wgrad);
 
 /*
  * Fused image losses of the decoder training step and their gradient (main/train_pano2gaussian_decoder.py:246-261
@@ -538,6 +577,9 @@ int ggd_densify_gather(ggd_ctx* ctx, void* stream, int32_t P, int32_t new_P, int
 int ggd_decoder_backward_wgrad(ggd_ctx* ctx, void* stream, int32_t N, int32_t chunk, const void* packed_t,
                                const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf, float* dout,
                                float* dfeat, float* dinfo, const float* feat, const float* pos, float* wgrad);
+int ggd_decoder_backward_wgrad_chain(ggd_ctx* ctx, void* stream, int32_t chain, int32_t N, int32_t chunk, const void* packed_t,
+                                     const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf, float* dout,
+                                     float* dfeat, float* dinfo, const float* feat, const float* pos, float* wgrad);
 
 /*
  * The fused decoder at REFERENCE PRECISION (the reference trains its decoder in fp32, main/decoder_models/base_decoder.py:8-27):
@@ -558,6 +600,14 @@ int ggd_decoder_forward_hl(ggd_ctx* ctx, void* stream, const float* feat, const 
 int ggd_decoder_backward_wgrad_hl(ggd_ctx* ctx, void* stream, int32_t N, int32_t chunk, const void* packed_t_hl,
                                   const float* attrs, const float* dattrs, const void* zbuf, void* dzbuf, float* dout,
                                   float* dfeat, float* dinfo, const float* feat, const float* pos, float* wgrad);
+int ggd_decoder_pack_hl_chain(ggd_ctx* ctx, void* stream, int32_t chain, const float* const* params40, void* packed_hl,
+                              void* packed_t_hl);
+int ggd_decoder_forward_hl_chain(ggd_ctx* ctx, void* stream, int32_t chain, const float* feat, const float* pos, int32_t N,
+                                 const void* packed_hl, float* attrs, void* zbuf);
+int ggd_decoder_backward_wgrad_hl_chain(ggd_ctx* ctx, void* stream, int32_t chain, int32_t N, int32_t chunk,
+                                        const void* packed_t_hl, const float* attrs, const float* dattrs, const void* zbuf,
+                                        void* dzbuf, float* dout, float* dfeat, float* dinfo, const float* feat,
+                                        const float* pos, float* wgrad);
 
 /*
  * The teacher's density field sampled on the device: what G.sample_mixed evaluates every iteration of the reference's

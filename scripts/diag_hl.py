@@ -46,7 +46,7 @@ for prec in ("bf16", "fp32"):
     f32 = feats64.detach().float().requires_grad_(True)
     params = [t for h in _head_tensors(mod) for t in h]
     packed, packed_t = device_pack(mod, params, None, prec == "fp32")
-    a = FusedDecoderFn.apply(f32, pos, packed, packed_t, prec == "fp32", *params)
+    a = FusedDecoderFn.apply(f32, pos, packed, packed_t, prec == "fp32", 0, *params)
     ob = SimpleNamespace(color=a[:, 0:3], opacity=a[:, 3:4], rotation=a[:, 4:8], scale=a[:, 8:11], xyz=a[:, 11:14])
     loss(ob).backward()
     print(prec, "outputs:", {k: f"{(getattr(oa, k) - getattr(ob, k).double()).abs().max().item():.2e}" for k in w})

@@ -17,7 +17,7 @@ pos = torch.rand(n, 3, device=dev) - 0.5
 w = torch.randn(n, 16, device=dev)
 def step():
     packed, packed_t = device_pack(dec, params, None, hl)
-    a = FusedDecoderFn.apply(feats, pos, packed, packed_t, hl, *params)
+    a = FusedDecoderFn.apply(feats, pos, packed, packed_t, hl, 0, *params)
     (a * w).sum().backward()
 for _ in range(3): step()
 torch.cuda.synchronize()

@@ -16,7 +16,7 @@ pos = torch.rand(n, 3, device=dev) - 0.5
 w = torch.randn(n, 16, device=dev)
 for _ in range(int(sys.argv[1]) if len(sys.argv) > 1 else 3):
     packed, packed_t = device_pack(dec, params, None, hl)
-    a = FusedDecoderFn.apply(feats, pos, packed, packed_t, hl, *params)
+    a = FusedDecoderFn.apply(feats, pos, packed, packed_t, hl, 0, *params)
     (a * w).sum().backward()
 # inference form (no z stores), same size
 from gaussian_gan_decoder_amd.fused_decoder import FusedDecoder
