@@ -23,7 +23,7 @@ EXPORTS = [
     "ggd_decoder_forward_train", "ggd_decoder_backward", "ggd_decoder_wgrad_floats", "ggd_decoder_wgrad", "ggd_decoder_backward_wgrad", "ggd_decoder_packed_hl_bytes", "ggd_decoder_packed_t_hl_bytes", "ggd_decoder_dzbuf_hl_bytes", "ggd_decoder_pack_hl", "ggd_decoder_forward_hl", "ggd_decoder_backward_wgrad_hl",
     "ggd_decoder_pack_chain", "ggd_decoder_forward_chain", "ggd_decoder_forward_train_chain", "ggd_decoder_backward_chain", "ggd_decoder_wgrad_chain",
     "ggd_decoder_backward_wgrad_chain", "ggd_decoder_pack_hl_chain", "ggd_decoder_forward_hl_chain", "ggd_decoder_backward_wgrad_hl_chain",
-    "ggd_image_loss_tmp_bytes", "ggd_image_loss", "ggd_image_loss_masked", "ggd_mask_composite", "ggd_set_option", "ggd_get_option", "ggd_blend_stats", "ggd_blend_backward_stats", "ggd_blend_timeline", "ggd_set_profiling", "ggd_stage_count", "ggd_stage_name", "ggd_stage_times",
+    "ggd_image_loss_tmp_bytes", "ggd_image_loss", "ggd_image_loss_masked", "ggd_mask_composite", "ggd_geometry_loss_tmp_bytes", "ggd_geometry_loss", "ggd_set_option", "ggd_get_option", "ggd_blend_stats", "ggd_blend_backward_stats", "ggd_blend_timeline", "ggd_set_profiling", "ggd_stage_count", "ggd_stage_name", "ggd_stage_times",
     "ggd_knn_tmp_bytes", "ggd_knn_leaf_size", "ggd_knn_max_points", "ggd_knn3", "ggd_knn3_stage",
     "ggd_densify_tmp_bytes", "ggd_densify_stats", "ggd_densify_plan", "ggd_prune_plan", "ggd_densify_emit", "ggd_densify_gather",
     "ggd_density_points", "ggd_density_grid", "ggd_density_lattice", "ggd_teacher_render",
@@ -130,6 +130,8 @@ def load():
         lib.ggd_image_loss.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz]
         lib.ggd_image_loss_masked.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz]
         lib.ggd_mask_composite.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp]
+        lib.ggd_geometry_loss_tmp_bytes.restype = sz; lib.ggd_geometry_loss_tmp_bytes.argtypes = [i32, i32]
+        lib.ggd_geometry_loss.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, sz]
         lib.ggd_set_option.argtypes = [vp, C.c_int, C.c_int]
         lib.ggd_get_option.argtypes = [vp, C.c_int]
         lib.ggd_blend_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_ulonglong)]

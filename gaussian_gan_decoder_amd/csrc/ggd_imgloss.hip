@@ -55,12 +55,16 @@ __device__ __forceinline__ MaskAxis mask_axis(int dst, float f, int n) {
 }
 
 // along x for both rows, then along y; a factor of 1 gives l = 0 and returns the cell unchanged
+__device__ __forceinline__ float mask_blend(float v00, float v01, float v10, float v11, const MaskAxis& ay, const MaskAxis& ax) {
+  const float top = v00 * (1.f - ax.l) + v01 * ax.l;
+  const float bot = v10 * (1.f - ax.l) + v11 * ax.l;
+  return top * (1.f - ay.l) + bot * ay.l;
+}
+
 __device__ __forceinline__ float mask_value(const Mask& mk, const MaskAxis& ay, const MaskAxis& ax) {
   const float* r0 = mk.m + (size_t)ay.i0 * mk.w;
   const float* r1 = mk.m + (size_t)ay.i1 * mk.w;
-  const float top = r0[ax.i0] * (1.f - ax.l) + r0[ax.i1] * ax.l;
-  const float bot = r1[ax.i0] * (1.f - ax.l) + r1[ax.i1] * ax.l;
-  return top * (1.f - ay.l) + bot * ay.l;
+  return mask_blend(r0[ax.i0], r0[ax.i1], r1[ax.i0], r1[ax.i1], ay, ax);
 }
 
 __device__ __forceinline__ float mask_at(const Mask& mk, int gy, int gx) {
@@ -293,7 +297,101 @@ __global__ __launch_bounds__(256) void mask_composite_kernel(int W, int H, int c
   for (int c = 0; c < channels; ++c) dst[c * plane + p] = backward ? src[c * plane + p] * m : composite(src[c * plane + p], m);
 }
 
+// ---- geometry loss: the student's depth / alpha maps against the teacher's depth / weight maps ----
+// Per pixel: m = up(w), q = up(w * z) with z the teacher's ray distance turned into view-space z at the teacher's cell,
+// r_m = A - m, r_d = m*D - A*q; the terms are mean|r_m| and mean|r_d|.  Two launches: the pixel kernel writes both gradient
+// maps (their scale is known up front) and one partial sum per workgroup and term; the finalise adds the partials in a fixed
+// order.  No atomics: bit-identical from run to run.
+
+struct GeomTeacher { const float* t; Mask w; float tanx, tany; int ray_depth; };
+
+// the premultiplied view-space depth p = w * z of one teacher cell
+__device__ __forceinline__ float teacher_p(const GeomTeacher& g, int i, int j) {
+  const size_t c = (size_t)i * g.w.w + j;
+  float z = g.t[c];
+  if (g.ray_depth) {
+    const float xl = (2.f * ((float)j + 0.5f) / (float)g.w.w - 1.f) * g.tanx;
+    const float yl = (2.f * ((float)i + 0.5f) / (float)g.w.h - 1.f) * g.tany;
+    z = z / sqrtf(1.f + xl * xl + yl * yl);
+  }
+  return g.w.m[c] * z;
+}
+
+__device__ __forceinline__ float sign_of(float v) { return (float)((v > 0.f) - (v < 0.f)); }
+
+__global__ __launch_bounds__(256) void geometry_loss_kernel(int W, int H, const float* __restrict__ depth,
+                                                            const float* __restrict__ alpha, GeomTeacher g, float s_mask,
+                                                            float s_depth, float* __restrict__ grad_depth,
+                                                            float* __restrict__ grad_alpha, float* __restrict__ partials) {
+  __shared__ float red[4];
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  float a_m = 0.f, a_d = 0.f;
+  if (x < W && y < H) {
+    const MaskAxis ay = mask_axis(y, g.w.fy, g.w.h), ax = mask_axis(x, g.w.fx, g.w.w);
+    const float m = mask_value(g.w, ay, ax);
+    const float q = mask_blend(teacher_p(g, ay.i0, ax.i0), teacher_p(g, ay.i0, ax.i1), teacher_p(g, ay.i1, ax.i0),
+                               teacher_p(g, ay.i1, ax.i1), ay, ax);
+    const size_t p = (size_t)y * W + x;
+    const float D = depth[p], A = alpha[p];
+    const float r_m = A - m, r_d = m * D - A * q;
+    const float sm = sign_of(r_m), sd = sign_of(r_d);
+    grad_depth[p] = s_depth * sd * m;
+    grad_alpha[p] = s_mask * sm - s_depth * sd * q;
+    a_m = fabsf(r_m); a_d = fabsf(r_d);
+  }
+  const float t_m = block_sum(a_m, red), t_d = block_sum(a_d, red);
+  if (threadIdx.x == 0) {
+    const int wg = blockIdx.y * gridDim.x + blockIdx.x, n_wg = gridDim.x * gridDim.y;
+    partials[wg] = t_m; partials[n_wg + wg] = t_d;
+  }
+}
+
+// one workgroup: lane t adds partials t, t + 256, ... in that order, then the block's fixed tree
+__global__ __launch_bounds__(256) void geometry_loss_finalise_kernel(int n_wg, const float* __restrict__ partials, float n_pix,
+                                                                     float w_mask, float w_depth, float* __restrict__ terms) {
+  __shared__ float red[4];
+  float a_m = 0.f, a_d = 0.f;
+  for (int i = threadIdx.x; i < n_wg; i += 256) { a_m += partials[i]; a_d += partials[n_wg + i]; }
+  const float t_m = block_sum(a_m, red), t_d = block_sum(a_d, red);
+  if (threadIdx.x == 0) {
+    const float l_m = t_m / n_pix, l_d = t_d / n_pix;
+    terms[0] = l_m; terms[1] = l_d; terms[2] = w_mask * l_m + w_depth * l_d;
+  }
+}
+
+static inline size_t geometry_loss_workgroups(int32_t W, int32_t H) { return (size_t)((W + 63) / 64) * (size_t)((H + 3) / 4); }
+
 }  // namespace
+
+extern "C" size_t ggd_geometry_loss_tmp_bytes(int32_t W, int32_t H) {
+  if (W <= 0 || H <= 0) return 0;
+  return ggd_align(2 * geometry_loss_workgroups(W, H) * sizeof(float));   // one partial per workgroup and term
+}
+
+extern "C" int ggd_geometry_loss(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, const float* depth, const float* alpha,
+                                 const float* teacher_depth, const float* teacher_weights, int32_t tw, int32_t th,
+                                 float tanfovx, float tanfovy, int32_t ray_depth, const float* weights2, float* terms3,
+                                 float* grad_depth, float* grad_alpha, void* tmp, size_t tmp_bytes) {
+  if (!ctx) return GGD_E_INVALID;
+  if (W <= 0 || H <= 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_geometry_loss: empty image");
+  if (!depth || !alpha || !teacher_depth || !teacher_weights || !weights2 || !terms3 || !grad_depth || !grad_alpha || !tmp)
+    return ggd_fail(ctx, GGD_E_INVALID, "ggd_geometry_loss: NULL pointer");
+  if (tw <= 0 || th <= 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_geometry_loss: empty teacher maps");
+  if (H % th != 0 || W % tw != 0)
+    return ggd_fail(ctx, GGD_E_INVALID, "ggd_geometry_loss: the teacher maps' size must divide the image size");
+  if (tmp_bytes < ggd_geometry_loss_tmp_bytes(W, H)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_geometry_loss: tmp too small");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const GeomTeacher g{teacher_depth, Mask{teacher_weights, tw, th, (float)(W / tw), (float)(H / th)}, tanfovx, tanfovy, ray_depth};
+  const float n_pix = (float)H * (float)W;
+  const dim3 grid((W + 63) / 64, (H + 3) / 4);
+  float* partials = static_cast<float*>(tmp);
+  hipLaunchKernelGGL(geometry_loss_kernel, grid, dim3(256), 0, s, W, H, depth, alpha, g, weights2[0] / n_pix,
+                     weights2[1] / n_pix, grad_depth, grad_alpha, partials);
+  hipLaunchKernelGGL(geometry_loss_finalise_kernel, dim3(1), dim3(256), 0, s, (int)geometry_loss_workgroups(W, H), partials,
+                     n_pix, weights2[0], weights2[1], terms3);
+  GGD_HIP(hipGetLastError());
+  return GGD_OK;
+}
 
 extern "C" size_t ggd_image_loss_tmp_bytes(int32_t W, int32_t H) {
   if (W <= 0 || H <= 0) return 0;

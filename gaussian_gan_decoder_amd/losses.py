@@ -8,6 +8,9 @@ same terms lives under tests/ (the checker).  With `mask=` the reference's --app
 white before every term) happens inside the same three launches.
 `composite_mask`: that composite as an operator of its own, for what needs the composited image itself (the perceptual
 term, logging, eval).
+`fused_geometry_loss`: the rasterizer's differentiable depth and alpha maps against the teacher's depth and weight maps
+(teacher.render_teacher) -- a mask term and a cross-multiplied depth term with both gradient maps in two HIP launches
+(DESIGN.md section 6s); `geometry_loss_torch` is the same loss as a torch expression (CPU tensors, the timing baseline).
 `PerceptualStandIn`: the slot of the reference's LPIPS term (main/loss_utils/lpips.py:6-34: VGG16 features of the image
 and the target at 256 x 256, squared distance).  The pretrained VGG is an external download and out of scope; the
 stand-in is a FIXED, seeded, random-initialised network of the same shape (VGG16's 13 3x3 convolutions, taps after
@@ -23,14 +26,14 @@ import torch
 import torch.nn.functional as F
 
 
-def _mask_2d(mask, H, W, what):
-    """The low-resolution mask as a contiguous float32 [mh, mw]; ValueError unless its size divides the image's."""
+def _mask_2d(mask, H, W, what, dtype=torch.float32):
+    """The low-resolution mask as a contiguous float32 (`dtype`) [mh, mw]; ValueError unless its size divides the image's."""
     if mask.dim() not in (2, 3, 4) or any(int(n) != 1 for n in mask.shape[:-2]):
         raise ValueError(f"{what}: mask must be [mh,mw], [1,mh,mw] or [1,1,mh,mw], got {tuple(mask.shape)}")
     mh, mw = int(mask.shape[-2]), int(mask.shape[-1])
     if mh <= 0 or mw <= 0 or H % mh != 0 or W % mw != 0:
         raise ValueError(f"{what}: the mask size {mh} x {mw} must divide the image size {H} x {W}")
-    return mask.detach().reshape(mh, mw).contiguous().float()
+    return mask.detach().reshape(mh, mw).contiguous().to(dtype)
 
 
 class _FusedImageLoss(torch.autograd.Function):
@@ -138,6 +141,106 @@ def composite_mask(image, mask):
     if not per_scene:      # one mask for everything: the batch folds into the channel axis of one launch
         return _CompositeMask.apply(image.reshape(-1, H, W), masks[0]).view(image.shape)
     return torch.stack([_CompositeMask.apply(image[b], masks[b]) for b in range(B)])
+
+
+def _geometry_args(depth, alpha, teacher_depth, teacher_weights, tanfovx, tanfovy, what, float32_only):
+    """The four maps as contiguous 2-D tensors ([H,W] twice, [th,tw] twice; the teacher's detached) after the checks both forms
+    share: ValueError for shapes, a size that does not divide and a non-positive tanfov, TypeError for a dtype other than
+    float32 (float32_only) or mixed dtypes, RuntimeError for tensors on different devices."""
+    for name, t in (("depth", depth), ("alpha", alpha)):
+        if t.dim() not in (2, 3) or (t.dim() == 3 and int(t.shape[0]) != 1):
+            raise ValueError(f"{what}: {name} must be [H,W] or [1,H,W], got {tuple(t.shape)}")
+    if tuple(depth.shape[-2:]) != tuple(alpha.shape[-2:]):
+        raise ValueError(f"{what}: depth {tuple(depth.shape)} and alpha {tuple(alpha.shape)} must have one size")
+    if not (float(tanfovx) > 0.0 and float(tanfovy) > 0.0):
+        raise ValueError(f"{what}: tanfovx and tanfovy must be positive, got {tanfovx}, {tanfovy}")
+    maps = (depth, alpha, teacher_depth, teacher_weights)
+    if any(not torch.is_tensor(t) or t.dtype != (torch.float32 if float32_only else depth.dtype) for t in maps):
+        raise TypeError(f"{what}: {'float32 tensors' if float32_only else 'tensors of one dtype'} expected, got "
+                        f"{[getattr(t, 'dtype', type(t)) for t in maps]}")
+    if any(t.device != depth.device for t in maps):
+        raise RuntimeError(f"{what}: depth, alpha and the teacher's maps must live on one device")
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    if H <= 0 or W <= 0:
+        raise ValueError(f"{what}: empty image")
+    if tuple(teacher_depth.shape[-2:]) != tuple(teacher_weights.shape[-2:]):
+        raise ValueError(f"{what}: the teacher's depth {tuple(teacher_depth.shape)} and weights "
+                         f"{tuple(teacher_weights.shape)} must have one size")
+    t, w = (_mask_2d(m, H, W, what, depth.dtype) for m in (teacher_depth, teacher_weights))
+    return depth.reshape(H, W).contiguous(), alpha.reshape(H, W).contiguous(), t, w
+
+
+def geometry_loss_torch(depth, alpha, teacher_depth, teacher_weights, tanfovx, tanfovy, mask_weight=1.0, depth_weight=1.0,
+                        ray_depth=True):
+    """fused_geometry_loss as a torch expression in the tensors' own dtype and on their own device: the form CPU tensors take
+    (the gloo trainer, the host tests; float64 for gradcheck) and, on device tensors, the ~20-launch composition the kernel is
+    timed against.  Not a hot path.  Same arguments, same (total, terms[3]); differentiable in depth and alpha only."""
+    D, A, t, w = _geometry_args(depth, alpha, teacher_depth, teacher_weights, tanfovx, tanfovy, "geometry_loss_torch", False)
+    (H, W), (th, tw) = D.shape, t.shape
+    z = t
+    if ray_depth:
+        xl = (2 * (torch.arange(tw, dtype=t.dtype, device=t.device) + 0.5) / tw - 1) * float(tanfovx)
+        yl = (2 * (torch.arange(th, dtype=t.dtype, device=t.device) + 0.5) / th - 1) * float(tanfovy)
+        z = t / torch.sqrt(1 + xl[None, :] ** 2 + yl[:, None] ** 2)
+    up = lambda v: F.interpolate(v[None, None], scale_factor=(H // th, W // tw), mode="bilinear")[0, 0]
+    m, q = up(w), up(w * z)
+    l_mask = (A - m).abs().mean()
+    l_depth = (m * D - A * q).abs().mean()
+    total = float(mask_weight) * l_mask + float(depth_weight) * l_depth
+    return total, torch.stack([l_mask, l_depth, total]).detach()
+
+
+class _FusedGeometryLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, alpha, t, w, tanfovx, tanfovy, weights, ray_depth):
+        from . import _capi
+        dev = depth.device
+        H, W = (int(n) for n in depth.shape)
+        cx = _capi.context_for(dev)
+        nbytes = cx.lib.ggd_geometry_loss_tmp_bytes(W, H)
+        tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        terms = torch.empty((3,), dtype=torch.float32, device=dev)
+        grad_depth, grad_alpha = torch.empty_like(depth), torch.empty_like(alpha)
+        w2 = (C.c_float * 2)(*[float(x) for x in weights])
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with torch.cuda.device(dev):
+            cx.check(cx.lib.ggd_geometry_loss(cx.handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), W, H, p(depth),
+                                              p(alpha), p(t), p(w), int(t.shape[1]), int(t.shape[0]), float(tanfovx),
+                                              float(tanfovy), int(bool(ray_depth)), w2, p(terms), p(grad_depth), p(grad_alpha),
+                                              p(tmp), nbytes))
+        ctx.save_for_backward(grad_depth, grad_alpha)
+        ctx.mark_non_differentiable(terms)
+        return terms[2].clone(), terms
+
+    @staticmethod
+    def backward(ctx, g_total, _g_terms):
+        grad_depth, grad_alpha = ctx.saved_tensors
+        return grad_depth * g_total, grad_alpha * g_total, None, None, None, None, None, None
+
+
+def fused_geometry_loss(depth, alpha, teacher_depth, teacher_weights, tanfovx, tanfovy, mask_weight=1.0, depth_weight=1.0,
+                        ray_depth=True):
+    """(total, terms[3] = L_mask, L_depth, total): the student's `depth` (sum alpha_i T_i z_i) and `alpha` (1 - final T) renders
+    -- render_simple(..., render_depth_alpha=True); float32 [H,W] or [1,H,W] -- against the teacher's depth t and weights w
+    (teacher.TeacherRender.geometry; float32 [th,tw], leading 1-axes allowed, H % th == 0 and W % tw == 0):
+      z = t / sqrt(1 + xl^2 + yl^2), xl = (2 (j + 0.5) / tw - 1) tanfovx, yl = (2 (i + 0.5) / th - 1) tanfovy   (ray_depth: t is a
+          distance along a unit ray, the rasterizer's depth is view-space z; ray_depth=False: z = t);
+      m = up(w), q = up(w z): the masked image loss's bilinear upsample (interpolate, align_corners=False) -- the teacher's depth
+          is clamped garbage where w ~ 0, so only the premultiplied depth is interpolated;
+      L_mask = mean |A - m|,  L_depth = mean |m D - A q|,  total = mask_weight L_mask + depth_weight L_depth.
+    The depth residual is cross-multiplied: zero exactly where the expected depths D / A and q / m agree, no division (bounded
+    gradients at low opacity), zero where the teacher sees nothing.  Differentiable in depth and alpha only; the teacher's maps
+    come out of a no_grad synthesis.  Precondition (not checked): t is finite (render_teacher clamps it).
+    Device tensors: two HIP launches (csrc/ggd_imgloss.hip), one autograd node, bit-identical from run to run.  CPU tensors:
+    geometry_loss_torch.  ValueError: shapes, a size that does not divide, non-positive tanfov; TypeError: tensors that are not
+    float32; RuntimeError: tensors on different devices.
+    The default weights (1, 1) are placeholders: nobody has tuned them."""
+    D, A, t, w = _geometry_args(depth, alpha, teacher_depth, teacher_weights, tanfovx, tanfovy, "fused_geometry_loss", True)
+    if not depth.is_cuda:
+        return geometry_loss_torch(depth, alpha, teacher_depth, teacher_weights, tanfovx, tanfovy, mask_weight, depth_weight,
+                                   ray_depth)
+    total, terms = _FusedGeometryLoss.apply(D, A, t, w, tanfovx, tanfovy, (mask_weight, depth_weight), ray_depth)
+    return total, terms
 
 
 class PerceptualStandIn(torch.nn.Module):

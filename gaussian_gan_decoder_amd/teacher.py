@@ -63,6 +63,17 @@ class TeacherRender(namedtuple("TeacherRender", "features depth weights activati
             feat = feat * 2 - 1
         return feat, self.depth.view(N, 1, R, R), self.weights.view(N, 1, R, R) * (1 + 2 * 0.001) - 0.001
 
+    def geometry(self, resolution):
+        """-> depth [N, 1, R, R], weights [N, 1, R, R]: the raw maps, reshaped as images() reshapes them -- what the student's
+        depth / alpha renders are supervised against (losses.fused_geometry_loss).  The weights are NOT image_mask's
+        weights * 1.002 - 0.001: they stay in [0, 1] with exact zeros where no sample contributed."""
+        R = int(resolution)
+        M = self.depth.shape[0]
+        if R <= 0 or M % (R * R):
+            raise ValueError(f"{M} rays are no whole number of {R} x {R} images")
+        N = M // (R * R)
+        return self.depth.view(N, 1, R, R), self.weights.view(N, 1, R, R)
+
 
 def camera_rays(cam2world, intrinsics, resolution):
     """RaySampler.forward (training/volumetric_rendering/ray_sampler.py:24-63) in torch ops: cam2world [N, 4, 4], intrinsics

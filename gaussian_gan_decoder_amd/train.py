@@ -34,7 +34,7 @@ import torch
 
 from .cameras import CustomCam, look_at_cam2world
 from .decoder import DECODER_TYPES
-from .losses import composite_mask, fused_image_loss, PerceptualStandIn
+from .losses import composite_mask, fused_geometry_loss, fused_image_loss, PerceptualStandIn
 from .gaussian_model import GaussianModel
 
 BUCKET_BYTES = 32 << 20
@@ -48,17 +48,46 @@ class SceneBatch:
     target: torch.Tensor      # [B, 3, S, S]
     scene_id: torch.Tensor    # [B] global scene indices (which latent / plane set)
     mask: Optional[torch.Tensor] = None   # [B, 1, S/8, S/8]  the generator's image_mask (apply_mask_to_rendering)
+    teacher_depth: Optional[torch.Tensor] = None     # [B, 1, S/8, S/8]  the teacher's depth along the ray (mask_weight /
+    teacher_weights: Optional[torch.Tensor] = None   # [B, 1, S/8, S/8]  and weights in [0, 1]          depth_weight)
 
 
-def make_scene_batch(scene_ids, n_points: int, size: int, device, seed: int = 0, with_mask: bool = False) -> SceneBatch:
+SHELL_RADIUS = 0.3   # make_scene_batch draws its positions from the shell of this radius about the origin
+
+
+def _sphere_geometry(cam2world, fov_deg: float, res: int, rim_cells: float = 2.0):
+    """What a teacher would render of the sphere of SHELL_RADIUS about the origin from a camera that looks at the origin: the
+    ray distance of the first intersection per pixel centre of a res x res image (outside the silhouette: the distance of the
+    ray's closest approach, finite and continuous across the edge) and weights clip((radius - miss distance) / (rim_cells
+    cells), 0, 1) -- 1 inside, exactly 0 outside.  Evaluated in float64, returned as float32 [res, res] each."""
+    dist = float(cam2world[:3, 3].double().norm())
+    tan = math.tan(float(fov_deg) / 360 * 2 * math.pi / 2)
+    c = (2 * (torch.arange(res, dtype=torch.float64) + 0.5) / res - 1) * tan
+    yl, xl = torch.meshgrid(c, c, indexing="ij")
+    along = dist / torch.sqrt(1 + xl ** 2 + yl ** 2)             # ray distance of the closest approach to the origin
+    miss = torch.sqrt(torch.clamp(dist ** 2 - along ** 2, min=0.0))
+    depth = along - torch.sqrt(torch.clamp(SHELL_RADIUS ** 2 - miss ** 2, min=0.0))
+    cell = dist * 2 * tan / res
+    weights = torch.clip((SHELL_RADIUS - miss) / (rim_cells * cell), 0.0, 1.0)
+    return depth.float(), weights.float()
+
+
+def make_scene_batch(scene_ids, n_points: int, size: int, device, seed: int = 0, with_mask: bool = False,
+                     with_geometry: bool = False) -> SceneBatch:
     """Deterministic synthetic stand-in for TargetDataloader.get_data (target_dataloader.py:59-132): head-like
     shell positions, camera h,v ~ U around pi/2 (main/decoder_utils/camera.py:6-35), fov ~ U[5,17]
     (target_dataloader.py:71).  Each global scene id gets its own seed, so any rank can build any scene.
     with_mask: also a stand-in for the generator's image_mask at 1/8 resolution, derived from the target's blob without a
     draw from the generator (every other field is the same with and without it): clip((blob - 0.2) / 0.5, 0, 1) -- an
-    exact-0 rim, an exact-1 core and a ramp between them."""
+    exact-0 rim, an exact-1 core and a ramp between them.
+    with_geometry: also a stand-in for the teacher's depth and weight maps at 1/8 resolution (teacher.TeacherRender.geometry),
+    analytic: the sphere of radius 0.3 about the origin -- the shell the positions are drawn from -- seen from the scene's own
+    camera (_sphere_geometry: ray distance of the first intersection, weights 1 inside falling to exactly 0 over a rim two
+    cells wide).  Every other field is the same with and without it."""
     pos, c2w, fov, tgt = [], [], [], []
     mask = None
+    if with_geometry and size % 8 != 0:
+        raise ValueError("make_scene_batch(with_geometry=True) needs an image size that is a multiple of 8")
     if with_mask:
         if size % 8 != 0:
             raise ValueError("make_scene_batch(with_mask=True) needs an image size that is a multiple of 8")
@@ -79,8 +108,12 @@ def make_scene_batch(scene_ids, n_points: int, size: int, device, seed: int = 0,
         blob = torch.exp(-(xx ** 2 + yy ** 2) * 3.0)
         col = torch.rand(3, generator=g)
         tgt.append(0.5 + (col[:, None, None] - 0.5) * blob[None])
+    geometry = (None, None)
+    if with_geometry:
+        maps = [_sphere_geometry(c, float(torch.tensor(f)), size // 8) for c, f in zip(c2w, fov)]
+        geometry = tuple(torch.stack([m[k] for m in maps])[:, None].to(device) for k in (0, 1))
     return SceneBatch(torch.stack(pos).to(device), torch.stack(c2w), torch.tensor(fov),
-                      torch.stack(tgt).to(device), torch.tensor(list(scene_ids)), mask)
+                      torch.stack(tgt).to(device), torch.tensor(list(scene_ids)), mask, *geometry)
 
 
 class DecoderTrainer:
@@ -94,7 +127,8 @@ class DecoderTrainer:
                  backbone_params: int = 0, perceptual_weight: float = 0.0, perceptual_width_div: int = 1,
                  scene_streams: bool = False, decoder_precision: str = "bf16", plane_axes: str = "eg3d",
                  triplane_depth=None, fused_planes=None, force_comm=None, antialiasing: bool = False,
-                 apply_mask_to_rendering: bool = False, decoder_type: str = "sequential_reversed"):
+                 apply_mask_to_rendering: bool = False, decoder_type: str = "sequential_reversed",
+                 mask_weight: float = 0.0, depth_weight: float = 0.0, geometry_loss_fn=None):
         """plane_axes / triplane_depth: the generator whose planes are decoded -- ("eg3d", None): tri-planes
         [3, C, res, res]; ("panohead", 3): PanoHead's tri-grids [3, C * 3, res, res] sampled with a 3-D grid_sample
         (the reference's default generator: main/train_pano2gaussian_decoder.py:43, PanoHead/train.py:230,318,
@@ -113,7 +147,13 @@ class DecoderTrainer:
         is an error.
         decoder_type: the reference's option of that name (main/train_pano2gaussian_decoder.py:45,170-192):
         "sequential_reversed" (SequentialDecoderReverse, the default), "sequential" (SequentialDecoder) or "parallel"
-        (ParallelDecoder); fused_decoder=True runs any of them on the MFMA kernels."""
+        (ParallelDecoder); fused_decoder=True runs any of them on the MFMA kernels.
+        mask_weight, depth_weight (default 0: off, nothing changes): geometry supervision against the batch's teacher_depth /
+        teacher_weights.  With either positive the scene is rendered with render_depth_alpha=True (passed to render_fn only
+        then) and geometry_loss_fn(depth, alpha, teacher_depth, teacher_weights, tanfovx, tanfovy, mask_weight, depth_weight)
+        [0] of the same render call is added to the scene's loss; the default geometry_loss_fn is losses.fused_geometry_loss
+        (two HIP launches; the torch expression on the CPU).  A batch without the two maps is an error.  The weights are
+        untuned."""
         import os
         import torch.distributed as dist
         self.force_comm = bool(int(os.environ.get("GGD_FORCE_COMM", "0"))) if force_comm is None else bool(force_comm)
@@ -177,7 +217,14 @@ class DecoderTrainer:
         if antialiasing:
             self.render_kwargs["antialiasing"] = True
         self.apply_mask_to_rendering = bool(apply_mask_to_rendering)
-        self.bg = torch.tensor([0.55717, 0.52256, 0.51045], dtype=torch.float32, device=self.device)
+        self.mask_weight, self.depth_weight = float(mask_weight), float(depth_weight)
+        if self.mask_weight < 0 or self.depth_weight < 0:
+            raise ValueError("mask_weight and depth_weight must not be negative")
+        self.geometry = self.mask_weight > 0 or self.depth_weight > 0
+        if self.geometry:
+            self.render_kwargs["render_depth_alpha"] = True
+        self.geometry_loss_fn = geometry_loss_fn if geometry_loss_fn is not None else fused_geometry_loss
+        self.bg =torch.tensor([0.55717, 0.52256, 0.51045], dtype=torch.float32, device=self.device)
         # scene_streams: every local scene's raster + loss on its own HIP stream (own ggd_ctx).  Measured on one MI355X
         # (4 scenes x 500 k points, fused decoder): 21.13 ms / step with and without -- the single-call forward already
         # enqueues the whole frame before it waits for num_rendered, so the GPU never idles on that read-back -- hence off
@@ -419,10 +466,15 @@ class DecoderTrainer:
         cam = CustomCam(size=self.image_size, fov=fov, extr=batch.cam2world[b].cpu())
         for name in ("world_view_transform", "full_proj_transform", "camera_center"):
             setattr(cam, name, getattr(cam, name).to(self.device, non_blocking=True))
-        image = self.render_fn(cam, gs, bg_color=self.bg, **self.render_kwargs)["render"][:3]
+        out = self.render_fn(cam, gs, bg_color=self.bg, **self.render_kwargs)
+        image = out["render"][:3]
         target = batch.target[b]
         mask_kw = {"mask": batch.mask[b]} if self.apply_mask_to_rendering else {}
         loss = self.loss_fn(image, target, **self.loss_w, **mask_kw)[0]
+        if self.geometry:
+            tan = math.tan(fov / 2)
+            loss = loss + self.geometry_loss_fn(out["depth"], out["alpha"], batch.teacher_depth[b], batch.teacher_weights[b],
+                                                tan, tan, self.mask_weight, self.depth_weight)[0]
         if self.perceptual is not None:
             # the reference evaluates its perceptual network on the whole batch at once (lpips.py:29-31): the rendered
             # images are collected and local_loss makes ONE call on the stack
@@ -436,6 +488,9 @@ class DecoderTrainer:
         if self.apply_mask_to_rendering and batch.mask is None:
             raise ValueError("DecoderTrainer(apply_mask_to_rendering=True) needs a batch with a mask "
                              "(make_scene_batch(..., with_mask=True))")
+        if self.geometry and (batch.teacher_depth is None or batch.teacher_weights is None):
+            raise ValueError("DecoderTrainer(mask_weight / depth_weight > 0) needs a batch with the teacher's depth and weights "
+                             "(make_scene_batch(..., with_geometry=True))")
         attrs = None
         feats = self._scene_features(batch, scene_ids) if self.fused_planes else None
         if feats is not None and not self.fused_decoder:

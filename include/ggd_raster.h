@@ -492,6 +492,26 @@ int ggd_mask_composite(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, int32_t
                        const float* mask, int32_t mask_w, int32_t mask_h, int32_t backward, float* dst);
 
 /*
+ * Geometry loss: the rasterizer's depth D = sum alpha_i T_i z_i and alpha A = 1 - final T (device [H,W] fp32, the aux maps
+ * of ggd_forward_aux) against the teacher's depth t and weights w (device [th,tw] fp32; H % th == 0 and W % tw == 0,
+ * otherwise GGD_E_INVALID), and its gradient.  With xl = (2 (j + 0.5) / tw - 1) tanfovx, yl = (2 (i + 0.5) / th - 1) tanfovy:
+ *   z[i,j] = t[i,j] / sqrt(1 + xl^2 + yl^2) if ray_depth != 0 (t is a distance along a unit ray), else t[i,j];   p = w z;
+ *   m = up(w), q = up(p): the bilinear upsample of ggd_image_loss_masked by the integer factors H / th, W / tw;
+ *   r_m = A - m,  r_d = m D - A q;   L_mask = mean |r_m|,  L_depth = mean |r_d|  (means over H W);
+ *   total = weights2[0] L_mask + weights2[1] L_depth.
+ * weights2: HOST array of 2 floats.  terms3 (device, 3 floats): L_mask, L_depth, total.  grad_depth, grad_alpha (device
+ * [H,W]): dtotal/dD = weights2[1] sgn(r_d) m / (H W), dtotal/dA = (weights2[0] sgn(r_m) - weights2[1] sgn(r_d) q) / (H W),
+ * sgn(0) = 0.  No gradient for the teacher's maps.  Precondition (not checked): t is finite.
+ * tmp: device scratch of ggd_geometry_loss_tmp_bytes(W, H) bytes.  Two kernel launches, no host sync, no float atomics:
+ * terms and gradients are bit-identical from run to run.
+ */
+size_t ggd_geometry_loss_tmp_bytes(int32_t W, int32_t H);
+int ggd_geometry_loss(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, const float* depth, const float* alpha,
+                      const float* teacher_depth, const float* teacher_weights, int32_t tw, int32_t th, float tanfovx,
+                      float tanfovy, int32_t ray_depth, const float* weights2, float* terms3, float* grad_depth,
+                      float* grad_alpha, void* tmp, size_t tmp_bytes);
+
+/*
  * Exact 3-nearest-neighbour search: the `distCUDA2` of the simple_knn module that gaussian_splatting/scene/gaussian_model.py
  * imports (:20) to seed the scales of a new model (:132, :160).  points: DEVICE float32 [P][3], 4 <= P <= ggd_knn_max_points()
  * (2^26; fewer than 4 points have no three neighbours: GGD_E_INVALID).  For every point i, over all j != i (a different INDEX:
