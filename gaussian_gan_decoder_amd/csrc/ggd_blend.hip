@@ -445,9 +445,13 @@ __device__ __forceinline__ uint32_t bwd_pixel_init(Pix& st, bool in, size_t pix0
 // Lanes that hold a result of wave_reduce_swap (is_writer: lanes 0,4,8,12 | 32,36,40,44, lane 1 the opacity sum, AUX: lane 33
 // the depth sum) and the word of the accumulator record it belongs to: reduction output index (colour r g b | conic A B C |
 // mean sums x y | opacity | AUX: depth) -> slot in the record's order (conic A B C | opacity | mean x y | colour r g b | depth)
-template <bool AUX>
+// ABS (absgrad extension): lanes 6 and 38 hold the two absolute mean sums; they have no accumulator-order place below slot
+// GGD_ACC_ABS that every instance shares, so the value returned for them is their COLUMN in the parked row, right after the
+// other sums (9, 10; AUX: 10, 11) -- the flush maps it to GGD_ACC_ABS, GGD_ACC_ABS + 1
+template <bool AUX, bool ABS = false>
 __device__ __forceinline__ int bwd_writer_comp(int lane, bool& is_writer) {
-  is_writer = (lane & 19) == 0 || lane == 1 || (AUX && lane == 33);
+  is_writer = (lane & 19) == 0 || lane == 1 || (AUX && lane == 33) || (ABS && (lane & 31) == 6);
+  if (ABS && (lane & 31) == 6) return 9 + (AUX ? 1 : 0) + (lane >> 5);
   const int val = lane == 1 ? 8 : ((AUX && lane == 33) ? 9 : 4 * (lane >> 5) + (((lane >> 2) & 1) << 1) + ((lane >> 3) & 1));
   return val < 3 ? GGD_ACC_COLOR + val
        : (val < 6 ? GGD_ACC_CONIC + (val - 3)
@@ -466,10 +470,14 @@ __device__ __forceinline__ void bwd_stage_padding(float4* rec, int lane, int nk,
   }
 }
 
-template <int EXP_MODE, bool AUX = false, typename Pix = BwdPixel>
+// ABS (absgrad extension): sabs[0..1] = this pixel's |2 hA wx + nB wy|, |2 hC wy + nB wx| -- the expressions bwd_scale applies to
+// the REDUCED sums, evaluated per pixel, because the absolute value has to be taken before the sum over the pixels (the
+// non-negative factors op * 0.5 W, op * 0.5 H stay with the flush).  A pixel that does not see the record has wx = wy = 0.
+template <int EXP_MODE, bool AUX = false, bool ABS = false, typename Pix = BwdPixel>
 __device__ __forceinline__ uint64_t bwd_update(Pix& st, float pw, float dx, float dy, uint64_t need, float opacity,
                                                const float (&col)[3], float (&s)[8], float& sop, float z = 0.0f,
-                                               float* sz = nullptr) {
+                                               float* sz = nullptr, float hA = 0.0f, float nB = 0.0f, float hC = 0.0f,
+                                               float* sabs = nullptr) {
   float g0, adec;
   if constexpr (EXP_MODE == 3) {
     // the default pairing (bare v_exp_f32 in the forward, compensated 2^x here): the forward's G is exactly the `e` this form
@@ -517,6 +525,10 @@ __device__ __forceinline__ uint64_t bwd_update(Pix& st, float pw, float dx, floa
   s[6] = wx;
   s[7] = wy;
   sop = G * dL_dalpha;
+  if constexpr (ABS) {
+    sabs[0] = __builtin_fabsf(__builtin_fmaf(2.0f * hA, wx, nB * wy));
+    sabs[1] = __builtin_fabsf(__builtin_fmaf(2.0f * hC, wy, nB * wx));
+  }
   return live;
 }
 
@@ -540,11 +552,16 @@ __device__ __forceinline__ float bwd_scale(int comp, float v, float swx, float s
 //   (l & 3) != 1:  value 4 * (l >> 5) + {0, 2, 1, 3}[(l >> 2) & 3]     l < 32 and (l & 3) == 1:  the ninth value
 // TENTH (AUX: the depth sum): a tenth value takes the ninth's four in-row steps and rides in the redundant lanes 4b + 1 of the
 // OTHER folded register (v[4]): after the two swaps lanes 32 <= l < 64 with (l & 3) == 1 hold it.
-// The text of the two forms is assembled from the same pieces: ONLY10(x) is x in the ten-value form and nothing in the other.
+// ABS (absgrad extension: the two absolute mean sums): an eleventh and a twelfth value take the same four in-row steps and ride
+// in the NEXT redundant lane, 4b + 2, of the two folded registers (eleventh: v[0], twelfth: v[4]): after the swaps lanes l < 32
+// with (l & 3) == 2 hold the eleventh, lanes 32 <= l < 64 with (l & 3) == 2 the twelfth.  Their DPP steps follow the ninth's
+// (tenth's) in each group, so every value's step is at least as far from the write it reads as the ninth's is.
+// The text of the four forms is assembled from the same pieces: ONLY10(x) is x in the forms with a tenth value and nothing in
+// the others, ONLYABS(x) likewise for the eleventh and twelfth.
 #define GGD_RED_ROWSUM(r, ctl) "v_add_f32_dpp " r ", " r ", " r " " ctl " row_mask:0xf bank_mask:0xf\n\t"
 #define GGD_RED_KEEP(x) x
 #define GGD_RED_DROP(x)
-#define GGD_RED_TEXT(ONLY10)                                                                  \
+#define GGD_RED_TEXT(ONLY10, ONLYABS)                                                                \
       "s_nop 1\n\t"                                                                           \
       "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"                     \
       "v_add_f32_dpp %2, %2, %2 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"                     \
@@ -555,21 +572,27 @@ __device__ __forceinline__ float bwd_scale(int comp, float v, float swx, float s
       "v_add_f32_dpp %4, %5, %5 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                     \
       "v_add_f32_dpp %6, %7, %7 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                     \
       GGD_RED_ROWSUM("%[ninth]", "row_ror:8") ONLY10(GGD_RED_ROWSUM("%[tenth]", "row_ror:8"))  \
+      ONLYABS(GGD_RED_ROWSUM("%[absx]", "row_ror:8") GGD_RED_ROWSUM("%[absy]", "row_ror:8"))                      \
       "s_nop 0\n\t"                                                                           \
       "v_add_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"                     \
       "v_add_f32_dpp %4, %4, %4 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"                     \
       GGD_RED_ROWSUM("%[ninth]", "row_ror:4") ONLY10(GGD_RED_ROWSUM("%[tenth]", "row_ror:4"))  \
+      ONLYABS(GGD_RED_ROWSUM("%[absx]", "row_ror:4") GGD_RED_ROWSUM("%[absy]", "row_ror:4"))                      \
       "v_add_f32_dpp %0, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"                     \
       "v_add_f32_dpp %4, %6, %6 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"                     \
       "s_nop 1\n\t"                                                                           \
       GGD_RED_ROWSUM("%0", "quad_perm:[2,3,0,1]") GGD_RED_ROWSUM("%4", "quad_perm:[2,3,0,1]")  \
       GGD_RED_ROWSUM("%[ninth]", "quad_perm:[2,3,0,1]") ONLY10(GGD_RED_ROWSUM("%[tenth]", "quad_perm:[2,3,0,1]")) \
+      ONLYABS(GGD_RED_ROWSUM("%[absx]", "quad_perm:[2,3,0,1]") GGD_RED_ROWSUM("%[absy]", "quad_perm:[2,3,0,1]"))  \
       "s_nop 0\n\t"                                                                           \
       GGD_RED_ROWSUM("%0", "quad_perm:[1,0,3,2]") GGD_RED_ROWSUM("%4", "quad_perm:[1,0,3,2]")  \
       GGD_RED_ROWSUM("%[ninth]", "quad_perm:[1,0,3,2]") ONLY10(GGD_RED_ROWSUM("%[tenth]", "quad_perm:[1,0,3,2]")) \
+      ONLYABS(GGD_RED_ROWSUM("%[absx]", "quad_perm:[1,0,3,2]") GGD_RED_ROWSUM("%[absy]", "quad_perm:[1,0,3,2]"))  \
       "s_nop 1\n\t"                                                                           \
       "v_cndmask_b32_e64 %0, %0, %[ninth], %[mask]\n\t"                                       \
       ONLY10("v_cndmask_b32_e64 %4, %4, %[tenth], %[mask]\n\t")                               \
+      ONLYABS("v_cndmask_b32_e64 %0, %0, %[absx], %[mask2]\n\t")                              \
+      ONLYABS("v_cndmask_b32_e64 %4, %4, %[absy], %[mask2]\n\t")                              \
       "s_nop 1\n\t"                                                                           \
       "v_permlane32_swap_b32 %0, %4\n\t"                                                      \
       "s_nop 1\n\t"                                                                           \
@@ -579,16 +602,28 @@ __device__ __forceinline__ float bwd_scale(int comp, float v, float swx, float s
       "v_permlane16_swap_b32 %0, %4\n\t"                                                      \
       "s_nop 1\n\t"                                                                           \
       "v_add_f32_e32 %0, %0, %4"
-template <bool TENTH>
-__device__ __forceinline__ float wave_reduce_swap(float (&v)[8], float ninth, float tenth) {
+template <bool TENTH, bool ABS = false>
+__device__ __forceinline__ float wave_reduce_swap(float (&v)[8], float ninth, float tenth, float absx = 0.0f,
+                                                  float absy = 0.0f) {
   const uint64_t ninth_lanes = 0x2222222222222222ull;   // lane 4b + 1 of every bank
-  if constexpr (TENTH)
-    asm volatile(GGD_RED_TEXT(GGD_RED_KEEP)
+  [[maybe_unused]] const uint64_t abs_lanes = 0x4444444444444444ull;     // lane 4b + 2 of every bank
+  if constexpr (TENTH && ABS)
+    asm volatile(GGD_RED_TEXT(GGD_RED_KEEP, GGD_RED_KEEP)
+                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
+                   [ninth] "+v"(ninth), [tenth] "+v"(tenth), [absx] "+v"(absx), [absy] "+v"(absy)
+                 : [mask] "s"(ninth_lanes), [mask2] "s"(abs_lanes));
+  else if constexpr (ABS)
+    asm volatile(GGD_RED_TEXT(GGD_RED_DROP, GGD_RED_KEEP)
+                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
+                   [ninth] "+v"(ninth), [absx] "+v"(absx), [absy] "+v"(absy)
+                 : [mask] "s"(ninth_lanes), [mask2] "s"(abs_lanes));
+  else if constexpr (TENTH)
+    asm volatile(GGD_RED_TEXT(GGD_RED_KEEP, GGD_RED_DROP)
                  : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
                    [ninth] "+v"(ninth), [tenth] "+v"(tenth)
                  : [mask] "s"(ninth_lanes));
   else
-    asm volatile(GGD_RED_TEXT(GGD_RED_DROP)
+    asm volatile(GGD_RED_TEXT(GGD_RED_DROP, GGD_RED_DROP)
                  : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
                    [ninth] "+v"(ninth)
                  : [mask] "s"(ninth_lanes));
@@ -781,192 +816,27 @@ __global__ __launch_bounds__(256) void blend_backward_tile_kernel(
 // record (a pad word: layout and memset unchanged); dL/dalpha of a pixel only enters through its final transmittance, i.e. as
 // -dL/dalpha folded into bgdot once.  Rows of 10 sums + slot and the staged depths: 6144 B of LDS per wave.  depth_keys,
 // dL_ddepth and dL_dalpha are NULL, and never read, in a plain backward.
-template <int EXP_MODE, bool CULL, bool STATS = false, bool AUX = false>
-__global__ __launch_bounds__(64) void blend_backward_quarter_kernel(
-    int W, int H, int gx, int gy, const ggd_splat* __restrict__ splat, const uint32_t* __restrict__ list,
-    const uint32_t* __restrict__ ranges, const float* __restrict__ bg, const float* __restrict__ final_T,
-    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ grad_acc,
-    unsigned long long* __restrict__ stats, const uint32_t* __restrict__ depth_keys, const float* __restrict__ dL_ddepth,
-    const float* __restrict__ dL_dalpha) {
-  constexpr int NS = AUX ? 10 : 9, ROW = NS + 1;   // reduced sums per record; parked row = sums | staging slot
-  uint32_t st_staged = 0, st_need = 0, st_live = 0, st_lanes = 0, st_spans = 0, st_rounds = 0;
-  __shared__ float4 s_rec[64 * 3];
-  // [touched record, in processing order][NS sums | staging slot] (5632 B of LDS per wave with s_rec; AUX: 6144 with s_z); ONE
-  // buffer: a round's rows are flushed at the top of the next round, before that round's first row is written (LDS operations
-  // of a wave execute in order)
-  __shared__ float s_sum[64][ROW];
-  __shared__ float s_z[AUX ? 64 : 1];   // AUX: the staged records' depths (unused, and not allocated, otherwise)
-  const int lane = threadIdx.x;
-  int tile, sub;
-  ggd_block_to_tile((int)blockIdx.x, 4, gx * gy, tile, sub);
-  const int tx = tile % gx, ty = tile / gx;
-  const int qx = sub & 1, qy = sub >> 1;
-  const int px0 = tx * 16 + qx * 8 + (lane & 7), py = ty * 16 + qy * 8 + (lane >> 3);
-  const uint2 rg = reinterpret_cast<const uint2*>(ranges)[tile];
-  const bool in = py < H && px0 < W;
-  const size_t HW = (size_t)H * W;
-  const size_t pix0 = (size_t)py * W + px0;
-
-  std::conditional_t<AUX, BwdPixelAux, BwdPixel> st;
-  const float pxf = (float)px0, pyf = (float)py;
-  const uint32_t lastn = bwd_pixel_init<AUX>(st, in, pix0, HW, bg, final_T, n_contrib, dL_dpix, dL_ddepth, dL_dalpha);
-  uint32_t maxn = lastn;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, d, 64));
-  maxn = (uint32_t)__builtin_amdgcn_readfirstlane((int)maxn);
-  if (maxn == 0) return;
-  const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
-  const float wx0 = (float)(tx * 16 + qx * 8), wy0 = (float)(ty * 16 + qy * 8);   // this wave's pixel rectangle
-  const float wx1 = wx0 + 7.0f, wy1 = wy0 + 7.0f;
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
-  // the writer lanes put their sum where it goes in the row (accumulator-record order); lane 2 adds the record's staging slot
-  // to the same LDS store
-  bool is_writer;
-  const int writer_comp = bwd_writer_comp<AUX>(lane, is_writer);
-  const bool stores = is_writer || lane == 2;
-  const int store_col = is_writer ? writer_comp : NS;
-
-  // staged = the record as loaded with three words replaced in place:
-  //   {x, y, hA, nB} {hC, power threshold, opacity, 0-based list position} {g, b, r, Gaussian id}
-  bool keep = false;
-  uint32_t id_cur = 0, id_nxt = 0;
-  float4 r0 = make_float4(0, 0, 0, 0), r1 = r0, r2 = r0;    // x y hA nB | hC thr opacity r | g b ex ey
-  uint32_t zk = 0;                                          // AUX: depth key of the record in r0..r2
-  const uint32_t last_pos = rg.x + maxn - 1u;
-  auto load_id = [&](uint32_t ce) {
-    const uint32_t cs = ce > rg.x ? bwd_round_start(ce, rg.x) : rg.x;
-    id_nxt = list[min(cs + (uint32_t)lane, last_pos)];
-  };
-  auto load_rec = [&]() {
-    id_cur = id_nxt;
-    const float4* p = reinterpret_cast<const float4*>(splat + id_nxt);
-    r0 = p[0]; r1 = p[1]; r2 = p[2];
-    if constexpr (AUX) zk = depth_keys[id_nxt];
-  };
-  // the pre-cull rectangle of a round = the bounding rectangle of the pixels that can see ANY record of the round (those
-  // whose last contributor lies at or behind the round's first position): walking back to front a wave starts at its
-  // deepest pixel, and until the others join, most records only reach pixels that are not live yet
-  float lx0 = wx0, lx1 = wx1, ly0 = wy0, ly1 = wy1;
-  auto shrink_rect = [&](uint32_t first_pos) {   // 0-based list position of the round's first record
-    const uint64_t live = __ballot(lastn > first_pos);
-    if (live != 0ull) {
-      const int rmin = __builtin_ctzll(live) >> 3, rmax = (63 - __builtin_clzll(live)) >> 3;
-      uint32_t m = (uint32_t)live | (uint32_t)(live >> 32);
-      m |= m >> 16; m |= m >> 8; m &= 0xffu;
-      const int cmin = __builtin_ctz(m), cmax = 31 - __builtin_clz(m);
-      lx0 = wx0 + (float)cmin; lx1 = wx0 + (float)cmax;
-      ly0 = wy0 + (float)rmin; ly1 = wy0 + (float)rmax;
-    }
-  };
-  auto consume = [&](uint32_t ce) {
-    keep = false;
-    const uint32_t cs = bwd_round_start(ce, rg.x);
-    if (CULL) shrink_rect(cs - rg.x);
-    if ((uint32_t)lane < ce - cs) {
-      keep = CULL ? (record_box_hits(r0.x, r0.y, r2.z, r2.w, lx0, lx1, ly0, ly1) &&
-                     record_reaches_block(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r2.z, lx0, lx1, ly0, ly1)) : true;
-      if (!CULL) r1.y = -__builtin_huge_valf();
-      r2.z = r1.w;
-      r1.w = __uint_as_float((cs - rg.x) + (uint32_t)lane);
-      r2.w = __uint_as_float(id_cur);
-    }
-  };
-  // the flush of one round's parked sums (cnt rows), reading the round's records where they were staged
-  auto flush = [&](int cnt) {
-    const float* rows = &s_sum[0][0];
-    for (int p = lane; p < cnt * NS; p += 64) {
-      const int r = p / NS, comp = p - NS * r;
-      const float v = rows[r * ROW + comp];
-      const float swx = rows[r * ROW + GGD_ACC_MEAN2D], swy = rows[r * ROW + GGD_ACC_MEAN2D + 1];
-      const int slot = (int)__float_as_uint(rows[r * ROW + NS]);
-      const float4 a = s_rec[slot * 3 + 0], b = s_rec[slot * 3 + 1];
-      const uint32_t id = __float_as_uint(s_rec[slot * 3 + 2].w);
-      atomicAdd(grad_acc + GGD_ACC_FLOATS * (size_t)id + comp,
-                bwd_scale(comp, v, swx, swy, a.z, a.w, b.x, b.z, ddelx_dx, ddely_dy));
-    }
-  };
-
-  uint32_t cend = rg.x + maxn;  // one past the last position this quarter needs
-  load_id(cend);
-  load_rec();
-  load_id(bwd_round_start(cend, rg.x));
-  int prev_cnt = 0;
-  while (cend > rg.x) {
-    const uint32_t cstart = bwd_round_start(cend, rg.x);
-    consume(cend);                                       // the records requested one round ago
-    __builtin_amdgcn_wave_barrier();                     // (the previous round's LDS reads are done: in-order per wave)
-    flush(prev_cnt);                                     // the previous round's sums: BEFORE its records are overwritten and
-    __builtin_amdgcn_wave_barrier();                     // before the new loads are issued
-    const uint64_t kept = __ballot(keep);
-    const int nk = __popcll(kept), n8 = (nk + 7) & ~7;
-    if (STATS) { st_staged += (uint32_t)nk; st_rounds += 1; st_spans += (uint32_t)prev_cnt; }
-    if (keep) {  // compacted, order preserved
-      const int slot = __popcll(kept & lt_mask);
-      s_rec[slot * 3 + 0] = r0; s_rec[slot * 3 + 1] = r1; s_rec[slot * 3 + 2] = r2;
-      if constexpr (AUX) s_z[slot] = __uint_as_float(zk);   // view-space depth (the key is its fp32 bits)
-    }
-    bwd_stage_padding(s_rec, lane, nk, n8);
-    load_rec();                                          // next round's records
-    load_id(cstart > rg.x ? bwd_round_start(cstart, rg.x) : rg.x); // and the list entries of the round after it
-    __builtin_amdgcn_wave_barrier();
-    int cnt = 0;
-    float* rows = &s_sum[0][0];
-    for (int j0 = n8 - 8; j0 >= 0; j0 -= 8) {
-      uint32_t ga = (uint32_t)(uintptr_t)(lds_cf4*)(s_rec + j0 * 3);   // see blend_forward_kernel
-      asm volatile("" : "+v"(ga));
-      lds_cf4* grp = (lds_cf4*)(uintptr_t)ga;
-      // (all twelve words one record ahead, inside the group: see the forward)
-      float4 a_nx = lds_read4(grp + 7 * 3), b_nx = lds_read4(grp + 7 * 3 + 1), c_nx = lds_read4(grp + 7 * 3 + 2);
-      const float* zgrp = AUX ? s_z + j0 : nullptr;
-      float z_nx = 0.0f;
-      if constexpr (AUX) z_nx = zgrp[7];
-#pragma unroll
-      for (int jj = 7; jj >= 0; --jj) {
-        const float4 a = a_nx, b = b_nx, c4 = c_nx;
-        const float z = z_nx;
-        asm volatile("" : : "v"(c4.w));   // (keeps the unused twelfth word's VGPR from being handed out while the load is in flight)
-        if (jj > 0) {
-          a_nx = lds_read4(grp + (jj - 1) * 3); b_nx = lds_read4(grp + (jj - 1) * 3 + 1); c_nx = lds_read4(grp + (jj - 1) * 3 + 2);
-          if constexpr (AUX) z_nx = zgrp[jj - 1];
-        }
-        const float dy = a.y - pyf;
-        const float nBdy = a.w * dy, hCdy2 = (b.x * dy) * dy;
-        const uint32_t pos0 = __float_as_uint(b.w);
-        const float dx = a.x - pxf;
-        const float pw = __builtin_fmaf(__builtin_fmaf(a.z, dx, nBdy), dx, hCdy2);
-        const uint64_t need = __ballot(pos0 < lastn) & __ballot(pw >= b.y);
-        if (need == 0ull) continue;
-        if (STATS) st_need += 1;
-        const float col[3] = {c4.z, c4.x, c4.y};                     // r | g, b
-        float s[8], sop, sz = 0.0f;                                  // colour r g b | conic A B C | mean sums x y ; opacity ; depth
-        const uint64_t live = bwd_update<EXP_MODE, AUX>(st, pw, dx, dy, need, b.z, col, s, sop, z, &sz);
-        if (live != 0ull) {   // wave-uniform: somebody in this wave saw the Gaussian
-          if (STATS) { st_live += 1; st_lanes += (uint32_t)__popcll(live); }
-          const float tot = wave_reduce_swap<AUX>(s, sop, sz);
-          // the writer lanes' sums (bwd_writer_comp); lane 2 the record's slot in the staging area
-          const float v = is_writer ? tot : __uint_as_float((uint32_t)(j0 + jj));
-          if (stores) rows[cnt * ROW + store_col] = v;
-          ++cnt;
-        }
-      }
-    }
-    prev_cnt = cnt;
-    cend = cstart;
-  }
-  __builtin_amdgcn_wave_barrier();
-  flush(prev_cnt);
-  if (STATS && lane == 0 && stats) {
-    unsigned long long* o = stats + GGD_STATS_BWD;
-    atomicAdd(o + 0, (unsigned long long)maxn);
-    atomicAdd(o + 1, (unsigned long long)st_staged);
-    atomicAdd(o + 2, (unsigned long long)st_need);
-    atomicAdd(o + 3, (unsigned long long)st_live);
-    atomicAdd(o + 4, (unsigned long long)st_lanes);
-    atomicAdd(o + 5, (unsigned long long)(st_spans + (uint32_t)prev_cnt));
-    atomicAdd(o + 6, (unsigned long long)st_rounds);
-    atomicAdd(o + 7, 1ull);
-  }
-}
+// ABS (ggd_backward_abs, with or without AUX): the per-pixel absolute values of the two mean-gradient components (bwd_update)
+// are the ELEVENTH and TWELFTH reduced values (lanes 6 and 38), parked in two more columns of the row and added, times
+// op * 0.5 W / op * 0.5 H, to slots GGD_ACC_ABS, GGD_ACC_ABS + 1 of the accumulator record (the two remaining pad words).
+// Rows of 11 (AUX: 12) sums + slot: 6144 B of LDS per wave (AUX: 6656).  The ABS instances are kernels of their own,
+// blend_backward_quarter_abs_kernel<EXP_MODE, CULL, AUX>, from the same text (ggd_blend_bwd_quarter.inc, included twice):
+// blend_backward_quarter_kernel keeps its name, its four template arguments and its code.
+#define GGD_BWDQ_TEMPLATE template <int EXP_MODE, bool CULL, bool STATS = false, bool AUX = false>
+#define GGD_BWDQ_NAME blend_backward_quarter_kernel
+#define GGD_BWDQ_LOCALS constexpr bool ABS = false;
+#include "ggd_blend_bwd_quarter.inc"
+#undef GGD_BWDQ_TEMPLATE
+#undef GGD_BWDQ_NAME
+#undef GGD_BWDQ_LOCALS
+// the absgrad backward (no statistics instance: stats is NULL)
+#define GGD_BWDQ_TEMPLATE template <int EXP_MODE, bool CULL, bool AUX = false>
+#define GGD_BWDQ_NAME blend_backward_quarter_abs_kernel
+#define GGD_BWDQ_LOCALS constexpr bool ABS = true, STATS = false;
+#include "ggd_blend_bwd_quarter.inc"
+#undef GGD_BWDQ_TEMPLATE
+#undef GGD_BWDQ_NAME
+#undef GGD_BWDQ_LOCALS
 
 }  // namespace
 
@@ -1003,7 +873,7 @@ int ggd_launch_blend(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const g
 int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
                               const uint32_t* list, const uint32_t* ranges, const float* final_T,
                               const uint32_t* n_contrib, const float* dL_dpix, float* grad_acc, bool aux,
-                              const uint32_t* depth_keys, const float* dL_ddepth, const float* dL_dalpha) {
+                              const uint32_t* depth_keys, const float* dL_ddepth, const float* dL_dalpha, bool abs) {
   const int gx = (prm.width + 15) / 16, gy = (prm.height + 15) / 16;
   if (gx * gy == 0) return GGD_OK;
   const int em = ctx->opt[GGD_OPT_EXP_MODE];   // 3 (default): compensated 2^x, contribution decision on the forward's bare v_exp_f32 value
@@ -1020,9 +890,9 @@ int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm
   if (split == 1) split = 4;
   static const int lds_pad = getenv("GGD_BLEND_BWD_LDS_PAD") ? atoi(getenv("GGD_BLEND_BWD_LDS_PAD")) : 0;   // experiment
   // the depth / alpha backward exists in the quarter form only: it is used whatever GGD_OPT_BLEND_SPLIT says (the tile form
-  // is an explicit, non-default choice kept for measurements)
+  // is an explicit, non-default choice kept for measurements); so does the absgrad backward
   if (aux && !depth_keys) return ggd_fail(ctx, GGD_E_INVALID, "internal: depth / alpha backward needs the depth keys");
-  if (!aux && split != 4) {
+  if (!aux && !abs && split != 4) {
     ggd_dispatch<4>(em, [&](auto e) {
       ggd_dispatch<2>(cull, [&](auto c) {
         hipLaunchKernelGGL((blend_backward_tile_kernel<decltype(e)::value, decltype(c)::value != 0>), dim3(T), dim3(256), 0, s,
@@ -1033,17 +903,19 @@ int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm
     return GGD_OK;
   }
   // quarter form, one instance per (exp mode, cull, variant); the variants exclude each other: no statistics instance of the
-  // depth / alpha backward
-  enum { PLAIN = 0, STATS = 1, AUX = 2 };
-  const int variant = aux ? AUX : (ctx->blend_stats ? STATS : PLAIN);
+  // depth / alpha backward, nor of the absgrad ones (ABS, AUXABS: the absolute sums without / with the depth / alpha terms)
+  enum { PLAIN = 0, STATS = 1, AUX = 2, ABS = 3, AUXABS = 4 };
+  const int variant = abs ? (aux ? AUXABS : ABS) : (aux ? AUX : (ctx->blend_stats ? STATS : PLAIN));
   ggd_dispatch<4>(em, [&](auto e) {
     ggd_dispatch<2>(cull, [&](auto c) {
-      ggd_dispatch<3>(variant, [&](auto v) {
-        constexpr int V = decltype(v)::value;
-        hipLaunchKernelGGL((blend_backward_quarter_kernel<decltype(e)::value, decltype(c)::value != 0, V == STATS, V == AUX>),
-                           dim3(4 * T), dim3(64), lds_pad, s, prm.width, prm.height, gx, gy, splat, list, ranges, prm.bg, final_T,
-                           n_contrib, dL_dpix, grad_acc, V == STATS ? ctx->blend_stats : nullptr,
-                           V == AUX ? depth_keys : nullptr, V == AUX ? dL_ddepth : nullptr, V == AUX ? dL_dalpha : nullptr);
+      ggd_dispatch<5>(variant, [&](auto v) {
+        constexpr int V = decltype(v)::value, E = decltype(e)::value;
+        constexpr bool C = decltype(c)::value != 0, VAUX = V == AUX || V == AUXABS;
+        const auto kernel = (V == ABS || V == AUXABS) ? blend_backward_quarter_abs_kernel<E, C, VAUX>
+                                                      : blend_backward_quarter_kernel<E, C, V == STATS, VAUX>;
+        hipLaunchKernelGGL(kernel, dim3(4 * T), dim3(64), lds_pad, s, prm.width, prm.height, gx, gy, splat, list, ranges, prm.bg,
+                           final_T, n_contrib, dL_dpix, grad_acc, V == STATS ? ctx->blend_stats : nullptr,
+                           VAUX ? depth_keys : nullptr, VAUX ? dL_ddepth : nullptr, VAUX ? dL_dalpha : nullptr);
       });
     });
   });

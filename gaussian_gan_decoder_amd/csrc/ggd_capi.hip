@@ -773,7 +773,8 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, cons
                          const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
                          const float* dL_dpix, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
                          float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
-                         float* dL_drots, bool aux, const float* dL_ddepth, const float* dL_dalpha) {
+                         float* dL_drots, bool aux, const float* dL_ddepth, const float* dL_dalpha,
+                         bool abs = false, float* dL_dmeans2D_abs = nullptr) {
   (void)hipGetLastError();   // a sticky error another library left in this thread is not ours to report
   int rc = check_params(ctx, prm);
   if (rc != GGD_OK) return rc;
@@ -784,6 +785,7 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, cons
   if (!radii || !geom_buf || !img_buf || !dL_dpix || !dL_dmeans2D || !dL_dcolors || !dL_dopacity ||
       !dL_dmeans3D || !dL_dcov3D || !dL_dscales || !dL_drots || (prm->M > 0 && !dL_dsh) || (R > 0 && !binning_buf))
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward: NULL buffer");
+  if (abs && !dL_dmeans2D_abs) return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward_abs: NULL dL_dmeans2D_abs");
   if (prm->raw_attributes && (!opacities || cov3D_precomp))
     return ggd_fail(ctx, GGD_E_INVALID, "raw_attributes needs opacities and scales/rotations (no cov3D_precomp)");
   if (prm->antialiasing && !opacities)   // dL/dh of the opacity compensation is dL/do_eff times the opacity
@@ -809,14 +811,15 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, cons
   if (R > 0) {
     StageTimer t(ctx, ST_BLEND_BWD, s);
     rc = ggd_launch_blend_backward(ctx, s, *prm, g.splat, b.list, im.ranges, im.final_T, im.n_contrib, dL_dpix, grad_acc, aux,
-                                   g.depth_keys, dL_ddepth, dL_dalpha);
+                                   g.depth_keys, dL_ddepth, dL_dalpha, abs);
     if (rc != GGD_OK) return rc;
   }
   {
     StageTimer t(ctx, ST_PREPROCESS_BWD, s);
     rc = ggd_launch_preprocess_backward(ctx, s, *prm, means3D, shs, colors_precomp, opacities, dL_dopacity, scales, rotations,
                                         cov3D_precomp, radii, shs ? g.clamped : nullptr, grad_acc, dL_dmeans2D,
-                                        dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots, aux);
+                                        dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots, aux,
+                                        abs ? dL_dmeans2D_abs : nullptr);
     if (rc != GGD_OK) return rc;
   }
   return GGD_OK;
@@ -844,6 +847,21 @@ extern "C" int ggd_backward_aux(ggd_ctx* ctx, void* stream, const ggd_params* pr
   return backward_impl(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii,
                        geom_buf, binning_buf, img_buf, R, dL_dpix, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D,
                        dL_dcov3D, dL_dsh, dL_dscales, dL_drots, true, dL_ddepth, dL_dalpha);
+}
+
+// the absgrad backward: ggd_backward_aux's arguments + dL_dmeans2D_abs; without dL_ddepth and dL_dalpha it is the plain
+// backward's arithmetic (the ABS instances), with either the depth / alpha backward's (AUX + ABS)
+extern "C" int ggd_backward_abs(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
+                                const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+                                const float* rotations, const float* cov3D_precomp, const int32_t* radii,
+                                const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
+                                const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, float* dL_dmeans2D,
+                                float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                                float* dL_dscales, float* dL_drots, float* dL_dmeans2D_abs) {
+  return backward_impl(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii,
+                       geom_buf, binning_buf, img_buf, R, dL_dpix, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D,
+                       dL_dcov3D, dL_dsh, dL_dscales, dL_drots, dL_ddepth || dL_dalpha, dL_ddepth, dL_dalpha, true,
+                       dL_dmeans2D_abs);
 }
 
 extern "C" int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D,

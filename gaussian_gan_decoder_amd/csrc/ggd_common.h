@@ -267,24 +267,28 @@ int ggd_launch_blend(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const g
 // Backward accumulator record (library scratch, one per Gaussian, zeroed with ONE memset): the blend backward adds its
 // per-(tile, Gaussian) sums here, the per-Gaussian backward reads it once and writes every caller-visible gradient
 // (zeros for culled Gaussians), so the caller's 8 gradient arrays need no zero-fill passes.
-constexpr int GGD_ACC_FLOATS = 12;   // 48 B: conic A,B,C | opacity | mean2D x,y | colour r,g,b | depth (aux only) | 2 pad
+constexpr int GGD_ACC_FLOATS = 12;   // 48 B: conic A,B,C | opacity | mean2D x,y | colour r,g,b | depth (aux only) | abs mean2D x,y
 constexpr int GGD_ACC_CONIC = 0, GGD_ACC_OPACITY = 3, GGD_ACC_MEAN2D = 4, GGD_ACC_COLOR = 6;
 constexpr int GGD_ACC_DEPTH = 9;     // dL/dz (view-space depth), written only by the depth / alpha backward
+constexpr int GGD_ACC_ABS = 10;      // sum over pixels of |d/d mean2D x|, |.. y| (slots 10, 11), written only by an absgrad backward
 // aux: the depth / alpha backward (blend_backward_quarter_kernel<..., AUX>, always the quarter form); depth_keys as in
-// ggd_launch_blend, dL_ddepth / dL_dalpha [H, W] (NULL = zero)
+// ggd_launch_blend, dL_ddepth / dL_dalpha [H, W] (NULL = zero).  abs: the absolute screen-space gradient sums as well (slots
+// GGD_ACC_ABS; quarter form only, with or without aux)
 int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
                               const uint32_t* list, const uint32_t* ranges, const float* final_T,
                               const uint32_t* n_contrib, const float* dL_dpix, float* grad_acc /*[P][GGD_ACC_FLOATS]*/,
                               bool aux = false, const uint32_t* depth_keys = nullptr, const float* dL_ddepth = nullptr,
-                              const float* dL_dalpha = nullptr);
+                              const float* dL_dalpha = nullptr, bool abs = false);
 // aux: also adds dL/dz (accumulator slot GGD_ACC_DEPTH) times dz/dmean = (view[2], view[6], view[10]) to dL_dmeans3D
+// dL_dmean2D_abs (NULL = not wanted): [P, 3] = (accumulator slots GGD_ACC_ABS, 0), zeros for culled Gaussians
 int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const float* means3D,
                                    const float* shs, const float* colors_precomp, const float* opacities,
                                    float* dL_dopacity, const float* scales,
                                    const float* rotations, const float* cov3D_precomp, const int32_t* radii,
                                    const uint8_t* clamped, const float* grad_acc, float* dL_dmean2D,
                                    float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                                   float* dL_dscales, float* dL_drots, bool aux = false);
+                                   float* dL_dscales, float* dL_drots, bool aux = false,
+                                   float* dL_dmean2D_abs = nullptr);
 
 // ---- device helpers -----------------------------------------------------------------------------------------
 #ifdef __HIPCC__

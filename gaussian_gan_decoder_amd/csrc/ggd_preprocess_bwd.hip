@@ -24,7 +24,9 @@ using namespace ggdm;
 // w = 0.3 dilation.  With g = dL/do_eff (acc0.w): dL/do = g h, and while the clamp is off dL/dr = g o / (2 h) adds
 //   dL/dx += k w (y^2 + w y + z^2),  dL/dy += k w (x^2 + w x + z^2),  dL/dz += -2 k w z (x + y + w),  k = g o / (2 h det1^2)
 // to the conic's dL/da, dL/dc, dL/db before they are taken on to cov3D and the view-space point
-template <bool SHVEC, bool DREG = false, bool AUX = false, bool AA = false>
+// ABS (absgrad extension): dL_dmean2D_abs[i] = (accumulator slots GGD_ACC_ABS, GGD_ACC_ABS + 1, 0) -- the blend's sums of the
+// per-pixel absolute screen-space gradients, already scaled -- and zeros for a culled Gaussian; nothing else changes
+template <bool SHVEC, bool DREG = false, bool AUX = false, bool AA = false, bool ABS = false>
 __device__ __forceinline__ void preprocess_backward_body(
     int i, float* dsh_stage,
     int P, int M, int deg, int W, int H, float tanfovx, float tanfovy, float mod, int raw,
@@ -35,10 +37,11 @@ __device__ __forceinline__ void preprocess_backward_body(
     const int32_t* __restrict__ radii, const uint8_t* __restrict__ clamped,
     const float* __restrict__ grad_acc, float* __restrict__ dL_dmean2D, float* __restrict__ dL_dcolors,
     float* __restrict__ dL_dmeans3D, float* __restrict__ dL_dcov3D, float* __restrict__ dL_dsh,
-    float* __restrict__ dL_dscales, float* __restrict__ dL_drots) {
+    float* __restrict__ dL_dscales, float* __restrict__ dL_drots, float* __restrict__ dL_dmean2D_abs) {
   const size_t ii = (size_t)i;
   if (radii[i] <= 0) {  // culled: every gradient of this Gaussian is zero (the caller does not pre-fill the arrays)
     dL_dmean2D[3 * ii] = 0.0f; dL_dmean2D[3 * ii + 1] = 0.0f; dL_dmean2D[3 * ii + 2] = 0.0f;
+    if constexpr (ABS) { dL_dmean2D_abs[3 * ii] = 0.0f; dL_dmean2D_abs[3 * ii + 1] = 0.0f; dL_dmean2D_abs[3 * ii + 2] = 0.0f; }
     dL_dcolors[3 * ii] = 0.0f; dL_dcolors[3 * ii + 1] = 0.0f; dL_dcolors[3 * ii + 2] = 0.0f;
     dL_dopacity[i] = 0.0f;
     dL_dmeans3D[3 * ii] = 0.0f; dL_dmeans3D[3 * ii + 1] = 0.0f; dL_dmeans3D[3 * ii + 2] = 0.0f;
@@ -61,9 +64,13 @@ __device__ __forceinline__ void preprocess_backward_body(
   }
   const float4 acc0 = reinterpret_cast<const float4*>(grad_acc)[3 * ii];      // conic A, B, C | opacity
   const float4 acc1 = reinterpret_cast<const float4*>(grad_acc)[3 * ii + 1];  // mean2D x, y | colour r, g
-  const float4 acc2 = reinterpret_cast<const float4*>(grad_acc)[3 * ii + 2];  // colour b
+  const float4 acc2 = reinterpret_cast<const float4*>(grad_acc)[3 * ii + 2];  // colour b | depth | abs mean2D x, y
   const float gcol3[3] = {acc1.z, acc1.w, acc2.x};
   dL_dmean2D[3 * ii] = acc1.x; dL_dmean2D[3 * ii + 1] = acc1.y; dL_dmean2D[3 * ii + 2] = 0.0f;
+  if constexpr (ABS) {
+    static_assert(GGD_ACC_ABS == 10, "absolute mean gradients are read from acc2.z, acc2.w");
+    dL_dmean2D_abs[3 * ii] = acc2.z; dL_dmean2D_abs[3 * ii + 1] = acc2.w; dL_dmean2D_abs[3 * ii + 2] = 0.0f;
+  }
   dL_dcolors[3 * ii] = gcol3[0]; dL_dcolors[3 * ii + 1] = gcol3[1]; dL_dcolors[3 * ii + 2] = gcol3[2];
   const Mat16 V = load_mat(view);
   const Mat16 PV = load_mat(proj);
@@ -357,18 +364,34 @@ __device__ __forceinline__ void preprocess_backward_body(
 
 // The three forms of the kernel.  AA: the anti-aliasing h chain (ggd_params.antialiasing); AUX: the depth term of the
 // depth / alpha extension (ggd_backward_aux).  Both off: the plain backward.
+// The absgrad extension (ggd_backward_abs) has kernels of its own, preprocess_abs_backward{,_vec,_staged}_kernel: the same
+// bodies with ABS on and one more argument, dL_dmean2D_abs.  The kernels below keep their names, arguments and code.
 template <bool AA = false, bool AUX = false>
 __global__ __launch_bounds__(256) void preprocess_backward_kernel(GGD_PPB_PARAMS) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= P) return;
-  preprocess_backward_body<false, false, AUX, AA>(i, nullptr, GGD_PPB_ARGS);
+  preprocess_backward_body<false, false, AUX, AA>(i, nullptr, GGD_PPB_ARGS, nullptr);
+}
+
+template <bool AA = false, bool AUX = false>
+__global__ __launch_bounds__(256) void preprocess_abs_backward_kernel(GGD_PPB_PARAMS, float* __restrict__ dL_dmean2D_abs) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  preprocess_backward_body<false, false, AUX, AA, true>(i, nullptr, GGD_PPB_ARGS, dL_dmean2D_abs);
 }
 
 template <bool AA = false, bool AUX = false>
 __global__ __launch_bounds__(256) void preprocess_backward_vec_kernel(GGD_PPB_PARAMS) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= P) return;
-  preprocess_backward_body<true, true, AUX, AA>(i, nullptr, GGD_PPB_ARGS);
+  preprocess_backward_body<true, true, AUX, AA>(i, nullptr, GGD_PPB_ARGS, nullptr);
+}
+
+template <bool AA = false, bool AUX = false>
+__global__ __launch_bounds__(256) void preprocess_abs_backward_vec_kernel(GGD_PPB_PARAMS, float* __restrict__ dL_dmean2D_abs) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  preprocess_backward_body<true, true, AUX, AA, true>(i, nullptr, GGD_PPB_ARGS, dL_dmean2D_abs);
 }
 
 // SH degree > 0 (M > 1 coefficients per channel): a Gaussian's 3 M gradients are 12 M bytes apart from its neighbour's, so
@@ -376,13 +399,10 @@ __global__ __launch_bounds__(256) void preprocess_backward_vec_kernel(GGD_PPB_PA
 // 494 us for this kernel against 88 us at M = 1).  Here every lane parks its row in LDS and the wave writes its 64 rows --
 // one contiguous 768 M-byte span of dL_dsh -- with lane-consecutive (16-byte where 3 M allows) stores.  (1 M Gaussians,
 // M = 16: 247 -> 146 us; preprocess_backward_vec_kernel above does as well without LDS where the rows allow dwordx4.)
-template <bool SHVEC, bool AA = false, bool AUX = false>
-__global__ __launch_bounds__(256) void preprocess_backward_staged_kernel(GGD_PPB_PARAMS) {
-  extern __shared__ float s_dsh[];   // [256][3 M + 1]
-  const int i = blockIdx.x * 256 + threadIdx.x;
+// (the write-out of the staged rows, after the wave's lanes have parked them)
+__device__ __forceinline__ void preprocess_backward_flush_rows(const float* s_dsh, float* __restrict__ dL_dsh, int P, int M) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int rl = 3 * M, rowlen = rl + 1;
-  if (i < P) preprocess_backward_body<SHVEC, false, AUX, AA>(i, s_dsh + (size_t)threadIdx.x * rowlen, GGD_PPB_ARGS);
   __builtin_amdgcn_wave_barrier();
   __threadfence_block();
   const int i0 = blockIdx.x * 256 + wv * 64;
@@ -405,6 +425,24 @@ __global__ __launch_bounds__(256) void preprocess_backward_staged_kernel(GGD_PPB
   }
 }
 
+template <bool SHVEC, bool AA = false, bool AUX = false>
+__global__ __launch_bounds__(256) void preprocess_backward_staged_kernel(GGD_PPB_PARAMS) {
+  extern __shared__ float s_dsh[];   // [256][3 M + 1]
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < P) preprocess_backward_body<SHVEC, false, AUX, AA>(i, s_dsh + (size_t)threadIdx.x * (3 * M + 1), GGD_PPB_ARGS, nullptr);
+  preprocess_backward_flush_rows(s_dsh, dL_dsh, P, M);
+}
+
+template <bool SHVEC, bool AA = false, bool AUX = false>
+__global__ __launch_bounds__(256) void preprocess_abs_backward_staged_kernel(GGD_PPB_PARAMS,
+                                                                             float* __restrict__ dL_dmean2D_abs) {
+  extern __shared__ float s_dsh[];   // [256][3 M + 1]
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < P)
+    preprocess_backward_body<SHVEC, false, AUX, AA, true>(i, s_dsh + (size_t)threadIdx.x * (3 * M + 1), GGD_PPB_ARGS, dL_dmean2D_abs);
+  preprocess_backward_flush_rows(s_dsh, dL_dsh, P, M);
+}
+
 }  // namespace
 
 int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const float* means3D,
@@ -413,20 +451,30 @@ int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params
                                    const float* rotations, const float* cov3D_precomp, const int32_t* radii,
                                    const uint8_t* clamped, const float* grad_acc, float* dL_dmean2D,
                                    float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                                   float* dL_dscales, float* dL_drots, bool aux) {
+                                   float* dL_dscales, float* dL_drots, bool aux, float* dL_dmean2D_abs) {
   if (prm.P == 0) return GGD_OK;
   // the staged form whenever there is more than the band-0 coefficient per channel (and room: 256 rows of 3 M + 1 floats)
   const bool staged = !colors_precomp && prm.M > 1 && (size_t)256 * (3 * prm.M + 1) * sizeof(float) <= 64 * 1024;
   // rows that are a multiple of 16 bytes (M = 4, 8, 12, 16): read and written from registers with dwordx4 accesses (145 us
   // at M = 16, 1 M Gaussians; the LDS-staged form measures 152 with the same loads and is kept for the other M)
   const bool shvec = staged && prm.M <= 16 && ((3 * prm.M) & 3) == 0;
-  // the feature flags (h chain, depth term) pick the instance, the SH layout picks the form
+  // the feature flags (h chain, depth term, absolute gradients) pick the instance, the SH layout picks the form
+  const size_t lds = (staged && !shvec) ? (size_t)256 * (3 * prm.M + 1) * sizeof(float) : 0;
   ggd_dispatch<2>(prm.antialiasing != 0, [&](auto aa) {
     ggd_dispatch<2>(aux, [&](auto ax) {
       constexpr bool AA = decltype(aa)::value != 0, AUX = decltype(ax)::value != 0;
+      if (dL_dmean2D_abs) {   // the absgrad kernels: one more argument
+        const auto kernel = shvec ? preprocess_abs_backward_vec_kernel<AA, AUX>
+                          : staged ? preprocess_abs_backward_staged_kernel<false, AA, AUX> : preprocess_abs_backward_kernel<AA, AUX>;
+        hipLaunchKernelGGL(kernel, dim3((prm.P + 255) / 256), dim3(256), lds, s, prm.P, prm.M, prm.sh_degree, prm.width,
+                           prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier, prm.raw_attributes, opacities, dL_dopacity,
+                           prm.viewmatrix, prm.projmatrix, prm.campos, means3D, shs, colors_precomp, scales, rotations,
+                           cov3D_precomp, radii, clamped, grad_acc, dL_dmean2D, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh,
+                           dL_dscales, dL_drots, dL_dmean2D_abs);
+        return;
+      }
       const auto kernel = shvec ? preprocess_backward_vec_kernel<AA, AUX>
                         : staged ? preprocess_backward_staged_kernel<false, AA, AUX> : preprocess_backward_kernel<AA, AUX>;
-      const size_t lds = (staged && !shvec) ? (size_t)256 * (3 * prm.M + 1) * sizeof(float) : 0;
       hipLaunchKernelGGL(kernel, dim3((prm.P + 255) / 256), dim3(256), lds, s, prm.P, prm.M, prm.sh_degree, prm.width,
                          prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier, prm.raw_attributes, opacities, dL_dopacity,
                          prm.viewmatrix, prm.projmatrix, prm.campos, means3D, shs, colors_precomp, scales, rotations,

@@ -269,16 +269,22 @@ class GaussianModel:
             raise RuntimeError(f"GaussianModel.{who} needs HIP device tensors (there is no CPU fallback)")
         return int(self._xyz.shape[0])
 
-    def _stats(self, who, viewspace_point_tensor, radii, update_filter):
+    def _stats(self, who, viewspace_point_tensor, radii, update_filter, use_absgrad=False):
         from . import _capi
+        if use_absgrad:   # the same [P, 3] layout, handed to the same launch
+            grad = getattr(viewspace_point_tensor, "absgrad", None)
+            if grad is None:
+                raise ValueError(f"{who}: use_absgrad=True, but viewspace_point_tensor has no .absgrad (render with "
+                                 "absgrad=True and call backward first)")
         P = self._device_rows(who)
-        grad = viewspace_point_tensor.grad
+        if not use_absgrad:
+            grad = viewspace_point_tensor.grad
         if grad is None:
             raise ValueError(f"{who}: viewspace_point_tensor has no .grad (call backward first)")
         for t in (self.xyz_gradient_accum, self.denom):   # updated in place
             if tuple(t.shape) != (P, 1) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
                 raise ValueError(f"{who}: call training_setup first (contiguous float32 device statistics [{P}, 1] expected)")
-        for t, name, dtypes, shape in ((grad, "viewspace_point_tensor.grad", (torch.float32,), (P, 3)),
+        for t, name, dtypes, shape in ((grad, "viewspace_point_tensor." + ("absgrad" if use_absgrad else "grad"), (torch.float32,), (P, 3)),
                                        (radii, "radii", (torch.int32,), (P,)),
                                        (update_filter, "update_filter", (torch.bool, torch.uint8), (P,))):
             if t is None:
@@ -302,14 +308,18 @@ class GaussianModel:
             cx.check(cx.lib.ggd_densify_stats(cx.handle, C.c_void_p(stream), P, ptr(grad), ptr(radii), ptr(filt),
                                               ptr(self.xyz_gradient_accum), ptr(self.denom), ptr(max_radii)))
 
-    def add_densification_stats(self, viewspace_point_tensor, update_filter):
-        """On the rows of the bool filter: xyz_gradient_accum += |grad[:, :2]|, denom += 1.  One launch, no host wait."""
-        self._stats("add_densification_stats", viewspace_point_tensor, None, update_filter)
+    def add_densification_stats(self, viewspace_point_tensor, update_filter, use_absgrad=False):
+        """On the rows of the bool filter: xyz_gradient_accum += |grad[:, :2]|, denom += 1.  One launch, no host wait.
+        use_absgrad=True: the statistic is taken from `viewspace_point_tensor.absgrad` (a render with absgrad=True: the
+        per-pixel ABSOLUTE screen-space gradients, AbsGS) instead of `.grad`; a ValueError if the attribute is missing.  The
+        absolute statistic is larger than the signed one, so densify_and_prune wants a larger threshold: AbsGS used 2-4 x
+        the usual 0.0002; no default in this package is tuned for it."""
+        self._stats("add_densification_stats", viewspace_point_tensor, None, update_filter, use_absgrad)
 
-    def update_densification_stats(self, viewspace_point_tensor, radii):
+    def update_densification_stats(self, viewspace_point_tensor, radii, use_absgrad=False):
         """The loop's two statistics lines in one launch: rows with radii > 0 are visible; on them max_radii2D =
-        max(max_radii2D, radii) and add_densification_stats' update."""
-        self._stats("update_densification_stats", viewspace_point_tensor, radii, None)
+        max(max_radii2D, radii) and add_densification_stats' update (use_absgrad: see there)."""
+        self._stats("update_densification_stats", viewspace_point_tensor, radii, None, use_absgrad)
 
     def _regather(self, plan):
         """plan(context, stream, tmp pointer, tmp bytes, counts) fills the source map and the counts and returns the noise (or

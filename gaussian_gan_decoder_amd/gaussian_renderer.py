@@ -30,11 +30,12 @@ def _screenspace_points(pc):
 
 
 def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attributes=False, render_depth_alpha=False,
-              antialiasing=False):
+              antialiasing=False, absgrad=False):
     return GaussianRasterizationSettings(
         raw_attributes=raw_attributes,
         render_depth_alpha=render_depth_alpha,
         antialiasing=antialiasing,
+        absgrad=absgrad,
         image_height=int(viewpoint_camera.image_height),
         image_width=int(viewpoint_camera.image_width),
         tanfovx=math.tan(viewpoint_camera.FoVx * 0.5),
@@ -51,14 +52,17 @@ def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attri
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           render_depth_alpha=False, antialiasing=False):
+           render_depth_alpha=False, antialiasing=False, absgrad=False):
     """Stock 3DGS render (reference :19-102).  `pipe` needs .debug, .compute_cov3D_python, .convert_SHs_python.
     render_depth_alpha=True (extension): the dict also holds "depth" (sum alpha_i T_i z_i) and "alpha" (1 - final T),
     differentiable float32 [1, H, W] maps.
-    antialiasing=True (extension, upstream's GaussianRasterizationSettings flag): the opacity-compensated 2D filter."""
+    antialiasing=True (extension, upstream's GaussianRasterizationSettings flag): the opacity-compensated 2D filter.
+    absgrad=True (extension, gsplat's flag): after backward() `out["viewspace_points"].absgrad` holds the absolute
+    screen-space gradients (float32 [P, 3], overwritten by each backward) for GaussianModel's use_absgrad statistics."""
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, pipe.debug,
-                                              render_depth_alpha=render_depth_alpha, antialiasing=antialiasing))
+                                              render_depth_alpha=render_depth_alpha, antialiasing=antialiasing,
+                                              absgrad=absgrad))
     scales = rotations = cov3D_precomp = None
     if pipe.compute_cov3D_python:
         cov3D_precomp = pc.get_covariance(scaling_modifier)
@@ -87,7 +91,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
 
 
 def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None, scaling_modifier=1.0,
-                  override_color=None, debug=False, fused_activations=False, render_depth_alpha=False, antialiasing=False):
+                  override_color=None, debug=False, fused_activations=False, render_depth_alpha=False, antialiasing=False,
+                  absgrad=False):
     """Decoder-path render (reference :105-186): scale/rotation always from the model, SH unless override_color.
     "alpha" and "depth" are the radii placeholders the reference returns (:184-185).
     fused_activations=True (extension): hand the RAW `_opacity/_scaling/_rotation` to the
@@ -97,11 +102,12 @@ def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None,
     and "alpha" (1 - final T) are the rasterizer's differentiable float32 [1, H, W] maps instead of the placeholders.
     antialiasing=True (extension): the opacity-compensated 2D filter -- each Gaussian's opacity times
     sqrt(det(cov2D) / det(cov2D + 0.3 I)), so that a Gaussian far smaller than a pixel does not grow brighter and thicker
-    when zoomed out; combines with fused_activations and render_depth_alpha."""
+    when zoomed out; combines with fused_activations and render_depth_alpha.
+    absgrad=True (extension): as in `render`; combines with all of the above."""
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug,
                                               raw_attributes=fused_activations, render_depth_alpha=render_depth_alpha,
-                                              antialiasing=antialiasing))
+                                              antialiasing=antialiasing, absgrad=absgrad))
     means3D = pc.get_xyz
     if xyz_offset is not None:
         means3D = means3D + xyz_offset

@@ -55,20 +55,29 @@ class GaussianRasterizationSettings(_SettingsFields):
 
     antialiasing (keyword only, default False): upstream's flag of the same name -- the opacity-compensated 2D filter,
     each Gaussian's opacity times sqrt(det(cov2D) / det(cov2D + 0.3 I)).  It is an attribute, not a tuple field: upstream's
-    13th positional slot is our raw_attributes, and the fields and their positions stay what callers already rely on."""
-    antialiasing: bool = False   # (instances made without __new__, e.g. by _make, read this class default)
+    13th positional slot is our raw_attributes, and the fields and their positions stay what callers already rely on.
 
-    def __new__(cls, *args, antialiasing: bool = False, **kwargs):
+    absgrad (keyword only, default False; gsplat's flag of the same name): the backward also computes the ABSOLUTE
+    screen-space gradients of AbsGS -- per Gaussian the sum over pixels of |each pixel's contribution| to means2D.grad's x
+    and y -- and sets them as `means2D.absgrad`, a float32 [P, 3] tensor (third column 0), on the means2D tensor the
+    rasterizer was called with.  As in gsplat the attribute is OVERWRITTEN by every backward, not accumulated.  An
+    attribute like antialiasing, for the same reason."""
+    antialiasing: bool = False   # (instances made without __new__, e.g. by _make, read these class defaults)
+    absgrad: bool = False
+
+    def __new__(cls, *args, antialiasing: bool = False, absgrad: bool = False, **kwargs):
         self = super().__new__(cls, *args, **kwargs)
         self.antialiasing = bool(antialiasing)
+        self.absgrad = bool(absgrad)
         return self
 
     def _replace(self, **kwargs):
         aa = kwargs.pop("antialiasing", self.antialiasing)
-        return type(self)(*super()._replace(**kwargs), antialiasing=aa)
+        ab = kwargs.pop("absgrad", self.absgrad)
+        return type(self)(*super()._replace(**kwargs), antialiasing=aa, absgrad=ab)
 
     def __repr__(self):
-        return super().__repr__()[:-1] + f", antialiasing={self.antialiasing})"
+        return super().__repr__()[:-1] + f", antialiasing={self.antialiasing}, absgrad={self.absgrad})"
 
 
 def _f32c(t: torch.Tensor, name: str, device) -> torch.Tensor:
@@ -360,12 +369,15 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
                                         cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, dL_dout_color, sh,
                                         degree, campos, geomBuffer, R, binningBuffer, imgBuffer, debug,
                                         raw_attributes=False, opacities=None, *, dL_ddepth=None, dL_dalpha=None,
-                                        antialiasing=False):
+                                        antialiasing=False, absgrad=False):
     """== upstream `_C.rasterize_gaussians_backward(...)`: returns
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
     dL_ddepth / dL_dalpha (extension, [1, H, W] or [H, W]; None = zero): gradients of the depth and alpha maps of a
     render_depth_alpha forward -- with either given the call is ggd_backward_aux, else today's ggd_backward.
-    antialiasing=True: the backward of an antialiasing forward; it needs `opacities` (the forward's, as passed to it)."""
+    antialiasing=True: the backward of an antialiasing forward; it needs `opacities` (the forward's, as passed to it).
+    absgrad=True (extension): the call is ggd_backward_abs and a NINTH tensor follows the eight, dL_dmeans2D_abs [P, 3] =
+    (0.5 W sum_pixels |g_x|, 0.5 H sum_pixels |g_y|, 0) with g the per-pixel terms whose signed sums are dL_dmeans2D; the
+    eight are those of ggd_backward (no dL_ddepth / dL_dalpha) or ggd_backward_aux (either given)."""
     if antialiasing and opacities is None:
         raise ValueError("the antialiasing backward needs the opacities of the forward (opacities=None)")
     H, W = int(dL_dout_color.size(-2)), int(dL_dout_color.size(-1))
@@ -406,12 +418,22 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
     dL_dsh = torch.empty((P, M, 3), **f32)
     dL_dscales = torch.empty((P, 3), **f32)
     dL_drotations = torch.empty((P, 4), **f32)
+    dL_dmeans2D_abs = torch.empty((P, 3), **f32) if absgrad else None
     if ctx.poison_outputs:   # tests: the library must write every element itself (it does not rely on pre-zeroed arrays)
         for t in (dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations):
             t.fill_(float("nan"))
+        if absgrad:
+            dL_dmeans2D_abs.fill_(float("nan"))
     if P > 0:
         with torch.cuda.device(dev):
-            if aux:
+            if absgrad:
+                ctx.check(lib.ggd_backward_abs(ctx.handle, _stream(dev), C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c),
+                                               _ptr(op_c), _ptr(sc_c), _ptr(rot_c), _ptr(cov_c), _ptr(radii), _ptr(geomBuffer),
+                                               _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g), _ptr(gD), _ptr(gA),
+                                               _ptr(dL_dmeans2D), _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D),
+                                               _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations),
+                                               _ptr(dL_dmeans2D_abs)))
+            elif aux:
                 ctx.check(lib.ggd_backward_aux(ctx.handle, _stream(dev), C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c),
                                                _ptr(op_c), _ptr(sc_c), _ptr(rot_c), _ptr(cov_c), _ptr(radii), _ptr(geomBuffer),
                                                _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g), _ptr(gD), _ptr(gA),
@@ -423,6 +445,9 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
                                            _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g), _ptr(dL_dmeans2D),
                                            _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D), _ptr(dL_dcov3D),
                                            _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations)))
+    if absgrad:
+        return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
+                dL_dmeans2D_abs)
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
 
 
@@ -455,6 +480,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         num_rendered, color, radii, geom, binning, img = out[:6]
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
+        # absgrad: the backward sets `.absgrad` on the tensor the CALLER holds (inside apply() the inputs are the caller's own
+        # objects), so it is kept by reference, not saved for backward
+        ctx.means2D_ref = means2D if getattr(rs, "absgrad", False) else None
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
                               img, opacities)
         ctx.mark_non_differentiable(radii)
@@ -479,11 +507,16 @@ class _RasterizeGaussians(torch.autograd.Function):
             aux = dict(dL_ddepth=grad_depth, dL_dalpha=grad_alpha)
         if aa:   # (only when set: a plain render calls the backward exactly as before)
             aux["antialiasing"] = True
+        absgrad = bool(getattr(rs, "absgrad", False))
+        if absgrad:   # (likewise)
+            aux["absgrad"] = True
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = rasterize_gaussians_backward_native(
+         grad_rotations, *grad_abs) = rasterize_gaussians_backward_native(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, geom,
             ctx.num_rendered, binning, img, rs.debug, raw, opacities if (raw or aa) else None, **aux)
+        if absgrad and isinstance(ctx.means2D_ref, torch.Tensor):
+            ctx.means2D_ref.absgrad = grad_abs[0]   # gsplat's convention: overwritten by each backward, not accumulated
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
                 grad_rotations, grad_cov3Ds_precomp, None)
 

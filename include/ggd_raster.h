@@ -236,6 +236,28 @@ int ggd_backward_aux(ggd_ctx* ctx, void* stream, const ggd_params* prm,
                      float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
                      float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots);
 
+/*
+ * Absolute screen-space gradients (opt-in extension, the densification signal of AbsGS; ggd_backward and ggd_backward_aux
+ * are unchanged by it).  ggd_backward_abs == ggd_backward_aux + one more output:
+ *   dL_dmeans2D_abs : float[P,3], written in full = (0.5 W sum_q |g_x(q,i)|, 0.5 H sum_q |g_y(q,i)|, 0), where g_x, g_y are
+ *                     the per-pixel terms whose SIGNED sums are dL_dmeans2D[i] -- same contributors, same skip and stop rules,
+ *                     the depth / alpha terms included when dL_ddepth / dL_dalpha are given; zeros for culled Gaussians.
+ * dL_ddepth and dL_dalpha may both be NULL: the other eight gradients are then those of ggd_backward (the plain arithmetic),
+ * with either they are those of ggd_backward_aux.  Same validation as ggd_backward_aux (GGD_E_INVALID for a NULL
+ * dL_dmeans2D_abs).  Runs the quarter form of the backward blend whatever GGD_OPT_BLEND_SPLIT says.  Like every blend
+ * gradient the sums are float atomics: not bit-reproducible from run to run.
+ */
+int ggd_backward_abs(ggd_ctx* ctx, void* stream, const ggd_params* prm,
+                     const float* means3D, const float* shs, const float* colors_precomp,
+                     const float* opacities /* only read when prm->raw_attributes or prm->antialiasing */,
+                     const float* scales, const float* rotations, const float* cov3D_precomp,
+                     const int32_t* radii,
+                     const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t num_rendered,
+                     const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
+                     float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                     float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots,
+                     float* dL_dmeans2D_abs);
+
 /* present[i] = 1 iff Gaussian i passes the view-space z > 0.2 frustum test. */
 int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D,
                      const float* viewmatrix, const float* projmatrix, uint8_t* present);
