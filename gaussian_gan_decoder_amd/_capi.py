@@ -51,7 +51,9 @@ class ImgView(C.Structure):
 
 
 OPT_EXP_MODE, OPT_BLEND_CULL, OPT_BINNING, OPT_BLEND_SPLIT, OPT_FOLD, OPT_MSD_SORT, OPT_PREPROCESS_WGS = 0, 1, 2, 3, 4, 5, 6
+OPT_L1_COUNTED = 7
 STAT_FLAT_STREAK, STAT_SORT_RERUNS, STAT_MSD_FRAMES, STAT_SCAN_IN_SCATTER_FRAMES = 100, 101, 102, 103   # read-only, through get_option
+STAT_L1_COUNTED_FRAMES = 104
 SPLAT_BYTES = 48
 SPLAT_FIELDS = ("x", "y", "hA", "nB", "hC", "thr", "opacity", "r", "g", "b", "ex", "ey")
 

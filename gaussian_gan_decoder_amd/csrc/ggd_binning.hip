@@ -537,7 +537,8 @@ __global__ __launch_bounds__(MSDF_THREADS, 8) void sort_msd_finish_kernel(const 
                                                                        uint32_t* __restrict__ keys_out,
                                                                        uint32_t* __restrict__ vals_out,
                                                                        const uint32_t* __restrict__ hist /* [GGD_MSD_BINS] totals */,
-                                                                       const uint32_t* __restrict__ table, int ntiles, int kshift) {
+                                                                       const uint32_t* __restrict__ table, int ntiles, int kshift,
+                                                                       msd_rows rows /* rect == nullptr: no counted level 1 behind */) {
   __shared__ msd_lds L;
   const int tid = threadIdx.x;
   const uint32_t b = blockIdx.x;
@@ -561,14 +562,30 @@ __global__ __launch_bounds__(MSDF_THREADS, 8) void sort_msd_finish_kernel(const 
       const size_t src = msd_piece_src_big(L, table, b, ntiles, p);
       vals_out[(size_t)base + p] = vals_in[src];
     }
+  } else if (nb > (uint32_t)MSD_XCAP) {   // exchange through the bucket's slice of the output; pass 2 leaves the final order there
+    msd_bucket_sort<true, MSDF_ITEMS>(L, keys_in, vals_in, ntiles, nb, kshift, keys_out + base, vals_out + base, rows, base);
+  }
+  uint32_t run = 0;   // wave 0, lane = tile row: row entries of the bucket's elements in front of the window
+  if (nb > (uint32_t)MSD_XCAP) {
+    // the order is in this workgroup's slice of vals_out; the rows for the counted level 1, a window of GGD_MSD_CAP elements at a
+    // time (one window unless the bucket is oversized: that frame is rendered again, but the binning behind still runs on it once
+    // and is given complete tables -- in the order this kernel leaves, as without the counted level 1)
+    if (!rows.rect) return;
+    for (uint32_t p0 = 0; p0 < nb; p0 += (uint32_t)GGD_MSD_CAP) {
+      __syncthreads();   // the stores to vals_out above / the previous window's difference arrays have been read
+      msd_bucket_rows(L, rows, b, base, nb, p0, run, vals_out + base);
+    }
     return;
   }
-  if (nb > (uint32_t)MSD_XCAP) {   // exchange through the bucket's slice of the output; pass 2 leaves the final order there
-    msd_bucket_sort<true, MSDF_ITEMS>(L, keys_in, vals_in, ntiles, nb, kshift, keys_out + base, vals_out + base);
-    return;
+  // the usual bucket: with a counted level 1 behind, the sort's last pass fetched the rects and counted the rows on its way -- the
+  // values leave with the rects' bytes (L.kv[0, nb)) as `packed`, and wave 0 publishes the rows beside the copy-out
+  msd_bucket_sort<false, MSDX_ITEMS>(L, keys_in, vals_in, ntiles, nb, kshift, nullptr, nullptr, rows, base);
+  if (rows.rect && tid < 64) msd_publish_rows(reinterpret_cast<const int*>(&L.pp[0]), rows, b, base, base + nb, true, run);
+  for (uint32_t p = tid; p < nb; p += MSDF_THREADS) {
+    const uint32_t id = L.kv[MSD_XCAP + p];
+    vals_out[(size_t)base + p] = id;
+    if (rows.rect && base + p < rows.n) rows.packed[base + p] = make_uint2(id, L.kv[p]);
   }
-  msd_bucket_sort<false, MSDX_ITEMS>(L, keys_in, vals_in, ntiles, nb, kshift, nullptr, nullptr);
-  for (uint32_t p = tid; p < nb; p += MSDF_THREADS) vals_out[(size_t)base + p] = L.kv[MSD_XCAP + p];
 }
 
 // ------------------------------------------------------------------------------------------- tile ranges -----
@@ -716,7 +733,7 @@ bool ggd_sort32_msd_supported(int64_t n) { return n > 0 && (n + MSD_TILE - 1) / 
 // before, its step 3 is left to the caller's binning launch): result in (keys_a, vals_a); the consumers' "flat" word stays 0.
 int ggd_launch_sort32_msd(ggd_ctx* ctx, hipStream_t s, const uint32_t* keys_src, uint32_t* keys_a, uint32_t* vals_a,
                           uint32_t* keys_b, uint32_t* vals_b, int64_t n, uint32_t* table, const ggd_scan_piggy* piggy,
-                          const ggd_fold* fold) {
+                          const ggd_fold* fold, const ggd_l1_counted* counted) {
   if (n <= 0) return GGD_OK;
   if (!fold || !fold->msd || !piggy || !piggy->wg_info || !ggd_sort32_msd_supported(n))
     return ggd_fail(ctx, GGD_E_INVALID, "sort32 (two launches): needs the folded front end in its msd form");
@@ -727,8 +744,14 @@ int ggd_launch_sort32_msd(ggd_ctx* ctx, hipStream_t s, const uint32_t* keys_src,
   pg.n_valid = ctl.n_valid; pg.fold_hist = ctl.ghist;
   hipLaunchKernelGGL(sort_msd_partition_kernel, dim3(ntiles + 1), dim3(RS_THREADS), 0, s, keys_src, keys_b, vals_b, n, table,
                      ntiles, fold->msd_lo, fold->msd_shift, pg);
+  msd_rows rows = {};   // (rect == nullptr: the finish kernel sorts and nothing else)
+  if (counted) {
+    if (!counted->rect || !counted->packed || !counted->bucket_rows || !counted->boundary_rows || counted->chunks != rb_blocks1((int)n))
+      return ggd_fail(ctx, GGD_E_INVALID, "sort32 (two launches): incomplete arrays for the counted level 1");
+    rows = msd_rows{counted->rect, counted->packed, counted->bucket_rows, counted->boundary_rows, (uint32_t)counted->chunks, (uint32_t)n};
+  }
   hipLaunchKernelGGL(sort_msd_finish_kernel, dim3(GGD_MSD_BINS), dim3(MSDF_THREADS), 0, s, keys_b, vals_b, keys_a, vals_a,
-                     ctl.ghist, table, ntiles, fold->msd_shift);
+                     ctl.ghist, table, ntiles, fold->msd_shift, rows);
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }

@@ -168,8 +168,15 @@ static inline uint32_t rb_blocks2(uint32_t cap, bool wide) {                    
 // The row binning's scratch (byte offsets into tmp), both widths: the depth-ordered rects, level 1's per-chunk counts (nby bins
 // a chunk), the tables, the row entries, level 2's per-chunk counts (nbx bins a chunk).  nby / nbx: 64 bins per group of rows /
 // columns the grid needs (64 on the narrow path).
+// Counted level 1 (rb_level1_counted_kernel; frames of the two-launch sort on the narrow path): two row tables BEHIND `total`, so
+// that every offset above and `total` itself keep their values -- `total` is what the other forms need, `total_counted` what a
+// caller that may take the counted form reserves.
+//   bucket_rows[GGD_MSD_BINS][64]      row entries per tile row of every bucket of the two-launch sort
+//   boundary_rows[rb_blocks1(P)][64]   ... of the elements of the bucket that holds rank 1024 k in front of that rank
+// both written by sort_msd_finish_kernel with plain stores, read by the launch behind it.
 struct ggd_rowbin_tmp {
   size_t packed, counts1, tab, ent, counts2, total;
+  size_t bucket_rows, boundary_rows, total_counted;
 };
 static inline ggd_rowbin_tmp ggd_rowbin_layout(int P, uint32_t capacity, int W, int H) {
   const bool wide = rb_is_wide(W, H);
@@ -181,5 +188,8 @@ static inline ggd_rowbin_tmp ggd_rowbin_layout(int P, uint32_t capacity, int W, 
   t.ent = t.tab + ggd_align((size_t)(wide ? RBW_TAB_WORDS : RB_TAB_WORDS) * 4);
   t.counts2 = t.ent + ggd_align((size_t)capacity * 8);
   t.total = t.counts2 + ggd_align((size_t)rb_blocks2(capacity, wide) * (wide ? nbx : 64) * 4);
+  t.bucket_rows = t.total;
+  t.boundary_rows = t.bucket_rows + ggd_align((size_t)GGD_MSD_BINS * 64 * 4);
+  t.total_counted = t.boundary_rows + ggd_align((size_t)rb_blocks1(P) * 64 * 4);
   return t;
 }

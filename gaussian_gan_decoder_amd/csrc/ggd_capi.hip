@@ -164,6 +164,7 @@ extern "C" ggd_ctx* ggd_create(int device) {
   if (const char* e = getenv("GGD_FOLD")) ctx->opt[GGD_OPT_FOLD] = atoi(e) != 0;
   if (const char* e = getenv("GGD_MSD_SORT")) ctx->opt[GGD_OPT_MSD_SORT] = atoi(e) != 0;
   if (const char* e = getenv("GGD_PREPROCESS_WGS")) { const int v = atoi(e); if (v >= 0 && v <= GGD_PREPROCESS_WGS_MAX) ctx->opt[GGD_OPT_PREPROCESS_WGS] = v; }
+  if (const char* e = getenv("GGD_L1_COUNTED")) ctx->opt[GGD_OPT_L1_COUNTED] = atoi(e) != 0;
   if (const char* e = getenv("GGD_MSD_BUCKETS")) { const int v = atoi(e); if (v >= 16 && v <= GGD_MSD_BINS) ctx->spec.msd_buckets = v; }   // timing experiments
   int prev = 0;
   (void)hipGetDevice(&prev);
@@ -213,7 +214,7 @@ extern "C" const char* ggd_last_error(ggd_ctx* ctx) { return ctx ? ctx->err.c_st
 
 extern "C" int ggd_set_option(ggd_ctx* ctx, int option, int value) {
   if (!ctx) return GGD_E_INVALID;
-  static const int kMax[GGD_OPT_COUNT] = {3, 1, 3, 4, 1, 1, GGD_PREPROCESS_WGS_MAX};
+  static const int kMax[GGD_OPT_COUNT] = {3, 1, 3, 4, 1, 1, GGD_PREPROCESS_WGS_MAX, 1};
   if (option < 0 || option >= GGD_OPT_COUNT || value < 0 || value > kMax[option])
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_set_option: unknown option or value");
   ctx->opt[option] = value;
@@ -262,6 +263,7 @@ extern "C" int ggd_get_option(ggd_ctx* ctx, int option) {
   if (ctx && option == GGD_STAT_SORT_RERUNS) return (int)(ctx->spec.reruns & 0x7fffffffull);
   if (ctx && option == GGD_STAT_MSD_FRAMES) return (int)(ctx->spec.msd_frames & 0x7fffffffull);
   if (ctx && option == GGD_STAT_SCAN_IN_SCATTER_FRAMES) return (int)(ctx->scan_in_scatter_frames & 0x7fffffffull);
+  if (ctx && option == GGD_STAT_L1_COUNTED_FRAMES) return (int)(ctx->l1_counted_frames & 0x7fffffffull);
   if (!ctx || option < 0 || option >= GGD_OPT_COUNT) return GGD_E_INVALID;
   return ctx->opt[option];
 }
@@ -525,6 +527,8 @@ static int sort_depth_and_bin_tiles(ggd_ctx* ctx, hipStream_t s, const ggd_param
   ggd_scan_piggy pg;          // a scan that rides on this call's launches (see geometry_enqueue)
   ggd_fold fold;              // the folded front end's control block, if this call has one
   const uint32_t *n_vis_ptr = nullptr, *flat_ptr = nullptr;   // device words: kept keys, "last pass was flat"
+  const bool narrow = !rb_is_wide(prm->width, prm->height);   // grids of <= 64 x 64 tiles: the lane-per-bin binning kernels
+  bool counted = false;                                       // this frame's level 1 takes its row counts from the sort's finish launch
   {
     StageTimer t(ctx, ST_SORT, s);
     if (riding) {
@@ -548,10 +552,14 @@ static int sort_depth_and_bin_tiles(ggd_ctx* ctx, hipStream_t s, const ggd_param
     fr.report.folded = folded;
     fold.msd = msd ? 1 : 0;
     fold.msd_lo = fr.plan.lo; fold.msd_shift = fr.plan.shift;
-    if (msd)
+    if (msd) {
+      // counted level 1: the finish launch also fills the row tables in the binning's scratch (narrow grids; GGD_OPT_L1_COUNTED)
+      counted = ctx->opt[GGD_OPT_L1_COUNTED] != 0 && narrow;
+      const ggd_l1_counted l1c = ggd_rowbin_counted(bin_tmp_ptr, g.rect, prm->P, capacity, prm->width, prm->height);
       rc = ggd_launch_sort32_msd(ctx, s, g.depth_keys, ka, va, kb, vb, prm->P,
-                                 reinterpret_cast<uint32_t*>(sc + 4 * pairs + sort_tmp + bin_tmp), &pg, &fold);
-    else {
+                                 reinterpret_cast<uint32_t*>(sc + 4 * pairs + sort_tmp + bin_tmp), &pg, &fold,
+                                 counted ? &l1c : nullptr);
+    } else {
       ggd_sort32_opts so;
       so.clean_ctl = folded ? nullptr : clean_ctl;
       so.piggy = riding ? &pg : nullptr;
@@ -568,13 +576,14 @@ static int sort_depth_and_bin_tiles(ggd_ctx* ctx, hipStream_t s, const ggd_param
   }
   StageTimer t(ctx, ST_DUPLICATE, s);
   // the depth sort dropped the culled Gaussians (key 0xFFFFFFFF) and left the number of kept ones on the device
-  const bool l1 = folded && (prm->width + 15) / 16 <= 64 && (prm->height + 15) / 16 <= 64;
+  const bool l1 = folded && narrow;
   bool scan_in_scatter = false;
   rc = ggd_launch_rowbin(ctx, s, *prm, g.rect, va, n_vis_ptr, list, ranges, capacity, bin_tmp_ptr, bin_tmp, vb,
                          flat_ptr, riding ? &pg : nullptr, l1 ? ggd_fold_rowtot(fold.ctl) : nullptr,
                          l1 ? ggd_fold_l1_status(fold.ctl, prm->P) : nullptr, l1 ? ggd_fold_rowinst(fold.ctl, prm->P) : nullptr,
-                         &scan_in_scatter);
+                         &scan_in_scatter, counted ? ggd_sort_ctl::in_fold(fold.ctl).ghist : nullptr);
   if (scan_in_scatter) ++ctx->scan_in_scatter_frames;
+  if (counted && rc == GGD_OK) ++ctx->l1_counted_frames;
   return rc;
 }
 

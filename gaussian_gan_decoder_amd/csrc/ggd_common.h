@@ -70,6 +70,7 @@ struct ggd_ctx {
   int fold_cur = 0;                 // block the next folding preprocess accumulates into (cleared by the previous one)
   bool fold_poisoned = false;       // a folding launch failed: nothing is known about the blocks -- clear both before the next use
   unsigned long long scan_in_scatter_frames = 0;   // GGD_STAT_SCAN_IN_SCATTER_FRAMES
+  unsigned long long l1_counted_frames = 0;        // GGD_STAT_L1_COUNTED_FRAMES
   ggd_spec spec;                    // cross-frame speculation policy: three sort passes / the two-launch sort (ggd_spec.h)
   ggd_frame frame;                  // the one frame in flight
   // ggd_forward_enqueue ... ggd_forward_collect: the frame whose num_rendered has not been collected yet
@@ -78,7 +79,7 @@ struct ggd_ctx {
   void* gelu_tables = nullptr;      // GELU / GELU' interpolation tables of the reference-precision decoder kernels (built on first use)
   void *dbg_keys = nullptr, *dbg_vals = nullptr;   // debug copy of the unsorted list
   size_t dbg_cap = 0;
-  int opt[GGD_OPT_COUNT] = {3, 1, 1, 1, 1, 1, 0};  // exp: bare v_exp_f32 in the forward blend, compensated 2^x (1-2 ulp) in the backward
+  int opt[GGD_OPT_COUNT] = {3, 1, 1, 1, 1, 1, 0, 1};  // exp: bare v_exp_f32 in the forward blend, compensated 2^x (1-2 ulp) in the backward
   unsigned long long* blend_stats = nullptr;  // debug: device counters filled by the forward blend when non-null
   unsigned long long* stats_buf = nullptr;    // its storage: [0..5] counters, [GGD_STATS_MODE] 1 = per-wave timeline, slots from GGD_STATS_HEAD
   bool profiling = false;
@@ -240,23 +241,48 @@ int ggd_launch_sort32_iota(ggd_ctx* ctx, hipStream_t s, const uint32_t* keys_src
                            uint32_t* keys_b, uint32_t* vals_b, int64_t n, int nbits, void* tmp, size_t tmp_bytes,
                            const ggd_sort32_opts& opts = ggd_sort32_opts());
 bool ggd_sort32_msd_supported(int64_t n);
+// Counted level 1 of the row binning (GGD_OPT_L1_COUNTED; grids of <= 64 x 64 tiles behind the two-launch sort): the finish launch,
+// which holds every bucket in its final order, also gathers the rects and counts the row entries of its bucket -- per bucket and
+// in front of every 1024-rank chunk boundary inside it -- so that rb_level1_counted_kernel sums finished rows instead of looking
+// back over the chunks of its own launch.  The three arrays live in the row binning's scratch (ggd_rowbin_counted).
+struct ggd_l1_counted {
+  const uint2* rect = nullptr;        // [P] tile rect of every Gaussian (the preprocess kernel's)
+  uint2* packed = nullptr;            // [P] by depth rank: {id, x0 | x1 << 8 | y0 << 16 | y1 << 24}, zeros for an empty rect
+  uint32_t* bucket_rows = nullptr;    // [GGD_MSD_BINS][64]
+  uint32_t* boundary_rows = nullptr;  // [chunks][64]
+  int chunks = 0;                     // rb_blocks1(P)
+};
 int ggd_launch_sort32_msd(ggd_ctx* ctx, hipStream_t s, const uint32_t* keys_src, uint32_t* keys_a, uint32_t* vals_a,
                           uint32_t* keys_b, uint32_t* vals_b, int64_t n, uint32_t* table, const ggd_scan_piggy* piggy,
-                          const ggd_fold* fold);
+                          const ggd_fold* fold, const ggd_l1_counted* counted = nullptr);
 // Tile binning (GGD_OPT_BINNING = 1): sorted Gaussian order -> per-tile lists + ranges.
 bool ggd_rowbin_supported(int W, int H);
-static inline size_t ggd_rowbin_tmp_bytes(int P, uint32_t capacity, int W, int H) { return ggd_rowbin_layout(P, capacity, W, H).total; }
+static inline size_t ggd_rowbin_tmp_bytes(int P, uint32_t capacity, int W, int H) { return ggd_rowbin_layout(P, capacity, W, H).total_counted; }
+// the counted level 1's arrays inside the row binning's scratch (narrow grids only; tmp holds ggd_rowbin_tmp_bytes)
+static inline ggd_l1_counted ggd_rowbin_counted(void* tmp, const uint2* rect, int P, uint32_t capacity, int W, int H) {
+  const ggd_rowbin_tmp lay = ggd_rowbin_layout(P, capacity, W, H);
+  char* p = static_cast<char*>(tmp);
+  ggd_l1_counted c;
+  c.rect = rect; c.packed = reinterpret_cast<uint2*>(p + lay.packed);
+  c.bucket_rows = reinterpret_cast<uint32_t*>(p + lay.bucket_rows);
+  c.boundary_rows = reinterpret_cast<uint32_t*>(p + lay.boundary_rows);
+  c.chunks = rb_blocks1(P);
+  return c;
+}
 int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const uint2* rect, const uint32_t* order,
                       const uint32_t* n_vis_ptr, uint32_t* list, uint32_t* ranges, uint32_t capacity, void* tmp,
                       size_t tmp_bytes, const uint32_t* order_alt = nullptr, const uint32_t* use_alt = nullptr,
                       const ggd_scan_piggy* apply = nullptr, const uint32_t* fold_rowtot = nullptr, uint32_t* fold_status1 = nullptr,
-                      const uint32_t* fold_rowinst = nullptr, bool* scan_in_scatter = nullptr);   // apply: step 3 of a riding scan, as appended workgroups of the
+                      const uint32_t* fold_rowinst = nullptr, bool* scan_in_scatter = nullptr,
+                      const uint32_t* counted_hist = nullptr);   // apply: step 3 of a riding scan, as appended workgroups of the
                                                                  // last (longest) binning launch
                       // *use_alt != 0 (device): the depth order is in order_alt (see ggd_launch_sort32_iota)
                       // fold_rowtot / fold_status1 (folded front end, grids of <= 64 x 64 tiles): the entries per tile row were
                       // counted by the preprocess kernel -- level 1 is ONE launch (count, look-back over the chunks, scatter)
                       // fold_rowinst (with them): so were the instances per tile row -- level 2 is count + scatter, the scatter
                       // workgroups form their tile starts themselves (no scan launch); *scan_in_scatter reports that this form ran
+                      // counted_hist (with fold_rowtot; grids of <= 64 x 64 tiles): the two-launch sort's bucket histogram -- its
+                      // finish launch was given ggd_rowbin_counted(tmp, ...) and level 1 runs without its look-back
 int ggd_launch_ranges(ggd_ctx* ctx, hipStream_t s, const uint64_t* keys, int64_t n, uint32_t* ranges, int T);
 // out_depth / out_alpha non-null (both): the depth / alpha extension (blend_forward_kernel<..., AUX>), which also reads
 // depth_keys (the geometry buffer's: the fp32 bits of each Gaussian's view-space depth)

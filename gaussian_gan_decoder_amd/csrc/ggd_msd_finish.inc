@@ -90,6 +90,93 @@ __device__ __forceinline__ void msd_bucket_pieces(msd_lds& L, const uint32_t* __
   __syncthreads();
 }
 
+// The rows for the counted level 1 of the row binning (ggd_l1_counted, ggd_common.h).  Once an element's place p in the sorted bucket
+// is known it has depth rank base + p; with its rect -- the gather level 1 used to do through `order` -- the workgroup
+//   * stores {id, rect in bytes} to packed[base + p],
+//   * counts the tile rows the element covers in an LDS difference array, one per 1024-rank chunk the bucket (or one window of
+//     <= GGD_MSD_CAP elements of an oversized one) overlaps: <= MSD_ROW_SEGS of 65 words, by the rule of rb_level1_kernel (an
+//     empty rect covers nothing; rows are counted as wave_cols counts them).
+// Wave 0 (lane = row; `run` = the rows of the bucket's elements in front of the window) then walks the chunks: in front of chunk
+// k0 + s it has the rows of the bucket's elements below rank 1024 (k0 + s) -- boundary_rows of that chunk, when the boundary lies
+// inside the window (s > 0, or the window starts on it: a bucket that starts on a boundary writes its zero row) -- and behind the
+// bucket's last window the bucket's total.  Exactly one non-empty bucket holds a given rank below the kept count, so every row of
+// either table has one writer: plain stores, read by the next launch.
+// Two forms.  LDS exchange (the usual bucket): inside the LAST counting pass of msd_bucket_sort -- the rects are requested when
+// the pass has its values and are looked at when it scatters, a whole pass later; the scatter leaves the rect's bytes where the
+// sorted keys went (nobody reads those), so `packed` leaves with the values as coalesced stores; the difference arrays live in
+// L.pp, which is dead behind the gather.  Global exchange and oversized buckets (rare): msd_bucket_rows, behind the sort, from the
+// workgroup's own slice of vals_out; the difference arrays live in L.cnt.
+// Bounds: p < nb and base + nb <= the histogram's total <= P (rank < R.n states it again where `packed` is stored); the chunk index
+// is < MSD_ROW_SEGS because a window holds <= GGD_MSD_CAP elements (and is clamped); rows are clamped to 64, the last word of a
+// difference array; a rect is read at min(id, R.n - 1); boundary rows are written for k < R.chunks only; b < GGD_MSD_BINS is the
+// launch's grid.
+constexpr int MSD_ROW_SEGS = GGD_MSD_CAP / 1024 + 1;
+static_assert(MSD_ROW_SEGS * 65 * sizeof(int) <= sizeof(msd_lds::cnt) && MSD_ROW_SEGS * 65 * sizeof(int) <= sizeof(msd_lds::pp),
+              "the row difference arrays reuse the digit counts / the piece table");
+struct msd_rows {
+  const uint2* rect; uint2* packed; uint32_t* bucket_rows; uint32_t* boundary_rows;
+  uint32_t chunks, n;
+};
+
+// the element of depth rank `rank` with rect rc: counted in diff (whose first array is chunk k0's); returns the rect in bytes
+__device__ __forceinline__ uint32_t msd_count_rows(int* diff, uint32_t k0, uint32_t rank, uint2 rc) {
+  uint32_t x0 = rc.x & 0xffffu, x1 = rc.x >> 16, y0 = min(rc.y & 0xffffu, 64u), y1 = min(rc.y >> 16, 64u);
+  const bool any = (int)(x1 - x0) * (int)(y1 - y0) > 0 && y1 > y0;
+  if (!any) return 0u;
+  const uint32_t s = min((rank >> 10) - k0, (uint32_t)(MSD_ROW_SEGS - 1));
+  atomicAdd(&diff[s * 65u + y0], 1);
+  atomicAdd(&diff[s * 65u + y1], -1);
+  return (x0 & 0xffu) | ((x1 & 0xffu) << 8) | (y0 << 16) | (y1 << 24);
+}
+
+// wave 0 (tid = row), a barrier behind the counting: the window [first, end) of depth ranks, `last`: the bucket ends with it
+__device__ __forceinline__ void msd_publish_rows(const int* diff, const msd_rows& R, uint32_t b, uint32_t first, uint32_t end, bool last,
+                                                 uint32_t& run) {
+  const int tid = threadIdx.x;
+  const uint32_t k0 = first >> 10;
+  const uint32_t nseg = min(((end - 1u) >> 10) - k0 + 1u, (uint32_t)MSD_ROW_SEGS);
+  for (uint32_t s = 0; s < nseg; ++s) {
+    const uint32_t k = k0 + s;
+    if ((s > 0u || (first & 1023u) == 0u) && k < R.chunks) R.boundary_rows[(size_t)k * 64 + tid] = run;
+    run += (uint32_t)wave_inclusive_scan(diff[s * 65u + tid]);
+  }
+  if (last) R.bucket_rows[(size_t)b * 64 + tid] = run;
+}
+
+// the form behind the sort: elements [p0, p0 + GGD_MSD_CAP) of the bucket, whose order is in vals_g[0, nb) (a barrier behind it)
+__device__ __forceinline__ void msd_bucket_rows(msd_lds& L, const msd_rows& R, uint32_t b, uint32_t base, uint32_t nb, uint32_t p0,
+                                                uint32_t& run, const uint32_t* vals_g) {
+  const int tid = threadIdx.x;
+  int* diff = reinterpret_cast<int*>(&L.cnt[0][0]);   // [MSD_ROW_SEGS][65]
+  const uint32_t p1 = min(nb, p0 + (uint32_t)GGD_MSD_CAP);
+  const uint32_t k0 = (base + p0) >> 10;
+  for (uint32_t z = tid; z < (uint32_t)(MSD_ROW_SEGS * 65); z += MSDF_THREADS) diff[z] = 0;
+  __syncthreads();
+  // four elements a thread at a time, their gathers requested together (all twelve at once cost the kernel its 64-register budget)
+  constexpr int RB = 4;
+#pragma unroll 1
+  for (uint32_t q0 = p0; q0 < p1; q0 += (uint32_t)(RB * MSDF_THREADS)) {
+    uint32_t id[RB];
+    uint2 rc[RB];
+#pragma unroll
+    for (int r = 0; r < RB; ++r) {
+      const uint32_t p = q0 + (uint32_t)(r * MSDF_THREADS + tid);
+      id[r] = 0u; rc[r] = make_uint2(0u, 0u);
+      if (p < p1) {
+        id[r] = vals_g[p];
+        rc[r] = R.rect[min(id[r], R.n - 1u)];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RB; ++r) {
+      const uint32_t p = q0 + (uint32_t)(r * MSDF_THREADS + tid);
+      if (p < p1 && base + p < R.n) R.packed[base + p] = make_uint2(id[r], msd_count_rows(diff, k0, base + p, rc[r]));
+    }
+  }
+  __syncthreads();
+  if (tid < 64) msd_publish_rows(diff, R, b, base + p0, base + p1, p1 == nb, run);
+}
+
 // Step 2 (nb <= GGD_MSD_CAP): gather + two stable counting passes over the offsets' bits 0..7 and 8..shift-1.  LDS exchange (GLOBAL_X =
 // false, nb <= MSD_XCAP, ITEMS = MSDX_ITEMS): on return the sorted keys are in L.kv[0, nb), their values in L.kv[XCAP, XCAP +
 // nb), a barrier behind them.  Global exchange (GLOBAL_X = true): xk / xv = the bucket's slice of the output arrays; on return
@@ -101,9 +188,16 @@ __device__ __forceinline__ void msd_bucket_pieces(msd_lds& L, const uint32_t* __
 // instead of 16 us).
 template <bool GLOBAL_X, int ITEMS>
 __device__ __forceinline__ void msd_bucket_sort(msd_lds& L, const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
-                                                int ntiles, uint32_t nb, int kshift, uint32_t* xk_g, uint32_t* xv_g) {
+                                                int ntiles, uint32_t nb, int kshift, uint32_t* xk_g, uint32_t* xv_g,
+                                                const msd_rows& R, uint32_t base) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   uint32_t key[ITEMS], val[ITEMS], rank[ITEMS];
+  // LDS exchange with a counted level 1 behind: the last pass also fetches the rects and counts the rows (see above); on return
+  // L.kv[0, nb) holds the rects' bytes instead of the sorted keys and diff the counts, a barrier behind both
+  const bool rows_here = !GLOBAL_X && R.rect != nullptr;
+  int* diff = reinterpret_cast<int*>(&L.pp[0]);   // [MSD_ROW_SEGS][65]
+  constexpr int EARLY = GLOBAL_X ? 1 : 4;         // rounds whose rects are requested a pass ahead (buckets up to 4096 keys: all but the
+  uint2 rc[EARLY];                                // dense ones; every round's cost the kernel its 64-register budget)
   const int rounds = (int)((nb + MSDF_THREADS - 1) / MSDF_THREADS);
   const uint32_t pbase = (uint32_t)wv * (64u * (uint32_t)rounds) + (uint32_t)lane;
 #pragma unroll
@@ -134,8 +228,22 @@ __device__ __forceinline__ void msd_bucket_sort(msd_lds& L, const uint32_t* __re
         }
       }
     }
+    const bool count_rows = rows_here && (pass == 1 || kshift <= 8);   // (this is the last pass)
+    if constexpr (!GLOBAL_X) {
+      if (count_rows) {
+#pragma unroll
+        for (int r = 0; r < EARLY; ++r) {   // requested here, looked at in the scatter below
+          if (r >= rounds) break;
+          rc[r] = make_uint2(0u, 0u);
+          if (pbase + r * 64 < nb) rc[r] = R.rect[min(val[r], R.n - 1u)];
+        }
+      }
+    }
     for (int z = tid; z < MSDF_WAVES * 128; z += MSDF_THREADS) reinterpret_cast<uint32_t*>(&L.cnt[0][0])[z] = 0u;
     __syncthreads();
+    if (count_rows) {   // (behind the barrier: pass 0's gather has read L.pp for the last time)
+      for (int z = tid; z < MSD_ROW_SEGS * 65; z += MSDF_THREADS) diff[z] = 0;
+    }
 #pragma unroll
     for (int r = 0; r < ITEMS; ++r) {
       if (r >= rounds) break;
@@ -178,8 +286,12 @@ __device__ __forceinline__ void msd_bucket_sort(msd_lds& L, const uint32_t* __re
       if (pbase + r * 64 < nb) {
         const uint32_t d = (key[r] >> shift) & ((1u << nbits) - 1u);
         const uint32_t p = (uint32_t)L.cnt[wv][d] + rank[r];
-        if (GLOBAL_X) { xk_g[p] = key[r]; xv_g[p] = val[r]; }
-        else { L.kv[p] = key[r]; L.kv[MSD_XCAP + p] = val[r]; }
+        if constexpr (GLOBAL_X) { xk_g[p] = key[r]; xv_g[p] = val[r]; }
+        else {
+          L.kv[p] = !count_rows ? key[r]
+                               : msd_count_rows(diff, base >> 10, base + p, r < EARLY ? rc[r < EARLY ? r : 0] : R.rect[min(val[r], R.n - 1u)]);
+          L.kv[MSD_XCAP + p] = val[r];
+        }
       }
     }
     __syncthreads();

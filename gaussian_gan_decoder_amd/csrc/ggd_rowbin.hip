@@ -23,6 +23,8 @@
 // the transposes, two-level look-back over the earlier chunks (ggd_lookback.inc), scatter.  It counted the instances per row too,
 // the only cross-row quantity of level 2: level 2 is then TWO launches, count and scatter -- every scatter workgroup sums the
 // count rows of its tile row's blocks itself (rb_scatter2_kernel<true>; no scan launch, no hand-off between workgroups).
+// Behind the two-launch depth sort level 1 is rb_level1_counted_kernel: the sort's finish launch counted the row entries of every
+// bucket and in front of every chunk boundary, so the chunks sum finished rows and look back over nothing (GGD_OPT_L1_COUNTED).
 // Scratch and table layouts: ggd_binning_layout.h (ggd_rowbin_tmp, RB_TAB_* / RBW_TAB_*).
 #include "ggd_common.h"
 
@@ -349,6 +351,159 @@ __global__ __launch_bounds__(RB_THREADS) void rb_level1_kernel(const uint2* __re
   });
 }
 
+// ---- level 1 behind the two-launch depth sort (GGD_OPT_L1_COUNTED): rb_level1_kernel without the look-back.  The sort's finish
+//      launch left, by plain stores (msd_bucket_rows, ggd_msd_finish.inc): packed[rank] = {id, rect}, bucket_rows[b][row] = the row
+//      entries of bucket b, boundary_rows[k][row] = those of the elements in front of rank 1024 k inside the bucket that holds
+//      it.  Chunk k starts in row r at
+//        row start[r] + sum of bucket_rows[b'][r] over the buckets b' that lie wholly in front of rank 1024 k + boundary_rows[k][r]
+//      -- every term is final when this launch starts; no workgroup waits for another, no status words, no atomics.
+//      Two round trips: {bucket histogram, row totals, kept count, the chunk's packed items, its boundary row}, then the bucket rows
+//      (16-byte loads, a lane four rows of the grid, sixteen lanes a bucket, the buckets dealt to the four waves).  A bucket counts
+//      when it is non-empty (an empty one has no workgroup that writes its row) and ends at or below rank 1024 k; which those are
+//      follows from the histogram's prefix.  A frame the front end's verdict fails (a key outside the window, clamped into the last
+//      bucket; a bucket above GGD_MSD_CAP, left in index order) has complete tables too: the lists are those of the order the sort left.
+//      Bounds: items are read at min(rank, P - 1); rows unpacked from `packed` are clamped to 64; bucket indices come from the
+//      1024-word histogram; k < gridDim = the rows boundary_rows has; ent is written below ent_cap only, the staging buffer below
+//      the chunk's own total.
+__global__ __launch_bounds__(RB_THREADS) void rb_level1_counted_kernel(const uint2* __restrict__ packed,
+                                                                       const uint32_t* __restrict__ hist /* [GGD_MSD_BINS] */,
+                                                                       const uint32_t* __restrict__ n_vis_ptr, int P,
+                                                                       const uint32_t* __restrict__ rowtot,
+                                                                       const uint32_t* __restrict__ bucket_rows,
+                                                                       const uint32_t* __restrict__ boundary_rows,
+                                                                       uint32_t* __restrict__ tab, uint2* __restrict__ ent,
+                                                                       uint32_t ent_cap, const uint32_t* __restrict__ rowinst) {
+  __shared__ uint4 slab[RB_WAVES][64];
+  __shared__ uint32_t wcnt[RB_WAVES][64];
+  __shared__ uint2 stage[RB_STAGE1];
+  __shared__ uint32_t s_scan[RB_WAVES][2];
+  __shared__ __attribute__((aligned(16))) uint32_t s_rows[RB_WAVES][64];         // the waves' partial sums of their bucket rows
+  // the buckets in front of the chunk that count: in the staging buffer, which is first written behind the barrier that follows
+  // their last use (with them in LDS of their own the kernel fell from four workgroups a CU to three)
+  uint16_t* s_used = reinterpret_cast<uint16_t*>(stage);
+  static_assert(GGD_MSD_BINS * sizeof(uint16_t) <= sizeof(stage), "the bucket list fits the staging buffer");
+  static_assert(GGD_MSD_BINS == 4 * RB_THREADS, "a thread takes four buckets of the histogram");
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint32_t base = (uint32_t)blockIdx.x * RB_CHUNK;
+  const uint32_t wbeg = base + (uint32_t)wv * RB_WCHUNK;
+  // first round trip: nothing below depends on another load's value
+  const uint32_t n_vis = min((uint32_t)P, *n_vis_ptr);
+  const uint4 h4 = reinterpret_cast<const uint4*>(hist)[tid];
+  uint32_t tot = 0;
+#pragma unroll
+  for (int r = 0; r < GGD_FOLD_REPS; ++r) tot += rowtot[r * 64 + lane];
+  const uint32_t bound = boundary_rows[(size_t)blockIdx.x * 64 + lane];
+  uint2 raw[RB_IPL];
+#pragma unroll
+  for (int q = 0; q < RB_IPL; ++q) raw[q] = packed[min(wbeg + (uint32_t)(q * 64 + lane), (uint32_t)P - 1u)];
+  const uint32_t inc = wave_inclusive_scan(tot);
+  const uint32_t rowstart = inc - tot;
+  if (blockIdx.x == 0 && wv == 0) {
+    rb_write_row_tables(tab, lane, tot, inc, ent_cap);
+    if (rowinst) {   // the instances per row, for rb_scatter2_kernel<true> (plain stores: the next launch reads them)
+      uint32_t inst = 0;
+#pragma unroll
+      for (int r = 0; r < GGD_FOLD_REPS; ++r) inst += rowinst[r * 64 + lane];
+      tab[RB_TAB_ROWINST + lane] = inst;
+    }
+  }
+  if (base >= n_vis) return;
+  const int n_items = (int)min((uint32_t)RB_WCHUNK, n_vis > wbeg ? n_vis - wbeg : 0u);
+  // the buckets that end at or below `base`: thread t holds buckets 4 t .. 4 t + 3; one scan carries their sizes and their number
+  uint32_t n_used;
+  {
+    const uint32_t h[4] = {h4.x, h4.y, h4.z, h4.w};
+    const uint32_t hsum = h4.x + h4.y + h4.z + h4.w;
+    const uint32_t hinc = wave_inclusive_scan(hsum);
+    if (lane == 63) s_scan[wv][0] = hinc;
+    __syncthreads();
+    uint32_t end = hinc - hsum;   // keys in front of bucket 4 t
+#pragma unroll
+    for (int w = 0; w < RB_WAVES; ++w) if (w < wv) end += s_scan[w][0];
+    uint32_t use = 0;             // bit j: bucket 4 t + j counts
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      end += h[j];
+      if (h[j] != 0u && end <= base) use |= 1u << j;
+    }
+    const uint32_t ucnt = (uint32_t)__popc(use);
+    const uint32_t uinc = wave_inclusive_scan(ucnt);
+    if (lane == 63) s_scan[wv][1] = uinc;
+    __syncthreads();
+    uint32_t pos = uinc - ucnt;
+    n_used = 0;
+#pragma unroll
+    for (int w = 0; w < RB_WAVES; ++w) { const uint32_t c = s_scan[w][1]; if (w < wv) pos += c; n_used += c; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (use & (1u << j)) s_used[pos++] = (uint16_t)(4 * tid + j);   // pos < n_used <= GGD_MSD_BINS
+  }
+  uint32_t iv[RB_IPL], pa[RB_IPL], pb[RB_IPL];
+#pragma unroll
+  for (int q = 0; q < RB_IPL; ++q) {
+    const bool have = q * 64 + lane < n_items;
+    const uint32_t y0 = min((raw[q].y >> 16) & 0xffu, 64u), y1 = min(raw[q].y >> 24, 64u);
+    pa[q] = have ? raw[q].x : 0u;
+    pb[q] = have ? raw[q].y & 0xffffu : 0u;
+    iv[q] = have ? y0 | (y1 << 8) : 0u;
+  }
+  uint64_t cols[RB_IPL];
+  const uint32_t mine = wave_cols(iv, n_items, cols);
+  wcnt[wv][lane] = mine;
+  __syncthreads();   // s_used is complete (and wcnt, for the barrier below to publish with s_rows)
+  {
+    // second (and last) round trip: the rows of the buckets in front
+    constexpr int BATCH = 8;
+    const uint32_t sub = (uint32_t)lane >> 4, c4 = ((uint32_t)lane & 15u) * 4u;
+    uint4 acc = make_uint4(0, 0, 0, 0);
+    for (uint32_t i0 = (uint32_t)wv * 4u; i0 < n_used; i0 += 4u * RB_WAVES * BATCH) {
+      uint4 v[BATCH];
+#pragma unroll
+      for (int j = 0; j < BATCH; ++j) {
+        const uint32_t i = i0 + sub + (uint32_t)(4 * RB_WAVES * j);
+        v[j] = make_uint4(0, 0, 0, 0);
+        if (i < n_used) v[j] = *reinterpret_cast<const uint4*>(bucket_rows + (size_t)s_used[i] * 64 + c4);
+      }
+#pragma unroll
+      for (int j = 0; j < BATCH; ++j) { acc.x += v[j].x; acc.y += v[j].y; acc.z += v[j].z; acc.w += v[j].w; }
+    }
+#pragma unroll
+    for (int d = 16; d <= 32; d <<= 1) {   // the wave's four bucket groups hold the same rows
+      acc.x += (uint32_t)__shfl_xor((int)acc.x, d, 64); acc.y += (uint32_t)__shfl_xor((int)acc.y, d, 64);
+      acc.z += (uint32_t)__shfl_xor((int)acc.z, d, 64); acc.w += (uint32_t)__shfl_xor((int)acc.w, d, 64);
+    }
+    if (lane < 16) *reinterpret_cast<uint4*>(&s_rows[wv][c4]) = acc;
+  }
+  __syncthreads();
+  uint32_t before = 0, rowtot_c = 0;   // lane = row: this chunk's entries of the earlier waves / of the whole chunk
+#pragma unroll
+  for (int w = 0; w < RB_WAVES; ++w) { const uint32_t c = wcnt[w][lane]; if (w < wv) before += c; rowtot_c += c; }
+  const uint32_t gbase = rowstart + bound + s_rows[0][lane] + s_rows[1][lane] + s_rows[2][lane] + s_rows[3][lane];
+  // staging and copy-out as in rb_level1_kernel
+  const uint32_t rowend = wave_inclusive_scan(rowtot_c);          // same in every wave
+  const uint32_t total = (uint32_t)__shfl((int)rowend, 63, 64);
+  const uint32_t rowbeg = rowend - rowtot_c;
+  if (total <= (uint32_t)RB_STAGE1) {
+    uint32_t ldst = rowbeg + before;
+    wave_emit<true>(iv, pa, pb, cols, n_items, ldst, slab[wv], [&](uint32_t d, uint32_t id, uint32_t xx) { stage[d] = make_uint2(id, xx); });
+    __syncthreads();
+#pragma unroll 4
+    for (int c = wv; c < 64; c += RB_WAVES) {
+      const uint32_t n = (uint32_t)__shfl((int)rowtot_c, c, 64);
+      if (n == 0) continue;
+      const uint32_t b0 = (uint32_t)__shfl((int)rowbeg, c, 64), g = (uint32_t)__shfl((int)gbase, c, 64);
+      for (uint32_t k = lane; k < n; k += 64) {
+        const uint32_t d = g + k;
+        if (d < ent_cap) ent[d] = stage[b0 + k];
+      }
+    }
+    return;
+  }
+  uint32_t dst = gbase + before;
+  wave_emit<true>(iv, pa, pb, cols, n_items, dst, slab[wv], [&](uint32_t d, uint32_t id, uint32_t xx) {
+    if (d < ent_cap) ent[d] = make_uint2(id, xx);
+  });
+}
+
 // level-2 block -> (row, chunk within the row)
 // (one load per lane + a ballot: a binary search over the table is six DEPENDENT global loads, which was most of a
 // level-2 workgroup's lifetime)
@@ -609,7 +764,8 @@ bool ggd_rowbin_supported(int W, int H) { return W > 0 && H > 0 && (W + 15) / 16
 int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const uint2* rect, const uint32_t* order,
                       const uint32_t* n_vis_ptr, uint32_t* list, uint32_t* ranges, uint32_t capacity, void* tmp,
                       size_t tmp_bytes, const uint32_t* order_alt, const uint32_t* use_alt, const ggd_scan_piggy* apply,
-                      const uint32_t* fold_rowtot, uint32_t* fold_status1, const uint32_t* fold_rowinst, bool* scan_in_scatter) {
+                      const uint32_t* fold_rowtot, uint32_t* fold_status1, const uint32_t* fold_rowinst, bool* scan_in_scatter,
+                      const uint32_t* counted_hist) {
   if (scan_in_scatter) *scan_in_scatter = false;
   if (!ggd_rowbin_supported(prm.width, prm.height)) return ggd_fail(ctx, GGD_E_INVALID, "tile grid too large for row binning");
   const ggd_rowbin_tmp lay = ggd_rowbin_layout(prm.P, capacity, prm.width, prm.height);
@@ -644,7 +800,14 @@ int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const 
   // the front end counted the instances per row as well: level 2 needs no scan launch (up to the block count the quadratic
   // reads of rb_scatter2_kernel<true> are admitted for)
   const bool fused2 = fold_rowtot && fold_status1 && fold_rowinst && nb2 <= RB_SCAN_IN_SCATTER_MAX_BLOCKS;
-  if (fold_rowtot && fold_status1) {   // (the group words were laid out for ggd_group_shift(chunks): ggd_fold_ctl_words)
+  if (counted_hist) {
+    // the two-launch sort's finish kernel left packed / bucket_rows / boundary_rows (ggd_rowbin_counted) and counted_hist is the
+    // bucket histogram it read: level 1 without the look-back
+    if (!fold_rowtot || tmp_bytes < lay.total_counted) return ggd_fail(ctx, GGD_E_INVALID, "rowbin: counted level 1 needs the folded front end and its row tables");
+    hipLaunchKernelGGL(rb_level1_counted_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, packed, counted_hist, n_vis_ptr, prm.P,
+                       fold_rowtot, reinterpret_cast<const uint32_t*>(p + lay.bucket_rows),
+                       reinterpret_cast<const uint32_t*>(p + lay.boundary_rows), tab, ent, capacity, fused2 ? fold_rowinst : nullptr);
+  } else if (fold_rowtot && fold_status1) {   // (the group words were laid out for ggd_group_shift(chunks): ggd_fold_ctl_words)
     hipLaunchKernelGGL(rb_level1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, rect, order, n_vis_ptr, prm.P, fold_rowtot,
                        fold_status1, nb1, ggd_group_shift(nb1), tab, ent, capacity, order_alt, use_alt,
                        fused2 ? fold_rowinst : nullptr);

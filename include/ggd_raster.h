@@ -301,6 +301,10 @@ enum {
   GGD_OPT_PREPROCESS_WGS = 6, /* workgroups of the per-Gaussian forward kernel, each of which strides over the 256-Gaussian tiles:
                              0 (default) = automatic (a fixed number per compute unit), n > 0 = exactly min(n, tiles).  Results are
                              identical; for timing experiments, and so that a small input can put many tiles on one workgroup. */
+  GGD_OPT_L1_COUNTED = 7, /* frames of the two-launch depth sort on grids of up to 64 x 64 tiles: 1 (default) = the sort's finish
+                             launch also counts every bucket's row entries, and level 1 of the row binning sums those finished rows
+                             instead of looking back over the chunks of its own launch; 0 = the look-back kernel.  Results are
+                             identical; for A/B timing and tests. */
   GGD_OPT_COUNT
 };
 #define GGD_PREPROCESS_WGS_MAX (1 << 20)
@@ -329,8 +333,10 @@ enum {
   GGD_STAT_FLAT_STREAK = 100,   /* consecutive frames whose top depth digit was constant */
   GGD_STAT_SORT_RERUNS = 101,   /* frames re-rendered because the speculated short form of the depth sort did not hold */
   GGD_STAT_MSD_FRAMES = 102,    /* frames whose depth sort ran as two launches (GGD_OPT_MSD_SORT) */
-  GGD_STAT_SCAN_IN_SCATTER_FRAMES = 103   /* frames (binning passes) whose row binning ran without its level-2 scan launch: the per-Gaussian
+  GGD_STAT_SCAN_IN_SCATTER_FRAMES = 103,  /* frames (binning passes) whose row binning ran without its level-2 scan launch: the per-Gaussian
                                              kernel counted the instances per tile row, the scatter workgroups form their tile starts */
+  GGD_STAT_L1_COUNTED_FRAMES = 104        /* frames (binning passes) whose level 1 took its row counts from the sort's finish launch
+                                             (GGD_OPT_L1_COUNTED) */
 };
 
 /*
