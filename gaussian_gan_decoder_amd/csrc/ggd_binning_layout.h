@@ -152,6 +152,17 @@ constexpr int RBW_TAB_ROWSTART = 0, RBW_TAB_ROWBLK = RBW_BINS + 1, RBW_TAB_ROWIN
               RBW_TAB_FLAG = RBW_TAB_ROWINST + RBW_BINS, RBW_TAB_TILESTART = RBW_TAB_FLAG + RBW_BINS,
               RBW_TAB_WORDS = RBW_TAB_TILESTART + RBW_BINS * RBW_BINS;
 
+// The `packed` record, one per depth rank: {id, x0 | x1 << 8 | y0 << 16 | y1 << 24} -- the tile rect [x0, x1) x [y0, y1) in bytes
+// (grids up to 255 x 255), all zero for an empty rect.  Written by rb_count1_kernel / rbw_count1_kernel and by the depth sort's
+// finish launch (msd_count_rows, ggd_msd_finish.inc); read by the level-1 scatters and by rb_level1_counted_kernel.
+GGD_HOST_DEVICE inline uint32_t rb_pack_rect(uint32_t x0, uint32_t x1, uint32_t y0, uint32_t y1) {
+  return x0 | (x1 << 8) | (y0 << 16) | (y1 << 24);
+}
+GGD_HOST_DEVICE inline uint32_t rb_packed_cols(uint32_t w) { return w & 0xffffu; }       // x0 | x1 << 8: the payload of a row entry
+GGD_HOST_DEVICE inline uint32_t rb_packed_rows(uint32_t w) { return w >> 16; }           // y0 | y1 << 8: the interval of rows
+GGD_HOST_DEVICE inline uint32_t rb_packed_y0(uint32_t w) { return (w >> 16) & 0xffu; }
+GGD_HOST_DEVICE inline uint32_t rb_packed_y1(uint32_t w) { return w >> 24; }
+
 static inline bool rb_is_wide(int W, int H) { return (W + 15) / 16 > 64 || (H + 15) / 16 > 64; }
 static inline int rb_blocks1(int P) { return (P + RB_CHUNK - 1) / RB_CHUNK; }                      // level-1 workgroups
 // The scan-in-scatter form of level 2 (rb_scatter2_kernel<true>) has every workgroup of a tile row read the count rows of all of

@@ -119,6 +119,8 @@ struct msd_rows {
 };
 
 // the element of depth rank `rank` with rect rc: counted in diff (whose first array is chunk k0's); returns the rect in bytes
+// (the `packed` record's second word, rb_pack_rect).  Unlike rb_count1_kernel this writer cannot rely on the grid for its bounds --
+// the rows index LDS here -- so rows are clamped to 64 and the columns masked to their byte before they are packed.
 __device__ __forceinline__ uint32_t msd_count_rows(int* diff, uint32_t k0, uint32_t rank, uint2 rc) {
   uint32_t x0 = rc.x & 0xffffu, x1 = rc.x >> 16, y0 = min(rc.y & 0xffffu, 64u), y1 = min(rc.y >> 16, 64u);
   const bool any = (int)(x1 - x0) * (int)(y1 - y0) > 0 && y1 > y0;
@@ -126,7 +128,7 @@ __device__ __forceinline__ uint32_t msd_count_rows(int* diff, uint32_t k0, uint3
   const uint32_t s = min((rank >> 10) - k0, (uint32_t)(MSD_ROW_SEGS - 1));
   atomicAdd(&diff[s * 65u + y0], 1);
   atomicAdd(&diff[s * 65u + y1], -1);
-  return (x0 & 0xffu) | ((x1 & 0xffu) << 8) | (y0 << 16) | (y1 << 24);
+  return rb_pack_rect(x0 & 0xffu, x1 & 0xffu, y0, y1);
 }
 
 // wave 0 (tid = row), a barrier behind the counting: the window [first, end) of depth ranks, `last`: the bucket ends with it

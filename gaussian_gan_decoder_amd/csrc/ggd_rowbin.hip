@@ -8,24 +8,32 @@
 //   level 1 (rows):    Gaussian [y0, y1)  -> one entry {id, x0, x1} in the list of every tile ROW it touches
 //   level 2 (columns): row entry [x0, x1) -> the Gaussian id in the list of every TILE of that row it touches
 // Both levels are stable (items are consumed in order, chunk by chunk of 1024), so depth order survives and the final lists
-// equal the radix-sort path's bit for bit.  Per level three launches:
-//   count    per chunk and bin.  An LDS difference array (+1 at lo, -1 at hi, prefix over the lanes): these kernels do
-//            nothing else, and atomics are cheaper than the transposes below (see rb_count2_kernel).
-//   scan     exclusive prefix over the chunks per bin, bin starts: one workgroup at level 1, one per tile row at level 2 (the
-//            rows above are summed from their published totals).
+// equal the radix-sort path's bit for bit.  A level is three steps:
+//   count    per chunk and bin.  Where a kernel does nothing else: an LDS difference array (+1 at lo, -1 at hi, prefix over the
+//            lanes) -- atomics are cheaper than the transposes below (see rb_count2_kernel).
+//   scan     exclusive prefix over the chunks per bin, bin starts.
 //   scatter  a wave turns each round of 64 items into the 64 x 64 item / bin bit matrix and transposes it (wave_cols: lane b then
 //            holds the items that cover bin b, in item order, and their popcount is the bin's count); wave_emit walks either
 //            the items (a lane keeps its item and looks up {mask, running destination} of every bin it covers in the wave's
 //            LDS slab) or the bins (a lane drains its bin, payloads come over by shuffle), whichever is shorter for the round.
 //            A chunk's output is staged in LDS in (bin, item) order where it fits and leaves as lane-consecutive runs per bin;
 //            entries of one (chunk, bin) are consecutive in memory either way.
-// Folded front end (the preprocess kernel counted the entries per row): level 1 is ONE launch, rb_level1_kernel -- count from
-// the transposes, two-level look-back over the earlier chunks (ggd_lookback.inc), scatter.  It counted the instances per row too,
-// the only cross-row quantity of level 2: level 2 is then TWO launches, count and scatter -- every scatter workgroup sums the
-// count rows of its tile row's blocks itself (rb_scatter2_kernel<true>; no scan launch, no hand-off between workgroups).
-// Behind the two-launch depth sort level 1 is rb_level1_counted_kernel: the sort's finish launch counted the row entries of every
-// bucket and in front of every chunk boundary, so the chunks sum finished rows and look back over nothing (GGD_OPT_L1_COUNTED).
-// Scratch and table layouts: ggd_binning_layout.h (ggd_rowbin_tmp, RB_TAB_* / RBW_TAB_*).
+// Which kernels take those steps (ggd_launch_rowbin), by what the launches in front have left:
+//   counted  folded front end behind the two-launch depth sort (GGD_OPT_L1_COUNTED).  The sort's finish launch stored `packed` and
+//            counted the row entries of every bucket and in front of every chunk boundary: rb_level1_counted_kernel sums finished
+//            rows and scatters.  Level 2 as on the folded path.  Three launches.
+//   folded   the preprocess kernel counted the entries and the instances per row.  rb_level1_kernel: count from the transposes,
+//            two-level look-back over the earlier chunks (ggd_lookback.inc), scatter.  Level 2: rb_count2_kernel, then
+//            rb_scatter2_kernel<true>, whose workgroups sum the count rows of their tile row's blocks themselves -- no scan launch,
+//            no hand-off between workgroups (beyond RB_SCAN_IN_SCATTER_MAX_BLOCKS: level 2 of the plain path).  Three launches.
+//   plain    rb_count1 / rb_scan1 (one workgroup) / rb_scatter1 with `packed` between them, rb_count2 / rb_scan2 (one workgroup per
+//            tile row; the rows above are summed from their published totals) / rb_scatter2_kernel<false>.  Six launches.
+//   wide     grids beyond 64 x 64: the plain path's six launches as rbw_* (ggd_rowbin_wide.inc).
+// Stated once and shared: rb_emit_chunk (the emission tail of the three narrow kernels that stage: staging, copy-out, direct form),
+// rb_sum_count_rows (16-byte batched row sums: rb_level1_counted_kernel, rb_scatter2_kernel<true>), rb_level1_head (row starts and
+// workgroup 0's tables: both one-launch level-1 kernels), rb_write_row_tables, rb_prefix_over_chunks (the four scan kernels), rb_publish_row_sum_above (the two level-2 scans),
+// rb_block_row_range, wave_cols / wave_emit (narrow) and wave_cols_w / wave_emit_w (wide).
+// Scratch and table layouts, the `packed` record: ggd_binning_layout.h (ggd_rowbin_tmp, RB_TAB_* / RBW_TAB_*, rb_pack_rect).
 #include "ggd_common.h"
 
 namespace {
@@ -55,8 +63,58 @@ __device__ __forceinline__ void rb_write_row_tables(uint32_t* tab, int lane, uin
   tab[RB_TAB_FLAG + lane] = 0u;
 }
 
+// a per-row quantity of the folded front end (lane = row): the sum of its GGD_FOLD_REPS replicas
+__device__ __forceinline__ uint32_t rb_fold_sum(const uint32_t* __restrict__ reps, int lane) {
+  uint32_t s = 0;
+#pragma unroll
+  for (int r = 0; r < GGD_FOLD_REPS; ++r) s += reps[r * 64 + lane];
+  return s;
+}
+
+// The level-1 head of the one-launch kernels: the entries per row (lane = row; tot = rb_fold_sum of the row totals, loaded where the
+// caller wants the loads) scanned into row starts; returns the lane's.  The wave that is told to (one wave of workgroup 0) also writes
+// the tables level 2 reads and, when given `rowinst`, the instances per row for rb_scatter2_kernel<true> (plain stores: the next
+// launch reads them).
+__device__ __forceinline__ uint32_t rb_level1_head(uint32_t tot, bool write_tables, uint32_t* __restrict__ tab, uint32_t ent_cap,
+                                                   const uint32_t* __restrict__ rowinst) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t inc = wave_inclusive_scan(tot);
+  if (write_tables) {
+    rb_write_row_tables(tab, lane, tot, inc, ent_cap);
+    if (rowinst) tab[RB_TAB_ROWINST + lane] = rb_fold_sum(rowinst, lane);
+  }
+  return inc - tot;
+}
+
+// Per-bin prefix over chunks (the scan kernels: 16 waves, lane = bin `bin` of count rows `stride` words long): the waves split the
+// chunks [c0, c0 + n) evenly and sum their shares, the partial sums meet in part[wave][lane], and every count is replaced by the
+// running exclusive prefix of its bin over the chunks.  Returns the bin's total.  (Reusing `part` takes a barrier of the caller's.)
+template <int UNROLL>
+__device__ __forceinline__ uint32_t rb_prefix_over_chunks(uint32_t* __restrict__ counts, uint32_t c0, uint32_t n, size_t stride,
+                                                          int bin, uint32_t (&part)[16][64]) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t per = (n + 15u) / 16u;
+  const uint32_t b0 = c0 + min(n, (uint32_t)wv * per), b1 = min(c0 + n, b0 + per);
+  uint32_t s = 0;
+#pragma unroll UNROLL
+  for (uint32_t b = b0; b < b1; ++b) s += counts[(size_t)b * stride + bin];
+  part[wv][lane] = s;
+  __syncthreads();
+  uint32_t run = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) { const uint32_t p = part[w][lane]; if (w < wv) run += p; tot += p; }
+#pragma unroll UNROLL
+  for (uint32_t b = b0; b < b1; ++b) {
+    const size_t idx = (size_t)b * stride + bin;
+    const uint32_t c = counts[idx];
+    counts[idx] = run;
+    run += c;
+  }
+  return tot;
+}
+
 // ---- level 1 count: rect of every depth-ordered Gaussian (kept, packed, for the scatter) + per-row counts of the chunk
-__global__ __launch_bounds__(RB_THREADS) void rb_count1_kernel(int W, int H, const uint2* __restrict__ rect,
+__global__ __launch_bounds__(RB_THREADS) void rb_count1_kernel(const uint2* __restrict__ rect,
                                                                const uint32_t* __restrict__ order,
                                                                const uint32_t* __restrict__ n_vis_ptr, int P,
                                                                uint2* __restrict__ packed, uint32_t* __restrict__ counts1,
@@ -76,10 +134,9 @@ __global__ __launch_bounds__(RB_THREADS) void rb_count1_kernel(int W, int H, con
     if (rnk < n_vis) {
       const uint32_t id = order[rnk];
       const uint2 rc = rect[id];   // {minx | maxx << 16, miny | maxy << 16} (grids up to 64 x 64 here)
-      int x0 = (int)(rc.x & 0xffffu), x1 = (int)(rc.x >> 16), y0 = (int)(rc.y & 0xffffu), y1 = (int)(rc.y >> 16);
+      const int x0 = (int)(rc.x & 0xffffu), x1 = (int)(rc.x >> 16), y0 = (int)(rc.y & 0xffffu), y1 = (int)(rc.y >> 16);
       const int n = (x1 - x0) * (y1 - y0);
-      if (n <= 0) { x0 = x1 = y0 = y1 = 0; }
-      packed[rnk] = make_uint2(id, (uint32_t)x0 | ((uint32_t)x1 << 8) | ((uint32_t)y0 << 16) | ((uint32_t)y1 << 24));
+      packed[rnk] = make_uint2(id, n > 0 ? rb_pack_rect((uint32_t)x0, (uint32_t)x1, (uint32_t)y0, (uint32_t)y1) : 0u);
       if (n > 0) { atomicAdd(&diff[y0], 1); atomicAdd(&diff[y1], -1); }
     }
   }
@@ -95,24 +152,7 @@ __global__ __launch_bounds__(1024) void rb_scan1_kernel(uint32_t* __restrict__ c
   __shared__ uint32_t part[16][64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t n_vis = min((uint32_t)P, *n_vis_ptr);
-  const int nb = (int)((n_vis + RB_CHUNK - 1) / RB_CHUNK);
-  const int per = (nb + 15) / 16;
-  const int r0 = min(nb, wv * per), r1 = min(nb, r0 + per);
-  uint32_t s = 0;
-#pragma unroll 8
-  for (int r = r0; r < r1; ++r) s += counts1[(size_t)r * 64 + lane];
-  part[wv][lane] = s;
-  __syncthreads();
-  uint32_t run = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 16; ++w) { const uint32_t p = part[w][lane]; if (w < wv) run += p; tot += p; }
-#pragma unroll 8
-  for (int r = r0; r < r1; ++r) {
-    const size_t idx = (size_t)r * 64 + lane;
-    const uint32_t c = counts1[idx];
-    counts1[idx] = run;
-    run += c;
-  }
+  const uint32_t tot = rb_prefix_over_chunks<8>(counts1, 0u, (n_vis + RB_CHUNK - 1) / RB_CHUNK, 64, lane, part);
   if (wv == 0) rb_write_row_tables(tab, lane, tot, wave_inclusive_scan(tot), ent_cap);
 }
 
@@ -217,6 +257,101 @@ __device__ __forceinline__ void wave_emit(const uint32_t (&iv)[RB_IPL], const ui
   }
 }
 
+// What a chunk emits: a row entry {id, x0 | x1 << 8} at level 1, the Gaussian id at level 2.
+struct rb_row_entry {
+  using type = uint2;
+  static constexpr bool TWO = true;
+  static __device__ __forceinline__ uint2 pack(uint32_t id, uint32_t xx) { return make_uint2(id, xx); }
+};
+struct rb_instance {
+  using type = uint32_t;
+  static constexpr bool TWO = false;
+  static __device__ __forceinline__ uint32_t pack(uint32_t id, uint32_t) { return id; }
+};
+
+// The emission tail of a chunk (all four waves; lane = bin): bintot = the chunk's entries per bin, before = those of the earlier
+// waves, gbase = where the chunk's run of the bin starts in `out`.  The output is staged in LDS in (bin, item) order and copied out
+// with every bin's run as lane-consecutive stores, the bins dealt to the four waves: emitted directly every entry is a lone store
+// into one of 64 lists (level 2: 2.2x write amplification, those stores were 15 of rb_scatter2_kernel's 27 us; level 1: the
+// head-like scene writes 3.3 M of them).  A chunk with more output than the staging buffer holds keeps the direct form, behind the
+// bound check.  `stage` is written below the chunk's own total only, `out` below out_cap only.
+template <typename Pay>
+__device__ __forceinline__ void rb_emit_chunk(const uint32_t (&iv)[RB_IPL], const uint32_t (&pa)[RB_IPL],
+                                              const uint32_t (&pb)[RB_IPL], const uint64_t (&cols)[RB_IPL], int n_items,
+                                              uint32_t bintot, uint32_t before, uint32_t gbase, uint4* slab /* [64], this wave's */,
+                                              typename Pay::type* stage, uint32_t stage_cap,
+                                              typename Pay::type* __restrict__ out, uint32_t out_cap) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t binend = wave_inclusive_scan(bintot);          // same in every wave
+  const uint32_t total = (uint32_t)__shfl((int)binend, 63, 64);
+  const uint32_t binbeg = binend - bintot;
+  if (total <= stage_cap) {
+    uint32_t ldst = binbeg + before;
+    wave_emit<Pay::TWO>(iv, pa, pb, cols, n_items, ldst, slab, [&](uint32_t d, uint32_t a, uint32_t b) { stage[d] = Pay::pack(a, b); });
+    __syncthreads();
+#pragma unroll 4
+    for (int c = wv; c < 64; c += RB_WAVES) {
+      const uint32_t n = (uint32_t)__shfl((int)bintot, c, 64);
+      if (n == 0) continue;
+      const uint32_t b0 = (uint32_t)__shfl((int)binbeg, c, 64), g = (uint32_t)__shfl((int)gbase, c, 64);
+      for (uint32_t k = lane; k < n; k += 64) {
+        const uint32_t d = g + k;
+        if (d < out_cap) out[d] = stage[b0 + k];
+      }
+    }
+    return;
+  }
+  uint32_t dst = gbase + before;
+  wave_emit<Pay::TWO>(iv, pa, pb, cols, n_items, dst, slab, [&](uint32_t d, uint32_t a, uint32_t b) {
+    if (d < out_cap) out[d] = Pay::pack(a, b);
+  });
+}
+
+// Sums n count rows of 64 words over the workgroup: row_of(i) = the address of row i.  16 lanes take a row as four 16-byte columns,
+// a wave four rows per load instruction, the rows are dealt to the four waves, and a lane has BATCH = 8 independent loads in flight
+// (128 rows per round trip of the workgroup) -- all of a batch requested before any is consumed: these sums sit on the one
+// dependent round trip of their kernels, and a load per wait made it n / 16 trips.  The wave's four row groups are folded by
+// two shuffles and lanes 0 - 15 store the wave's partial sums to s_tot[64] (this wave's); BEFORE: those of the rows below `split` to
+// s_bef[64] as well.  The caller adds the four waves' partials behind its next barrier.
+template <bool BEFORE, typename RowOf>
+__device__ __forceinline__ void rb_sum_count_rows(uint32_t n, uint32_t split, RowOf&& row_of, uint32_t* s_tot, uint32_t* s_bef) {
+  constexpr int BATCH = 8;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t sub = (uint32_t)lane >> 4, c4 = ((uint32_t)lane & 15u) * 4u;
+  uint4 bef4 = make_uint4(0, 0, 0, 0), tot4 = make_uint4(0, 0, 0, 0);
+  for (uint32_t k0 = (uint32_t)wv * 4u; k0 < n; k0 += 4u * RB_WAVES * BATCH) {
+    uint4 v[BATCH];
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      const uint32_t k = k0 + sub + (uint32_t)(4 * RB_WAVES * j);
+      v[j] = make_uint4(0, 0, 0, 0);
+      if (k < n) v[j] = *reinterpret_cast<const uint4*>(row_of(k) + c4);
+    }
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      tot4.x += v[j].x; tot4.y += v[j].y; tot4.z += v[j].z; tot4.w += v[j].w;
+      if constexpr (BEFORE) {
+        const uint32_t k = k0 + sub + (uint32_t)(4 * RB_WAVES * j);
+        const uint32_t m = k < split ? 0xffffffffu : 0u;
+        bef4.x += v[j].x & m; bef4.y += v[j].y & m; bef4.z += v[j].z & m; bef4.w += v[j].w & m;
+      }
+    }
+  }
+#pragma unroll
+  for (int d = 16; d <= 32; d <<= 1) {   // the wave's four row groups hold the same columns
+    tot4.x += (uint32_t)__shfl_xor((int)tot4.x, d, 64); tot4.y += (uint32_t)__shfl_xor((int)tot4.y, d, 64);
+    tot4.z += (uint32_t)__shfl_xor((int)tot4.z, d, 64); tot4.w += (uint32_t)__shfl_xor((int)tot4.w, d, 64);
+    if constexpr (BEFORE) {
+      bef4.x += (uint32_t)__shfl_xor((int)bef4.x, d, 64); bef4.y += (uint32_t)__shfl_xor((int)bef4.y, d, 64);
+      bef4.z += (uint32_t)__shfl_xor((int)bef4.z, d, 64); bef4.w += (uint32_t)__shfl_xor((int)bef4.w, d, 64);
+    }
+  }
+  if (lane < 16) {
+    if constexpr (BEFORE) *reinterpret_cast<uint4*>(&s_bef[c4]) = bef4;
+    *reinterpret_cast<uint4*>(&s_tot[c4]) = tot4;
+  }
+}
+
 // ---- level 1 scatter: {id, x0 | x1 << 8} into the list of every row in [y0, y1)
 __global__ __launch_bounds__(RB_THREADS) void rb_scatter1_kernel(const uint2* __restrict__ packed,
                                                                  const uint32_t* __restrict__ n_vis_ptr, int P,
@@ -237,8 +372,8 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scatter1_kernel(const uint2* __
     const int i = q * 64 + lane;
     uint2 it = make_uint2(0, 0);
     if (i < n_items) it = packed[wbeg + i];
-    pa[q] = it.x; pb[q] = it.y & 0xffffu;
-    iv[q] = it.y >> 16;   // y0 | y1 << 8
+    pa[q] = it.x; pb[q] = rb_packed_cols(it.y);
+    iv[q] = rb_packed_rows(it.y);
   }
   uint64_t cols[RB_IPL];
   const uint32_t mine = wave_cols(iv, n_items, cols);
@@ -274,22 +409,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_level1_kernel(const uint2* __re
   const uint32_t n_vis = min((uint32_t)P, *n_vis_ptr);
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   uint32_t rowstart = 0;
-  if (wv == 0) {
-    uint32_t tot = 0;
-#pragma unroll
-    for (int r = 0; r < GGD_FOLD_REPS; ++r) tot += rowtot[r * 64 + lane];
-    const uint32_t inc = wave_inclusive_scan(tot);
-    rowstart = inc - tot;
-    if (blockIdx.x == 0) {
-      rb_write_row_tables(tab, lane, tot, inc, ent_cap);
-      if (rowinst) {   // the instances per row, for rb_scatter2_kernel<true> (plain stores: the next launch reads them)
-        uint32_t inst = 0;
-#pragma unroll
-        for (int r = 0; r < GGD_FOLD_REPS; ++r) inst += rowinst[r * 64 + lane];
-        tab[RB_TAB_ROWINST + lane] = inst;
-      }
-    }
-  }
+  if (wv == 0) rowstart = rb_level1_head(rb_fold_sum(rowtot, lane), blockIdx.x == 0, tab, ent_cap, rowinst);
   const uint32_t base = (uint32_t)blockIdx.x * RB_CHUNK;
   if (base >= n_vis) return;
   const uint32_t wbeg = base + (uint32_t)wv * RB_WCHUNK;
@@ -322,33 +442,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_level1_kernel(const uint2* __re
   uint32_t before = 0, rowtot_c = 0;   // lane = row: this chunk's entries of the earlier waves / of the whole chunk
 #pragma unroll
   for (int w = 0; w < RB_WAVES; ++w) { const uint32_t c = wcnt[w][lane]; if (w < wv) before += c; rowtot_c += c; }
-  // As in rb_scatter2_kernel: the chunk's entries are staged in LDS in (row, item) order and every row's run leaves as
-  // lane-consecutive 8-byte stores -- emitted directly every entry was a lone store into one of 64 row lists (the head-like
-  // scene writes 3.3 M of them).  Chunks with more entries than the buffer holds keep the direct form.
-  const uint32_t rowend = wave_inclusive_scan(rowtot_c);          // same in every wave
-  const uint32_t total = (uint32_t)__shfl((int)rowend, 63, 64);
-  const uint32_t rowbeg = rowend - rowtot_c;
-  const uint32_t gbase = s_base[lane];
-  if (total <= (uint32_t)RB_STAGE1) {
-    uint32_t ldst = rowbeg + before;
-    wave_emit<true>(iv, pa, pb, cols, n_items, ldst, slab[wv], [&](uint32_t d, uint32_t id, uint32_t xx) { stage[d] = make_uint2(id, xx); });
-    __syncthreads();
-#pragma unroll 4
-    for (int c = wv; c < 64; c += RB_WAVES) {
-      const uint32_t n = (uint32_t)__shfl((int)rowtot_c, c, 64);
-      if (n == 0) continue;
-      const uint32_t b0 = (uint32_t)__shfl((int)rowbeg, c, 64), g = (uint32_t)__shfl((int)gbase, c, 64);
-      for (uint32_t k = lane; k < n; k += 64) {
-        const uint32_t d = g + k;
-        if (d < ent_cap) ent[d] = stage[b0 + k];
-      }
-    }
-    return;
-  }
-  uint32_t dst = gbase + before;
-  wave_emit<true>(iv, pa, pb, cols, n_items, dst, slab[wv], [&](uint32_t d, uint32_t id, uint32_t xx) {
-    if (d < ent_cap) ent[d] = make_uint2(id, xx);
-  });
+  rb_emit_chunk<rb_row_entry>(iv, pa, pb, cols, n_items, rowtot_c, before, s_base[lane], slab[wv], stage, RB_STAGE1, ent, ent_cap);
 }
 
 // ---- level 1 behind the two-launch depth sort (GGD_OPT_L1_COUNTED): rb_level1_kernel without the look-back.  The sort's finish
@@ -358,9 +452,9 @@ __global__ __launch_bounds__(RB_THREADS) void rb_level1_kernel(const uint2* __re
 //        row start[r] + sum of bucket_rows[b'][r] over the buckets b' that lie wholly in front of rank 1024 k + boundary_rows[k][r]
 //      -- every term is final when this launch starts; no workgroup waits for another, no status words, no atomics.
 //      Two round trips: {bucket histogram, row totals, kept count, the chunk's packed items, its boundary row}, then the bucket rows
-//      (16-byte loads, a lane four rows of the grid, sixteen lanes a bucket, the buckets dealt to the four waves).  A bucket counts
-//      when it is non-empty (an empty one has no workgroup that writes its row) and ends at or below rank 1024 k; which those are
-//      follows from the histogram's prefix.  A frame the front end's verdict fails (a key outside the window, clamped into the last
+//      (rb_sum_count_rows); behind them the shared emission tail, rb_emit_chunk.  A bucket counts when it is non-empty (an empty one
+//      has no workgroup that writes its row) and ends at or below rank 1024 k; which those are follows from the histogram's prefix.
+//      A frame the front end's verdict fails (a key outside the window, clamped into the last
 //      bucket; a bucket above GGD_MSD_CAP, left in index order) has complete tables too: the lists are those of the order the sort left.
 //      Bounds: items are read at min(rank, P - 1); rows unpacked from `packed` are clamped to 64; bucket indices come from the
 //      1024-word histogram; k < gridDim = the rows boundary_rows has; ent is written below ent_cap only, the staging buffer below
@@ -389,24 +483,12 @@ __global__ __launch_bounds__(RB_THREADS) void rb_level1_counted_kernel(const uin
   // first round trip: nothing below depends on another load's value
   const uint32_t n_vis = min((uint32_t)P, *n_vis_ptr);
   const uint4 h4 = reinterpret_cast<const uint4*>(hist)[tid];
-  uint32_t tot = 0;
-#pragma unroll
-  for (int r = 0; r < GGD_FOLD_REPS; ++r) tot += rowtot[r * 64 + lane];
+  const uint32_t tot = rb_fold_sum(rowtot, lane);
   const uint32_t bound = boundary_rows[(size_t)blockIdx.x * 64 + lane];
   uint2 raw[RB_IPL];
 #pragma unroll
   for (int q = 0; q < RB_IPL; ++q) raw[q] = packed[min(wbeg + (uint32_t)(q * 64 + lane), (uint32_t)P - 1u)];
-  const uint32_t inc = wave_inclusive_scan(tot);
-  const uint32_t rowstart = inc - tot;
-  if (blockIdx.x == 0 && wv == 0) {
-    rb_write_row_tables(tab, lane, tot, inc, ent_cap);
-    if (rowinst) {   // the instances per row, for rb_scatter2_kernel<true> (plain stores: the next launch reads them)
-      uint32_t inst = 0;
-#pragma unroll
-      for (int r = 0; r < GGD_FOLD_REPS; ++r) inst += rowinst[r * 64 + lane];
-      tab[RB_TAB_ROWINST + lane] = inst;
-    }
-  }
+  const uint32_t rowstart = rb_level1_head(tot, blockIdx.x == 0 && wv == 0, tab, ent_cap, rowinst);
   if (base >= n_vis) return;
   const int n_items = (int)min((uint32_t)RB_WCHUNK, n_vis > wbeg ? n_vis - wbeg : 0u);
   // the buckets that end at or below `base`: thread t holds buckets 4 t .. 4 t + 3; one scan carries their sizes and their number
@@ -441,67 +523,23 @@ __global__ __launch_bounds__(RB_THREADS) void rb_level1_counted_kernel(const uin
 #pragma unroll
   for (int q = 0; q < RB_IPL; ++q) {
     const bool have = q * 64 + lane < n_items;
-    const uint32_t y0 = min((raw[q].y >> 16) & 0xffu, 64u), y1 = min(raw[q].y >> 24, 64u);
+    const uint32_t y0 = min(rb_packed_y0(raw[q].y), 64u), y1 = min(rb_packed_y1(raw[q].y), 64u);
     pa[q] = have ? raw[q].x : 0u;
-    pb[q] = have ? raw[q].y & 0xffffu : 0u;
+    pb[q] = have ? rb_packed_cols(raw[q].y) : 0u;
     iv[q] = have ? y0 | (y1 << 8) : 0u;
   }
   uint64_t cols[RB_IPL];
   const uint32_t mine = wave_cols(iv, n_items, cols);
   wcnt[wv][lane] = mine;
   __syncthreads();   // s_used is complete (and wcnt, for the barrier below to publish with s_rows)
-  {
-    // second (and last) round trip: the rows of the buckets in front
-    constexpr int BATCH = 8;
-    const uint32_t sub = (uint32_t)lane >> 4, c4 = ((uint32_t)lane & 15u) * 4u;
-    uint4 acc = make_uint4(0, 0, 0, 0);
-    for (uint32_t i0 = (uint32_t)wv * 4u; i0 < n_used; i0 += 4u * RB_WAVES * BATCH) {
-      uint4 v[BATCH];
-#pragma unroll
-      for (int j = 0; j < BATCH; ++j) {
-        const uint32_t i = i0 + sub + (uint32_t)(4 * RB_WAVES * j);
-        v[j] = make_uint4(0, 0, 0, 0);
-        if (i < n_used) v[j] = *reinterpret_cast<const uint4*>(bucket_rows + (size_t)s_used[i] * 64 + c4);
-      }
-#pragma unroll
-      for (int j = 0; j < BATCH; ++j) { acc.x += v[j].x; acc.y += v[j].y; acc.z += v[j].z; acc.w += v[j].w; }
-    }
-#pragma unroll
-    for (int d = 16; d <= 32; d <<= 1) {   // the wave's four bucket groups hold the same rows
-      acc.x += (uint32_t)__shfl_xor((int)acc.x, d, 64); acc.y += (uint32_t)__shfl_xor((int)acc.y, d, 64);
-      acc.z += (uint32_t)__shfl_xor((int)acc.z, d, 64); acc.w += (uint32_t)__shfl_xor((int)acc.w, d, 64);
-    }
-    if (lane < 16) *reinterpret_cast<uint4*>(&s_rows[wv][c4]) = acc;
-  }
+  // second (and last) round trip: the rows of the buckets in front
+  rb_sum_count_rows<false>(n_used, 0u, [&](uint32_t i) { return bucket_rows + (size_t)s_used[i] * 64; }, s_rows[wv], nullptr);
   __syncthreads();
   uint32_t before = 0, rowtot_c = 0;   // lane = row: this chunk's entries of the earlier waves / of the whole chunk
 #pragma unroll
   for (int w = 0; w < RB_WAVES; ++w) { const uint32_t c = wcnt[w][lane]; if (w < wv) before += c; rowtot_c += c; }
   const uint32_t gbase = rowstart + bound + s_rows[0][lane] + s_rows[1][lane] + s_rows[2][lane] + s_rows[3][lane];
-  // staging and copy-out as in rb_level1_kernel
-  const uint32_t rowend = wave_inclusive_scan(rowtot_c);          // same in every wave
-  const uint32_t total = (uint32_t)__shfl((int)rowend, 63, 64);
-  const uint32_t rowbeg = rowend - rowtot_c;
-  if (total <= (uint32_t)RB_STAGE1) {
-    uint32_t ldst = rowbeg + before;
-    wave_emit<true>(iv, pa, pb, cols, n_items, ldst, slab[wv], [&](uint32_t d, uint32_t id, uint32_t xx) { stage[d] = make_uint2(id, xx); });
-    __syncthreads();
-#pragma unroll 4
-    for (int c = wv; c < 64; c += RB_WAVES) {
-      const uint32_t n = (uint32_t)__shfl((int)rowtot_c, c, 64);
-      if (n == 0) continue;
-      const uint32_t b0 = (uint32_t)__shfl((int)rowbeg, c, 64), g = (uint32_t)__shfl((int)gbase, c, 64);
-      for (uint32_t k = lane; k < n; k += 64) {
-        const uint32_t d = g + k;
-        if (d < ent_cap) ent[d] = stage[b0 + k];
-      }
-    }
-    return;
-  }
-  uint32_t dst = gbase + before;
-  wave_emit<true>(iv, pa, pb, cols, n_items, dst, slab[wv], [&](uint32_t d, uint32_t id, uint32_t xx) {
-    if (d < ent_cap) ent[d] = make_uint2(id, xx);
-  });
+  rb_emit_chunk<rb_row_entry>(iv, pa, pb, cols, n_items, rowtot_c, before, gbase, slab[wv], stage, RB_STAGE1, ent, ent_cap);
 }
 
 // level-2 block -> (row, chunk within the row)
@@ -553,6 +591,23 @@ __global__ __launch_bounds__(RB_THREADS) void rb_count2_kernel(const uint2* __re
   if (tid < 64) counts2[(size_t)blockIdx.x * 64 + tid] = (uint32_t)wave_inclusive_scan(diff[tid]);
 }
 
+// Wave 0 of the scan workgroup of tile row r: publishes the row's instances (`mine`, taken from lane 63; release) and returns those
+// of the rows above, summed from their published totals (relaxed poll, one acquire).  inst / flag: the tables' [row] words.
+__device__ __forceinline__ uint32_t rb_publish_row_sum_above(uint32_t* inst, uint32_t* flag, int r, uint32_t mine) {
+  const int lane = threadIdx.x & 63;
+  if (lane == 63) {
+    inst[r] = mine;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __hip_atomic_store(&flag[r], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  for (int rr = lane; rr < r; rr += 64)
+    while (__hip_atomic_load(&flag[rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {}
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  uint32_t above = 0;
+  for (int rr = lane; rr < r; rr += 64) above += __hip_atomic_load(&inst[rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan(above), 63);
+}
+
 // ---- level-2 scan, one workgroup per tile row: exclusive prefix over the row's chunks (lane = column, 16 waves split
 //      the chunks), tile totals, then the start of every tile list.  The only cross-row quantity is the number of
 //      instances in the rows above: every workgroup publishes its row total (release) and sums the totals of the lower
@@ -563,38 +618,10 @@ __global__ __launch_bounds__(1024) void rb_scan2_kernel(uint32_t* __restrict__ c
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int r = blockIdx.x;
   const uint32_t b0 = tab[RB_TAB_ROWBLK + r], b1 = tab[RB_TAB_ROWBLK + r + 1];
-  const uint32_t nb = b1 - b0, per = (nb + 15u) / 16u;
-  const uint32_t c0 = b0 + min(nb, (uint32_t)wv * per), c1 = min(b1, c0 + per);
-  uint32_t s = 0;
-#pragma unroll 4
-  for (uint32_t b = c0; b < c1; ++b) s += counts2[(size_t)b * 64 + lane];
-  part[wv][lane] = s;
-  __syncthreads();
-  uint32_t run = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 16; ++w) { const uint32_t p = part[w][lane]; if (w < wv) run += p; tot += p; }
-#pragma unroll 4
-  for (uint32_t b = c0; b < c1; ++b) {
-    const size_t idx = (size_t)b * 64 + lane;
-    const uint32_t c = counts2[idx];
-    counts2[idx] = run;
-    run += c;
-  }
+  const uint32_t tot = rb_prefix_over_chunks<4>(counts2, b0, b1 - b0, 64, lane, part);
   if (wv == 0) {
     const uint32_t inc = wave_inclusive_scan(tot);
-    if (lane == 63) {
-      tab[RB_TAB_ROWINST + r] = inc;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      __hip_atomic_store(&tab[RB_TAB_FLAG + r], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    uint32_t below = 0;
-    if (lane < r) {
-      while (__hip_atomic_load(&tab[RB_TAB_FLAG + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {}
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (lane < r) below = __hip_atomic_load(&tab[RB_TAB_ROWINST + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t binc = wave_inclusive_scan(below);
-    const uint32_t rowbase = (uint32_t)__builtin_amdgcn_readlane((int)binc, 63);
+    const uint32_t rowbase = rb_publish_row_sum_above(tab + RB_TAB_ROWINST, tab + RB_TAB_FLAG, r, inc);
     if (lane < gx) {
       const uint32_t start = rowbase + inc - tot;
       tab[RB_TAB_TILESTART + r * 64 + lane] = start;
@@ -609,9 +636,8 @@ __global__ __launch_bounds__(1024) void rb_scan2_kernel(uint32_t* __restrict__ c
 // instances per row as the preprocess kernel counted them.  The workgroup of block (row r, chunk c) forms its tile starts itself:
 //   start(r, col) = instances of the rows above r + exclusive prefix over the columns of total[col] + before[col],
 //   total / before = sum of counts2[b][col] over all blocks b of row r / over the blocks in front of chunk c
-// -- the count rows of the row's blocks (16 lanes a row of four columns each, rows dealt to the four waves, 8 independent 16-byte
-// loads a lane) are requested in the same round trip as the entries, and the waves' partial sums meet at the barrier behind
-// wave_cols.  Nothing is handed from one workgroup to another (the two forms that did, profiles/REJECTED.md round 5, doubled
+// -- the count rows of the row's blocks (rb_sum_count_rows) are requested in the same round trip as the entries, and the waves'
+// partial sums meet at the barrier behind wave_cols.  Nothing is handed from one workgroup to another (the two forms that did, profiles/REJECTED.md round 5, doubled
 // rb_count2_kernel).
 // Chunk 0 of a row writes the row's ranges; a row without blocks has no workgroup, so workgroup z < gy writes the zero ranges of
 // row z when that row has none.  The reads grow with the square of a row's blocks: RB_SCAN_IN_SCATTER_MAX_BLOCKS.
@@ -663,38 +689,8 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scatter2_kernel(const uint2* __
   if constexpr (SCAN) {
     const uint32_t blk0 = blockIdx.x - chunk;                                        // first block of the row
     const uint32_t nblk_row = (uint32_t)__shfl((int)rowblks, row, 64);               // >= chunk + 1
-    // a lane takes four columns of a count row (one 16-byte load), a wave four rows per load instruction, the workgroup
-    // 16 x BATCH rows per round trip: the cube's 19 blocks a row, the shell's 50 - 130 are one batch
-    constexpr int BATCH = 8;
-    const uint32_t sub = (uint32_t)lane >> 4, c4 = ((uint32_t)lane & 15u) * 4u;
-    uint4 bef4 = make_uint4(0, 0, 0, 0), tot4 = make_uint4(0, 0, 0, 0);
-    for (uint32_t k0 = (uint32_t)wv * 4u; k0 < nblk_row; k0 += 4u * RB_WAVES * BATCH) {
-      uint4 v[BATCH];
-#pragma unroll
-      for (int j = 0; j < BATCH; ++j) {
-        const uint32_t k = k0 + sub + (uint32_t)(4 * RB_WAVES * j);
-        v[j] = make_uint4(0, 0, 0, 0);
-        if (k < nblk_row) v[j] = *reinterpret_cast<const uint4*>(prefix2 + (size_t)(blk0 + k) * 64 + c4);
-      }
-#pragma unroll
-      for (int j = 0; j < BATCH; ++j) {
-        const uint32_t k = k0 + sub + (uint32_t)(4 * RB_WAVES * j);
-        tot4.x += v[j].x; tot4.y += v[j].y; tot4.z += v[j].z; tot4.w += v[j].w;
-        const uint32_t m = k < chunk ? 0xffffffffu : 0u;
-        bef4.x += v[j].x & m; bef4.y += v[j].y & m; bef4.z += v[j].z & m; bef4.w += v[j].w & m;
-      }
-    }
-#pragma unroll
-    for (int d = 16; d <= 32; d <<= 1) {   // the wave's four row groups hold the same columns
-      tot4.x += (uint32_t)__shfl_xor((int)tot4.x, d, 64); tot4.y += (uint32_t)__shfl_xor((int)tot4.y, d, 64);
-      tot4.z += (uint32_t)__shfl_xor((int)tot4.z, d, 64); tot4.w += (uint32_t)__shfl_xor((int)tot4.w, d, 64);
-      bef4.x += (uint32_t)__shfl_xor((int)bef4.x, d, 64); bef4.y += (uint32_t)__shfl_xor((int)bef4.y, d, 64);
-      bef4.z += (uint32_t)__shfl_xor((int)bef4.z, d, 64); bef4.w += (uint32_t)__shfl_xor((int)bef4.w, d, 64);
-    }
-    if (lane < 16) {
-      *reinterpret_cast<uint4*>(&wsum[wv][c4]) = bef4;
-      *reinterpret_cast<uint4*>(&wsum[RB_WAVES + wv][c4]) = tot4;
-    }
+    // (the cube's 19 blocks a row, the shell's 50 - 130 are one batch of rb_sum_count_rows)
+    rb_sum_count_rows<true>(nblk_row, chunk, [&](uint32_t k) { return prefix2 + (size_t)(blk0 + k) * 64; }, wsum[RB_WAVES + wv], wsum[wv]);
   } else {
     gbase = tab[RB_TAB_TILESTART + row * 64 + lane] + prefix2[(size_t)blockIdx.x * 64 + lane];
   }
@@ -725,32 +721,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scatter2_kernel(const uint2* __
   uint32_t before = 0, coltot = 0;   // lane = column: instances of the earlier waves / of the whole chunk
 #pragma unroll
   for (int w = 0; w < RB_WAVES; ++w) { const uint32_t c = wcnt[w][lane]; if (w < wv) before += c; coltot += c; }
-  // The chunk's instances are staged in LDS in (column, item) order and copied out with every column's run as
-  // lane-consecutive stores: emitted directly, the list goes out as lone 4-byte words (2.2x write amplification; those
-  // stores were 15 of the kernel's 27 us).  Chunks with more instances than the buffer holds keep the direct form.
-  const uint32_t colend = wave_inclusive_scan(coltot);          // same in every wave
-  const uint32_t total = (uint32_t)__shfl((int)colend, 63, 64);
-  const uint32_t colbeg = colend - coltot;
-  if (total <= (uint32_t)RB_STAGE) {
-    uint32_t ldst = colbeg + before;
-    wave_emit<false>(iv, pa, pb, cols, n_items, ldst, slab[wv], [&](uint32_t d, uint32_t id, uint32_t) { stage[d] = id; });
-    __syncthreads();
-#pragma unroll 4
-    for (int c = wv; c < 64; c += RB_WAVES) {
-      const uint32_t n = (uint32_t)__shfl((int)coltot, c, 64);
-      if (n == 0) continue;
-      const uint32_t b0 = (uint32_t)__shfl((int)colbeg, c, 64), g = (uint32_t)__shfl((int)gbase, c, 64);
-      for (uint32_t k = lane; k < n; k += 64) {
-        const uint32_t d = g + k;
-        if (d < capacity) list[d] = stage[b0 + k];
-      }
-    }
-    return;
-  }
-  uint32_t dst = gbase + before;
-  wave_emit<false>(iv, pa, pb, cols, n_items, dst, slab[wv], [&](uint32_t d, uint32_t id, uint32_t) {
-    if (d < capacity) list[d] = id;
-  });
+  rb_emit_chunk<rb_instance>(iv, pa, pb, cols, n_items, coltot, before, gbase, slab[wv], stage, RB_STAGE, list, capacity);
 }
 
 #include "ggd_rowbin_wide.inc"
@@ -812,8 +783,8 @@ int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const 
                        fold_status1, nb1, ggd_group_shift(nb1), tab, ent, capacity, order_alt, use_alt,
                        fused2 ? fold_rowinst : nullptr);
   } else {
-    hipLaunchKernelGGL(rb_count1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, prm.width, prm.height, rect, order,
-                       n_vis_ptr, prm.P, packed, counts1, order_alt, use_alt);
+    hipLaunchKernelGGL(rb_count1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, rect, order, n_vis_ptr, prm.P, packed, counts1,
+                       order_alt, use_alt);
     hipLaunchKernelGGL(rb_scan1_kernel, dim3(1), dim3(1024), 0, s, counts1, n_vis_ptr, prm.P, tab, capacity);
     hipLaunchKernelGGL(rb_scatter1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, packed, n_vis_ptr, prm.P, counts1, tab,
                        ent, capacity);

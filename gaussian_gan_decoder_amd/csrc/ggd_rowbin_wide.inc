@@ -43,10 +43,9 @@ __global__ __launch_bounds__(RB_THREADS) void rbw_count1_kernel(const uint2* __r
     if (rnk < n_vis) {
       const uint32_t id = order[rnk];
       const uint2 rc = rect[id];   // {minx | maxx << 16, miny | maxy << 16}, all <= 255 on the grids this path takes
-      int x0 = (int)(rc.x & 0xffffu), x1 = (int)(rc.x >> 16), y0 = (int)(rc.y & 0xffffu), y1 = (int)(rc.y >> 16);
+      const int x0 = (int)(rc.x & 0xffffu), x1 = (int)(rc.x >> 16), y0 = (int)(rc.y & 0xffffu), y1 = (int)(rc.y >> 16);
       const int n = (x1 - x0) * (y1 - y0);
-      if (n <= 0) { x0 = x1 = y0 = y1 = 0; }
-      packed[rnk] = make_uint2(id, (uint32_t)x0 | ((uint32_t)x1 << 8) | ((uint32_t)y0 << 16) | ((uint32_t)y1 << 24));
+      packed[rnk] = make_uint2(id, n > 0 ? rb_pack_rect((uint32_t)x0, (uint32_t)x1, (uint32_t)y0, (uint32_t)y1) : 0u);
       if (n > 0) { atomicAdd(&diff[y0], 1); atomicAdd(&diff[y1], -1); }
     }
   }
@@ -62,32 +61,16 @@ __global__ __launch_bounds__(1024) void rbw_scan1_kernel(uint32_t* __restrict__ 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int nbins = 64 * ng;
   const uint32_t n_vis = min((uint32_t)P, *n_vis_ptr);
-  const int nblk = (int)((n_vis + RB_CHUNK - 1) / RB_CHUNK);
-  const int per = (nblk + 15) / 16;
-  const int r0 = min(nblk, wv * per), r1 = min(nblk, r0 + per);
+  const uint32_t nblk = (n_vis + RB_CHUNK - 1) / RB_CHUNK;
   uint32_t row_carry = 0, blk_carry = 0;   // wave 0: entries / level-2 blocks of the earlier groups
   for (int g = 0; g < ng; ++g) {
     const int bin = 64 * g + lane;
-    uint32_t s = 0;
-#pragma unroll 8
-    for (int r = r0; r < r1; ++r) s += counts1[(size_t)r * nbins + bin];
-    part[wv][lane] = s;
-    __syncthreads();
-    uint32_t run = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) { const uint32_t p = part[w][lane]; if (w < wv) run += p; tot += p; }
-#pragma unroll 8
-    for (int r = r0; r < r1; ++r) {
-      const size_t idx = (size_t)r * nbins + bin;
-      const uint32_t c = counts1[idx];
-      counts1[idx] = run;
-      run += c;
-    }
+    const uint32_t tot = rb_prefix_over_chunks<8>(counts1, 0u, nblk, nbins, bin, part);
     if (wv == 0) {
       const uint32_t inc = row_carry + wave_inclusive_scan(tot);
       const uint32_t rs = inc - tot;
       tab[RBW_TAB_ROWSTART + bin] = rs;
-      const uint32_t have = rs < ent_cap ? min(tot, ent_cap - rs) : 0u;   // see rb_scan1_kernel
+      const uint32_t have = rs < ent_cap ? min(tot, ent_cap - rs) : 0u;   // see rb_write_row_tables
       const uint32_t nb2 = (have + RB_CHUNK - 1) / RB_CHUNK;
       const uint32_t binc = blk_carry + wave_inclusive_scan(nb2);
       tab[RBW_TAB_ROWBLK + bin] = binc - nb2;
@@ -201,8 +184,8 @@ __global__ __launch_bounds__(RB_THREADS) void rbw_scatter1_kernel(const uint2* _
     const int i = q * 64 + lane;
     uint2 it = make_uint2(0, 0);
     if (i < n_items) it = packed[wbeg + i];
-    pa[q] = it.x; pb[q] = it.y & 0xffffu;
-    iv[q] = it.y >> 16;   // y0 | y1 << 8
+    pa[q] = it.x; pb[q] = rb_packed_cols(it.y);
+    iv[q] = rb_packed_rows(it.y);
   }
   uint32_t mine[RBW_NG];
   uint64_t cols[RB_IPL][RBW_NG];
@@ -276,31 +259,13 @@ __global__ __launch_bounds__(1024) void rbw_scan2_kernel(uint32_t* __restrict__ 
   const int nbins = 64 * ng;
   const int r = blockIdx.x;
   const uint32_t b0 = tab[RBW_TAB_ROWBLK + r], b1 = tab[RBW_TAB_ROWBLK + r + 1];
-  const uint32_t nb = b1 - b0, per = (nb + 15u) / 16u;
-  const uint32_t c0 = b0 + min(nb, (uint32_t)wv * per), c1 = min(b1, c0 + per);
   uint32_t tots[RBW_NG];
 #pragma unroll
   for (int g = 0; g < RBW_NG; ++g) {
     tots[g] = 0;
     if (g >= ng) continue;
-    const int col = 64 * g + lane;
-    uint32_t s = 0;
-#pragma unroll 4
-    for (uint32_t b = c0; b < c1; ++b) s += counts2[(size_t)b * nbins + col];
-    part[wv][lane] = s;
-    __syncthreads();
-    uint32_t run = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) { const uint32_t p = part[w][lane]; if (w < wv) run += p; tot += p; }
-#pragma unroll 4
-    for (uint32_t b = c0; b < c1; ++b) {
-      const size_t idx = (size_t)b * nbins + col;
-      const uint32_t c = counts2[idx];
-      counts2[idx] = run;
-      run += c;
-    }
-    tots[g] = tot;
-    __syncthreads();
+    tots[g] = rb_prefix_over_chunks<4>(counts2, b0, b1 - b0, nbins, 64 * g + lane, part);
+    __syncthreads();   // part is reused by the next group
   }
   if (wv == 0) {
     uint32_t incs[RBW_NG];
@@ -310,19 +275,7 @@ __global__ __launch_bounds__(1024) void rbw_scan2_kernel(uint32_t* __restrict__ 
       incs[g] = carry + wave_inclusive_scan(tots[g]);
       carry = (uint32_t)__shfl((int)incs[g], 63, 64);
     }
-    if (lane == 63) {   // carry = instances of this row
-      tab[RBW_TAB_ROWINST + r] = carry;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      __hip_atomic_store(&tab[RBW_TAB_FLAG + r], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    for (int rr = lane; rr < r; rr += 64)
-      while (__hip_atomic_load(&tab[RBW_TAB_FLAG + rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {}
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    uint32_t below = 0;
-    for (int rr = lane; rr < r; rr += 64)
-      below += __hip_atomic_load(&tab[RBW_TAB_ROWINST + rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t binc = wave_inclusive_scan(below);
-    const uint32_t rowbase = (uint32_t)__builtin_amdgcn_readlane((int)binc, 63);
+    const uint32_t rowbase = rb_publish_row_sum_above(tab + RBW_TAB_ROWINST, tab + RBW_TAB_FLAG, r, carry);   // carry = instances of this row
 #pragma unroll
     for (int g = 0; g < RBW_NG; ++g) {
       const int col = 64 * g + lane;
@@ -391,7 +344,7 @@ __global__ __launch_bounds__(RB_THREADS) void rbw_scatter2_kernel(const uint2* _
     }
   }
   const uint32_t total = carry;
-  if (total <= (uint32_t)RB_STAGE) {   // staged copy-out, see rb_scatter2_kernel
+  if (total <= (uint32_t)RB_STAGE) {   // staged copy-out as rb_emit_chunk's, over (group, lane) bins: the runs' ends go through LDS
     uint32_t ldst[RBW_NG];
 #pragma unroll
     for (int g = 0; g < RBW_NG; ++g) {
