@@ -85,17 +85,20 @@ def load():
         lib.ggd_destroy.restype = None; lib.ggd_destroy.argtypes = [vp]
         lib.ggd_last_error.restype = C.c_char_p; lib.ggd_last_error.argtypes = [vp]
         lib.ggd_version.restype = C.c_char_p
-        lib.ggd_forward_geometry.argtypes = [vp, vp, C.POINTER(Params)] + [vp] * 7 + [vp, vp, C.POINTER(i64)]
+        # ctx, stream, params, the seven per-Gaussian inputs; then geom_buf, radii (forward) / radii, the three buffers, R, dL_dpix (backward)
+        inputs = [vp, vp, C.POINTER(Params)] + [vp] * 7
+        fwd, bwd = inputs + [vp, vp], inputs + [vp, vp, vp, vp, i64, vp]
+        lib.ggd_forward_geometry.argtypes = fwd + [C.POINTER(i64)]
         lib.ggd_forward_render.argtypes = [vp, vp, C.POINTER(Params), vp, i64, vp, vp, vp]
-        lib.ggd_forward.argtypes = [vp, vp, C.POINTER(Params)] + [vp] * 7 + [vp, vp, vp, i64, vp, vp, C.POINTER(i64)]
-        lib.ggd_forward_enqueue.argtypes = [vp, vp, C.POINTER(Params)] + [vp] * 7 + [vp, vp, vp, i64, vp, vp]
+        lib.ggd_forward_render_aux.argtypes = lib.ggd_forward_render.argtypes + [vp, vp]
+        lib.ggd_forward.argtypes = fwd + [vp, i64, vp, vp, C.POINTER(i64)]
+        lib.ggd_forward_aux.argtypes = fwd + [vp, i64, vp, vp, vp, vp, C.POINTER(i64)]
+        lib.ggd_forward_enqueue.argtypes = fwd + [vp, i64, vp, vp]
         lib.ggd_forward_collect.argtypes = [vp, vp, C.POINTER(i64)]
         lib.ggd_forward_can_speculate.argtypes = [vp, C.POINTER(Params), i64]
-        lib.ggd_backward.argtypes = [vp, vp, C.POINTER(Params)] + [vp] * 7 + [vp, vp, vp, vp, i64, vp] + [vp] * 8
-        lib.ggd_forward_aux.argtypes = [vp, vp, C.POINTER(Params)] + [vp] * 7 + [vp, vp, vp, i64, vp, vp, vp, vp, C.POINTER(i64)]
-        lib.ggd_forward_render_aux.argtypes = [vp, vp, C.POINTER(Params), vp, i64, vp, vp, vp, vp, vp]
-        lib.ggd_backward_aux.argtypes = [vp, vp, C.POINTER(Params)] + [vp] * 7 + [vp, vp, vp, vp, i64, vp, vp, vp] + [vp] * 8
-        lib.ggd_backward_abs.argtypes = [vp, vp, C.POINTER(Params)] + [vp] * 7 + [vp, vp, vp, vp, i64, vp, vp, vp] + [vp] * 9
+        lib.ggd_backward.argtypes = bwd + [vp] * 8
+        lib.ggd_backward_aux.argtypes = bwd + [vp, vp] + [vp] * 8
+        lib.ggd_backward_abs.argtypes = bwd + [vp, vp] + [vp] * 9
         lib.ggd_mark_visible.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         lib.ggd_debug_unsorted.argtypes = [vp, vp, vp, vp, i64]
         lib.ggd_triplane_forward.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, C.c_float, vp]
@@ -243,17 +246,6 @@ class Context:
 _contexts: dict = {}
 
 
-def context_for(device) -> Context:
-    """Per-(device, stream) context cache."""
-    import torch
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, int(torch.cuda.current_stream(idx).cuda_stream))
-    ctx = _contexts.get(key)
-    if ctx is None:
-        ctx = _contexts[key] = Context(idx)
-    return ctx
-
-
 def context_and_stream(device):
     """(context of the current stream of `device`, that stream's raw handle) with one current_stream lookup."""
     import torch
@@ -264,6 +256,11 @@ def context_and_stream(device):
     if ctx is None:
         ctx = _contexts[key] = Context(idx)
     return ctx, handle
+
+
+def context_for(device) -> Context:
+    """Per-(device, stream) context cache."""
+    return context_and_stream(device)[0]
 
 
 def geom_view(P: int) -> GeomView:

@@ -872,8 +872,8 @@ int ggd_launch_blend(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const g
 
 int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
                               const uint32_t* list, const uint32_t* ranges, const float* final_T,
-                              const uint32_t* n_contrib, const float* dL_dpix, float* grad_acc, bool aux,
-                              const uint32_t* depth_keys, const float* dL_ddepth, const float* dL_dalpha, bool abs) {
+                              const uint32_t* n_contrib, const ggd_pix_grads& pix, float* grad_acc, bool aux,
+                              const uint32_t* depth_keys, bool abs) {
   const int gx = (prm.width + 15) / 16, gy = (prm.height + 15) / 16;
   if (gx * gy == 0) return GGD_OK;
   const int em = ctx->opt[GGD_OPT_EXP_MODE];   // 3 (default): compensated 2^x, contribution decision on the forward's bare v_exp_f32 value
@@ -896,7 +896,7 @@ int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm
     ggd_dispatch<4>(em, [&](auto e) {
       ggd_dispatch<2>(cull, [&](auto c) {
         hipLaunchKernelGGL((blend_backward_tile_kernel<decltype(e)::value, decltype(c)::value != 0>), dim3(T), dim3(256), 0, s,
-                           prm.width, prm.height, gx, gy, splat, list, ranges, prm.bg, final_T, n_contrib, dL_dpix, grad_acc);
+                           prm.width, prm.height, gx, gy, splat, list, ranges, prm.bg, final_T, n_contrib, pix.dL_dpix, grad_acc);
       });
     });
     GGD_HIP(hipGetLastError());
@@ -914,8 +914,8 @@ int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm
         const auto kernel = (V == ABS || V == AUXABS) ? blend_backward_quarter_abs_kernel<E, C, VAUX>
                                                       : blend_backward_quarter_kernel<E, C, V == STATS, VAUX>;
         hipLaunchKernelGGL(kernel, dim3(4 * T), dim3(64), lds_pad, s, prm.width, prm.height, gx, gy, splat, list, ranges, prm.bg,
-                           final_T, n_contrib, dL_dpix, grad_acc, V == STATS ? ctx->blend_stats : nullptr,
-                           VAUX ? depth_keys : nullptr, VAUX ? dL_ddepth : nullptr, VAUX ? dL_dalpha : nullptr);
+                           final_T, n_contrib, pix.dL_dpix, grad_acc, V == STATS ? ctx->blend_stats : nullptr,
+                           VAUX ? depth_keys : nullptr, VAUX ? pix.dL_ddepth : nullptr, VAUX ? pix.dL_dalpha : nullptr);
       });
     });
   });

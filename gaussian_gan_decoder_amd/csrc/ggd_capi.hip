@@ -12,6 +12,7 @@
 //                     histogram launch and four passes, binning, blend -- no second preprocess
 // The frame in flight (ggd_frame) is assigned fresh where a frame begins, in geometry_enqueue, and where it is collected.
 // Every other frame: preprocess -> scan -> read-back of num_rendered (a stream synchronise) -> either binning path -> blend.
+// (Below the extern "C" entry points the arguments travel in the groups of ggd_common.h: ggd_inputs, ggd_frame_bufs, ...)
 #include <stdlib.h>
 #include <string.h>
 
@@ -148,6 +149,18 @@ extern "C" const char* ggd_version(void) { return "ggd-raster 0.1 (gfx950)"; }
 extern "C" int ggd_stage_count(void) { return ST_COUNT; }
 extern "C" const char* ggd_stage_name(int s) { return (s >= 0 && s < ST_COUNT) ? kStageNames[s] : ""; }
 
+// Every option, in the order of its number (include/ggd_raster.h): the environment variable that sets it when a context is created
+// and its largest value.
+static constexpr struct { int option; const char* env; int max; } kOptions[GGD_OPT_COUNT] = {
+    {GGD_OPT_EXP_MODE, "GGD_EXP_MODE", 3}, {GGD_OPT_BLEND_CULL, "GGD_BLEND_CULL", 1}, {GGD_OPT_BINNING, "GGD_BINNING", 3},
+    {GGD_OPT_BLEND_SPLIT, "GGD_BLEND_SPLIT", 4}, {GGD_OPT_FOLD, "GGD_FOLD", 1}, {GGD_OPT_MSD_SORT, "GGD_MSD_SORT", 1},
+    {GGD_OPT_PREPROCESS_WGS, "GGD_PREPROCESS_WGS", GGD_PREPROCESS_WGS_MAX}, {GGD_OPT_L1_COUNTED, "GGD_L1_COUNTED", 1}};
+static_assert([] { for (int i = 0; i < GGD_OPT_COUNT; ++i) if (kOptions[i].option != i) return false; return true; }(),
+              "kOptions is indexed by the option's number");
+static bool option_value_ok(int option, int value) {
+  return option >= 0 && option < GGD_OPT_COUNT && value >= 0 && value <= kOptions[option].max;
+}
+
 extern "C" ggd_ctx* ggd_create(int device) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
@@ -157,14 +170,11 @@ extern "C" ggd_ctx* ggd_create(int device) {
   ggd_ctx* ctx = new (std::nothrow) ggd_ctx();
   if (!ctx) { ggd_fail(nullptr, GGD_E_NOMEM, "out of host memory"); return nullptr; }
   ctx->device = device;
-  if (const char* e = getenv("GGD_EXP_MODE")) { const int v = atoi(e); if (v >= 0 && v <= 3) ctx->opt[GGD_OPT_EXP_MODE] = v; }
-  if (const char* e = getenv("GGD_BINNING")) { const int v = atoi(e); if (v >= 0 && v <= 3) ctx->opt[GGD_OPT_BINNING] = v; }
-  if (const char* e = getenv("GGD_BLEND_SPLIT")) { const int v = atoi(e); if (v >= 0 && v <= 4) ctx->opt[GGD_OPT_BLEND_SPLIT] = v; }
-  if (const char* e = getenv("GGD_BLEND_CULL")) ctx->opt[GGD_OPT_BLEND_CULL] = atoi(e) != 0;
-  if (const char* e = getenv("GGD_FOLD")) ctx->opt[GGD_OPT_FOLD] = atoi(e) != 0;
-  if (const char* e = getenv("GGD_MSD_SORT")) ctx->opt[GGD_OPT_MSD_SORT] = atoi(e) != 0;
-  if (const char* e = getenv("GGD_PREPROCESS_WGS")) { const int v = atoi(e); if (v >= 0 && v <= GGD_PREPROCESS_WGS_MAX) ctx->opt[GGD_OPT_PREPROCESS_WGS] = v; }
-  if (const char* e = getenv("GGD_L1_COUNTED")) ctx->opt[GGD_OPT_L1_COUNTED] = atoi(e) != 0;
+  for (const auto& d : kOptions) {   // a value out of range is ignored; an on / off option (maximum 1) takes any non-zero number as 1
+    const char* e = getenv(d.env);
+    const int v = !e ? -1 : (d.max == 1 ? atoi(e) != 0 : atoi(e));
+    if (option_value_ok(d.option, v)) ctx->opt[d.option] = v;
+  }
   if (const char* e = getenv("GGD_MSD_BUCKETS")) { const int v = atoi(e); if (v >= 16 && v <= GGD_MSD_BINS) ctx->spec.msd_buckets = v; }   // timing experiments
   int prev = 0;
   (void)hipGetDevice(&prev);
@@ -214,9 +224,7 @@ extern "C" const char* ggd_last_error(ggd_ctx* ctx) { return ctx ? ctx->err.c_st
 
 extern "C" int ggd_set_option(ggd_ctx* ctx, int option, int value) {
   if (!ctx) return GGD_E_INVALID;
-  static const int kMax[GGD_OPT_COUNT] = {3, 1, 3, 4, 1, 1, GGD_PREPROCESS_WGS_MAX, 1};
-  if (option < 0 || option >= GGD_OPT_COUNT || value < 0 || value > kMax[option])
-    return ggd_fail(ctx, GGD_E_INVALID, "ggd_set_option: unknown option or value");
+  if (!option_value_ok(option, value)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_set_option: unknown option or value");
   ctx->opt[option] = value;
   if (option == GGD_OPT_MSD_SORT || option == GGD_OPT_FOLD) {
     // (re)setting the sort options restarts the cross-frame speculation state: the window of recent key ranges, the pause after
@@ -301,18 +309,16 @@ static int check_params(ggd_ctx* ctx, const ggd_params* prm) {
   return GGD_OK;
 }
 
-static int check_inputs(ggd_ctx* ctx, const ggd_params* prm, const float* means3D, const float* shs,
-                        const float* colors_precomp, const float* scales, const float* rotations,
-                        const float* cov3D_precomp) {
+static int check_inputs(ggd_ctx* ctx, const ggd_params* prm, const ggd_inputs& in) {
   if (prm->P == 0) return GGD_OK;
-  if (!means3D) return ggd_fail(ctx, GGD_E_INVALID, "means3D is NULL");
-  if ((shs == nullptr) == (colors_precomp == nullptr))
+  if (!in.means3D) return ggd_fail(ctx, GGD_E_INVALID, "means3D is NULL");
+  if ((in.shs == nullptr) == (in.colors_precomp == nullptr))
     return ggd_fail(ctx, GGD_E_INVALID, "Please provide excatly one of either SHs or precomputed colors!");
-  if (((scales == nullptr) || (rotations == nullptr)) == (cov3D_precomp == nullptr) ||
-      ((scales == nullptr) != (rotations == nullptr)))
+  if (((in.scales == nullptr) || (in.rotations == nullptr)) == (in.cov3D_precomp == nullptr) ||
+      ((in.scales == nullptr) != (in.rotations == nullptr)))
     return ggd_fail(ctx, GGD_E_INVALID,
                     "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
-  if (shs && (prm->sh_degree + 1) * (prm->sh_degree + 1) > prm->M)
+  if (in.shs && (prm->sh_degree + 1) * (prm->sh_degree + 1) > prm->M)
     return ggd_fail(ctx, GGD_E_INVALID, "shs holds fewer coefficients than sh_degree needs");
   return GGD_OK;
 }
@@ -369,25 +375,24 @@ static int fold_prepare(ggd_ctx* ctx, hipStream_t s, const ggd_params* prm, ggd_
 }
 
 // Enqueue the per-Gaussian kernels + scan + the asynchronous read-back of {R, prefilter trap}; no host sync.
-static int geometry_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
-                            const float* shs, const float* colors_precomp, const float* opacities,
-                            const float* scales, const float* rotations, const float* cov3D_precomp,
-                            void* geom_buf, int32_t* radii, int64_t* num_rendered, bool defer_scan = false) {
+// (of `fb` the geometry buffer and radii; defer_scan: the scan is left to the depth sort of the render_enqueue that follows)
+static int geometry_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const ggd_inputs& in, const ggd_frame_bufs& fb,
+                            int64_t* num_rendered, bool defer_scan) {
   (void)hipGetLastError();   // a sticky error another library left in this thread is not ours to report
   int rc = check_params(ctx, prm);
   if (rc != GGD_OK) return rc;
-  rc = check_inputs(ctx, prm, means3D, shs, colors_precomp, scales, rotations, cov3D_precomp);
+  rc = check_inputs(ctx, prm, in);
   if (rc != GGD_OK) return rc;
   if (!num_rendered) return ggd_fail(ctx, GGD_E_INVALID, "num_rendered is NULL");
   *num_rendered = 0;
   frame_renew(ctx);            // whatever an earlier frame left -- one that failed half way too -- ends here
   ggd_frame& fr = ctx->frame;
   if (prm->P == 0) return GGD_OK;
-  if (!geom_buf || !radii || !opacities) return ggd_fail(ctx, GGD_E_INVALID, "geom_buf / radii / opacities is NULL");
-  if (prm->raw_attributes && cov3D_precomp)
+  if (!fb.geom_buf || !fb.radii || !in.opacities) return ggd_fail(ctx, GGD_E_INVALID, "geom_buf / radii / opacities is NULL");
+  if (prm->raw_attributes && in.cov3D_precomp)
     return ggd_fail(ctx, GGD_E_INVALID, "raw_attributes needs scales/rotations (no cov3D_precomp)");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const geom_ptrs g = geom_view(prm, geom_buf);
+  const geom_ptrs g = geom_view(prm, fb.geom_buf);
 
   rc = ggd_reserve_scratch(ctx, ggd_scan_tmp_bytes(prm->P), s);
   if (rc != GGD_OK) return rc;
@@ -403,8 +408,7 @@ static int geometry_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, c
   {
     StageTimer t(ctx, ST_PREPROCESS, s);
     const bool old_ctl = !fr.geom.folded && ctx->sortctl;
-    rc = ggd_launch_preprocess(ctx, s, *prm, means3D, shs, colors_precomp, opacities, scales, rotations,
-                               cov3D_precomp, g.splat, g.tiles, shs ? g.clamped : nullptr, radii, g.depth_keys, g.rect,
+    rc = ggd_launch_preprocess(ctx, s, *prm, in, g.splat, g.tiles, in.shs ? g.clamped : nullptr, fb.radii, g.depth_keys, g.rect,
                                ctx->d_words + 1, old_ctl ? ctx->sortctl : nullptr, old_ctl ? (int)ggd_sort_ctrl_words() : 0,
                                fr.geom.folded ? &fold : nullptr);
     if (rc != GGD_OK) { ctx->fold_poisoned = fr.geom.folded; return rc; }
@@ -493,10 +497,29 @@ extern "C" int ggd_forward_geometry(ggd_ctx* ctx, void* stream, const ggd_params
                                     const float* scales, const float* rotations, const float* cov3D_precomp,
                                     void* geom_buf, int32_t* radii, int64_t* num_rendered) {
   if (ctx && ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, kPendingMsg);
-  const int rc = geometry_enqueue(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations,
-                                  cov3D_precomp, geom_buf, radii, num_rendered);
+  const ggd_inputs in = {.means3D = means3D, .shs = shs, .colors_precomp = colors_precomp, .opacities = opacities,
+                         .scales = scales, .rotations = rotations, .cov3D_precomp = cov3D_precomp};
+  const ggd_frame_bufs fb = {.geom_buf = geom_buf, .radii = radii};
+  const int rc = geometry_enqueue(ctx, stream, prm, in, fb, num_rendered, false);
   if (rc != GGD_OK || prm->P == 0) return rc;
   return geometry_finish(ctx, stream, prm, num_rendered);
+}
+
+// The scratch of binning path 1: [four pair arrays | the depth sort's tmp, alive through the binning pass | the row binning's tmp | msd table]
+struct sort_bin_scratch { uint32_t *ka, *va, *kb, *vb; void* sort_tmp; size_t sort_tmp_bytes; void* bin_tmp; size_t bin_tmp_bytes; uint32_t* msd_table; };
+static int reserve_sort_bin_scratch(ggd_ctx* ctx, hipStream_t s, const ggd_params* prm, uint32_t capacity, bool msd,
+                                    sort_bin_scratch* out) {
+  const size_t pairs = ggd_align((size_t)prm->P * sizeof(uint32_t));
+  out->sort_tmp_bytes = ggd_sort32_tmp_bytes(prm->P);
+  out->bin_tmp_bytes = ggd_rowbin_tmp_bytes(prm->P, capacity, prm->width, prm->height);
+  const size_t msd_tab = msd ? ggd_sort32_msd_table_bytes(prm->P) : 0;
+  const int rc = ggd_reserve_scratch(ctx, 4 * pairs + out->sort_tmp_bytes + out->bin_tmp_bytes + msd_tab, s);
+  if (rc != GGD_OK) return rc;
+  char* next = static_cast<char*>(ctx->scratch);
+  const auto take = [&next](size_t bytes) { uint32_t* p = reinterpret_cast<uint32_t*>(next); next += bytes; return p; };
+  out->ka = take(pairs); out->va = take(pairs); out->kb = take(pairs); out->vb = take(pairs);
+  out->sort_tmp = take(out->sort_tmp_bytes); out->bin_tmp = take(out->bin_tmp_bytes); out->msd_table = take(msd_tab);
+  return GGD_OK;
 }
 
 // Binning path 1: depth-sort the Gaussians once (32-bit keys), then one stable row / column binning pass.  speculative: the true
@@ -511,19 +534,9 @@ static int sort_depth_and_bin_tiles(ggd_ctx* ctx, hipStream_t s, const ggd_param
   // falls back to the memset)
   uint32_t* clean_ctl = fr.geom.sortctl_clean ? ctx->sortctl : nullptr;
   fr.geom = {};
-  const size_t pairs = ggd_align((size_t)prm->P * sizeof(uint32_t));
-  const size_t sort_tmp = ggd_sort32_tmp_bytes(prm->P);
-  const size_t bin_tmp = ggd_rowbin_tmp_bytes(prm->P, capacity, prm->width, prm->height);
-  const size_t msd_tab = msd ? ggd_sort32_msd_table_bytes(prm->P) : 0;
-  int rc = ggd_reserve_scratch(ctx, 4 * pairs + sort_tmp + bin_tmp + msd_tab, s);
+  sort_bin_scratch w;
+  int rc = reserve_sort_bin_scratch(ctx, s, prm, capacity, msd, &w);
   if (rc != GGD_OK) return rc;
-  char* sc = static_cast<char*>(ctx->scratch);
-  uint32_t* ka = reinterpret_cast<uint32_t*>(sc);
-  uint32_t* va = reinterpret_cast<uint32_t*>(sc + pairs);
-  uint32_t* kb = reinterpret_cast<uint32_t*>(sc + 2 * pairs);
-  uint32_t* vb = reinterpret_cast<uint32_t*>(sc + 3 * pairs);
-  void* tmp = sc + 4 * pairs;
-  void* bin_tmp_ptr = sc + 4 * pairs + sort_tmp;  // the sort's histogram block stays alive for the binning pass
   ggd_scan_piggy pg;          // a scan that rides on this call's launches (see geometry_enqueue)
   ggd_fold fold;              // the folded front end's control block, if this call has one
   const uint32_t *n_vis_ptr = nullptr, *flat_ptr = nullptr;   // device words: kept keys, "last pass was flat"
@@ -555,9 +568,8 @@ static int sort_depth_and_bin_tiles(ggd_ctx* ctx, hipStream_t s, const ggd_param
     if (msd) {
       // counted level 1: the finish launch also fills the row tables in the binning's scratch (narrow grids; GGD_OPT_L1_COUNTED)
       counted = ctx->opt[GGD_OPT_L1_COUNTED] != 0 && narrow;
-      const ggd_l1_counted l1c = ggd_rowbin_counted(bin_tmp_ptr, g.rect, prm->P, capacity, prm->width, prm->height);
-      rc = ggd_launch_sort32_msd(ctx, s, g.depth_keys, ka, va, kb, vb, prm->P,
-                                 reinterpret_cast<uint32_t*>(sc + 4 * pairs + sort_tmp + bin_tmp), &pg, &fold,
+      const ggd_l1_counted l1c = ggd_rowbin_counted(w.bin_tmp, g.rect, prm->P, capacity, prm->width, prm->height);
+      rc = ggd_launch_sort32_msd(ctx, s, g.depth_keys, w.ka, w.va, w.kb, w.vb, prm->P, w.msd_table, &pg, &fold,
                                  counted ? &l1c : nullptr);
     } else {
       ggd_sort32_opts so;
@@ -567,24 +579,25 @@ static int sort_depth_and_bin_tiles(ggd_ctx* ctx, hipStream_t s, const ggd_param
       so.flag_flat_last = true;
       so.apply_here = false;             // the offsets are left to the binning's last launch
       so.skip_last = fr.three_passes;
-      rc = ggd_launch_sort32_iota(ctx, s, g.depth_keys, ka, va, kb, vb, prm->P, 32, tmp, sort_tmp, so);
+      rc = ggd_launch_sort32_iota(ctx, s, g.depth_keys, w.ka, w.va, w.kb, w.vb, prm->P, 32, w.sort_tmp, w.sort_tmp_bytes, so);
     }
     if (rc != GGD_OK) return rc;
     fr.r_pending = riding;
-    const ggd_sort_ctl sc = ggd_sort_ctl::select(tmp, clean_ctl, folded ? fold.ctl : nullptr);
+    const ggd_sort_ctl sc = ggd_sort_ctl::select(w.sort_tmp, clean_ctl, folded ? fold.ctl : nullptr);
     n_vis_ptr = sc.n_valid; flat_ptr = sc.flat;
   }
   StageTimer t(ctx, ST_DUPLICATE, s);
   // the depth sort dropped the culled Gaussians (key 0xFFFFFFFF) and left the number of kept ones on the device
-  const bool l1 = folded && narrow;
-  bool scan_in_scatter = false;
-  rc = ggd_launch_rowbin(ctx, s, *prm, g.rect, va, n_vis_ptr, list, ranges, capacity, bin_tmp_ptr, bin_tmp, vb,
-                         flat_ptr, riding ? &pg : nullptr, l1 ? ggd_fold_rowtot(fold.ctl) : nullptr,
-                         l1 ? ggd_fold_l1_status(fold.ctl, prm->P) : nullptr, l1 ? ggd_fold_rowinst(fold.ctl, prm->P) : nullptr,
-                         &scan_in_scatter, counted ? ggd_sort_ctl::in_fold(fold.ctl).ghist : nullptr);
-  if (scan_in_scatter) ++ctx->scan_in_scatter_frames;
-  if (counted && rc == GGD_OK) ++ctx->l1_counted_frames;
-  return rc;
+  ggd_rowbin_opts ro = {.order_alt = w.vb, .use_alt = flat_ptr, .apply = riding ? &pg : nullptr};
+  if (folded && narrow)   // level 1 in one launch
+    ro.fold = {.rowtot = ggd_fold_rowtot(fold.ctl), .status1 = ggd_fold_l1_status(fold.ctl, prm->P),
+               .rowinst = ggd_fold_rowinst(fold.ctl, prm->P)};
+  if (counted) ro.counted_hist = ggd_sort_ctl::in_fold(fold.ctl).ghist;
+  const ggd_rowbin_result rb = ggd_launch_rowbin(ctx, s, *prm, g.rect, w.va, n_vis_ptr, list, ranges, capacity, w.bin_tmp,
+                                                 w.bin_tmp_bytes, ro);
+  if (rb.scan_in_scatter) ++ctx->scan_in_scatter_frames;
+  if (counted && rb.rc == GGD_OK) ++ctx->l1_counted_frames;
+  return rb.rc;
 }
 
 // Binning path 2 (GGD_OPT_BINNING = 0, the debug taps, grids beyond 255 x 255 tiles, R = 0): one (tile | depth) key per instance,
@@ -620,22 +633,20 @@ static int duplicate_sort_ranges(ggd_ctx* ctx, hipStream_t s, const ggd_params* 
   return ggd_launch_ranges(ctx, s, b.keys, R, ranges, T);
 }
 
-// layout_R: what binning_buf was laid out for; R: number of instances to process (== layout_R unless the caller
-// over-allocated).  speculative: R is only a CAPACITY (the true num_rendered is still on the device); only the tile-binning
-// path can run that way.  out_depth / out_alpha (both or neither): the depth / alpha planes of the *_aux entry points
-static int render_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const void* geom_buf, int64_t layout_R,
-                          int64_t R, void* binning_buf, void* img_buf, float* out_color, bool speculative,
-                          float* out_depth = nullptr, float* out_alpha = nullptr) {
+// R: number of instances to process (<= fb.capacity; equal unless the caller over-allocated).  speculative: R is only a CAPACITY
+// (the true num_rendered is still on the device); only the tile-binning path can run that way
+static int render_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const ggd_frame_bufs& fb, int64_t R,
+                          bool speculative) {
   (void)hipGetLastError();   // a sticky error another library left in this thread is not ours to report
   int rc = check_params(ctx, prm);
   if (rc != GGD_OK) return rc;
   if (R < 0) return ggd_fail(ctx, GGD_E_INVALID, "num_rendered < 0");
-  if (!img_buf || !out_color) return ggd_fail(ctx, GGD_E_INVALID, "img_buf / out_color is NULL");
-  if (R > 0 && (!geom_buf || !binning_buf)) return ggd_fail(ctx, GGD_E_INVALID, "geom_buf / binning_buf is NULL");
+  if (!fb.img_buf || !fb.out_color) return ggd_fail(ctx, GGD_E_INVALID, "img_buf / out_color is NULL");
+  if (R > 0 && (!fb.geom_buf || !fb.binning_buf)) return ggd_fail(ctx, GGD_E_INVALID, "geom_buf / binning_buf is NULL");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const geom_ptrs g = geom_view(prm, geom_buf);
-  const binning_ptrs b = binning_view(layout_R, binning_buf);
-  const img_ptrs im = img_view(prm->width, prm->height, img_buf);
+  const geom_ptrs g = geom_view(prm, fb.geom_buf);
+  const binning_ptrs b = binning_view(fb.capacity, fb.binning_buf);
+  const img_ptrs im = img_view(prm->width, prm->height, fb.img_buf);
   const bool tiles = use_tile_binning(ctx, prm, R);
   if (speculative && !tiles) return ggd_fail(ctx, GGD_E_INVALID, "speculative render needs the tile-binning path");
   const uint32_t capacity = R > 0xffffffffll ? 0xffffffffu : (uint32_t)R;
@@ -643,15 +654,17 @@ static int render_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, con
                         : duplicate_sort_ranges(ctx, s, prm, g, b, im.ranges, R);
   if (rc != GGD_OK) return rc;
   StageTimer t(ctx, ST_BLEND, s);
-  return ggd_launch_blend(ctx, s, *prm, g.splat, b.list, im.ranges, capacity, out_color, im.final_T, im.n_contrib, g.depth_keys,
-                          out_depth, out_alpha);
+  return ggd_launch_blend(ctx, s, *prm, g.splat, b.list, im.ranges, capacity, fb.out_color, im.final_T, im.n_contrib, g.depth_keys,
+                          fb.out_depth, fb.out_alpha);
 }
 
 extern "C" int ggd_forward_render(ggd_ctx* ctx, void* stream, const ggd_params* prm, const void* geom_buf,
                                   int64_t R, void* binning_buf, void* img_buf, float* out_color) {
   // (another forward would begin a new ctx->frame: the pending one's missed speculation would never be rendered again)
   if (ctx && ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, kPendingMsg);
-  return render_enqueue(ctx, stream, prm, geom_buf, R, R, binning_buf, img_buf, out_color, false);
+  const ggd_frame_bufs fb = {.geom_buf = const_cast<void*>(geom_buf), .binning_buf = binning_buf, .capacity = R,   // (laid out for R)
+                             .img_buf = img_buf, .out_color = out_color};
+  return render_enqueue(ctx, stream, prm, fb, R, false);
 }
 
 static int check_aux_planes(ggd_ctx* ctx, const float* out_depth, const float* out_alpha) {
@@ -666,7 +679,9 @@ extern "C" int ggd_forward_render_aux(ggd_ctx* ctx, void* stream, const ggd_para
   const int rc = check_aux_planes(ctx, out_depth, out_alpha);
   if (rc != GGD_OK) return rc;
   if (ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, kPendingMsg);
-  return render_enqueue(ctx, stream, prm, geom_buf, R, R, binning_buf, img_buf, out_color, false, out_depth, out_alpha);
+  const ggd_frame_bufs fb = {.geom_buf = const_cast<void*>(geom_buf), .binning_buf = binning_buf, .capacity = R,
+                             .img_buf = img_buf, .out_color = out_color, .out_depth = out_depth, .out_alpha = out_alpha};
+  return render_enqueue(ctx, stream, prm, fb, R, false);
 }
 
 extern "C" int ggd_forward_can_speculate(ggd_ctx* ctx, const ggd_params* prm, int64_t capacity) {
@@ -675,60 +690,44 @@ extern "C" int ggd_forward_can_speculate(ggd_ctx* ctx, const ggd_params* prm, in
 
 // The speculative route of the single-call forward in its two halves: everything is enqueued before the host looks at
 // num_rendered (the GPU never idles on that read-back) ...
-static int forward_spec_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D, const float* shs,
-                                const float* colors_precomp, const float* opacities, const float* scales,
-                                const float* rotations, const float* cov3D_precomp, void* geom_buf, int32_t* radii,
-                                void* binning_buf, int64_t capacity, void* img_buf, float* out_color, int64_t* num_rendered,
-                                float* out_depth = nullptr, float* out_alpha = nullptr) {
-  int rc = geometry_enqueue(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations,
-                            cov3D_precomp, geom_buf, radii, num_rendered, true);
+static int forward_spec_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const ggd_inputs& in, const ggd_frame_bufs& fb,
+                                int64_t* num_rendered) {
+  const int rc = geometry_enqueue(ctx, stream, prm, in, fb, num_rendered, true);
   if (rc != GGD_OK) return rc;
-  return render_enqueue(ctx, stream, prm, geom_buf, capacity, capacity, binning_buf, img_buf, out_color, true, out_depth,
-                        out_alpha);
+  return render_enqueue(ctx, stream, prm, fb, fb.capacity, true);
 }
 // ... and the collection of num_rendered and the frame's report once the launch that delivers them has run; binning and blend
 // may still be running.  A frame for which the short form of the sort did not hold is binned and blended again, in full.
-static int forward_spec_collect(ggd_ctx* ctx, void* stream, const ggd_params* prm, const void* geom_buf, void* binning_buf,
-                                int64_t capacity, void* img_buf, float* out_color, int64_t* num_rendered,
-                                float* out_depth = nullptr, float* out_alpha = nullptr) {
+static int forward_spec_collect(ggd_ctx* ctx, void* stream, const ggd_params* prm, const ggd_frame_bufs& fb,
+                                int64_t* num_rendered) {
   const int rc = geometry_finish(ctx, stream, prm, num_rendered);
   if (rc != GGD_OK) return rc;
   const ggd_frame done = frame_renew(ctx);   // (a re-render below is a frame of its own: nothing to ride on, nothing to collect)
-  const bool too_small = *num_rendered > capacity;
+  const bool too_small = *num_rendered > fb.capacity;
   const bool again = ctx->spec.observe(done.plan, done.three_passes, done.report, too_small);
   if (too_small)
     return ggd_fail(ctx, GGD_E_CAPACITY, "binning_buf capacity is below num_rendered: re-run with a larger buffer");
   if (!again) return GGD_OK;
-  return render_enqueue(ctx, stream, prm, geom_buf, capacity, *num_rendered, binning_buf, img_buf, out_color, false, out_depth,
-                        out_alpha);
+  return render_enqueue(ctx, stream, prm, fb, *num_rendered, false);
 }
 
-static int forward_single_call(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D, const float* shs,
-                               const float* colors_precomp, const float* opacities, const float* scales,
-                               const float* rotations, const float* cov3D_precomp, void* geom_buf, int32_t* radii,
-                               void* binning_buf, int64_t capacity, void* img_buf, float* out_color,
-                               int64_t* num_rendered, float* out_depth, float* out_alpha) {
-  if (capacity < 0) return ggd_fail(ctx, GGD_E_INVALID, "capacity < 0");
+static int forward_single_call(ggd_ctx* ctx, void* stream, const ggd_params* prm, const ggd_inputs& in, const ggd_frame_bufs& fb,
+                               int64_t* num_rendered) {
+  if (fb.capacity < 0) return ggd_fail(ctx, GGD_E_INVALID, "capacity < 0");
   if (ctx && ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, kPendingMsg);
-  if (prm && prm->P > 0 && capacity > 0 && ggd_forward_can_speculate(ctx, prm, capacity)) {
-    const int rc = forward_spec_enqueue(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations,
-                                        cov3D_precomp, geom_buf, radii, binning_buf, capacity, img_buf, out_color, num_rendered,
-                                        out_depth, out_alpha);
+  if (prm && prm->P > 0 && fb.capacity > 0 && ggd_forward_can_speculate(ctx, prm, fb.capacity)) {
+    const int rc = forward_spec_enqueue(ctx, stream, prm, in, fb, num_rendered);
     if (rc != GGD_OK) return rc;
-    return forward_spec_collect(ctx, stream, prm, geom_buf, binning_buf, capacity, img_buf, out_color, num_rendered, out_depth,
-                                out_alpha);
+    return forward_spec_collect(ctx, stream, prm, fb, num_rendered);
   }
-  int rc = geometry_enqueue(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations,
-                            cov3D_precomp, geom_buf, radii, num_rendered, false);
+  int rc = geometry_enqueue(ctx, stream, prm, in, fb, num_rendered, false);
   if (rc != GGD_OK) return rc;
-  if (prm->P == 0)
-    return render_enqueue(ctx, stream, prm, geom_buf, capacity, 0, binning_buf, img_buf, out_color, false, out_depth, out_alpha);
+  if (prm->P == 0) return render_enqueue(ctx, stream, prm, fb, 0, false);
   rc = geometry_finish(ctx, stream, prm, num_rendered);
   if (rc != GGD_OK) return rc;
-  if (*num_rendered > capacity)
+  if (*num_rendered > fb.capacity)
     return ggd_fail(ctx, GGD_E_CAPACITY, "binning_buf capacity is below num_rendered: re-run with a larger buffer");
-  return render_enqueue(ctx, stream, prm, geom_buf, capacity, *num_rendered, binning_buf, img_buf, out_color, false, out_depth,
-                        out_alpha);
+  return render_enqueue(ctx, stream, prm, fb, *num_rendered, false);
 }
 
 extern "C" int ggd_forward(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D, const float* shs,
@@ -736,8 +735,11 @@ extern "C" int ggd_forward(ggd_ctx* ctx, void* stream, const ggd_params* prm, co
                            const float* rotations, const float* cov3D_precomp, void* geom_buf, int32_t* radii,
                            void* binning_buf, int64_t capacity, void* img_buf, float* out_color,
                            int64_t* num_rendered) {
-  return forward_single_call(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                             geom_buf, radii, binning_buf, capacity, img_buf, out_color, num_rendered, nullptr, nullptr);
+  const ggd_inputs in = {.means3D = means3D, .shs = shs, .colors_precomp = colors_precomp, .opacities = opacities,
+                         .scales = scales, .rotations = rotations, .cov3D_precomp = cov3D_precomp};
+  const ggd_frame_bufs fb = {.geom_buf = geom_buf, .radii = radii, .binning_buf = binning_buf, .capacity = capacity,
+                             .img_buf = img_buf, .out_color = out_color};
+  return forward_single_call(ctx, stream, prm, in, fb, num_rendered);
 }
 
 extern "C" int ggd_forward_aux(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D, const float* shs,
@@ -747,8 +749,11 @@ extern "C" int ggd_forward_aux(ggd_ctx* ctx, void* stream, const ggd_params* prm
                                float* out_alpha, int64_t* num_rendered) {
   const int rc = check_aux_planes(ctx, out_depth, out_alpha);
   if (rc != GGD_OK) return rc;
-  return forward_single_call(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                             geom_buf, radii, binning_buf, capacity, img_buf, out_color, num_rendered, out_depth, out_alpha);
+  const ggd_inputs in = {.means3D = means3D, .shs = shs, .colors_precomp = colors_precomp, .opacities = opacities,
+                         .scales = scales, .rotations = rotations, .cov3D_precomp = cov3D_precomp};
+  const ggd_frame_bufs fb = {.geom_buf = geom_buf, .radii = radii, .binning_buf = binning_buf, .capacity = capacity,
+                             .img_buf = img_buf, .out_color = out_color, .out_depth = out_depth, .out_alpha = out_alpha};
+  return forward_single_call(ctx, stream, prm, in, fb, num_rendered);
 }
 
 extern "C" int ggd_forward_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D, const float* shs,
@@ -759,11 +764,14 @@ extern "C" int ggd_forward_enqueue(ggd_ctx* ctx, void* stream, const ggd_params*
   if (ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, "ggd_forward_enqueue: the previous frame of this context has not been collected");
   if (!prm || prm->P <= 0 || capacity <= 0 || !ggd_forward_can_speculate(ctx, prm, capacity))
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_forward_enqueue needs the tile-binning path, P > 0 and a capacity (ggd_forward_can_speculate)");
+  const ggd_inputs in = {.means3D = means3D, .shs = shs, .colors_precomp = colors_precomp, .opacities = opacities,
+                         .scales = scales, .rotations = rotations, .cov3D_precomp = cov3D_precomp};
+  const ggd_frame_bufs fb = {.geom_buf = geom_buf, .radii = radii, .binning_buf = binning_buf, .capacity = capacity,
+                             .img_buf = img_buf, .out_color = out_color};
   int64_t dummy = 0;
-  const int rc = forward_spec_enqueue(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations,
-                                      cov3D_precomp, geom_buf, radii, binning_buf, capacity, img_buf, out_color, &dummy);
+  const int rc = forward_spec_enqueue(ctx, stream, prm, in, fb, &dummy);
   if (rc != GGD_OK) return rc;
-  ctx->pending = {true, *prm, geom_buf, binning_buf, capacity, img_buf, out_color};
+  ctx->pending = {true, *prm, fb};
   return GGD_OK;
 }
 
@@ -771,33 +779,34 @@ extern "C" int ggd_forward_collect(ggd_ctx* ctx, void* stream, int64_t* num_rend
   if (!ctx || !num_rendered) return GGD_E_INVALID;
   if (!ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, "ggd_forward_collect: no frame is pending on this context");
   ctx->pending.valid = false;
-  return forward_spec_collect(ctx, stream, &ctx->pending.prm, ctx->pending.geom, ctx->pending.binning, ctx->pending.capacity,
-                              ctx->pending.img, ctx->pending.out, num_rendered);
+  return forward_spec_collect(ctx, stream, &ctx->pending.prm, ctx->pending.bufs, num_rendered);
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------
-static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
-                         const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
-                         const float* rotations, const float* cov3D_precomp, const int32_t* radii,
-                         const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
-                         const float* dL_dpix, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                         float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
-                         float* dL_drots, bool aux, const float* dL_ddepth, const float* dL_dalpha,
-                         bool abs = false, float* dL_dmeans2D_abs = nullptr) {
+// entry: which entry point called.  ggd_backward_aux always runs the depth / alpha (AUX) instances, with both of its gradients NULL
+// too; ggd_backward_abs the absgrad ones, with the depth / alpha terms exactly when one of the two gradients is given (without: the
+// plain backward's arithmetic).  radii and the three buffers are the forward's, R its num_rendered
+enum bwd_entry { BWD_PLAIN, BWD_AUX, BWD_ABS };
+static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, bwd_entry entry, const ggd_inputs& in,
+                         const int32_t* radii, const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
+                         const ggd_pix_grads& pix, const ggd_grads& out) {
   (void)hipGetLastError();   // a sticky error another library left in this thread is not ours to report
   int rc = check_params(ctx, prm);
   if (rc != GGD_OK) return rc;
-  rc = check_inputs(ctx, prm, means3D, shs, colors_precomp, scales, rotations, cov3D_precomp);
+  rc = check_inputs(ctx, prm, in);
   if (rc != GGD_OK) return rc;
   const int P = prm->P;
   if (P == 0) return GGD_OK;
-  if (!radii || !geom_buf || !img_buf || !dL_dpix || !dL_dmeans2D || !dL_dcolors || !dL_dopacity ||
-      !dL_dmeans3D || !dL_dcov3D || !dL_dscales || !dL_drots || (prm->M > 0 && !dL_dsh) || (R > 0 && !binning_buf))
+  if (!radii || !geom_buf || !img_buf || !pix.dL_dpix || !out.dL_dmeans2D || !out.dL_dcolors || !out.dL_dopacity ||
+      !out.dL_dmeans3D || !out.dL_dcov3D || !out.dL_dscales || !out.dL_drots || (prm->M > 0 && !out.dL_dsh) ||
+      (R > 0 && !binning_buf))
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward: NULL buffer");
-  if (abs && !dL_dmeans2D_abs) return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward_abs: NULL dL_dmeans2D_abs");
-  if (prm->raw_attributes && (!opacities || cov3D_precomp))
+  const bool abs = entry == BWD_ABS;
+  const bool aux = entry == BWD_AUX || (abs && (pix.dL_ddepth || pix.dL_dalpha));
+  if (abs && !out.dL_dmeans2D_abs) return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward_abs: NULL dL_dmeans2D_abs");
+  if (prm->raw_attributes && (!in.opacities || in.cov3D_precomp))
     return ggd_fail(ctx, GGD_E_INVALID, "raw_attributes needs opacities and scales/rotations (no cov3D_precomp)");
-  if (prm->antialiasing && !opacities)   // dL/dh of the opacity compensation is dL/do_eff times the opacity
+  if (prm->antialiasing && !in.opacities)   // dL/dh of the opacity compensation is dL/do_eff times the opacity
     return ggd_fail(ctx, GGD_E_INVALID, "antialiasing needs the opacities in the backward");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const geom_ptrs g = geom_view(prm, geom_buf);
@@ -811,24 +820,22 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, cons
   // the only zero-fill of the backward: the accumulator records.  Every caller array is written in full by the
   // per-Gaussian kernel, except the ones a mode never produces (kept zero like upstream's zero-initialised outputs).
   GGD_HIP(hipMemsetAsync(grad_acc, 0, acc_bytes, s));
-  if (cov3D_precomp) {
-    GGD_HIP(hipMemsetAsync(dL_dscales, 0, (size_t)P * 3 * sizeof(float), s));
-    GGD_HIP(hipMemsetAsync(dL_drots, 0, (size_t)P * 4 * sizeof(float), s));
+  if (in.cov3D_precomp) {
+    GGD_HIP(hipMemsetAsync(out.dL_dscales, 0, (size_t)P * 3 * sizeof(float), s));
+    GGD_HIP(hipMemsetAsync(out.dL_drots, 0, (size_t)P * 4 * sizeof(float), s));
   }
-  if (colors_precomp && prm->M > 0 && dL_dsh) GGD_HIP(hipMemsetAsync(dL_dsh, 0, (size_t)P * prm->M * 3 * sizeof(float), s));
+  if (in.colors_precomp && prm->M > 0 && out.dL_dsh)
+    GGD_HIP(hipMemsetAsync(out.dL_dsh, 0, (size_t)P * prm->M * 3 * sizeof(float), s));
 
   if (R > 0) {
     StageTimer t(ctx, ST_BLEND_BWD, s);
-    rc = ggd_launch_blend_backward(ctx, s, *prm, g.splat, b.list, im.ranges, im.final_T, im.n_contrib, dL_dpix, grad_acc, aux,
-                                   g.depth_keys, dL_ddepth, dL_dalpha, abs);
+    rc = ggd_launch_blend_backward(ctx, s, *prm, g.splat, b.list, im.ranges, im.final_T, im.n_contrib, pix, grad_acc, aux,
+                                   g.depth_keys, abs);
     if (rc != GGD_OK) return rc;
   }
   {
     StageTimer t(ctx, ST_PREPROCESS_BWD, s);
-    rc = ggd_launch_preprocess_backward(ctx, s, *prm, means3D, shs, colors_precomp, opacities, dL_dopacity, scales, rotations,
-                                        cov3D_precomp, radii, shs ? g.clamped : nullptr, grad_acc, dL_dmeans2D,
-                                        dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots, aux,
-                                        abs ? dL_dmeans2D_abs : nullptr);
+    rc = ggd_launch_preprocess_backward(ctx, s, *prm, in, radii, in.shs ? g.clamped : nullptr, grad_acc, out, aux);
     if (rc != GGD_OK) return rc;
   }
   return GGD_OK;
@@ -841,9 +848,13 @@ extern "C" int ggd_backward(ggd_ctx* ctx, void* stream, const ggd_params* prm, c
                             const float* dL_dpix, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
                             float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
                             float* dL_drots) {
-  return backward_impl(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii,
-                       geom_buf, binning_buf, img_buf, R, dL_dpix, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D,
-                       dL_dcov3D, dL_dsh, dL_dscales, dL_drots, false, nullptr, nullptr);
+  const ggd_inputs in = {.means3D = means3D, .shs = shs, .colors_precomp = colors_precomp, .opacities = opacities,
+                         .scales = scales, .rotations = rotations, .cov3D_precomp = cov3D_precomp};
+  const ggd_pix_grads pix = {.dL_dpix = dL_dpix};
+  const ggd_grads out = {.dL_dmeans2D = dL_dmeans2D, .dL_dcolors = dL_dcolors, .dL_dopacity = dL_dopacity,
+                         .dL_dmeans3D = dL_dmeans3D, .dL_dcov3D = dL_dcov3D, .dL_dsh = dL_dsh, .dL_dscales = dL_dscales,
+                         .dL_drots = dL_drots};
+  return backward_impl(ctx, stream, prm, BWD_PLAIN, in, radii, geom_buf, binning_buf, img_buf, R, pix, out);
 }
 
 extern "C" int ggd_backward_aux(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
@@ -853,13 +864,16 @@ extern "C" int ggd_backward_aux(ggd_ctx* ctx, void* stream, const ggd_params* pr
                                 const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, float* dL_dmeans2D,
                                 float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                                 float* dL_dscales, float* dL_drots) {
-  return backward_impl(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii,
-                       geom_buf, binning_buf, img_buf, R, dL_dpix, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D,
-                       dL_dcov3D, dL_dsh, dL_dscales, dL_drots, true, dL_ddepth, dL_dalpha);
+  const ggd_inputs in = {.means3D = means3D, .shs = shs, .colors_precomp = colors_precomp, .opacities = opacities,
+                         .scales = scales, .rotations = rotations, .cov3D_precomp = cov3D_precomp};
+  const ggd_pix_grads pix = {.dL_dpix = dL_dpix, .dL_ddepth = dL_ddepth, .dL_dalpha = dL_dalpha};
+  const ggd_grads out = {.dL_dmeans2D = dL_dmeans2D, .dL_dcolors = dL_dcolors, .dL_dopacity = dL_dopacity,
+                         .dL_dmeans3D = dL_dmeans3D, .dL_dcov3D = dL_dcov3D, .dL_dsh = dL_dsh, .dL_dscales = dL_dscales,
+                         .dL_drots = dL_drots};
+  return backward_impl(ctx, stream, prm, BWD_AUX, in, radii, geom_buf, binning_buf, img_buf, R, pix, out);
 }
 
-// the absgrad backward: ggd_backward_aux's arguments + dL_dmeans2D_abs; without dL_ddepth and dL_dalpha it is the plain
-// backward's arithmetic (the ABS instances), with either the depth / alpha backward's (AUX + ABS)
+// the absgrad backward: ggd_backward_aux's arguments + dL_dmeans2D_abs
 extern "C" int ggd_backward_abs(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
                                 const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
                                 const float* rotations, const float* cov3D_precomp, const int32_t* radii,
@@ -867,10 +881,13 @@ extern "C" int ggd_backward_abs(ggd_ctx* ctx, void* stream, const ggd_params* pr
                                 const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, float* dL_dmeans2D,
                                 float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                                 float* dL_dscales, float* dL_drots, float* dL_dmeans2D_abs) {
-  return backward_impl(ctx, stream, prm, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii,
-                       geom_buf, binning_buf, img_buf, R, dL_dpix, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D,
-                       dL_dcov3D, dL_dsh, dL_dscales, dL_drots, dL_ddepth || dL_dalpha, dL_ddepth, dL_dalpha, true,
-                       dL_dmeans2D_abs);
+  const ggd_inputs in = {.means3D = means3D, .shs = shs, .colors_precomp = colors_precomp, .opacities = opacities,
+                         .scales = scales, .rotations = rotations, .cov3D_precomp = cov3D_precomp};
+  const ggd_pix_grads pix = {.dL_dpix = dL_dpix, .dL_ddepth = dL_ddepth, .dL_dalpha = dL_dalpha};
+  const ggd_grads out = {.dL_dmeans2D = dL_dmeans2D, .dL_dcolors = dL_dcolors, .dL_dopacity = dL_dopacity,
+                         .dL_dmeans3D = dL_dmeans3D, .dL_dcov3D = dL_dcov3D, .dL_dsh = dL_dsh, .dL_dscales = dL_dscales,
+                         .dL_drots = dL_drots, .dL_dmeans2D_abs = dL_dmeans2D_abs};
+  return backward_impl(ctx, stream, prm, BWD_ABS, in, radii, geom_buf, binning_buf, img_buf, R, pix, out);
 }
 
 extern "C" int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D,

@@ -34,6 +34,28 @@ constexpr int GGD_STATS_MAX_WAVES = 1 << 17;
 // (two-launch depth sort: described at ggd_fold below; GGD_MSD_BINS / CAP / MAX_TILES are in ggd_binning_layout.h, the constants
 // the host's policy needs in ggd_spec.h)
 
+// One frame's arguments as the entry points of the C ABI receive them, in four groups: each entry point of ggd_capi.hip fills them
+// once, field by name, and everything below it -- the host functions there, the launchers declared at the end of this file -- takes
+// the groups.  Host only: no kernel receives one.  Every field has a default: a group filled in part is well defined.
+struct ggd_inputs {       // [P, ...] fp32 each; which may be NULL: check_inputs (ggd_capi.hip)
+  const float *means3D = nullptr, *shs = nullptr, *colors_precomp = nullptr, *opacities = nullptr;
+  const float *scales = nullptr, *rotations = nullptr, *cov3D_precomp = nullptr;
+};
+struct ggd_frame_bufs {   // the caller's buffers of one forward frame
+  void* geom_buf = nullptr; int32_t* radii = nullptr;
+  void* binning_buf = nullptr; int64_t capacity = 0;   // capacity: instances binning_buf was laid out for (ggd_binning_layout), >= the R processed
+  void* img_buf = nullptr;
+  float *out_color = nullptr, *out_depth = nullptr, *out_alpha = nullptr;   // depth / alpha: the *_aux entry points' planes (both or neither)
+};
+struct ggd_pix_grads {    // the backward's incoming gradients: [3, H, W] and, NULL = zero, [H, W] each
+  const float *dL_dpix = nullptr, *dL_ddepth = nullptr, *dL_dalpha = nullptr;
+};
+struct ggd_grads {        // the backward's results, each written in full by the library
+  float *dL_dmeans2D = nullptr, *dL_dcolors = nullptr, *dL_dopacity = nullptr, *dL_dmeans3D = nullptr, *dL_dcov3D = nullptr;
+  float *dL_dsh = nullptr, *dL_dscales = nullptr, *dL_drots = nullptr;
+  float* dL_dmeans2D_abs = nullptr;   // ggd_backward_abs only: [P, 3] = (accumulator slots GGD_ACC_ABS, 0), zeros for culled Gaussians
+};
+
 // The frame in flight: what geometry_enqueue leaves for render_enqueue, and render_enqueue for the collection of num_rendered.
 // A frame begins in geometry_enqueue, which assigns a fresh one (only the tag carries over); nothing else clears these.
 struct ggd_frame {
@@ -74,8 +96,7 @@ struct ggd_ctx {
   ggd_spec spec;                    // cross-frame speculation policy: three sort passes / the two-launch sort (ggd_spec.h)
   ggd_frame frame;                  // the one frame in flight
   // ggd_forward_enqueue ... ggd_forward_collect: the frame whose num_rendered has not been collected yet
-  struct { bool valid = false; ggd_params prm; const void* geom = nullptr; void* binning = nullptr; int64_t capacity = 0;
-           void* img = nullptr; float* out = nullptr; } pending;
+  struct { bool valid = false; ggd_params prm; ggd_frame_bufs bufs; } pending;
   void* gelu_tables = nullptr;      // GELU / GELU' interpolation tables of the reference-precision decoder kernels (built on first use)
   void *dbg_keys = nullptr, *dbg_vals = nullptr;   // debug copy of the unsorted list
   size_t dbg_cap = 0;
@@ -198,10 +219,8 @@ static inline void ggd_dispatch(int v, F&& f) {
 }
 
 // ---- kernels launched by the C API (defined in the .hip files) ------------------------------------------------
-int ggd_launch_preprocess(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const float* means3D,
-                          const float* shs, const float* colors_precomp, const float* opacities,
-                          const float* scales, const float* rotations, const float* cov3D_precomp,
-                          ggd_splat* splat, uint32_t* tiles_touched, uint8_t* clamped, int32_t* radii,
+int ggd_launch_preprocess(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_inputs& in, ggd_splat* splat,
+                          uint32_t* tiles_touched, uint8_t* clamped, int32_t* radii,
                           uint32_t* depth_keys, uint2* rect, uint32_t* trap_flag, uint32_t* zero_ptr = nullptr,
                           int zero_words = 0,    // zero_words words at zero_ptr are cleared by the first workgroups
                           const ggd_fold* fold = nullptr);
@@ -269,20 +288,22 @@ static inline ggd_l1_counted ggd_rowbin_counted(void* tmp, const uint2* rect, in
   c.chunks = rb_blocks1(P);
   return c;
 }
-int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const uint2* rect, const uint32_t* order,
-                      const uint32_t* n_vis_ptr, uint32_t* list, uint32_t* ranges, uint32_t capacity, void* tmp,
-                      size_t tmp_bytes, const uint32_t* order_alt = nullptr, const uint32_t* use_alt = nullptr,
-                      const ggd_scan_piggy* apply = nullptr, const uint32_t* fold_rowtot = nullptr, uint32_t* fold_status1 = nullptr,
-                      const uint32_t* fold_rowinst = nullptr, bool* scan_in_scatter = nullptr,
-                      const uint32_t* counted_hist = nullptr);   // apply: step 3 of a riding scan, as appended workgroups of the
-                                                                 // last (longest) binning launch
-                      // *use_alt != 0 (device): the depth order is in order_alt (see ggd_launch_sort32_iota)
-                      // fold_rowtot / fold_status1 (folded front end, grids of <= 64 x 64 tiles): the entries per tile row were
-                      // counted by the preprocess kernel -- level 1 is ONE launch (count, look-back over the chunks, scatter)
-                      // fold_rowinst (with them): so were the instances per tile row -- level 2 is count + scatter, the scatter
-                      // workgroups form their tile starts themselves (no scan launch); *scan_in_scatter reports that this form ran
-                      // counted_hist (with fold_rowtot; grids of <= 64 x 64 tiles): the two-launch sort's bucket histogram -- its
-                      // finish launch was given ggd_rowbin_counted(tmp, ...) and level 1 runs without its look-back
+struct ggd_rowbin_opts {
+  const uint32_t *order_alt = nullptr, *use_alt = nullptr;   // *use_alt != 0 (device): the depth order is in order_alt (ggd_launch_sort32_iota)
+  const ggd_scan_piggy* apply = nullptr; // step 3 of a riding scan, as appended workgroups of the last (longest) binning launch
+  // folded front end, grids of <= 64 x 64 tiles (all three or none): the preprocess kernel counted the entries per tile row -- level 1 is
+  // ONE launch (count, look-back, scatter) -- and the instances per tile row -- level 2's scatter forms its tile starts itself (no scan launch)
+  struct { const uint32_t* rowtot = nullptr; uint32_t* status1 = nullptr; const uint32_t* rowinst = nullptr; } fold;   // ggd_fold_rowtot, ..
+  const uint32_t* counted_hist = nullptr;   // (with fold; grids of <= 64 x 64 tiles) the two-launch sort's bucket histogram -- its finish
+                                            // launch was given ggd_rowbin_counted(tmp, ...) and level 1 runs without its look-back
+};
+struct ggd_rowbin_result {
+  int rc = GGD_OK;
+  bool scan_in_scatter = false;   // level 2 ran without its scan launch
+};
+ggd_rowbin_result ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const uint2* rect, const uint32_t* order,
+                                    const uint32_t* n_vis_ptr, uint32_t* list, uint32_t* ranges, uint32_t capacity, void* tmp,
+                                    size_t tmp_bytes, const ggd_rowbin_opts& opts = ggd_rowbin_opts());
 int ggd_launch_ranges(ggd_ctx* ctx, hipStream_t s, const uint64_t* keys, int64_t n, uint32_t* ranges, int T);
 // out_depth / out_alpha non-null (both): the depth / alpha extension (blend_forward_kernel<..., AUX>), which also reads
 // depth_keys (the geometry buffer's: the fp32 bits of each Gaussian's view-space depth)
@@ -298,23 +319,17 @@ constexpr int GGD_ACC_CONIC = 0, GGD_ACC_OPACITY = 3, GGD_ACC_MEAN2D = 4, GGD_AC
 constexpr int GGD_ACC_DEPTH = 9;     // dL/dz (view-space depth), written only by the depth / alpha backward
 constexpr int GGD_ACC_ABS = 10;      // sum over pixels of |d/d mean2D x|, |.. y| (slots 10, 11), written only by an absgrad backward
 // aux: the depth / alpha backward (blend_backward_quarter_kernel<..., AUX>, always the quarter form); depth_keys as in
-// ggd_launch_blend, dL_ddepth / dL_dalpha [H, W] (NULL = zero).  abs: the absolute screen-space gradient sums as well (slots
-// GGD_ACC_ABS; quarter form only, with or without aux)
+// ggd_launch_blend, pix.dL_ddepth / pix.dL_dalpha [H, W] (NULL = zero; read only when aux).  abs: the absolute screen-space
+// gradient sums as well (slots GGD_ACC_ABS; quarter form only, with or without aux)
 int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
                               const uint32_t* list, const uint32_t* ranges, const float* final_T,
-                              const uint32_t* n_contrib, const float* dL_dpix, float* grad_acc /*[P][GGD_ACC_FLOATS]*/,
-                              bool aux = false, const uint32_t* depth_keys = nullptr, const float* dL_ddepth = nullptr,
-                              const float* dL_dalpha = nullptr, bool abs = false);
+                              const uint32_t* n_contrib, const ggd_pix_grads& pix, float* grad_acc /*[P][GGD_ACC_FLOATS]*/,
+                              bool aux, const uint32_t* depth_keys, bool abs);
 // aux: also adds dL/dz (accumulator slot GGD_ACC_DEPTH) times dz/dmean = (view[2], view[6], view[10]) to dL_dmeans3D
-// dL_dmean2D_abs (NULL = not wanted): [P, 3] = (accumulator slots GGD_ACC_ABS, 0), zeros for culled Gaussians
-int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const float* means3D,
-                                   const float* shs, const float* colors_precomp, const float* opacities,
-                                   float* dL_dopacity, const float* scales,
-                                   const float* rotations, const float* cov3D_precomp, const int32_t* radii,
-                                   const uint8_t* clamped, const float* grad_acc, float* dL_dmean2D,
-                                   float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                                   float* dL_dscales, float* dL_drots, bool aux = false,
-                                   float* dL_dmean2D_abs = nullptr);
+// out.dL_dmeans2D_abs non-null: the absgrad kernels, which write it too
+int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_inputs& in,
+                                   const int32_t* radii, const uint8_t* clamped, const float* grad_acc, const ggd_grads& out,
+                                   bool aux);
 
 // ---- device helpers -----------------------------------------------------------------------------------------
 #ifdef __HIPCC__

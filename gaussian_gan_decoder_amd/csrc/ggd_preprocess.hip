@@ -418,11 +418,8 @@ __global__ __launch_bounds__(256) void mark_visible_kernel(int P, const float* _
 
 }  // namespace
 
-int ggd_launch_preprocess(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const float* means3D,
-                          const float* shs, const float* colors_precomp, const float* opacities,
-                          const float* scales, const float* rotations, const float* cov3D_precomp,
-                          ggd_splat* splat, uint32_t* tiles_touched, uint8_t* clamped, int32_t* radii,
-                          uint32_t* depth_keys, uint2* rect, uint32_t* trap_flag, uint32_t* zero_ptr, int zero_words,
+int ggd_launch_preprocess(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_inputs& in, ggd_splat* splat,
+                          uint32_t* tiles_touched, uint8_t* clamped, int32_t* radii, uint32_t* depth_keys, uint2* rect, uint32_t* trap_flag, uint32_t* zero_ptr, int zero_words,
                           const ggd_fold* fold) {
   if (prm.P == 0) return GGD_OK;
   // persistent grid: GGD_PREPROCESS_WGS_PER_CU workgroups per compute unit stride over the 256-Gaussian
@@ -430,7 +427,7 @@ int ggd_launch_preprocess(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, co
   const int tiles = (prm.P + 255) / 256;
   const int want = ctx->opt[GGD_OPT_PREPROCESS_WGS] > 0 ? ctx->opt[GGD_OPT_PREPROCESS_WGS] : GGD_PREPROCESS_WGS_PER_CU * ctx->cus;
   const int grid = min(tiles, max(want, 1));
-  const bool shvec = !colors_precomp && prm.M > 1 && prm.M <= 16 && ((3 * prm.M) & 3) == 0;
+  const bool shvec = !in.colors_precomp && prm.M > 1 && prm.M <= 16 && ((3 * prm.M) & 3) == 0;
   const ggd_fold f = fold ? *fold : ggd_fold{};
   // focal lengths: wave-uniform correctly rounded divisions, done once here (same fp32 expression, same result)
   const float fx = (float)prm.width / (2.0f * prm.tanfovx), fy = (float)prm.height / (2.0f * prm.tanfovy);
@@ -439,8 +436,8 @@ int ggd_launch_preprocess(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, co
   a.tanfovx = prm.tanfovx; a.tanfovy = prm.tanfovy; a.fx = fx; a.fy = fy; a.mod = prm.scale_modifier;
   a.prefiltered = prm.prefiltered; a.raw = prm.raw_attributes;
   a.view = prm.viewmatrix; a.proj = prm.projmatrix; a.campos = prm.campos;
-  a.means3D = means3D; a.shs = shs; a.colors_precomp = colors_precomp; a.opacities = opacities; a.scales = scales;
-  a.rotations = rotations; a.cov3D_precomp = cov3D_precomp;
+  a.means3D = in.means3D; a.shs = in.shs; a.colors_precomp = in.colors_precomp; a.opacities = in.opacities; a.scales = in.scales;
+  a.rotations = in.rotations; a.cov3D_precomp = in.cov3D_precomp;
   a.splat = splat; a.tiles_touched = tiles_touched; a.clamped = clamped; a.radii = radii; a.depth_keys = depth_keys; a.rect = rect;
   a.trap_flag = trap_flag; a.zero_ptr = zero_ptr; a.zero_words = zero_ptr ? zero_words : 0;
   a.fold = f;

@@ -445,16 +445,12 @@ __global__ __launch_bounds__(256) void preprocess_abs_backward_staged_kernel(GGD
 
 }  // namespace
 
-int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const float* means3D,
-                                   const float* shs, const float* colors_precomp, const float* opacities,
-                                   float* dL_dopacity, const float* scales,
-                                   const float* rotations, const float* cov3D_precomp, const int32_t* radii,
-                                   const uint8_t* clamped, const float* grad_acc, float* dL_dmean2D,
-                                   float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                                   float* dL_dscales, float* dL_drots, bool aux, float* dL_dmean2D_abs) {
+int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_inputs& in,
+                                   const int32_t* radii, const uint8_t* clamped, const float* grad_acc, const ggd_grads& out,
+                                   bool aux) {
   if (prm.P == 0) return GGD_OK;
   // the staged form whenever there is more than the band-0 coefficient per channel (and room: 256 rows of 3 M + 1 floats)
-  const bool staged = !colors_precomp && prm.M > 1 && (size_t)256 * (3 * prm.M + 1) * sizeof(float) <= 64 * 1024;
+  const bool staged = !in.colors_precomp && prm.M > 1 && (size_t)256 * (3 * prm.M + 1) * sizeof(float) <= 64 * 1024;
   // rows that are a multiple of 16 bytes (M = 4, 8, 12, 16): read and written from registers with dwordx4 accesses (145 us
   // at M = 16, 1 M Gaussians; the LDS-staged form measures 152 with the same loads and is kept for the other M)
   const bool shvec = staged && prm.M <= 16 && ((3 * prm.M) & 3) == 0;
@@ -463,23 +459,23 @@ int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params
   ggd_dispatch<2>(prm.antialiasing != 0, [&](auto aa) {
     ggd_dispatch<2>(aux, [&](auto ax) {
       constexpr bool AA = decltype(aa)::value != 0, AUX = decltype(ax)::value != 0;
-      if (dL_dmean2D_abs) {   // the absgrad kernels: one more argument
+      if (out.dL_dmeans2D_abs) {   // the absgrad kernels: one more argument
         const auto kernel = shvec ? preprocess_abs_backward_vec_kernel<AA, AUX>
                           : staged ? preprocess_abs_backward_staged_kernel<false, AA, AUX> : preprocess_abs_backward_kernel<AA, AUX>;
         hipLaunchKernelGGL(kernel, dim3((prm.P + 255) / 256), dim3(256), lds, s, prm.P, prm.M, prm.sh_degree, prm.width,
-                           prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier, prm.raw_attributes, opacities, dL_dopacity,
-                           prm.viewmatrix, prm.projmatrix, prm.campos, means3D, shs, colors_precomp, scales, rotations,
-                           cov3D_precomp, radii, clamped, grad_acc, dL_dmean2D, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh,
-                           dL_dscales, dL_drots, dL_dmean2D_abs);
+                           prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier, prm.raw_attributes, in.opacities,
+                           out.dL_dopacity, prm.viewmatrix, prm.projmatrix, prm.campos, in.means3D, in.shs, in.colors_precomp,
+                           in.scales, in.rotations, in.cov3D_precomp, radii, clamped, grad_acc, out.dL_dmeans2D, out.dL_dcolors,
+                           out.dL_dmeans3D, out.dL_dcov3D, out.dL_dsh, out.dL_dscales, out.dL_drots, out.dL_dmeans2D_abs);
         return;
       }
       const auto kernel = shvec ? preprocess_backward_vec_kernel<AA, AUX>
                         : staged ? preprocess_backward_staged_kernel<false, AA, AUX> : preprocess_backward_kernel<AA, AUX>;
       hipLaunchKernelGGL(kernel, dim3((prm.P + 255) / 256), dim3(256), lds, s, prm.P, prm.M, prm.sh_degree, prm.width,
-                         prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier, prm.raw_attributes, opacities, dL_dopacity,
-                         prm.viewmatrix, prm.projmatrix, prm.campos, means3D, shs, colors_precomp, scales, rotations,
-                         cov3D_precomp, radii, clamped, grad_acc, dL_dmean2D, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh,
-                         dL_dscales, dL_drots);
+                         prm.height, prm.tanfovx, prm.tanfovy, prm.scale_modifier, prm.raw_attributes, in.opacities,
+                         out.dL_dopacity, prm.viewmatrix, prm.projmatrix, prm.campos, in.means3D, in.shs, in.colors_precomp,
+                         in.scales, in.rotations, in.cov3D_precomp, radii, clamped, grad_acc, out.dL_dmeans2D, out.dL_dcolors,
+                         out.dL_dmeans3D, out.dL_dcov3D, out.dL_dsh, out.dL_dscales, out.dL_drots);
     });
   });
   GGD_HIP(hipGetLastError());

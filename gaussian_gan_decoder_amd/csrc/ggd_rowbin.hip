@@ -731,16 +731,20 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scatter2_kernel(const uint2* __
 // grids up to 64 x 64 tiles: the lane-per-bin kernels above; up to 255 x 255: ggd_rowbin_wide.inc
 bool ggd_rowbin_supported(int W, int H) { return W > 0 && H > 0 && (W + 15) / 16 <= 255 && (H + 15) / 16 <= 255; }
 
+static int rb_launch_status(ggd_ctx* ctx) {   // the launches above, as a return code
+  GGD_HIP(hipGetLastError());
+  return GGD_OK;
+}
+
 // capacity: upper bound on num_rendered (the level-1 entry count is <= num_rendered); order = depth-sorted ids.
-int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const uint2* rect, const uint32_t* order,
-                      const uint32_t* n_vis_ptr, uint32_t* list, uint32_t* ranges, uint32_t capacity, void* tmp,
-                      size_t tmp_bytes, const uint32_t* order_alt, const uint32_t* use_alt, const ggd_scan_piggy* apply,
-                      const uint32_t* fold_rowtot, uint32_t* fold_status1, const uint32_t* fold_rowinst, bool* scan_in_scatter,
-                      const uint32_t* counted_hist) {
-  if (scan_in_scatter) *scan_in_scatter = false;
-  if (!ggd_rowbin_supported(prm.width, prm.height)) return ggd_fail(ctx, GGD_E_INVALID, "tile grid too large for row binning");
+ggd_rowbin_result ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const uint2* rect, const uint32_t* order,
+                                    const uint32_t* n_vis_ptr, uint32_t* list, uint32_t* ranges, uint32_t capacity, void* tmp,
+                                    size_t tmp_bytes, const ggd_rowbin_opts& opts) {
+  const ggd_scan_piggy* apply = opts.apply;
+  const auto& fold = opts.fold;
+  if (!ggd_rowbin_supported(prm.width, prm.height)) return {ggd_fail(ctx, GGD_E_INVALID, "tile grid too large for row binning")};
   const ggd_rowbin_tmp lay = ggd_rowbin_layout(prm.P, capacity, prm.width, prm.height);
-  if (tmp_bytes < lay.total) return ggd_fail(ctx, GGD_E_INVALID, "rowbin tmp too small");
+  if (tmp_bytes < lay.total) return {ggd_fail(ctx, GGD_E_INVALID, "rowbin tmp too small")};
   const int gx = (prm.width + 15) / 16, gy = (prm.height + 15) / 16;
   const bool wide = rb_is_wide(prm.width, prm.height);
   char* p = static_cast<char*>(tmp);
@@ -757,7 +761,7 @@ int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const 
   if (wide) {
     const int ngy = (gy + 63) / 64, ngx = (gx + 63) / 64, nby = 64 * ngy, nbx = 64 * ngx;
     hipLaunchKernelGGL(rbw_count1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, rect, order, n_vis_ptr, prm.P, nby, packed,
-                       counts1, order_alt, use_alt);
+                       counts1, opts.order_alt, opts.use_alt);
     hipLaunchKernelGGL(rbw_scan1_kernel, dim3(1), dim3(1024), 0, s, counts1, n_vis_ptr, prm.P, ngy, tab, capacity);
     hipLaunchKernelGGL(rbw_scatter1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, packed, n_vis_ptr, prm.P, ngy, counts1, tab,
                        ent, capacity);
@@ -765,26 +769,25 @@ int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const 
     hipLaunchKernelGGL(rbw_scan2_kernel, dim3(gy), dim3(1024), 0, s, counts2, tab, gx, gy, ngx, ranges);
     hipLaunchKernelGGL(rbw_scatter2_kernel, dim3(nb2 + nb_apply), dim3(RB_THREADS), 0, s, ent, capacity, tab, ngx, counts2, list,
                        capacity, nb2, pg);
-    GGD_HIP(hipGetLastError());
-    return GGD_OK;
+    return {rb_launch_status(ctx)};
   }
   // the front end counted the instances per row as well: level 2 needs no scan launch (up to the block count the quadratic
   // reads of rb_scatter2_kernel<true> are admitted for)
-  const bool fused2 = fold_rowtot && fold_status1 && fold_rowinst && nb2 <= RB_SCAN_IN_SCATTER_MAX_BLOCKS;
-  if (counted_hist) {
-    // the two-launch sort's finish kernel left packed / bucket_rows / boundary_rows (ggd_rowbin_counted) and counted_hist is the
+  const bool fused2 = fold.rowtot && fold.status1 && fold.rowinst && nb2 <= RB_SCAN_IN_SCATTER_MAX_BLOCKS;
+  if (opts.counted_hist) {
+    // the two-launch sort's finish kernel left packed / bucket_rows / boundary_rows (ggd_rowbin_counted) and opts.counted_hist is the
     // bucket histogram it read: level 1 without the look-back
-    if (!fold_rowtot || tmp_bytes < lay.total_counted) return ggd_fail(ctx, GGD_E_INVALID, "rowbin: counted level 1 needs the folded front end and its row tables");
-    hipLaunchKernelGGL(rb_level1_counted_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, packed, counted_hist, n_vis_ptr, prm.P,
-                       fold_rowtot, reinterpret_cast<const uint32_t*>(p + lay.bucket_rows),
-                       reinterpret_cast<const uint32_t*>(p + lay.boundary_rows), tab, ent, capacity, fused2 ? fold_rowinst : nullptr);
-  } else if (fold_rowtot && fold_status1) {   // (the group words were laid out for ggd_group_shift(chunks): ggd_fold_ctl_words)
-    hipLaunchKernelGGL(rb_level1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, rect, order, n_vis_ptr, prm.P, fold_rowtot,
-                       fold_status1, nb1, ggd_group_shift(nb1), tab, ent, capacity, order_alt, use_alt,
-                       fused2 ? fold_rowinst : nullptr);
+    if (!fold.rowtot || tmp_bytes < lay.total_counted) return {ggd_fail(ctx, GGD_E_INVALID, "rowbin: counted level 1 needs the folded front end and its row tables")};
+    hipLaunchKernelGGL(rb_level1_counted_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, packed, opts.counted_hist, n_vis_ptr, prm.P,
+                       fold.rowtot, reinterpret_cast<const uint32_t*>(p + lay.bucket_rows),
+                       reinterpret_cast<const uint32_t*>(p + lay.boundary_rows), tab, ent, capacity, fused2 ? fold.rowinst : nullptr);
+  } else if (fold.rowtot && fold.status1) {   // (the group words were laid out for ggd_group_shift(chunks): ggd_fold_ctl_words)
+    hipLaunchKernelGGL(rb_level1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, rect, order, n_vis_ptr, prm.P, fold.rowtot,
+                       fold.status1, nb1, ggd_group_shift(nb1), tab, ent, capacity, opts.order_alt, opts.use_alt,
+                       fused2 ? fold.rowinst : nullptr);
   } else {
     hipLaunchKernelGGL(rb_count1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, rect, order, n_vis_ptr, prm.P, packed, counts1,
-                       order_alt, use_alt);
+                       opts.order_alt, opts.use_alt);
     hipLaunchKernelGGL(rb_scan1_kernel, dim3(1), dim3(1024), 0, s, counts1, n_vis_ptr, prm.P, tab, capacity);
     hipLaunchKernelGGL(rb_scatter1_kernel, dim3(nb1), dim3(RB_THREADS), 0, s, packed, n_vis_ptr, prm.P, counts1, tab,
                        ent, capacity);
@@ -793,12 +796,10 @@ int ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const 
   if (fused2) {
     hipLaunchKernelGGL(rb_scatter2_kernel<true>, dim3(nb2 + nb_apply), dim3(RB_THREADS), 0, s, ent, capacity, tab, counts2, list,
                        capacity, nb2, pg, gx, gy, ranges);
-    if (scan_in_scatter) *scan_in_scatter = true;
   } else {
     hipLaunchKernelGGL(rb_scan2_kernel, dim3(gy), dim3(1024), 0, s, counts2, tab, gx, gy, ranges);
     hipLaunchKernelGGL(rb_scatter2_kernel<false>, dim3(nb2 + nb_apply), dim3(RB_THREADS), 0, s, ent, capacity, tab, counts2, list,
                        capacity, nb2, pg, gx, gy, ranges);
   }
-  GGD_HIP(hipGetLastError());
-  return GGD_OK;
+  return {rb_launch_status(ctx), fused2};
 }

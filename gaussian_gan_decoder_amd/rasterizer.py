@@ -156,21 +156,18 @@ def _require_cuda(t: torch.Tensor):
                            "there is no CPU fallback")
 
 
-def _marshal_forward(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
-                     projmatrix, tanfovx, tanfovy, image_height, image_width, sh, degree, campos, prefiltered, debug,
-                     raw_attributes=False, antialiasing=False):
-    """Validation and marshalling of one forward call, shared by `rasterize_gaussians_native` and `FramePipeline.submit` (a
-    mis-shaped input must become a ValueError on both paths, not an out-of-bounds device read).  Returns (dev, P, the seven
-    contiguous fp32 input tensors or None, prm, keep): `keep` holds every tensor the C call reads, for as long as it may."""
-    _require_cuda(means3D)
+def _marshal_inputs(means3D, sh, colors_precomp, scales, rotations, cov3D_precomp, opacities=None):
+    """The per-Gaussian inputs of a forward or backward call: (dev, P, (means3D, sh, colors_precomp, opacities, scales, rotations,
+    cov3D_precomp)) -- the order of the C entry points -- as contiguous fp32 tensors, None for an absent (None or empty) one.  A
+    mis-sized input is a ValueError, not an out-of-bounds read.  opacities: the forward's, converted and counted where the forward
+    has always reported them (the backward marshals its own: it reads them in two modes only).  means3D is a device tensor."""
     dev = means3D.device
-    if means3D.dim() != 2 or means3D.size(1) != 3:
-        raise ValueError("means3D must have dimensions (num_points, 3)")
     P = means3D.size(0)
     means3D = _f32c(means3D, "means3D", dev)
-    opacities = _f32c(opacities, "opacities", dev)
-    if opacities.numel() != P:
-        raise ValueError("opacities must hold one value per point")
+    if opacities is not None:
+        opacities = _f32c(opacities, "opacities", dev)
+        if opacities.numel() != P:
+            raise ValueError("opacities must hold one value per point")
     have = lambda t: t is not None and t.numel() > 0
     sh_c = _f32c(sh, "sh", dev) if have(sh) else None
     col_c = _f32c(colors_precomp, "colors_precomp", dev) if have(colors_precomp) else None
@@ -180,17 +177,44 @@ def _marshal_forward(bg, means3D, colors_precomp, opacities, scales, rotations, 
     for t, n, what in ((col_c, 3, "colors_precomp"), (sc_c, 3, "scales"), (rot_c, 4, "rotations"), (cov_c, 6, "cov3D_precomp")):
         if t is not None and t.numel() != P * n:
             raise ValueError(f"{what} must have dimensions (num_points, {n})")
-    M = 0
-    if sh_c is not None:
-        if sh_c.dim() != 3 or sh_c.size(0) != P or sh_c.size(2) != 3:
-            raise ValueError("sh must have dimensions (num_points, num_coeffs, 3)")
-        M = sh_c.size(1)
+    return dev, P, (means3D, sh_c, col_c, opacities, sc_c, rot_c, cov_c)
+
+
+def _marshal_forward(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                     projmatrix, tanfovx, tanfovy, image_height, image_width, sh, degree, campos, prefiltered, debug,
+                     raw_attributes=False, antialiasing=False):
+    """Validation and marshalling of one forward call, shared by `rasterize_gaussians_native` and `FramePipeline.submit`.
+    Returns (dev, P, the seven input tensors (or None) in the order of the C entry points, prm, keep): `keep` holds every tensor
+    the C call reads, for as long as it may."""
+    _require_cuda(means3D)
+    if means3D.dim() != 2 or means3D.size(1) != 3:
+        raise ValueError("means3D must have dimensions (num_points, 3)")
+    if opacities is None:
+        raise TypeError("opacities must be a torch.Tensor")
+    dev, P, inputs = _marshal_inputs(means3D, sh, colors_precomp, scales, rotations, cov3D_precomp, opacities)
+    sh_c = inputs[1]
+    if sh_c is not None and (sh_c.dim() != 3 or sh_c.size(0) != P or sh_c.size(2) != 3):
+        raise ValueError("sh must have dimensions (num_points, num_coeffs, 3)")
+    M = sh_c.size(1) if sh_c is not None else 0
     rs = GaussianRasterizationSettings(image_height, image_width, tanfovx, tanfovy, bg, scale_modifier,
                                        viewmatrix, projmatrix, degree, campos, prefiltered, debug, raw_attributes,
                                        antialiasing=bool(antialiasing))
-    keep: list = [means3D, opacities, sh_c, col_c, sc_c, rot_c, cov_c]
+    keep: list = list(inputs)
     prm = _params(rs, P, M, dev, keep)
-    return dev, P, (means3D, opacities, sh_c, col_c, sc_c, rot_c, cov_c), prm, keep
+    return dev, P, inputs, prm, keep
+
+
+def _bytes(n: int, dev) -> torch.Tensor:
+    return torch.empty((n,), dtype=torch.uint8, device=dev)
+
+
+def _alloc_outputs(dev, P: int, W: int, H: int, depth_alpha: bool = False):
+    """A frame's outputs (color, radii, geom, img, depth, alpha); the binning buffer's size depends on the frame's route."""
+    color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    radii = torch.empty((P,), dtype=torch.int32, device=dev)
+    depth = torch.empty((1, H, W), dtype=torch.float32, device=dev) if depth_alpha else None
+    alpha = torch.empty((1, H, W), dtype=torch.float32, device=dev) if depth_alpha else None
+    return color, radii, _bytes(_sizes("g", P, 0), dev), _bytes(_sizes("i", W, H), dev), depth, alpha
 
 
 def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier,
@@ -204,7 +228,7 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     with the depth and alpha maps, float32 [1, H, W] each (ggd_forward_aux / ggd_forward_render_aux); everything else is
     bit-identical to the plain call.  antialiasing=True (extension): the opacity-compensated 2D filter (ggd_params.antialiasing);
     radii and the three buffers' sort / binning contents are those of the plain call, the colour changes."""
-    dev, P, (means3D, opacities, sh_c, col_c, sc_c, rot_c, cov_c), prm, keep = _marshal_forward(
+    dev, P, inputs, prm, keep = _marshal_forward(
         bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         tanfovx, tanfovy, image_height, image_width, sh, degree, campos, prefiltered, debug, raw_attributes, antialiasing)
     # (the GPU idles while this wrapper runs between two frames of a render loop: sizes are cached, the stream is looked
@@ -212,50 +236,39 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     ctx, stream_handle = _capi.context_and_stream(dev)
     lib = ctx.lib
     H, W = int(image_height), int(image_width)
-    u8 = dict(dtype=torch.uint8, device=dev)
-    color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-    radii = torch.empty((P,), dtype=torch.int32, device=dev)
-    geom = torch.empty((_sizes("g", P, 0),), **u8)
-    img = torch.empty((_sizes("i", W, H),), **u8)
-    aux = ()
-    if render_depth_alpha:
-        depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-        alpha = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-        aux = (_ptr(depth), _ptr(alpha))
+    color, radii, geom, img, depth, alpha = _alloc_outputs(dev, P, W, H, render_depth_alpha)
+    aux = (_ptr(depth), _ptr(alpha)) if render_depth_alpha else ()
     R = C.c_int64(0)
     stream = C.c_void_p(stream_handle)
     key = (P, W, H)
     hint = ctx.capacity_hint.get(key)
+    head = (ctx.handle, stream, C.byref(prm), *map(_ptr, inputs), _ptr(geom), _ptr(radii))   # every entry point with a per-Gaussian stage begins so
     with _device_guard(dev):
         binning = None
         if hint is not None and P > 0 and not debug:   # debug: exact two-call form, buffers laid out for num_rendered
             # single-call forward: binning buffer sized from the recent frames of this shape (see _capacity); the GPU does
             # not wait for the num_rendered round trip.  Falls through to the exact two-phase path on overflow.
             cap = _capacity(hint)
-            binning = torch.empty((_sizes("b", cap, 0),), **u8)
-            rc = (lib.ggd_forward_aux if aux else lib.ggd_forward)(
-                ctx.handle, stream, C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c), _ptr(opacities), _ptr(sc_c),
-                _ptr(rot_c), _ptr(cov_c), _ptr(geom), _ptr(radii), _ptr(binning), cap, _ptr(img), _ptr(color), *aux, C.byref(R))
+            binning = _bytes(_sizes("b", cap, 0), dev)
+            rc = (lib.ggd_forward_aux if aux else lib.ggd_forward)(*head, _ptr(binning), cap, _ptr(img), _ptr(color), *aux,
+                                                                   C.byref(R))
             if rc == -6:       # GGD_E_CAPACITY: R is valid, redo the render phase with an exact buffer
                 binning = None
                 ctx.capacity_retries += 1
             else:
                 ctx.check(rc)
         else:
-            ctx.check(lib.ggd_forward_geometry(ctx.handle, stream, C.byref(prm), _ptr(means3D), _ptr(sh_c),
-                                               _ptr(col_c), _ptr(opacities), _ptr(sc_c), _ptr(rot_c), _ptr(cov_c),
-                                               _ptr(geom), _ptr(radii), C.byref(R)))
+            ctx.check(lib.ggd_forward_geometry(*head, C.byref(R)))
         if binning is None:
-            binning = torch.empty((lib.ggd_binning_bytes(R.value),), **u8)
+            binning = _bytes(lib.ggd_binning_bytes(R.value), dev)
             ctx.check((lib.ggd_forward_render_aux if aux else lib.ggd_forward_render)(
                 ctx.handle, stream, C.byref(prm), _ptr(geom), R.value, _ptr(binning), _ptr(img), _ptr(color), *aux))
     # the hint is a DECAYING RUNNING MAXIMUM of num_rendered, not the last frame's value: consecutive scenes of a training
     # step differ several-fold (the reference draws fov ~ U[5, 17] degrees per scene, target_dataloader.py:71), and with
     # "last frame x 1.25" every upward swing took the overflow -> exact-retry path, i.e. a host sync
     ctx.capacity_hint[key] = max(int(R.value), int((hint or 0) * _HINT_DECAY))
-    if render_depth_alpha:
-        return int(R.value), color, radii, geom, binning, img, depth, alpha
-    return int(R.value), color, radii, geom, binning, img
+    out = (int(R.value), color, radii, geom, binning, img)
+    return out + (depth, alpha) if render_depth_alpha else out
 
 
 class FramePipeline:
@@ -311,6 +324,11 @@ class FramePipeline:
             ev.record(slot["stream"])
         return res + (ev,)
 
+    def _submit_synchronously(self, slot, args, antialiasing, keep):
+        """The frame through the ordinary path on the slot's stream (which is current): no hint yet, P = 0, debug, unsupported."""
+        self.synchronous_frames += 1
+        slot["pending"] = dict(result=rasterize_gaussians_native(*args, antialiasing=antialiasing), keep=keep)
+
     def submit(self, bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                projmatrix, tanfovx, tanfovy, image_height, image_width, sh, degree, campos, prefiltered, debug,
                raw_attributes=False, *, antialiasing=False):
@@ -321,7 +339,7 @@ class FramePipeline:
         self._next = (self._next + 1) % len(self.slots)
         prev = self._collect(slot)
         # (validation and marshalling on the CALLER's stream: a conversion to contiguous fp32 is the caller's work)
-        dev, P, (means3D_c, opac_c, sh_c, col_c, sc_c, rot_c, cov_c), prm, keep = _marshal_forward(*args, antialiasing=aa)
+        dev, P, inputs, prm, keep = _marshal_forward(*args, antialiasing=aa)
         slot["stream"].wait_stream(torch.cuda.current_stream(dev))
         for t in keep:                            # allocated on the caller's stream, read on the slot's: the caching allocator
             if t is not None:                     # must not hand the block out again before the slot's work at the time of the
@@ -331,25 +349,15 @@ class FramePipeline:
             ctx, handle = _capi.context_and_stream(dev)
             key = (P, W, H)
             hint = ctx.capacity_hint.get(key)
-            if hint is None or P == 0 or debug:
-                self.synchronous_frames += 1
-                slot["pending"] = dict(result=rasterize_gaussians_native(*args, antialiasing=aa), keep=keep)
-                return prev
-            cap = _capacity(hint)
+            cap = _capacity(hint) if hint is not None else 0
             lib = ctx.lib
-            if not lib.ggd_forward_can_speculate(ctx.handle, C.byref(prm), cap):
-                self.synchronous_frames += 1
-                slot["pending"] = dict(result=rasterize_gaussians_native(*args, antialiasing=aa), keep=keep)
+            if hint is None or P == 0 or debug or not lib.ggd_forward_can_speculate(ctx.handle, C.byref(prm), cap):
+                self._submit_synchronously(slot, args, aa, keep)
                 return prev
-            u8 = dict(dtype=torch.uint8, device=dev)
-            color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-            radii = torch.empty((P,), dtype=torch.int32, device=dev)
-            geom = torch.empty((_sizes("g", P, 0),), **u8)
-            img = torch.empty((_sizes("i", W, H),), **u8)
-            binning = torch.empty((_sizes("b", cap, 0),), **u8)
+            color, radii, geom, img, _, _ = _alloc_outputs(dev, P, W, H)
+            binning = _bytes(_sizes("b", cap, 0), dev)
             with _device_guard(dev):
-                ctx.check(lib.ggd_forward_enqueue(ctx.handle, C.c_void_p(handle), C.byref(prm), _ptr(means3D_c), _ptr(sh_c),
-                                                  _ptr(col_c), _ptr(opac_c), _ptr(sc_c), _ptr(rot_c), _ptr(cov_c), _ptr(geom),
+                ctx.check(lib.ggd_forward_enqueue(ctx.handle, C.c_void_p(handle), C.byref(prm), *map(_ptr, inputs), _ptr(geom),
                                                   _ptr(radii), _ptr(binning), cap, _ptr(img), _ptr(color)))
             slot["pending"] = dict(outputs=(color, radii, geom, binning, img), key=key, args=args, antialiasing=aa, keep=keep,
                                    prm=prm)
@@ -387,19 +395,11 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
             raise ValueError(f"{name} must have dimensions (1, {H}, {W}) or ({H}, {W}) (got "
                              f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__})")
     _require_cuda(means3D)
-    dev = means3D.device
-    P = means3D.size(0)
-    means3D = _f32c(means3D, "means3D", dev)
-    have = lambda t: t is not None and t.numel() > 0
-    sh_c = _f32c(sh, "sh", dev) if have(sh) else None
-    col_c = _f32c(colors_precomp, "colors_precomp", dev) if have(colors_precomp) else None
-    sc_c = _f32c(scales, "scales", dev) if have(scales) else None
-    rot_c = _f32c(rotations, "rotations", dev) if have(rotations) else None
-    cov_c = _f32c(cov3D_precomp, "cov3D_precomp", dev) if have(cov3D_precomp) else None
+    dev, P, (means3D, sh_c, col_c, _, sc_c, rot_c, cov_c) = _marshal_inputs(means3D, sh, colors_precomp, scales, rotations, cov3D_precomp)
+    M = sh_c.size(1) if sh_c is not None else 0
     g = _f32c(dL_dout_color, "dL_dout_color", dev)
     gD = _f32c(dL_ddepth, "dL_ddepth", dev) if dL_ddepth is not None else None
     gA = _f32c(dL_dalpha, "dL_dalpha", dev) if dL_dalpha is not None else None
-    M = sh_c.size(1) if sh_c is not None else 0
     rs = GaussianRasterizationSettings(H, W, tanfovx, tanfovy, bg, scale_modifier, viewmatrix, projmatrix, degree,
                                        campos, False, debug, raw_attributes, antialiasing=bool(antialiasing))
     op_c = _f32c(opacities, "opacities", dev) if ((raw_attributes or antialiasing) and opacities is not None) else None
@@ -408,47 +408,23 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
     keep: list = []
     prm = _params(rs, P, M, dev, keep)
     ctx = _capi.context_for(dev)
-    lib = ctx.lib
-    f32 = dict(dtype=torch.float32, device=dev)
-    dL_dmeans3D = torch.empty((P, 3), **f32)
-    dL_dmeans2D = torch.empty((P, 3), **f32)
-    dL_dcolors = torch.empty((P, 3), **f32)
-    dL_dopacity = torch.empty((P, 1), **f32)
-    dL_dcov3D = torch.empty((P, 6), **f32)
-    dL_dsh = torch.empty((P, M, 3), **f32)
-    dL_dscales = torch.empty((P, 3), **f32)
-    dL_drotations = torch.empty((P, 4), **f32)
-    dL_dmeans2D_abs = torch.empty((P, 3), **f32) if absgrad else None
+    # dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations[, dL_dmeans2D_abs]: C order
+    shapes = [(P, 3), (P, 3), (P, 1), (P, 3), (P, 6), (P, M, 3), (P, 3), (P, 4)] + ([(P, 3)] if absgrad else [])
+    grads = [torch.empty(shape, dtype=torch.float32, device=dev) for shape in shapes]
     if ctx.poison_outputs:   # tests: the library must write every element itself (it does not rely on pre-zeroed arrays)
-        for t in (dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations):
+        for t in grads:
             t.fill_(float("nan"))
-        if absgrad:
-            dL_dmeans2D_abs.fill_(float("nan"))
     if P > 0:
+        # the arguments the three entry points share, then the incoming gradients, then the results
+        args = [ctx.handle, _stream(dev), C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c), _ptr(op_c), _ptr(sc_c),
+                _ptr(rot_c), _ptr(cov_c), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g)]
+        if aux or absgrad:
+            args += [_ptr(gD), _ptr(gA)]
+        args += [_ptr(t) for t in grads]
+        fn = ctx.lib.ggd_backward_abs if absgrad else (ctx.lib.ggd_backward_aux if aux else ctx.lib.ggd_backward)
         with torch.cuda.device(dev):
-            if absgrad:
-                ctx.check(lib.ggd_backward_abs(ctx.handle, _stream(dev), C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c),
-                                               _ptr(op_c), _ptr(sc_c), _ptr(rot_c), _ptr(cov_c), _ptr(radii), _ptr(geomBuffer),
-                                               _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g), _ptr(gD), _ptr(gA),
-                                               _ptr(dL_dmeans2D), _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D),
-                                               _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations),
-                                               _ptr(dL_dmeans2D_abs)))
-            elif aux:
-                ctx.check(lib.ggd_backward_aux(ctx.handle, _stream(dev), C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c),
-                                               _ptr(op_c), _ptr(sc_c), _ptr(rot_c), _ptr(cov_c), _ptr(radii), _ptr(geomBuffer),
-                                               _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g), _ptr(gD), _ptr(gA),
-                                               _ptr(dL_dmeans2D), _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D),
-                                               _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations)))
-            else:
-                ctx.check(lib.ggd_backward(ctx.handle, _stream(dev), C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c),
-                                           _ptr(op_c), _ptr(sc_c), _ptr(rot_c), _ptr(cov_c), _ptr(radii), _ptr(geomBuffer),
-                                           _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g), _ptr(dL_dmeans2D),
-                                           _ptr(dL_dcolors), _ptr(dL_dopacity), _ptr(dL_dmeans3D), _ptr(dL_dcov3D),
-                                           _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations)))
-    if absgrad:
-        return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
-                dL_dmeans2D_abs)
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+            ctx.check(fn(*args))
+    return tuple(grads)
 
 
 def mark_visible(positions, viewmatrix, projmatrix):

@@ -31,6 +31,11 @@ def test_option_and_counter_constants_match_the_header():
     assert (_capi.OPT_EXP_MODE, _capi.OPT_BLEND_CULL, _capi.OPT_BINNING, _capi.OPT_BLEND_SPLIT, _capi.OPT_FOLD) == tuple(
         val(n) for n in ("GGD_OPT_EXP_MODE", "GGD_OPT_BLEND_CULL", "GGD_OPT_BINNING", "GGD_OPT_BLEND_SPLIT", "GGD_OPT_FOLD"))
     assert (_capi.STAT_FLAT_STREAK, _capi.STAT_SORT_RERUNS) == (val("GGD_STAT_FLAT_STREAK"), val("GGD_STAT_SORT_RERUNS"))
+    # ... and every other one: each GGD_OPT_* / GGD_STAT_* enumerator the header gives a number has its _capi constant
+    enum = dict(re.findall(r"^\s*GGD_((?:OPT|STAT)_[A-Z0-9_]+)\s*=\s*(\d+)", hdr, flags=re.M))
+    assert len([n for n in enum if n.startswith("OPT_")]) == 8 and len([n for n in enum if n.startswith("STAT_")]) == 5
+    for n, v in enum.items():
+        assert getattr(_capi, n) == int(v), n
 
 
 def test_layouts_and_sort_bits(native_lib):
