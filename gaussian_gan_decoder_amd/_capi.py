@@ -18,7 +18,7 @@ EXPORTS = [
     "ggd_geom_bytes", "ggd_binning_bytes", "ggd_img_bytes", "ggd_geom_layout", "ggd_binning_layout",
     "ggd_img_layout", "ggd_sort_bits", "ggd_create", "ggd_destroy", "ggd_last_error", "ggd_version",
     "ggd_forward_geometry", "ggd_forward_render", "ggd_forward", "ggd_forward_enqueue", "ggd_forward_collect", "ggd_forward_can_speculate", "ggd_backward",
-    "ggd_forward_aux", "ggd_forward_render_aux", "ggd_backward_aux", "ggd_backward_abs", "ggd_mark_visible", "ggd_debug_unsorted",
+    "ggd_forward_aux", "ggd_forward_render_aux", "ggd_backward_aux", "ggd_backward_abs", "ggd_mark_visible", "ggd_debug_unsorted", "ggd_selftest_lanes",
     "ggd_triplane_forward", "ggd_triplane_backward", "ggd_trigrid_forward", "ggd_trigrid_backward", "ggd_planes_gather", "ggd_planes_scatter", "ggd_surface_tmp_bytes", "ggd_surface_sample", "ggd_attrs_split", "ggd_attrs_merge", "ggd_decoder_packed_bytes", "ggd_decoder_pack", "ggd_decoder_forward", "ggd_decoder_zbuf_bytes", "ggd_decoder_packed_t_bytes",
     "ggd_decoder_forward_train", "ggd_decoder_backward", "ggd_decoder_wgrad_floats", "ggd_decoder_wgrad", "ggd_decoder_backward_wgrad", "ggd_decoder_packed_hl_bytes", "ggd_decoder_packed_t_hl_bytes", "ggd_decoder_dzbuf_hl_bytes", "ggd_decoder_pack_hl", "ggd_decoder_forward_hl", "ggd_decoder_backward_wgrad_hl",
     "ggd_decoder_pack_chain", "ggd_decoder_forward_chain", "ggd_decoder_forward_train_chain", "ggd_decoder_backward_chain", "ggd_decoder_wgrad_chain",
@@ -55,6 +55,7 @@ OPT_L1_COUNTED = 7
 STAT_FLAT_STREAK, STAT_SORT_RERUNS, STAT_MSD_FRAMES, STAT_SCAN_IN_SCATTER_FRAMES = 100, 101, 102, 103   # read-only, through get_option
 STAT_L1_COUNTED_FRAMES = 104
 SPLAT_BYTES = 48
+LANES_SELFTEST_WORDS = 156   # GGD_LANES_SELFTEST_WORDS
 SPLAT_FIELDS = ("x", "y", "hA", "nB", "hC", "thr", "opacity", "r", "g", "b", "ex", "ey")
 
 _lib = None
@@ -101,6 +102,7 @@ def load():
         lib.ggd_backward_abs.argtypes = bwd + [vp, vp] + [vp] * 9
         lib.ggd_mark_visible.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         lib.ggd_debug_unsorted.argtypes = [vp, vp, vp, vp, i64]
+        lib.ggd_selftest_lanes.argtypes = [vp, vp, vp, vp, i32]
         lib.ggd_triplane_forward.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, C.c_float, vp]
         lib.ggd_triplane_backward.argtypes = [vp, vp, i32, i32, i32, vp, i32, C.c_float, vp, vp]
         lib.ggd_trigrid_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, C.c_float, vp]

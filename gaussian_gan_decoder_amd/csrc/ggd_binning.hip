@@ -14,6 +14,7 @@
 //     dropped in pass 0 and constant-digit passes degrade to copies.  Keys embed raw fp32 depth bits, so the sorted
 //     order (ties included) is identical to a stable sort of the emission order.
 #include "ggd_common.h"
+#include "ggd_lanes.h"
 
 namespace {
 

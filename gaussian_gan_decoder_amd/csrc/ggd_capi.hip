@@ -900,6 +900,14 @@ extern "C" int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const flo
   return ggd_launch_mark_visible(ctx, static_cast<hipStream_t>(stream), P, means3D, viewmatrix, present);
 }
 
+extern "C" int ggd_selftest_lanes(ggd_ctx* ctx, void* stream, const uint64_t* in, uint32_t* out, int32_t n_waves) {
+  if (!ctx) return GGD_E_INVALID;
+  if (n_waves < 0) return ggd_fail(ctx, GGD_E_INVALID, "n_waves < 0");
+  if (n_waves == 0) return GGD_OK;
+  if (!in || !out) return ggd_fail(ctx, GGD_E_INVALID, "ggd_selftest_lanes: NULL pointer");
+  return ggd_launch_selftest_lanes(ctx, static_cast<hipStream_t>(stream), in, out, n_waves);
+}
+
 extern "C" int ggd_debug_unsorted(ggd_ctx* ctx, void* stream, uint64_t* keys, uint32_t* values, int64_t R) {
   if (!ctx) return GGD_E_INVALID;
   if (R < 0 || (size_t)R > ctx->dbg_cap) return ggd_fail(ctx, GGD_E_INVALID, "no debug copy of that size (debug=1?)");

@@ -305,6 +305,8 @@ ggd_rowbin_result ggd_launch_rowbin(ggd_ctx* ctx, hipStream_t s, const ggd_param
                                     const uint32_t* n_vis_ptr, uint32_t* list, uint32_t* ranges, uint32_t capacity, void* tmp,
                                     size_t tmp_bytes, const ggd_rowbin_opts& opts = ggd_rowbin_opts());
 int ggd_launch_ranges(ggd_ctx* ctx, hipStream_t s, const uint64_t* keys, int64_t n, uint32_t* ranges, int T);
+// the cross-lane primitives of ggd_lanes.h next to their __shfl forms (ggd_selftest_lanes, ggd_raster.h)
+int ggd_launch_selftest_lanes(ggd_ctx* ctx, hipStream_t s, const uint64_t* in, uint32_t* out, int n_waves);
 // out_depth / out_alpha non-null (both): the depth / alpha extension (blend_forward_kernel<..., AUX>), which also reads
 // depth_keys (the geometry buffer's: the fp32 bits of each Gaussian's view-space depth)
 int ggd_launch_blend(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,

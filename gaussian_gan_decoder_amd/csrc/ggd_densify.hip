@@ -16,6 +16,7 @@
 // restated; max_screen_size only switches the world-size test on.)
 // No workgroup waits on another one anywhere in this file: every dependency is a kernel boundary.
 #include "ggd_common.h"
+#include "ggd_lanes.h"
 
 namespace {
 

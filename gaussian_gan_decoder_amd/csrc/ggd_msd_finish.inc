@@ -1,5 +1,5 @@
 // ggd_msd_finish.inc -- the per-bucket half of the two-launch depth sort (GGD_MSD_*, ggd_common.h), included inside the anonymous
-// namespace of ggd_binning.hip (sort_msd_finish_kernel).  Needs ggd_scan.inc (wave_inclusive_scan); MSD_TILE = the 4096 keys of a tile of launch 1 (ggd_binning_layout.h).  (Kept as an include since
+// namespace of ggd_binning.hip (sort_msd_finish_kernel).  Needs ggd_lanes.h (wave_inclusive_scan); MSD_TILE = the 4096 keys of a tile of launch 1 (ggd_binning_layout.h).  (Kept as an include since
 // round 5's experiment of running level 1 of the binning on the sorted bucket inside the same workgroup -- one launch and one
 // gather chain less, but 48.8 us against 16.5 + 23.0 for the two kernels: profiles/REJECTED.md.)
 //

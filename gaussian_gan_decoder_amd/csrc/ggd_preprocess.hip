@@ -9,6 +9,7 @@
 // (ggd_splat) so that the per-tile gather later touches a single 64 B-aligned-ish record instead of four arrays.
 // HBM-bound: 56 B in (degree 0) + 56 B out per visible Gaussian, 56 B in + 8 B out per culled one.
 #include "ggd_math.h"
+#include "ggd_lanes.h"
 
 namespace {
 using namespace ggdm;
@@ -356,16 +357,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(pre_args args) {
     // kept-key range of the frame (for the NEXT frames' two-launch-sort window): ~min and max, so that both reduce -- and
     // accumulate in the zeroed control block -- as maxima
     uint32_t nmin = visible ? ~key : 0u, kmax = visible ? key : 0u;
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-      tsum += __shfl_xor(tsum, sh, 64);
-      nmin = max(nmin, (uint32_t)__shfl_xor((int)nmin, sh, 64));
-      kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, sh, 64));
-    }
+    tsum = wave_sum_lane63(tsum); nmin = wave_max_lane63(nmin); kmax = wave_max_lane63(kmax);   // (lane 63 writes them)
     // (the tile after this one writes the other buffer, and nobody writes this one again before thread 0 has passed the next
     // tile's barrier: one barrier per tile)
     uint32_t* red = s_red + 16 * parity;
-    if (lane == 0) { red[wv] = tsum; red[4 + wv] = (uint32_t)__popcll(act); red[8 + wv] = nmin; red[12 + wv] = kmax; }
+    if (lane == 63) { red[wv] = tsum; red[4 + wv] = (uint32_t)__popcll(act); red[8 + wv] = nmin; red[12 + wv] = kmax; }
     __syncthreads();
     if (threadIdx.x == 0)
       as_global(a->fold.wg_info)[tile] = make_uint4(red[0] + red[1] + red[2] + red[3], red[4] + red[5] + red[6] + red[7],
@@ -391,12 +387,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(pre_args args) {
       if (c) atomicAdd(&hist[b], c);
     }
     if (a->fold.rows && threadIdx.x < 64) {
-      int c = s_rowdiff[lane], cw = s_rowwdiff[lane];
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(c, d, 64), ow = __shfl_up(cw, d, 64);
-        if (lane >= d) { c += o; cw += ow; }
-      }
+      const int c = wave_inclusive_scan(s_rowdiff[lane]), cw = wave_inclusive_scan(s_rowwdiff[lane]);
       if (c) {   // (a row without entries has no instances)
         atomicAdd(&ctl[GGD_FOLD_ROWTOT + (blockIdx.x % GGD_FOLD_REPS) * 64 + lane], (uint32_t)c);
         atomicAdd(&as_global(a->fold.rowinst)[(blockIdx.x % GGD_FOLD_REPS) * 64 + lane], (uint32_t)cw);

@@ -35,6 +35,7 @@
 // rb_block_row_range, wave_cols / wave_emit (narrow) and wave_cols_w / wave_emit_w (wide).
 // Scratch and table layouts, the `packed` record: ggd_binning_layout.h (ggd_rowbin_tmp, RB_TAB_* / RBW_TAB_*, rb_pack_rect).
 #include "ggd_common.h"
+#include "ggd_lanes.h"
 
 namespace {
 
@@ -156,35 +157,7 @@ __global__ __launch_bounds__(1024) void rb_scan1_kernel(uint32_t* __restrict__ c
   if (wv == 0) rb_write_row_tables(tab, lane, tot, wave_inclusive_scan(tot), ent_cap);
 }
 
-// 64 x 64 bit-matrix transpose across the wave: lane i passes row i (bit b = M[i][b]) and gets column `lane`
-// (bit i = M[i][lane]).  Six butterfly stages (block sizes 32 .. 1): in every lane pair (l, l ^ d) the off-diagonal
-// d x d blocks are exchanged; one cross-lane move per 32-bit word and stage.
-template <int D, uint32_t M>
-__device__ __forceinline__ void tr_stage(uint32_t& lo, uint32_t& hi, uint32_t lane) {
-  const bool up = (lane & (uint32_t)D) != 0;
-  const uint32_t keep = up ? ~M : M;
-  const uint32_t slo = up ? ((lo & M) << D) : ((lo & ~M) >> D);
-  const uint32_t shi = up ? ((hi & M) << D) : ((hi & ~M) >> D);
-  lo = (lo & keep) | (uint32_t)__shfl_xor((int)slo, D, 64);
-  hi = (hi & keep) | (uint32_t)__shfl_xor((int)shi, D, 64);
-}
-
-__device__ __forceinline__ uint64_t wave_transpose64(uint64_t row) {
-  const uint32_t lane = threadIdx.x & 63;
-  uint32_t lo = (uint32_t)row, hi = (uint32_t)(row >> 32);
-  {
-    const bool up = (lane & 32u) != 0;
-    const uint32_t recv = (uint32_t)__shfl_xor((int)(up ? lo : hi), 32, 64);
-    if (up) lo = recv; else hi = recv;
-  }
-  // stages 16 .. 1 act on the two 32-bit words independently (compile-time masks and lane distances)
-  tr_stage<16, 0x0000FFFFu>(lo, hi, lane);
-  tr_stage<8, 0x00FF00FFu>(lo, hi, lane);
-  tr_stage<4, 0x0F0F0F0Fu>(lo, hi, lane);
-  tr_stage<2, 0x33333333u>(lo, hi, lane);
-  tr_stage<1, 0x55555555u>(lo, hi, lane);
-  return (uint64_t)lo | ((uint64_t)hi << 32);
-}
+// (wave_transpose64 -- the 64 x 64 item / bin bit matrix across the wave -- is ggd_lanes.h's)
 
 // A wave's items (RB_IPL rounds of 64, lane = item, interval [lo, hi) of bins) against its 64 bins (lane = bin), round 5 form:
 //   wave_cols   every round's 64 x 64 item / bin bit matrix, transposed: cols[q] of lane b = the items of round q that cover bin
@@ -283,7 +256,7 @@ __device__ __forceinline__ void rb_emit_chunk(const uint32_t (&iv)[RB_IPL], cons
                                               typename Pay::type* __restrict__ out, uint32_t out_cap) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t binend = wave_inclusive_scan(bintot);          // same in every wave
-  const uint32_t total = (uint32_t)__shfl((int)binend, 63, 64);
+  const uint32_t total = wave_pick(binend, 63);
   const uint32_t binbeg = binend - bintot;
   if (total <= stage_cap) {
     uint32_t ldst = binbeg + before;
@@ -291,9 +264,9 @@ __device__ __forceinline__ void rb_emit_chunk(const uint32_t (&iv)[RB_IPL], cons
     __syncthreads();
 #pragma unroll 4
     for (int c = wv; c < 64; c += RB_WAVES) {
-      const uint32_t n = (uint32_t)__shfl((int)bintot, c, 64);
+      const uint32_t n = wave_pick(bintot, c);                    // (c is the same in every lane: scalars, as is the loop bound)
       if (n == 0) continue;
-      const uint32_t b0 = (uint32_t)__shfl((int)binbeg, c, 64), g = (uint32_t)__shfl((int)gbase, c, 64);
+      const uint32_t b0 = wave_pick(binbeg, c), g = wave_pick(gbase, c);
       for (uint32_t k = lane; k < n; k += 64) {
         const uint32_t d = g + k;
         if (d < out_cap) out[d] = stage[b0 + k];
@@ -311,7 +284,7 @@ __device__ __forceinline__ void rb_emit_chunk(const uint32_t (&iv)[RB_IPL], cons
 // a wave four rows per load instruction, the rows are dealt to the four waves, and a lane has BATCH = 8 independent loads in flight
 // (128 rows per round trip of the workgroup) -- all of a batch requested before any is consumed: these sums sit on the one
 // dependent round trip of their kernels, and a load per wait made it n / 16 trips.  The wave's four row groups are folded by
-// two shuffles and lanes 0 - 15 store the wave's partial sums to s_tot[64] (this wave's); BEFORE: those of the rows below `split` to
+// two lane-block swaps (lane_pair_sum) and lanes 0 - 15 store the wave's partial sums to s_tot[64] (this wave's); BEFORE: those of the rows below `split` to
 // s_bef[64] as well.  The caller adds the four waves' partials behind its next barrier.
 template <bool BEFORE, typename RowOf>
 __device__ __forceinline__ void rb_sum_count_rows(uint32_t n, uint32_t split, RowOf&& row_of, uint32_t* s_tot, uint32_t* s_bef) {
@@ -337,15 +310,12 @@ __device__ __forceinline__ void rb_sum_count_rows(uint32_t n, uint32_t split, Ro
       }
     }
   }
-#pragma unroll
-  for (int d = 16; d <= 32; d <<= 1) {   // the wave's four row groups hold the same columns
-    tot4.x += (uint32_t)__shfl_xor((int)tot4.x, d, 64); tot4.y += (uint32_t)__shfl_xor((int)tot4.y, d, 64);
-    tot4.z += (uint32_t)__shfl_xor((int)tot4.z, d, 64); tot4.w += (uint32_t)__shfl_xor((int)tot4.w, d, 64);
-    if constexpr (BEFORE) {
-      bef4.x += (uint32_t)__shfl_xor((int)bef4.x, d, 64); bef4.y += (uint32_t)__shfl_xor((int)bef4.y, d, 64);
-      bef4.z += (uint32_t)__shfl_xor((int)bef4.z, d, 64); bef4.w += (uint32_t)__shfl_xor((int)bef4.w, d, 64);
-    }
-  }
+  auto fold4 = [](uint4& v) {   // the wave's four row groups hold the same columns
+    v.x = lane_pair_sum<32>(lane_pair_sum<16>(v.x)); v.y = lane_pair_sum<32>(lane_pair_sum<16>(v.y));
+    v.z = lane_pair_sum<32>(lane_pair_sum<16>(v.z)); v.w = lane_pair_sum<32>(lane_pair_sum<16>(v.w));
+  };
+  fold4(tot4);
+  if constexpr (BEFORE) fold4(bef4);
   if (lane < 16) {
     if constexpr (BEFORE) *reinterpret_cast<uint4*>(&s_bef[c4]) = bef4;
     *reinterpret_cast<uint4*>(&s_tot[c4]) = tot4;
@@ -557,9 +527,9 @@ __device__ __forceinline__ bool rb_block_row_range(const uint32_t* __restrict__ 
   const uint32_t all = tab[RB_TAB_ROWSTART + 64];
   if (blk >= total) return false;
   const int r = __popcll(__ballot(first <= blk)) - 1;
-  row = r; chunk = blk - (uint32_t)__shfl((int)first, r, 64);
-  rbeg = (uint32_t)__shfl((int)start, r, 64);
-  rend = min(r == 63 ? all : (uint32_t)__shfl((int)start, (r + 1) & 63, 64), ent_cap);
+  row = r; chunk = blk - wave_pick(first, r);
+  rbeg = wave_pick(start, r);
+  rend = min(r == 63 ? all : wave_pick(start, (r + 1) & 63), ent_cap);
   return true;
 }
 
@@ -605,7 +575,7 @@ __device__ __forceinline__ uint32_t rb_publish_row_sum_above(uint32_t* inst, uin
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   uint32_t above = 0;
   for (int rr = lane; rr < r; rr += 64) above += __hip_atomic_load(&inst[rr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan(above), 63);
+  return wave_sum_to_all(above);
 }
 
 // ---- level-2 scan, one workgroup per tile row: exclusive prefix over the row's chunks (lane = column, 16 waves split
@@ -662,7 +632,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scatter2_kernel(const uint2* __
     rowinst = tab[RB_TAB_ROWINST + lane];
     rowblks = tab[RB_TAB_ROWBLK + lane + 1] - tab[RB_TAB_ROWBLK + lane];
     if ((int)blockIdx.x < gy && wv == 0) {
-      const uint32_t nb_z = (uint32_t)__shfl((int)rowblks, (int)blockIdx.x, 64);
+      const uint32_t nb_z = wave_pick(rowblks, (int)blockIdx.x);
       if (nb_z == 0u && lane < gx) {
         const int t = (int)blockIdx.x * gx + lane;
         ranges[2 * t] = 0u;
@@ -688,7 +658,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scatter2_kernel(const uint2* __
   uint32_t gbase = 0;
   if constexpr (SCAN) {
     const uint32_t blk0 = blockIdx.x - chunk;                                        // first block of the row
-    const uint32_t nblk_row = (uint32_t)__shfl((int)rowblks, row, 64);               // >= chunk + 1
+    const uint32_t nblk_row = wave_pick(rowblks, row);                               // >= chunk + 1
     // (the cube's 19 blocks a row, the shell's 50 - 130 are one batch of rb_sum_count_rows)
     rb_sum_count_rows<true>(nblk_row, chunk, [&](uint32_t k) { return prefix2 + (size_t)(blk0 + k) * 64; }, wsum[RB_WAVES + wv], wsum[wv]);
   } else {
@@ -709,7 +679,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scatter2_kernel(const uint2* __
 #pragma unroll
     for (int w = 0; w < RB_WAVES; ++w) { bef += wsum[w][lane]; tot += wsum[RB_WAVES + w][lane]; }
     const uint32_t rinc = wave_inclusive_scan(rowinst);
-    const uint32_t rowbase = (uint32_t)__shfl((int)(rinc - rowinst), row, 64);       // instances of the rows above
+    const uint32_t rowbase = wave_pick(rinc - rowinst, row);                         // instances of the rows above
     const uint32_t start = rowbase + wave_inclusive_scan(tot) - tot;
     gbase = start + bef;
     if (chunk == 0u && wv == 0 && lane < gx) {
@@ -726,7 +696,83 @@ __global__ __launch_bounds__(RB_THREADS) void rb_scatter2_kernel(const uint2* __
 
 #include "ggd_rowbin_wide.inc"
 
+// ---- self-test of ggd_lanes.h (ggd_selftest_lanes): one wave per 64 input words; lane l takes in[64 w + l] (x = its low word) and
+//      writes GGD_LANES_SELFTEST_WORDS words: every primitive next to the __shfl form it replaced, for the test to compare both with
+//      its own arithmetic.  Layout (ggd_raster.h): {new, shfl} pairs of scan (uint32), scan (int), sum, max; lane_xor<1 .. 32> new,
+//      then shfl; wave_pick of every lane new, then shfl; transpose {lo, hi} new, then shfl.
+namespace lanes_shfl {
+template <typename T>
+__device__ __forceinline__ T scan(T v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T o = __shfl_up(v, d, 64);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+template <int D, uint32_t M>
+__device__ __forceinline__ void tr_stage(uint32_t& lo, uint32_t& hi, uint32_t lane) {
+  const bool up = (lane & (uint32_t)D) != 0;
+  const uint32_t keep = up ? ~M : M;
+  const uint32_t slo = up ? ((lo & M) << D) : ((lo & ~M) >> D);
+  const uint32_t shi = up ? ((hi & M) << D) : ((hi & ~M) >> D);
+  lo = (lo & keep) | (uint32_t)__shfl_xor((int)slo, D, 64);
+  hi = (hi & keep) | (uint32_t)__shfl_xor((int)shi, D, 64);
+}
+__device__ __forceinline__ uint64_t transpose64(uint64_t row) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t lo = (uint32_t)row, hi = (uint32_t)(row >> 32);
+  {
+    const bool up = (lane & 32u) != 0;
+    const uint32_t recv = (uint32_t)__shfl_xor((int)(up ? lo : hi), 32, 64);
+    if (up) lo = recv; else hi = recv;
+  }
+  tr_stage<16, 0x0000FFFFu>(lo, hi, lane);
+  tr_stage<8, 0x00FF00FFu>(lo, hi, lane);
+  tr_stage<4, 0x0F0F0F0Fu>(lo, hi, lane);
+  tr_stage<2, 0x33333333u>(lo, hi, lane);
+  tr_stage<1, 0x55555555u>(lo, hi, lane);
+  return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+}  // namespace lanes_shfl
+
+__global__ __launch_bounds__(64) void selftest_lanes_kernel(const uint64_t* __restrict__ in, uint32_t* __restrict__ out) {
+  const int lane = threadIdx.x;
+  const uint64_t row = in[(size_t)blockIdx.x * 64 + lane];
+  const uint32_t x = (uint32_t)row;
+  uint32_t* o = out + ((size_t)blockIdx.x * 64 + lane) * GGD_LANES_SELFTEST_WORDS;
+  o[0] = wave_inclusive_scan(x);                 o[1] = lanes_shfl::scan(x);
+  o[2] = (uint32_t)wave_inclusive_scan((int)x);  o[3] = (uint32_t)lanes_shfl::scan((int)x);
+  o[4] = wave_sum_to_all(x);                     o[5] = (uint32_t)__shfl((int)lanes_shfl::scan(x), 63, 64);
+  uint32_t m = x;
+#pragma unroll
+  for (int sh = 32; sh >= 1; sh >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, sh, 64));
+  o[6] = wave_max_to_all(x);                     o[7] = m;
+  o[8] = lane_xor<1>(x);   o[9] = lane_xor<2>(x);   o[10] = lane_xor<4>(x);
+  o[11] = lane_xor<8>(x);  o[12] = lane_xor<16>(x); o[13] = lane_xor<32>(x);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) o[14 + k] = (uint32_t)__shfl_xor((int)x, 1 << k, 64);
+#pragma unroll 1
+  for (int c = 0; c < 64; ++c) {
+    o[20 + c] = wave_pick(x, c);
+    o[84 + c] = (uint32_t)__shfl((int)x, c, 64);
+  }
+  const uint64_t tn = wave_transpose64(row), ts = lanes_shfl::transpose64(row);
+  o[148] = (uint32_t)tn; o[149] = (uint32_t)(tn >> 32);
+  o[150] = (uint32_t)ts; o[151] = (uint32_t)(ts >> 32);
+  o[152] = lane_pair_sum<16>(x); o[153] = lane_pair_sum<32>(x);
+  o[154] = wave_max_lane63(x);   o[155] = wave_sum_lane63(x);
+}
+static_assert(GGD_LANES_SELFTEST_WORDS == 156, "selftest_lanes_kernel's layout");
+
 }  // namespace
+
+int ggd_launch_selftest_lanes(ggd_ctx* ctx, hipStream_t s, const uint64_t* in, uint32_t* out, int n_waves) {
+  selftest_lanes_kernel<<<n_waves, 64, 0, s>>>(in, out);
+  GGD_HIP(hipGetLastError());
+  return GGD_OK;
+}
 
 // grids up to 64 x 64 tiles: the lane-per-bin kernels above; up to 255 x 255: ggd_rowbin_wide.inc
 bool ggd_rowbin_supported(int W, int H) { return W > 0 && H > 0 && (W + 15) / 16 <= 255 && (H + 15) / 16 <= 255; }

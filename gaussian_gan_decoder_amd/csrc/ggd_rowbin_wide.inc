@@ -75,8 +75,8 @@ __global__ __launch_bounds__(1024) void rbw_scan1_kernel(uint32_t* __restrict__ 
       const uint32_t binc = blk_carry + wave_inclusive_scan(nb2);
       tab[RBW_TAB_ROWBLK + bin] = binc - nb2;
       tab[RBW_TAB_FLAG + bin] = 0u;
-      row_carry = (uint32_t)__shfl((int)inc, 63, 64);
-      blk_carry = (uint32_t)__shfl((int)binc, 63, 64);
+      row_carry = wave_pick(inc, 63);
+      blk_carry = wave_pick(binc, 63);
     }
     __syncthreads();   // part is reused by the next group
   }
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(1024) void rbw_scan2_kernel(uint32_t* __restrict__ 
 #pragma unroll
     for (int g = 0; g < RBW_NG; ++g) {
       incs[g] = carry + wave_inclusive_scan(tots[g]);
-      carry = (uint32_t)__shfl((int)incs[g], 63, 64);
+      carry = wave_pick(incs[g], 63);
     }
     const uint32_t rowbase = rb_publish_row_sum_above(tab + RBW_TAB_ROWINST, tab + RBW_TAB_FLAG, r, carry);   // carry = instances of this row
 #pragma unroll
@@ -340,7 +340,7 @@ __global__ __launch_bounds__(RB_THREADS) void rbw_scatter2_kernel(const uint2* _
       for (int w = 0; w < RB_WAVES; ++w) { const uint32_t c = wcnt[w][col]; if (w < wv) before[g] += c; coltot[g] += c; }
       const uint32_t colend = carry + wave_inclusive_scan(coltot[g]);   // same in every wave
       colbeg[g] = colend - coltot[g];
-      carry = (uint32_t)__shfl((int)colend, 63, 64);
+      carry = wave_pick(colend, 63);
     }
   }
   const uint32_t total = carry;

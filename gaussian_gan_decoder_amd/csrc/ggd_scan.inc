@@ -1,21 +1,11 @@
 // ggd_scan.inc -- workgroup-level pieces of the uint32 prefix scan (stage a5), included inside the anonymous namespace of
 // the translation units that run them: ggd_binning.hip (the scan kernels; the depth sort's appended workgroups) and
-// ggd_rowbin.hip (the apply step as appended workgroups of the last binning launch; the wave scan, for ints too).
+// ggd_rowbin.hip (the apply step as appended workgroups of the last binning launch).  The wave scan under them is
+// wave_inclusive_scan of ggd_lanes.h, which the including file includes first (outside its namespace).
 // ------------------------------------------------------------------------------------------------ block scan --
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;                        // per thread
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;  // 2048 per block
-
-template <typename T>
-__device__ __forceinline__ T wave_inclusive_scan(T v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
 
 // Exclusive prefix of `v` over the 256 threads of the block (4 waves); *total = block sum.
 __device__ __forceinline__ uint32_t block_exclusive_scan_256(uint32_t v, uint32_t* total, uint32_t* lds4) {
@@ -117,13 +107,10 @@ __device__ __forceinline__ uint4 scan_info_block(const uint4* __restrict__ info,
   }
   uint32_t vtot;
   block_exclusive_scan_256(valid, &vtot, lds4);
-#pragma unroll
-  for (int sh = 32; sh >= 1; sh >>= 1) {
-    nmin = max(nmin, (uint32_t)__shfl_xor((int)nmin, sh, 64));
-    kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, sh, 64));
-  }
+  nmin = wave_max_lane63(nmin);
+  kmax = wave_max_lane63(kmax);
   __syncthreads();
-  if ((threadIdx.x & 63) == 0) { lds4[threadIdx.x >> 6] = nmin; lds4[4 + (threadIdx.x >> 6)] = kmax; }   // (callers pass >= 8 words)
+  if ((threadIdx.x & 63) == 63) { lds4[threadIdx.x >> 6] = nmin; lds4[4 + (threadIdx.x >> 6)] = kmax; }   // (callers pass >= 8 words)
   __syncthreads();
   nmin = max(max(lds4[0], lds4[1]), max(lds4[2], lds4[3]));
   kmax = max(max(lds4[4], lds4[5]), max(lds4[6], lds4[7]));

@@ -266,6 +266,19 @@ int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D
  * to device buffers keys[R] / values[R] supplied by the caller.  Either pointer may be NULL. */
 int ggd_debug_unsorted(ggd_ctx* ctx, void* stream, uint64_t* keys, uint32_t* values, int64_t num_rendered);
 
+/* Self-test of the front-end kernels' cross-lane primitives (register forms: DPP, lane-block swaps, v_readlane) against the
+ * shuffle forms they replaced.  One wave per 64 input words: lane l of wave w takes in[64 w + l] (x = its low 32 bits; the whole
+ * word is row l of a 64 x 64 bit matrix) and writes GGD_LANES_SELFTEST_WORDS words at out[(64 w + l) * GGD_LANES_SELFTEST_WORDS]:
+ *   0, 1      inclusive scan of x over the lanes (uint32): new, shuffle form          2, 3   the same as int
+ *   4, 5      sum of x over the wave (every lane)                                     6, 7   maximum of x (unsigned)
+ *   8 .. 13   x of lane l ^ 1, 2, 4, 8, 16, 32: new                                   14 .. 19   shuffle form
+ *   20 .. 83  x of lane c, c = 0 .. 63: new                                           84 .. 147  shuffle form
+ *   148, 149  column l of the bit matrix (low, high word): new                        150, 151   shuffle form
+ *   152, 153  x + x of lane l ^ 16, l ^ 32 (new)      154, 155   maximum / sum of x with the result in lane 63 only (there: new)
+ * in: n_waves * 64 words, out: n_waves * 64 * GGD_LANES_SELFTEST_WORDS words, both on the device. */
+#define GGD_LANES_SELFTEST_WORDS 156
+int ggd_selftest_lanes(ggd_ctx* ctx, void* stream, const uint64_t* in, uint32_t* out, int32_t n_waves);
+
 /* Tuning / experiment knobs (do not change results beyond the documented tolerances).  Returns GGD_E_INVALID for an
  * unknown option or value. */
 enum {
