@@ -27,6 +27,7 @@ EXPORTS = [
     "ggd_knn_tmp_bytes", "ggd_knn_leaf_size", "ggd_knn_max_points", "ggd_knn3", "ggd_knn3_stage",
     "ggd_densify_tmp_bytes", "ggd_densify_stats", "ggd_densify_plan", "ggd_prune_plan", "ggd_densify_emit", "ggd_densify_gather",
     "ggd_density_points", "ggd_density_grid", "ggd_density_lattice", "ggd_teacher_render",
+    "ggd_adam_sparse",
 ]
 
 
@@ -36,6 +37,12 @@ class Params(C.Structure):
                 ("scale_modifier", C.c_float), ("prefiltered", C.c_int32), ("debug", C.c_int32),
                 ("viewmatrix", C.c_void_p), ("projmatrix", C.c_void_p), ("campos", C.c_void_p),
                 ("bg", C.c_void_p), ("raw_attributes", C.c_int32), ("antialiasing", C.c_int32)]
+
+
+class AdamGroup(C.Structure):
+    """ggd_adam_group: one [N][width] float32 parameter group of ggd_adam_sparse (grad NULL or width 0: skipped)."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("width", C.c_int32), ("lr", C.c_float), ("eps", C.c_float)]
 
 
 class GeomView(C.Structure):
@@ -160,6 +167,7 @@ def load():
         lib.ggd_prune_plan.argtypes = [vp, vp, i32, vp, vp, sz, C.POINTER(i64)]
         lib.ggd_densify_emit.argtypes = [vp, vp, i32, i32, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), vp, vp, sz]
         lib.ggd_densify_gather.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, sz]
+        lib.ggd_adam_sparse.argtypes = [vp, vp, i32, i32, C.POINTER(AdamGroup), vp, vp, f32, f32]
         lib.ggd_density_points.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp, i32, vp, vp]
         lib.ggd_density_grid.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, i32, C.c_double, i32, vp, vp]
         lib.ggd_density_lattice.argtypes = [vp, vp, i32, C.c_double, i32, vp]

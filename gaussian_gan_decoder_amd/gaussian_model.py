@@ -191,7 +191,14 @@ class GaussianModel:
     # ---- optimizer (reference: gaussian_model.py:65-97, 217-246) ------------------------------------------------------
     def training_setup(self, training_args, decoder_params=None):
         """Adam over the six named groups (lr 0.0 / eps 1e-15 defaults, per-group rates from `training_args`), the position
-        schedule, and zeroed densification statistics on the parameters' device."""
+        schedule, and zeroed densification statistics on the parameters' device.  training_args.optimizer_type (absent:
+        "default") chooses torch.optim.Adam ("default") or sparse_adam.SparseGaussianAdam ("sparse_adam": one launch per
+        step, over the rows the frame saw; `optimizer.step(radii, P)`; the six [P, ...] groups only, no decoder_params)."""
+        optimizer_type = getattr(training_args, "optimizer_type", "default")
+        if optimizer_type not in ("default", "sparse_adam"):
+            raise ValueError(f"training_setup: optimizer_type must be 'default' or 'sparse_adam' (got {optimizer_type!r})")
+        if optimizer_type == "sparse_adam" and decoder_params is not None:
+            raise ValueError("training_setup: optimizer_type='sparse_adam' takes no decoder_params (one [P, ...] tensor per group)")
         self.percent_dense = training_args.percent_dense
         P, dev = self._xyz.shape[0], self._xyz.device
         self.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
@@ -202,7 +209,11 @@ class GaussianModel:
         groups = [{"params": [getattr(self, attr)], "lr": rates[name], "name": name} for name, attr in PARAM_GROUPS]
         if decoder_params is not None:
             groups += decoder_params
-        self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+        if optimizer_type == "sparse_adam":
+            from .sparse_adam import SparseGaussianAdam
+            self.optimizer = SparseGaussianAdam(groups, lr=0.0, eps=1e-15)
+        else:
+            self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
         self.xyz_scheduler_args = get_expon_lr_func(lr_init=training_args.position_lr_init * self.spatial_lr_scale,
                                                     lr_final=training_args.position_lr_final * self.spatial_lr_scale,
                                                     lr_delay_mult=training_args.position_lr_delay_mult,

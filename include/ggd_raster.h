@@ -628,6 +628,30 @@ int ggd_densify_emit(ggd_ctx* ctx, void* stream, int32_t P, int32_t new_P, int32
 int ggd_densify_gather(ggd_ctx* ctx, void* stream, int32_t P, int32_t new_P, int32_t width, const float* in, float* out,
                        const void* tmp, size_t tmp_bytes);
 
+/*
+ * Sparse Adam of the fitting loop (csrc/ggd_adam.hip): the published adamUpdate rule of the accelerated 3DGS rasterizer
+ * (SparseGaussianAdam) over up to 8 parameter groups in ONE launch, in place, with no host wait, no allocation and no
+ * device-side table (`groups` is HOST memory and travels by value in the kernel arguments).
+ * A group is four DEVICE float32 arrays [N][width]; grad == NULL or width == 0 skips the group.  Exactly one of visible
+ * (uint8 [N]: row i is updated when visible[i] != 0) and radii (int32 [N]: when radii[i] > 0, as in ggd_densify_stats) is
+ * given.  Per element of an updated row, in fp32, every operation rounded on its own, in this order:
+ *   m' = (b1 * m) + ((1.0f - b1) * g)     v' = (b2 * v) + (((1.0f - b2) * g) * g)     p' = p + (((-lr) * m') / (sqrtf(v') + eps))
+ * (no bias correction, no step counter).  For a row that is not updated no byte of param, grad or the moments is loaded and
+ * none is stored: a NaN there is never seen.  Arrays whose four base pointers are congruent modulo 16 move as 16-byte
+ * accesses (any common offset from a 16-byte boundary will do); other groups are run one float at a time.
+ * GGD_E_INVALID, nothing launched: NULL ctx or table; N < 0 or N > 2^26; n_groups outside 1..8; both or neither of visible /
+ * radii; width < 0 or N * width >= 2^31; a group that is not skipped with a NULL param or moment, or a pointer that is not
+ * 4-byte aligned.  N == 0 and a table of skipped groups are legal and launch nothing.
+ */
+typedef struct {
+  float* param; const float* grad; float* exp_avg; float* exp_avg_sq;   /* [N][width] float32 each; grad NULL = skip group */
+  int32_t width;                                                        /* floats per row; 0 = skip group */
+  float lr, eps;
+} ggd_adam_group;
+int ggd_adam_sparse(ggd_ctx* ctx, void* stream, int32_t N, int32_t n_groups, const ggd_adam_group* groups /* host memory */,
+                    const uint8_t* visible /* [N] or NULL */, const int32_t* radii /* [N] or NULL */,
+                    float beta1, float beta2);
+
 /* ggd_decoder_backward + ggd_decoder_wgrad over point chunks of `chunk` points, each chunk's weight-gradient kernel launched
  * right behind its backward kernel so that it reads dz / z from the Infinity Cache.  chunk <= 0 or chunk > N: one chunk;
  * otherwise `chunk` is ROUNDED UP to a multiple of 256 points (one batch of a backward workgroup = four weight-gradient
