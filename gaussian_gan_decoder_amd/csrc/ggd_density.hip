@@ -87,8 +87,12 @@ __device__ __forceinline__ float dn_act(int act, float v) {
   return v;
 }
 
-// the mean over the three planes of the point's sample, channels 4 q .. 4 q + 3: gather4_kernel's expressions without the
-// modulation, restated (gather4_kernel calling one shared function compiles to another instruction stream; it stays as it is)
+// The mean over the three planes of the point's sample, channels 4 q .. 4 q + 3: gather4_kernel (ggd_triplane.hip) without the
+// modulation.  Shared with it, through ggd_planes.h: the cell, and the coordinates, inside test, weight and texel of each tap.
+// NOT shared: the loop around them (request every tap, then sum the inside ones) -- one per-point function called by both
+// kernels compiled to other instruction streams in both (density_kernel<true, *>: 156 -> 160 VGPRs), and so did taking the
+// tap's coordinates after the inside test instead of before it.  To re-check after a change here or in
+// ggd_planes.h: python scripts/kernel_diff.py OLD NEW over two builds; gather4_kernel and density_kernel must report `same`.
 template <bool G3>
 __device__ __forceinline__ float4 dn_gather(const float* __restrict__ grids_cl, int D, int H, int W, int axes, float x, float y,
                                             float z, int q) {
@@ -98,28 +102,19 @@ __device__ __forceinline__ float4 dn_gather(const float* __restrict__ grids_cl, 
   float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 #pragma unroll
   for (int p = 0; p < 3; ++p) {
-    float u, v, w = 0.0f;
-    if (G3) grid_uvw(axes, p, x, y, z, u, v, w); else plane_uv(p, x, y, z, u, v);
-    const float ix = ((u + 1.0f) * (float)W - 1.0f) * 0.5f;
-    const float iy = ((v + 1.0f) * (float)H - 1.0f) * 0.5f;
-    const float iz = G3 ? ((w + 1.0f) * (float)D - 1.0f) * 0.5f : 0.0f;
-    const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
-    const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
-    const float ax = ix - fx, ay = iy - fy, az = iz - fz;
+    const PlaneCell cell = plane_cell<G3>(axes, p, x, y, z, D, H, W);
+    const PlaneTap corner = cell_corner<G3>(cell);
     float4 t[G3 ? 8 : 4];   // all taps of the plane are requested before the first is used
     float wg[G3 ? 8 : 4];
     bool ins[G3 ? 8 : 4];
 #pragma unroll
     for (int k = 0; k < (G3 ? 8 : 4); ++k) {
-      const int xx = x0 + (k & 1), yy = y0 + ((k >> 1) & 1), zz = G3 ? z0 + (k >> 2) : 0;
-      const bool in = tap_inside(fx, k & 1, W) && tap_inside(fy, (k >> 1) & 1, H) && (!G3 || tap_inside(fz, k >> 2, Dd));
-      // weights in grid_sampler's order: (x) * (y) [* (z)]
-      float wk = ((k & 1) ? ax : 1.0f - ax) * ((k & 2) ? ay : 1.0f - ay);
-      if (G3) wk = wk * ((k & 4) ? az : 1.0f - az);
-      wg[k] = wk;
+      const PlaneTap tap = tap_at<G3>(corner, k);
+      const bool in = tap_in<G3>(cell, k, Dd, H, W);
+      wg[k] = tap_weight<G3>(cell, k);
       ins[k] = in;
       t[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (in) t[k] = *reinterpret_cast<const float4*>(grids_cl + p * grid_stride + (((size_t)zz * H + yy) * W + xx) * C + 4 * q);
+      if (in) t[k] = *reinterpret_cast<const float4*>(grids_cl + p * grid_stride + tap_texel(tap, H, W) * C + 4 * q);
     }
 #pragma unroll
     for (int k = 0; k < (G3 ? 8 : 4); ++k) {
@@ -253,22 +248,19 @@ bool lattice_source(int n, double cube_length, int lattice, DnSrc& src) {
   return true;
 }
 
-int launch_density(ggd_ctx* ctx, hipStream_t s, const char* who, const float* grids_cl, int C, int D, int H, int W, int axes,
-                   float box_warp, const float* w1, const float* b1, const float* w2, const float* b2, int act, const DnSrc& src,
-                   int64_t N, float* sigma, float* rgb) {
-  if (C != DN_C) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": 32 plane channels, 64 hidden units and 32 rgb channels only");
-  if (axes < 0 || axes > 1 || D < 0 || (D == 0 && axes != 0))
-    return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": bad axes / depth (the 2-D form has the EG3D axes only)");
-  if (act < 0 || act > 2) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": rgb_act is 0 (sigmoid), 1 (lrelu) or 2 (none)");
+int launch_density(ggd_ctx* ctx, hipStream_t s, const char* who, const ggd_plane_set& ps, const ggd_field_weights& fw,
+                   const DnSrc& src, int64_t N, float* sigma, float* rgb) {
+  const int rc = ggd_check_field(ctx, who, ps, fw);
+  if (rc != GGD_OK) return rc;
   if (N <= 0) return GGD_OK;
-  if (!grids_cl || !w1 || !b1 || !w2 || !b2 || !sigma || H <= 0 || W <= 0 || box_warp == 0.0f)
+  if (!ps.grids_cl || !fw.w1 || !fw.b1 || !fw.w2 || !fw.b2 || !sigma || ps.H <= 0 || ps.W <= 0 || ps.box_warp == 0.0f)
     return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": bad argument");
-  const float scale = 2.0f / box_warp;
+  const float scale = 2.0f / ps.box_warp;
   const dim3 grid((unsigned)((N + DN_POINTS - 1) / DN_POINTS));
-  ggd_dispatch<2>(D > 0, [&](auto g3) {
+  ggd_dispatch<2>(ps.D > 0, [&](auto g3) {
     ggd_dispatch<2>(rgb != nullptr, [&](auto want_rgb) {
       hipLaunchKernelGGL((density_kernel<decltype(g3)::value != 0, decltype(want_rgb)::value != 0>), grid, dim3(256), 0, s,
-                         grids_cl, D, H, W, axes, scale, w1, b1, w2, b2, act, src, N, sigma, rgb);
+                         ps.grids_cl, ps.D, ps.H, ps.W, ps.axes, scale, fw.w1, fw.b1, fw.w2, fw.b2, fw.act, src, N, sigma, rgb);
     });
   });
   GGD_HIP(hipGetLastError());
@@ -277,11 +269,17 @@ int launch_density(ggd_ctx* ctx, hipStream_t s, const char* who, const float* gr
 
 }  // namespace
 
-int ggd_launch_density_points(ggd_ctx* ctx, hipStream_t s, const char* who, const float* grids_cl, int C, int D, int H, int W,
-                              int axes, float box_warp, const float* w1, const float* b1, const float* w2, const float* b2, int act,
+int ggd_check_field(ggd_ctx* ctx, const char* who, const ggd_plane_set& ps, const ggd_field_weights& fw) {
+  if (ps.C != DN_C) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": 32 plane channels, 64 hidden units and 32 rgb channels only");
+  const int rc = ggd_check_plane_set(ctx, who, ps);
+  if (rc != GGD_OK) return rc;
+  if (fw.act < 0 || fw.act > 2) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": rgb_act is 0 (sigmoid), 1 (lrelu) or 2 (none)");
+  return GGD_OK;
+}
+
+int ggd_launch_density_points(ggd_ctx* ctx, hipStream_t s, const char* who, const ggd_plane_set& ps, const ggd_field_weights& fw,
                               const float* pos, int64_t N, float* sigma, float* rgb) {
-  const DnSrc src{pos, 0, 0, 0.0f, 0.0f};
-  return launch_density(ctx, s, who, grids_cl, C, D, H, W, axes, box_warp, w1, b1, w2, b2, act, src, N, sigma, rgb);
+  return launch_density(ctx, s, who, ps, fw, DnSrc{pos, 0, 0, 0.0f, 0.0f}, N, sigma, rgb);
 }
 
 extern "C" int ggd_density_points(ggd_ctx* ctx, void* stream, const float* grids_cl, int32_t C, int32_t D, int32_t H, int32_t W,
@@ -289,9 +287,9 @@ extern "C" int ggd_density_points(ggd_ctx* ctx, void* stream, const float* grids
                                   const float* b2, int32_t rgb_act, const float* pos, int32_t N, float* sigma, float* rgb) {
   if (!ctx) return GGD_E_INVALID;
   if (N > 0 && !pos) return ggd_fail(ctx, GGD_E_INVALID, "ggd_density_points: bad argument");
-  const DnSrc src{pos, 0, 0, 0.0f, 0.0f};
-  return launch_density(ctx, static_cast<hipStream_t>(stream), "ggd_density_points", grids_cl, C, D, H, W, axes, box_warp, w1, b1,
-                        w2, b2, rgb_act, src, N, sigma, rgb);
+  const ggd_plane_set ps = {.grids_cl = grids_cl, .C = C, .D = D, .H = H, .W = W, .axes = axes, .box_warp = box_warp};
+  const ggd_field_weights fw = {.w1 = w1, .b1 = b1, .w2 = w2, .b2 = b2, .act = rgb_act};
+  return ggd_launch_density_points(ctx, static_cast<hipStream_t>(stream), "ggd_density_points", ps, fw, pos, N, sigma, rgb);
 }
 
 extern "C" int ggd_density_grid(ggd_ctx* ctx, void* stream, const float* grids_cl, int32_t C, int32_t D, int32_t H, int32_t W,
@@ -302,8 +300,9 @@ extern "C" int ggd_density_grid(ggd_ctx* ctx, void* stream, const float* grids_c
   DnSrc src;
   if (!lattice_source(n, cube_length, lattice, src))
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_density_grid: 2 <= n <= 1024, cube_length > 0, lattice 0 (reference) or 1 (regular)");
-  return launch_density(ctx, static_cast<hipStream_t>(stream), "ggd_density_grid", grids_cl, C, D, H, W, axes, box_warp, w1, b1,
-                        w2, b2, rgb_act, src, (int64_t)n * n * n, sigma, rgb);
+  const ggd_plane_set ps = {.grids_cl = grids_cl, .C = C, .D = D, .H = H, .W = W, .axes = axes, .box_warp = box_warp};
+  const ggd_field_weights fw = {.w1 = w1, .b1 = b1, .w2 = w2, .b2 = b2, .act = rgb_act};
+  return launch_density(ctx, static_cast<hipStream_t>(stream), "ggd_density_grid", ps, fw, src, (int64_t)n * n * n, sigma, rgb);
 }
 
 extern "C" int ggd_density_lattice(ggd_ctx* ctx, void* stream, int32_t n, double cube_length, int32_t lattice, float* pos) {

@@ -311,8 +311,9 @@ extern "C" int ggd_teacher_render(ggd_ctx* ctx, void* stream, const float* grids
   if (M < 0 || (int64_t)M * (Nc + Ni) >= ((int64_t)1 << 31))
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_teacher_render: 0 <= rays, rays * samples < 2^31");
   // the field's own refusals (channels, axes, depth, activation), before anything is launched
-  int rc = ggd_launch_density_points(ctx, s, who, grids_cl, C, D, H, W, axes, box_warp, w1, b1, w2, b2, rgb_act, nullptr, 0, nullptr,
-                                     nullptr);
+  const ggd_plane_set ps = {.grids_cl = grids_cl, .C = C, .D = D, .H = H, .W = W, .axes = axes, .box_warp = box_warp};
+  const ggd_field_weights fw = {.w1 = w1, .b1 = b1, .w2 = w2, .b2 = b2, .act = rgb_act};
+  int rc = ggd_check_field(ctx, who, ps, fw);
   if (rc != GGD_OK) return rc;
   if (M == 0) return GGD_OK;
   if (!grids_cl || !w1 || !b1 || !w2 || !b2 || H <= 0 || W <= 0 || box_warp == 0.0f || !origins || !dirs || !coarse_table ||
@@ -340,14 +341,12 @@ extern "C" int ggd_teacher_render(ggd_ctx* ctx, void* stream, const float* grids
   hipLaunchKernelGGL(tr_coarse_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, tab, delta, Nc, (int64_t)nc, origins, dirs,
                      u_coarse, sm.depth_c, sm.xyz_c);
   GGD_HIP(hipGetLastError());
-  rc = ggd_launch_density_points(ctx, s, who, grids_cl, C, D, H, W, axes, box_warp, w1, b1, w2, b2, rgb_act, sm.xyz_c, (int64_t)nc,
-                                 sm.sigma_c, sm.rgb_c);
+  rc = ggd_launch_density_points(ctx, s, who, ps, fw, sm.xyz_c, (int64_t)nc, sm.sigma_c, sm.rgb_c);
   if (rc != GGD_OK) return rc;
   if (Ni > 0) {
     hipLaunchKernelGGL(tr_importance_kernel, rays, wg, 0, s, M, Nc, Ni, use_crop, lim, origins, dirs, u_fine, sm);
     GGD_HIP(hipGetLastError());
-    rc = ggd_launch_density_points(ctx, s, who, grids_cl, C, D, H, W, axes, box_warp, w1, b1, w2, b2, rgb_act, sm.xyz_f, (int64_t)nf,
-                                   sm.sigma_f, sm.rgb_f);
+    rc = ggd_launch_density_points(ctx, s, who, ps, fw, sm.xyz_f, (int64_t)nf, sm.sigma_f, sm.rgb_f);
     if (rc != GGD_OK) return rc;
   }
   hipLaunchKernelGGL(tr_composite_kernel, rays, wg, 0, s, M, Nc, Ni, use_crop, lim, white_back, sm, features, depth, weights, range);

@@ -11,35 +11,37 @@
 // line): lane = channel, 64/C points per wave; every texel access is one coalesced line read, and the backward's
 // scatter-add is one line-wide group of float atomics per texel (torch's NCHW grid_sampler_2d_backward issues one
 // scattered atomic per (point, channel): 9.6 ms per 5e5 points measured on MI355X; this kernel is HBM/L2 bound).
+//
+// Kernels: plane_kernel<C, G3, BACKWARD> (lane = channel; the forward for C < 16, the backward for few points or C < 16),
+// gather4_kernel<C, G3> (the forward for C >= 16), sr_keys_kernel<G3> + the library's sort + sr_accumulate_kernel<C, G3>
+// (the backward for many points, C >= 16).  G3: tri-grids (D > 0).  The tap arithmetic of all of them is ggd_planes.h's.
 #include "ggd_common.h"
 #include "ggd_planes.h"
 
 namespace {
 
-struct Tap { int idx[4]; float w[4]; };  // up to 4 texels (idx < 0: outside -> zero padding)
+bool channels_ok(int C) { return C > 0 && C <= 64 && (C & (C - 1)) == 0; }
 
-__device__ __forceinline__ Tap bilinear_taps(float u, float v, int H, int W) {
-  // grid_sample, align_corners = False: pixel = ((g + 1) * size - 1) / 2
-  const float ix = ((u + 1.0f) * (float)W - 1.0f) * 0.5f;
-  const float iy = ((v + 1.0f) * (float)H - 1.0f) * 0.5f;
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-  const float ax = ix - fx, ay = iy - fy;
-  Tap t;
-  t.w[0] = (1.0f - ax) * (1.0f - ay); t.w[1] = ax * (1.0f - ay); t.w[2] = (1.0f - ax) * ay; t.w[3] = ax * ay;
-  const bool vx0 = tap_inside(fx, 0, W), vx1 = tap_inside(fx, 1, W), vy0 = tap_inside(fy, 0, H), vy1 = tap_inside(fy, 1, H);
-  t.idx[0] = (vx0 && vy0) ? y0 * W + x0 : -1;
-  t.idx[1] = (vx1 && vy0) ? y0 * W + x1 : -1;
-  t.idx[2] = (vx0 && vy1) ? y1 * W + x0 : -1;
-  t.idx[3] = (vx1 && vy1) ? y1 * W + x1 : -1;
-  return t;
+// The runtime channel count as a compile-time constant: f(std::integral_constant<int, C>{}) for C in {1, 2, 4 .. 64};
+// false, and f not called, for every other count.
+template <typename F>
+bool dispatch_channels(int C, F&& f) {
+  if (!channels_ok(C)) return false;
+  ggd_dispatch<7>(__builtin_ctz((unsigned)C), [&](auto lg) { f(std::integral_constant<int, 1 << decltype(lg)::value>{}); });
+  return true;
 }
 
-template <int C, bool BACKWARD>
-__global__ __launch_bounds__(256) void triplane_kernel(const float* __restrict__ planes_cl, float* __restrict__ dplanes_cl,
-                                                       int H, int W, const float* __restrict__ pos, int N, float scale,
-                                                       const float* __restrict__ dout, float* __restrict__ out,
-                                                       const float* __restrict__ mod) {
+// One kernel for both forms (G3 = false: planes [3][H][W][C], D unused; true: grids [3][D][H][W][C]) and both directions.
+// Tri-grid: every "plane" is a C x D grid sampled with a 3-D grid_sample (trilinear, zero padding, align_corners = False) at
+// the point's three projected coordinates (PanoHead/training/volumetric_rendering/renderer.py:47-58; selected at
+// main/decoder_models/sequential_decoder_reverse.py:42-50).  mod: [C] (2-D) or [D][C], or null.
+// Each form keeps its order of operations: forward w * (texel * m); 2-D backward w * ((dout / 3) * m), m taken once per lane;
+// 3-D backward ((w * (dout / 3)) * m[z]).
+template <int C, bool G3, bool BACKWARD>
+__global__ __launch_bounds__(256) void plane_kernel(const float* __restrict__ grids_cl, float* __restrict__ dgrids_cl, int D,
+                                                    int H, int W, int axes, const float* __restrict__ pos, int N, float scale,
+                                                    const float* __restrict__ dout, float* __restrict__ out,
+                                                    const float* __restrict__ mod) {
   constexpr int PPW = 64 / C;  // points per wave
   const int lane = threadIdx.x & 63;
   const int c = lane % C;
@@ -47,67 +49,26 @@ __global__ __launch_bounds__(256) void triplane_kernel(const float* __restrict__
   const int64_t n = wave * PPW + lane / C;
   if (n >= N) return;
   const float x = scale * pos[3 * n], y = scale * pos[3 * n + 1], z = scale * pos[3 * n + 2];
-  const size_t plane_stride = (size_t)H * W * C;
+  const size_t grid_stride = (size_t)(G3 ? D : 1) * H * W * C;
   float acc = 0.0f;
-  const float m = mod ? mod[c] : 1.0f;   // per-channel modulation of the planes (texel * m, rounded, is what is sampled)
-  const float g = BACKWARD ? dout[n * C + c] * (1.0f / 3.0f) * m : 0.0f;
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    float u, v;
-    plane_uv(p, x, y, z, u, v);
-    const Tap t = bilinear_taps(u, v, H, W);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (t.idx[k] >= 0) {
-        const size_t off = p * plane_stride + (size_t)t.idx[k] * C + c;
-        if (BACKWARD) atomicAdd(dplanes_cl + off, t.w[k] * g);
-        else acc += t.w[k] * (planes_cl[off] * m);
-      }
-    }
-  }
-  if (!BACKWARD) out[n * C + c] = acc * (1.0f / 3.0f);
-}
-
-// ---- PanoHead tri-grid: every "plane" is a C x D grid sampled with a 3-D grid_sample (trilinear, zero padding,
-// align_corners = False) at the point's three projected coordinates (PanoHead/training/volumetric_rendering/
-// renderer.py:47-58; selected at main/decoder_models/sequential_decoder_reverse.py:42-50).  (u, v, w) index (W, H, D).
-// axes: 0 = EG3D plane axes (plane 2 -> (z, x, y)), 1 = PanoHead (plane 2 -> (y, z, x)); plane 0 -> (x, y, z),
-// plane 1 -> (x, z, y) in both.  Grids are channel-last [3][D][H][W][C]: lane = channel, one coalesced line per texel.
-// (grid_uvw: ggd_planes.h)
-template <int C, bool BACKWARD>
-__global__ __launch_bounds__(256) void trigrid_kernel(const float* __restrict__ grids_cl, float* __restrict__ dgrids_cl,
-                                                      int D, int H, int W, int axes, const float* __restrict__ pos, int N,
-                                                      float scale, const float* __restrict__ dout, float* __restrict__ out,
-                                                      const float* __restrict__ mod /*[D][C] or null*/) {
-  constexpr int PPW = 64 / C;  // points per wave
-  const int lane = threadIdx.x & 63;
-  const int c = lane % C;
-  const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-  const int64_t n = wave * PPW + lane / C;
-  if (n >= N) return;
-  const float x = scale * pos[3 * n], y = scale * pos[3 * n + 1], z = scale * pos[3 * n + 2];
-  const size_t grid_stride = (size_t)D * H * W * C;
-  float acc = 0.0f;
+  // modulation (texel * m, rounded, is what is sampled): [C], taken once per lane (2-D), or [D][C], taken at the tap's slice
+  const float m2 = (!G3 && mod) ? mod[c] : 1.0f;
   const float g = BACKWARD ? dout[n * C + c] * (1.0f / 3.0f) : 0.0f;
+  const float gm2 = g * m2;
 #pragma unroll
   for (int p = 0; p < 3; ++p) {
-    float u, v, w;
-    grid_uvw(axes, p, x, y, z, u, v, w);
-    const float ix = ((u + 1.0f) * (float)W - 1.0f) * 0.5f;
-    const float iy = ((v + 1.0f) * (float)H - 1.0f) * 0.5f;
-    const float iz = ((w + 1.0f) * (float)D - 1.0f) * 0.5f;
-    const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
-    const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
-    const float ax = ix - fx, ay = iy - fy, az = iz - fz;
+    const PlaneCell cell = plane_cell<G3>(axes, p, x, y, z, D, H, W);
+    const PlaneTap corner = cell_corner<G3>(cell);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int xx = x0 + (k & 1), yy = y0 + ((k >> 1) & 1), zz = z0 + (k >> 2);
-      if (tap_inside(fx, k & 1, W) && tap_inside(fy, (k >> 1) & 1, H) && tap_inside(fz, k >> 2, D)) {
-        // weights in grid_sampler_3d's order: (x) * (y) * (z)
-        const float wgt = ((k & 1) ? ax : 1.0f - ax) * ((k & 2) ? ay : 1.0f - ay) * ((k & 4) ? az : 1.0f - az);
-        const size_t off = p * grid_stride + (((size_t)zz * H + yy) * W + xx) * C + c;
-        const float m = mod ? mod[zz * C + c] : 1.0f;
-        if (BACKWARD) atomicAdd(dgrids_cl + off, wgt * g * m);
+    for (int k = 0; k < (G3 ? 8 : 4); ++k) {
+      const PlaneTap tap = tap_at<G3>(corner, k);   // (used under the test only)
+      // tap_in's three tests, written out: through the function they are evaluated without the branches between them, another
+      // instruction stream than the tri-grid form of this kernel has had
+      if (tap_inside(cell.fx, k & 1, W) && tap_inside(cell.fy, (k >> 1) & 1, H) && (!G3 || tap_inside(cell.fz, k >> 2, D))) {
+        const float wgt = tap_weight<G3>(cell, k);
+        const size_t off = p * grid_stride + tap_texel(tap, H, W) * C + c;
+        const float m = !G3 ? m2 : mod ? mod[tap.z * C + c] : 1.0f;
+        if (BACKWARD) atomicAdd(dgrids_cl + off, G3 ? wgt * g * m : wgt * gm2);
         else acc += wgt * (grids_cl[off] * m);
       }
     }
@@ -116,11 +77,11 @@ __global__ __launch_bounds__(256) void trigrid_kernel(const float* __restrict__ 
 }
 
 // ---- the gather, four channels per lane (C a multiple of 4, C / 4 a power of two <= 16) -----------------------------------
-// With lane = channel (the kernels above) the 64 / C points of a wave repeat the whole coordinate -> tap arithmetic in every
+// With lane = channel (the kernel above) the 64 / C points of a wave repeat the whole coordinate -> tap arithmetic in every
 // one of their C lanes (~175 VALU instructions per point), and a 128-byte texel line costs a wave instruction per tap and
 // point pair.  Here a point owns C / 4 lanes, each loading 16 bytes of a texel line: a wave holds 256 / C points (8 for
 // C = 32), one global_load_dwordx4 instruction fetches one tap of all of them, and the arithmetic is repeated C / 4 times
-// instead of C times.  Same operations per channel in the same order as the kernels above: bit-identical features.
+// instead of C times.  Same operations per channel in the same order as the kernel above: bit-identical features.
 // (Measured before the rewrite: visiting the points block by block of a 32^3 grid -- every line an L2 hit after its first
 // use -- bought 35 of 336 us and cost a 50 us sort: the gather was bound by its own instruction stream, not by the fabric.)
 template <int C, bool G3>
@@ -140,33 +101,24 @@ __global__ __launch_bounds__(256) void gather4_kernel(const float* __restrict__ 
   float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 #pragma unroll
   for (int p = 0; p < 3; ++p) {
-    float u, v, w = 0.0f;
-    if (G3) grid_uvw(axes, p, x, y, z, u, v, w); else plane_uv(p, x, y, z, u, v);
-    const float ix = ((u + 1.0f) * (float)W - 1.0f) * 0.5f;
-    const float iy = ((v + 1.0f) * (float)H - 1.0f) * 0.5f;
-    const float iz = G3 ? ((w + 1.0f) * (float)D - 1.0f) * 0.5f : 0.0f;
-    const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
-    const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
-    const float ax = ix - fx, ay = iy - fy, az = iz - fz;
+    const PlaneCell cell = plane_cell<G3>(axes, p, x, y, z, D, H, W);
+    const PlaneTap corner = cell_corner<G3>(cell);
     // all taps of the plane are requested before the first is used
     float4 t[G3 ? 8 : 4];
     float wg[G3 ? 8 : 4];
     int zs[G3 ? 8 : 4];
 #pragma unroll
     for (int k = 0; k < (G3 ? 8 : 4); ++k) {
-      const int xx = x0 + (k & 1), yy = y0 + ((k >> 1) & 1), zz = G3 ? z0 + (k >> 2) : 0;
-      const bool in = tap_inside(fx, k & 1, W) && tap_inside(fy, (k >> 1) & 1, H) && (!G3 || tap_inside(fz, k >> 2, Dd));
-      // weights in grid_sampler's order: (x) * (y) [* (z)]
-      float wk = ((k & 1) ? ax : 1.0f - ax) * ((k & 2) ? ay : 1.0f - ay);
-      if (G3) wk = wk * ((k & 4) ? az : 1.0f - az);
-      wg[k] = wk;
-      zs[k] = in ? zz : -1;
+      const PlaneTap tap = tap_at<G3>(corner, k);   // (used under `in` only; taken first: the order the stream depends on)
+      const bool in = tap_in<G3>(cell, k, Dd, H, W);
+      wg[k] = tap_weight<G3>(cell, k);
+      zs[k] = in ? tap.z : -1;
       t[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (in) t[k] = *reinterpret_cast<const float4*>(grids_cl + p * grid_stride + (((size_t)zz * H + yy) * W + xx) * C + 4 * q);
+      if (in) t[k] = *reinterpret_cast<const float4*>(grids_cl + p * grid_stride + tap_texel(tap, H, W) * C + 4 * q);
     }
 #pragma unroll
     for (int k = 0; k < (G3 ? 8 : 4); ++k) {
-      if (zs[k] >= 0) {   // (an outside tap adds nothing: skipped as the kernels above skip it, so that -0 / NaN texels cannot differ)
+      if (zs[k] >= 0) {   // (an outside tap adds nothing: skipped as the kernel above skips it, so that -0 / NaN texels cannot differ)
         float4 m = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
         if (mod) m = *reinterpret_cast<const float4*>(mod + zs[k] * C + 4 * q);
         acc.x += wg[k] * (t[k].x * m.x); acc.y += wg[k] * (t[k].y * m.y);
@@ -179,57 +131,26 @@ __global__ __launch_bounds__(256) void gather4_kernel(const float* __restrict__ 
 }
 
 template <int C>
-int launch_gather4(ggd_ctx* ctx, hipStream_t s, const float* grids_cl, int D, int H, int W, int axes, const float* pos, int N,
-                   float box_warp, float* out, const float* mod) {
+int launch_gather4(ggd_ctx* ctx, hipStream_t s, const ggd_plane_set& ps, const float* pos, int N, float* out, const float* mod) {
   constexpr int PPW = 64 / (C / 4);
   const int64_t waves = ((int64_t)N + PPW - 1) / PPW;
-  const float scale = 2.0f / box_warp;
-  if (D > 0)
-    hipLaunchKernelGGL((gather4_kernel<C, true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, grids_cl, D, H, W, axes,
-                       pos, N, scale, out, mod);
-  else
-    hipLaunchKernelGGL((gather4_kernel<C, false>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, grids_cl, D, H, W, axes,
-                       pos, N, scale, out, mod);
+  ggd_dispatch<2>(ps.D > 0, [&](auto g3) {
+    hipLaunchKernelGGL((gather4_kernel<C, decltype(g3)::value != 0>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s,
+                       ps.grids_cl, ps.D, ps.H, ps.W, ps.axes, pos, N, 2.0f / ps.box_warp, out, mod);
+  });
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }
 
-template <bool BACKWARD>
-int launch_trigrid(ggd_ctx* ctx, hipStream_t s, const float* grids_cl, float* dgrids_cl, int C, int D, int H, int W, int axes,
-                   const float* pos, int N, float box_warp, const float* dout, float* out, const float* mod) {
-  if (N <= 0) return GGD_OK;
-  const float scale = 2.0f / box_warp;
-#define GGD_TG(CC)                                                                                                  \
-  case CC: {                                                                                                        \
-    const int64_t waves = ((int64_t)N + (64 / CC) - 1) / (64 / CC);                                                 \
-    hipLaunchKernelGGL((trigrid_kernel<CC, BACKWARD>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s,          \
-                       grids_cl, dgrids_cl, D, H, W, axes, pos, N, scale, dout, out, mod);                          \
-  } break;
-  switch (C) {
-    GGD_TG(1) GGD_TG(2) GGD_TG(4) GGD_TG(8) GGD_TG(16) GGD_TG(32) GGD_TG(64)
-    default: return ggd_fail(ctx, GGD_E_INVALID, "trigrid: channel count must be a power of two <= 64");
-  }
-#undef GGD_TG
-  GGD_HIP(hipGetLastError());
-  return GGD_OK;
-}
-
-template <bool BACKWARD>
-int launch(ggd_ctx* ctx, hipStream_t s, const float* planes_cl, float* dplanes_cl, int C, int H, int W, const float* pos,
-           int N, float box_warp, const float* dout, float* out, const float* mod) {
-  if (N <= 0) return GGD_OK;
-  const float scale = 2.0f / box_warp;
-#define GGD_TP(CC)                                                                                                  \
-  case CC: {                                                                                                        \
-    const int64_t waves = ((int64_t)N + (64 / CC) - 1) / (64 / CC);                                                 \
-    hipLaunchKernelGGL((triplane_kernel<CC, BACKWARD>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s,         \
-                       planes_cl, dplanes_cl, H, W, pos, N, scale, dout, out, mod);                                 \
-  } break;
-  switch (C) {
-    GGD_TP(1) GGD_TP(2) GGD_TP(4) GGD_TP(8) GGD_TP(16) GGD_TP(32) GGD_TP(64)
-    default: return ggd_fail(ctx, GGD_E_INVALID, "triplane: channel count must be a power of two <= 64");
-  }
-#undef GGD_TP
+// the lane = channel kernel: forward (ps.grids_cl -> out) or backward (dout -> dgrids_cl)
+template <int C, bool BACKWARD>
+int launch_plane(ggd_ctx* ctx, hipStream_t s, const ggd_plane_set& ps, float* dgrids_cl, const float* pos, int N,
+                 const float* dout, float* out, const float* mod) {
+  const int64_t waves = ((int64_t)N + (64 / C) - 1) / (64 / C);
+  ggd_dispatch<2>(ps.D > 0, [&](auto g3) {
+    hipLaunchKernelGGL((plane_kernel<C, decltype(g3)::value != 0, BACKWARD>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s,
+                       ps.grids_cl, dgrids_cl, ps.D, ps.H, ps.W, ps.axes, pos, N, 2.0f / ps.box_warp, dout, out, mod);
+  });
   GGD_HIP(hipGetLastError());
   return GGD_OK;
 }
@@ -250,24 +171,31 @@ constexpr int SR_MIN_POINTS = 49152;   // below: the plain scatter-add (the sort
 struct SrGeom { int W, H, D, xb, yb, zb; };   // D = 0: 2-D planes; bit widths of the (x0 + 1), (y0 + 1), (z0 + 1) key fields
 static inline int sr_bits(int vmax) { int b = 1; while ((1 << b) <= vmax) ++b; return b; }   // bits to hold 0 .. vmax
 
-// cell key of item (point, plane p) and its interpolation fractions; ~0 when no tap lies inside the grid
+// cell key of item (point, plane p) -- plane | z0 + 1 | y0 + 1 | x0 + 1 -- and its interpolation fractions; ~0 when no tap
+// lies inside the grid
 template <bool G3>
 __device__ __forceinline__ uint32_t sr_item(const SrGeom& g, int axes, int p, float x, float y, float z, float& ax, float& ay,
                                             float& az) {
-  float u, v, w = 0.0f;
-  if (G3) grid_uvw(axes, p, x, y, z, u, v, w); else plane_uv(p, x, y, z, u, v);
-  const float ix = ((u + 1.0f) * (float)g.W - 1.0f) * 0.5f, iy = ((v + 1.0f) * (float)g.H - 1.0f) * 0.5f;
-  const float iz = G3 ? ((w + 1.0f) * (float)g.D - 1.0f) * 0.5f : 0.0f;
-  const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
-  ax = ix - fx; ay = iy - fy; az = iz - fz;
-  bool ok = fx >= -1.0f && fx <= (float)(g.W - 1) && fy >= -1.0f && fy <= (float)(g.H - 1);   // false for NaN
-  if (G3) ok = ok && fz >= -1.0f && fz <= (float)(g.D - 1);
+  const PlaneCell c = plane_cell<G3>(axes, p, x, y, z, g.D, g.H, g.W);
+  ax = c.ax(); ay = c.ay(); az = c.az();
+  // does any tap lie inside?  On the float floors, false for NaN.  (Written out here: as a function of ggd_planes.h the same
+  // lines compile sr_keys_kernel<true> to another instruction stream.)
+  bool ok = c.fx >= -1.0f && c.fx <= (float)(g.W - 1) && c.fy >= -1.0f && c.fy <= (float)(g.H - 1);
+  if (G3) ok = ok && c.fz >= -1.0f && c.fz <= (float)(g.D - 1);
   if (!ok) return ~0u;
+  const PlaneTap corner = cell_corner<G3>(c);   // sound under the test above
   uint32_t key = (uint32_t)p;
-  if (G3) key = (key << g.zb) | (uint32_t)((int)fz + 1);
-  key = (key << g.yb) | (uint32_t)((int)fy + 1);
-  key = (key << g.xb) | (uint32_t)((int)fx + 1);
+  if (G3) key = (key << g.zb) | (uint32_t)(corner.z + 1);
+  key = (key << g.yb) | (uint32_t)(corner.y + 1);
+  key = (key << g.xb) | (uint32_t)(corner.x + 1);
   return key;
+}
+
+// the corner of a key's cell: the fields hold corner + 1 >= 0, so these integers are sound and may be range-tested
+template <bool G3>
+__device__ __forceinline__ PlaneTap sr_corner(const SrGeom& g, uint32_t key) {
+  return PlaneTap{(int)(key & ((1u << g.xb) - 1u)) - 1, (int)((key >> g.xb) & ((1u << g.yb) - 1u)) - 1,
+                  G3 ? (int)((key >> (g.xb + g.yb)) & ((1u << g.zb) - 1u)) - 1 : 0};
 }
 
 template <bool G3>
@@ -315,19 +243,18 @@ __global__ __launch_bounds__(256) void sr_accumulate_kernel(
   uint32_t cur = ~0u;                  // the cell whose sums the lane group holds (~0: none)
 
   auto flush = [&](uint32_t key) {
-    const int x0 = (int)(key & ((1u << g.xb) - 1u)) - 1, y0 = (int)((key >> g.xb) & ((1u << g.yb) - 1u)) - 1;
-    const int z0 = G3 ? (int)((key >> (g.xb + g.yb)) & ((1u << g.zb) - 1u)) - 1 : 0;
+    const PlaneTap corner = sr_corner<G3>(g, key);
     const int p = (int)(key >> pshift);
     const int Dd = G3 ? g.D : 1;
     float* base = dgrid + (size_t)p * Dd * g.H * g.W * C + c;
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-      const int xx = x0 + (t & 1), yy = y0 + ((t >> 1) & 1), zz = z0 + (t >> 2);
-      if (xx >= 0 && xx < g.W && yy >= 0 && yy < g.H && zz >= 0 && zz < Dd) {
+      const PlaneTap tap = tap_at<G3>(corner, t);
+      if (tap.x >= 0 && tap.x < g.W && tap.y >= 0 && tap.y < g.H && tap.z >= 0 && tap.z < Dd) {
         float v = acc[t] * (1.0f / 3.0f);
-        if (mod_lds) v *= s_mod[zz * C + c];
-        else if (mod) v *= mod[zz * C + c];
-        atomicAdd(base + (((size_t)zz * g.H + yy) * g.W + xx) * C, v);
+        if (mod_lds) v *= s_mod[tap.z * C + c];
+        else if (mod) v *= mod[tap.z * C + c];
+        atomicAdd(base + tap_texel(tap, g.H, g.W) * C, v);
       }
     }
   };
@@ -393,19 +320,18 @@ size_t sr_tmp_bytes(int N) {
   return 5 * arr + ggd_sort32_tmp_bytes((int64_t)3 * N);
 }
 
-bool sr_supported(int C, int D, int H, int W, int N) {
-  if (!(C == 16 || C == 32 || C == 64) || N < SR_MIN_POINTS || (int64_t)3 * N >= (1ll << 31)) return false;
-  return 2 + sr_bits(W) + sr_bits(H) + (D > 0 ? sr_bits(D) : 0) <= 32;
+bool sr_supported(const ggd_plane_set& ps, int N) {
+  if (ps.C < 16 || N < SR_MIN_POINTS || (int64_t)3 * N >= (1ll << 31)) return false;
+  return 2 + sr_bits(ps.W) + sr_bits(ps.H) + (ps.D > 0 ? sr_bits(ps.D) : 0) <= 32;
 }
 
-// D = 0: the 2-D tri-plane form
 template <int C>
-int launch_sorted_backward(ggd_ctx* ctx, hipStream_t s, int D, int H, int W, int axes, const float* pos, int N, float box_warp,
-                           const float* dout, const float* mod, float* dgrid) {
+int launch_sorted_backward(ggd_ctx* ctx, hipStream_t s, const ggd_plane_set& ps, const float* pos, int N, const float* dout,
+                           const float* mod, float* dgrid) {
   int rc = ggd_reserve_scratch(ctx, sr_tmp_bytes(N), s);
   if (rc != GGD_OK) return rc;
-  const float scale = 2.0f / box_warp;
-  const SrGeom g{W, H, D, sr_bits(W), sr_bits(H), D > 0 ? sr_bits(D) : 0};
+  const float scale = 2.0f / ps.box_warp;
+  const SrGeom g{ps.W, ps.H, ps.D, sr_bits(ps.W), sr_bits(ps.H), ps.D > 0 ? sr_bits(ps.D) : 0};
   const int64_t M = (int64_t)3 * N;
   const size_t arr = ggd_align((size_t)M * sizeof(uint32_t));
   char* p = static_cast<char*>(ctx->scratch);
@@ -416,33 +342,22 @@ int launch_sorted_backward(ggd_ctx* ctx, hipStream_t s, int D, int H, int W, int
   uint32_t* vals_b = reinterpret_cast<uint32_t*>(p); p += arr;
   void* sort_tmp = p;
   const size_t sort_bytes = ggd_sort32_tmp_bytes(M);
-  if (D > 0) hipLaunchKernelGGL((sr_keys_kernel<true>), dim3((N + 255) / 256), dim3(256), 0, s, pos, N, scale, g, axes, keys_src);
-  else hipLaunchKernelGGL((sr_keys_kernel<false>), dim3((N + 255) / 256), dim3(256), 0, s, pos, N, scale, g, axes, keys_src);
+  ggd_dispatch<2>(ps.D > 0, [&](auto g3) {
+    hipLaunchKernelGGL((sr_keys_kernel<decltype(g3)::value != 0>), dim3((N + 255) / 256), dim3(256), 0, s, pos, N, scale, g,
+                       ps.axes, keys_src);
+  });
   ggd_sort32_opts so;
   so.flag_flat_last = true;
   rc = ggd_launch_sort32_iota(ctx, s, keys_src, keys_a, vals_a, keys_b, vals_b, M, 32, sort_tmp, sort_bytes, so);
   if (rc != GGD_OK) return rc;
   const ggd_sort_ctl sc = ggd_sort_ctl::in_tmp(sort_tmp);
-  const uint32_t* n_valid = sc.n_valid;
-  const uint32_t* flat = sc.flat;
   const unsigned blocks = (unsigned)((M + 4 * SR_CHUNK - 1) / (4 * SR_CHUNK));
-  if (D > 0)
-    hipLaunchKernelGGL((sr_accumulate_kernel<C, true>), dim3(blocks), dim3(256), 0, s, keys_a, vals_a, keys_b, vals_b, flat,
-                       n_valid, pos, N, scale, g, axes, dout, mod, dgrid);
-  else
-    hipLaunchKernelGGL((sr_accumulate_kernel<C, false>), dim3(blocks), dim3(256), 0, s, keys_a, vals_a, keys_b, vals_b, flat,
-                       n_valid, pos, N, scale, g, axes, dout, mod, dgrid);
+  ggd_dispatch<2>(ps.D > 0, [&](auto g3) {
+    hipLaunchKernelGGL((sr_accumulate_kernel<C, decltype(g3)::value != 0>), dim3(blocks), dim3(256), 0, s, keys_a, vals_a, keys_b,
+                       vals_b, sc.flat, sc.n_valid, pos, N, scale, g, ps.axes, dout, mod, dgrid);
+  });
   GGD_HIP(hipGetLastError());
   return GGD_OK;
-}
-
-int sorted_backward(ggd_ctx* ctx, hipStream_t s, int C, int D, int H, int W, int axes, const float* pos, int N, float box_warp,
-                    const float* dout, const float* mod, float* dgrid) {
-  switch (C) {
-    case 16: return launch_sorted_backward<16>(ctx, s, D, H, W, axes, pos, N, box_warp, dout, mod, dgrid);
-    case 32: return launch_sorted_backward<32>(ctx, s, D, H, W, axes, pos, N, box_warp, dout, mod, dgrid);
-    default: return launch_sorted_backward<64>(ctx, s, D, H, W, axes, pos, N, box_warp, dout, mod, dgrid);
-  }
 }
 
 }  // namespace
@@ -451,27 +366,32 @@ extern "C" int ggd_planes_gather(ggd_ctx* ctx, void* stream, const float* grids_
                                  int32_t W, int32_t axes, const float* mod, const float* pos, int32_t N, float box_warp,
                                  float* out) {
   if (!ctx) return GGD_E_INVALID;
-  if (axes < 0 || axes > 1 || D < 0 || (D == 0 && axes != 0))
-    return ggd_fail(ctx, GGD_E_INVALID, "ggd_planes_gather: bad axes / depth (the 2-D form has the EG3D axes only)");
+  const ggd_plane_set ps = {.grids_cl = grids_cl, .C = C, .D = D, .H = H, .W = W, .axes = axes, .box_warp = box_warp};
+  int rc = ggd_check_plane_set(ctx, "ggd_planes_gather", ps);
+  if (rc != GGD_OK) return rc;
   if (N > 0 && (!grids_cl || !pos || !out || H <= 0 || W <= 0 || box_warp == 0.0f))
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_planes_gather: bad argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (N <= 0) return GGD_OK;
   // four channels per lane where the channel count allows it (the decoder's 32); lane = channel otherwise
-  if (C == 16) return launch_gather4<16>(ctx, s, grids_cl, D, H, W, axes, pos, N, box_warp, out, mod);
-  if (C == 32) return launch_gather4<32>(ctx, s, grids_cl, D, H, W, axes, pos, N, box_warp, out, mod);
-  if (C == 64) return launch_gather4<64>(ctx, s, grids_cl, D, H, W, axes, pos, N, box_warp, out, mod);
-  if (D == 0) return launch<false>(ctx, s, grids_cl, nullptr, C, H, W, pos, N, box_warp, nullptr, out, mod);
-  return launch_trigrid<false>(ctx, s, grids_cl, nullptr, C, D, H, W, axes, pos, N, box_warp, nullptr, out, mod);
+  const bool known = dispatch_channels(C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    if constexpr (CC >= 16) rc = launch_gather4<CC>(ctx, s, ps, pos, N, out, mod);
+    else rc = launch_plane<CC, false>(ctx, s, ps, nullptr, pos, N, nullptr, out, mod);
+  });
+  if (!known)
+    return ggd_fail(ctx, GGD_E_INVALID, std::string(D > 0 ? "trigrid" : "triplane") + ": channel count must be a power of two <= 64");
+  return rc;
 }
 
 extern "C" int ggd_planes_scatter(ggd_ctx* ctx, void* stream, int32_t C, int32_t D, int32_t H, int32_t W, int32_t axes,
                                   const float* mod, const float* pos, int32_t N, float box_warp, const float* dout,
                                   float* dgrids_cl, int32_t accumulate) {
   if (!ctx) return GGD_E_INVALID;
-  if (!dgrids_cl || H <= 0 || W <= 0 || D < 0 || axes < 0 || axes > 1 || (D == 0 && axes != 0))
+  const ggd_plane_set ps = {.C = C, .D = D, .H = H, .W = W, .axes = axes, .box_warp = box_warp};   // the gradient buffer's shape
+  if (!dgrids_cl || H <= 0 || W <= 0 || !ggd_plane_axes_ok(ps))   // (this entry has always said "bad argument" for the axes too)
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_planes_scatter: bad argument");
-  if (C <= 0 || C > 64 || (C & (C - 1)) != 0)
+  if (!channels_ok(C))
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_planes_scatter: channel count must be a power of two <= 64");
   // every refusal comes before the clear: a refused call leaves the caller's gradient buffer as it was
   if (N > 0 && (!pos || !dout || box_warp == 0.0f)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_planes_scatter: bad argument");
@@ -480,9 +400,16 @@ extern "C" int ggd_planes_scatter(ggd_ctx* ctx, void* stream, int32_t C, int32_t
   if (!accumulate) GGD_HIP(hipMemsetAsync(dgrids_cl, 0, (size_t)3 * Dd * H * W * C * sizeof(float), s));
   if (N <= 0) return GGD_OK;
   // many points per cell: sort the (point, plane) items by cell and sum runs in registers; few: plain scatter-add
-  if (sr_supported(C, D, H, W, N)) return sorted_backward(ctx, s, C, D, H, W, axes, pos, N, box_warp, dout, mod, dgrids_cl);
-  if (D == 0) return launch<true>(ctx, s, nullptr, dgrids_cl, C, H, W, pos, N, box_warp, dout, nullptr, mod);
-  return launch_trigrid<true>(ctx, s, nullptr, dgrids_cl, C, D, H, W, axes, pos, N, box_warp, dout, nullptr, mod);
+  const bool sorted = sr_supported(ps, N);
+  int rc = GGD_OK;
+  dispatch_channels(C, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    if constexpr (CC >= 16) {
+      if (sorted) { rc = launch_sorted_backward<CC>(ctx, s, ps, pos, N, dout, mod, dgrids_cl); return; }
+    }
+    rc = launch_plane<CC, true>(ctx, s, ps, dgrids_cl, pos, N, dout, nullptr, mod);
+  });
+  return rc;
 }
 
 extern "C" int ggd_triplane_forward(ggd_ctx* ctx, void* stream, const float* planes_cl, int32_t C, int32_t H, int32_t W,

@@ -1,6 +1,6 @@
 """Time the plane gather / scatter kernels (csrc/ggd_triplane.hip) at the training step's size: 500 k head-shell points per
-scene, 256 x 256 planes, 32 channels -- EG3D tri-planes and PanoHead tri-grids (depth 3).  GGD_PLANES_BWD=tile|atomic selects
-the older backward forms for an A/B inside separate processes."""
+scene, 256 x 256 planes, 32 channels -- EG3D tri-planes and PanoHead tri-grids (depth 3).  N=<points> sets another size
+(below SR_MIN_POINTS the scatter is the plain scatter-add)."""
 import os
 import sys
 
@@ -28,7 +28,6 @@ def timed(fn):
 
 
 batch = make_scene_batch([0, 1, 2, 3], N, 64, dev, seed=0)
-mode = os.environ.get("GGD_PLANES_BWD", "sorted")
 for name, depth, axes in (("tri-plane", None, "eg3d"), ("tri-grid D=3", 3, "panohead")):
     D = depth or 1
     planes = torch.randn(3, 32 * D, 256, 256, device=dev)
@@ -40,11 +39,11 @@ for name, depth, axes in (("tri-plane", None, "eg3d"), ("tri-grid D=3", 3, "pano
         out = planes_gather(pcl, pos, 1.0, axes, depth, mod=m)
         t_f = timed(lambda: planes_gather(pcl.detach(), pos, 1.0, axes, depth, mod=m))
         t_b = timed(lambda: torch.autograd.grad(out, pcl, gout, retain_graph=True))
-        print(f"{name:14s} mod={'yes' if m is not None else 'no ':3s} N={N}: gather {t_f:7.1f} us   scatter {t_b:7.1f} us  (mode {mode})")
+        print(f"{name:14s} mod={'yes' if m is not None else 'no ':3s} N={N}: gather {t_f:7.1f} us   scatter {t_b:7.1f} us")
     # 4 scenes in one node
     mods = (1 + 0.25 * torch.randn(4, D, 32, device=dev))
     out = planes_gather(pcl, batch.positions, 1.0, axes, depth, mod=mods)
     g4 = torch.randn(4 * N, 32, device=dev)
     t_f = timed(lambda: planes_gather(pcl.detach(), batch.positions, 1.0, axes, depth, mod=mods))
     t_b = timed(lambda: torch.autograd.grad(out, pcl, g4, retain_graph=True))
-    print(f"{name:14s} 4 scenes: gather {t_f:7.1f} us   scatter {t_b:7.1f} us  (mode {mode})")
+    print(f"{name:14s} 4 scenes: gather {t_f:7.1f} us   scatter {t_b:7.1f} us")

@@ -334,7 +334,8 @@ def build(c):
 
 
 def points_per_wave(C, gather):
-    """points per wave of the kernel that runs: gather4 (four channels per lane) for C in {16, 32, 64}, lane = channel else"""
+    """points per wave of the kernel that runs: gather4_kernel (four channels per lane) for the gather with C in {16, 32, 64},
+    plane_kernel (lane = channel) else"""
     return 256 // C if gather and C in (16, 32, 64) else 64 // C
 
 

@@ -50,8 +50,9 @@ def test_panohead_decoder_forward_matches_reference_on_cpu():
 
 @pytest.mark.gpu
 def test_panohead_decoder_forward_matches_reference_on_gpu(native_lib):
-    """Same fixture through the HIP tri-grid gather (ggd_trigrid_forward) + the fp32 module (<= 2e-5) and through the
-    fused f16-MFMA decoder (<= 2e-3); the gather's backward against torch's grid_sample autograd."""
+    """Same fixture through the HIP tri-grid gather (ggd_planes_gather: gather4_kernel<32, true>) + the fp32 module (<= 2e-5)
+    and through the fused f16-MFMA decoder (<= 2e-3); the gather's backward (plane_kernel<32, true, true>) against torch's
+    grid_sample autograd."""
     from gaussian_gan_decoder_amd.fused_decoder import FusedDecoder
     f, planes, pos, dec, depth = _load()
     dev = torch.device("cuda:0")

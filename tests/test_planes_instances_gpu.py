@@ -3,7 +3,7 @@ restatement of tests/_planes_ref.py, element by element:  |gpu - ref64| <= 1e-7 
 term, elements of zero budget exactly 0.  The case table, the budgets and where KAPPA comes from: tests/_planes_ref.py;
 tests/test_planes_ref_host.py checks on the host that every case hits the edge it is named for.
 
-Groups: A every instance of the plain forms; B wave / workgroup edges with sentinel rows (direct calls); C the sorted-run
+Groups: A every instance of the plain forms (plane_kernel<C, G3, BACKWARD>, and gather4_kernel<C, G3> for C >= 16); B wave / workgroup edges with sentinel rows (direct calls); C the sorted-run
 backward against the plain one on both sides of SR_MIN_POINTS, modulation in LDS and in memory; D kept-item counts on and
 next to the chunk and stream edges; E 65 launched / 64 live sort tiles; F run lengths; G accumulate; H refusals."""
 import ctypes as C
