@@ -28,6 +28,7 @@ EXPORTS = [
     "ggd_densify_tmp_bytes", "ggd_densify_stats", "ggd_densify_plan", "ggd_prune_plan", "ggd_densify_emit", "ggd_densify_gather",
     "ggd_density_points", "ggd_density_grid", "ggd_density_lattice", "ggd_teacher_render",
     "ggd_adam_sparse",
+    "ggd_forward_features", "ggd_backward_features",
 ]
 
 
@@ -62,6 +63,8 @@ OPT_L1_COUNTED = 7
 STAT_FLAT_STREAK, STAT_SORT_RERUNS, STAT_MSD_FRAMES, STAT_SCAN_IN_SCATTER_FRAMES = 100, 101, 102, 103   # read-only, through get_option
 STAT_L1_COUNTED_FRAMES = 104
 SPLAT_BYTES = 48
+FEATURES_MAX_CHANNELS = 32   # GGD_FEATURES_MAX_CHANNELS
+FEATURES_ROUND = 64          # GGD_FEATURES_ROUND: list entries the feature kernels consume per round
 LANES_SELFTEST_WORDS = 156   # GGD_LANES_SELFTEST_WORDS
 SPLAT_FIELDS = ("x", "y", "hA", "nB", "hC", "thr", "opacity", "r", "g", "b", "ex", "ey")
 
@@ -107,6 +110,10 @@ def load():
         lib.ggd_backward.argtypes = bwd + [vp] * 8
         lib.ggd_backward_aux.argtypes = bwd + [vp, vp] + [vp] * 8
         lib.ggd_backward_abs.argtypes = bwd + [vp, vp] + [vp] * 9
+        # the feature maps: ctx, stream, params, the three buffers, R, features, C, feature_bg, out / ggd_backward_aux's arguments with
+        # (features, C, feature_bg, dL_dfeatmap) before the eight gradient arrays and dL_dfeatures behind them
+        lib.ggd_forward_features.argtypes = [vp, vp, C.POINTER(Params), vp, vp, vp, i64, vp, i32, vp, vp]
+        lib.ggd_backward_features.argtypes = bwd + [vp, vp] + [vp, i32, vp, vp] + [vp] * 9
         lib.ggd_mark_visible.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         lib.ggd_debug_unsorted.argtypes = [vp, vp, vp, vp, i64]
         lib.ggd_selftest_lanes.argtypes = [vp, vp, vp, vp, i32]

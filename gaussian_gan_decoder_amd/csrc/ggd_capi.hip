@@ -786,23 +786,40 @@ extern "C" int ggd_forward_collect(ggd_ctx* ctx, void* stream, int64_t* num_rend
 // entry: which entry point called.  ggd_backward_aux always runs the depth / alpha (AUX) instances, with both of its gradients NULL
 // too; ggd_backward_abs the absgrad ones, with the depth / alpha terms exactly when one of the two gradients is given (without: the
 // plain backward's arithmetic).  radii and the three buffers are the forward's, R its num_rendered
-enum bwd_entry { BWD_PLAIN, BWD_AUX, BWD_ABS };
+// feat (ggd_backward_features): the feature blend's backward runs between the blend backward and the per-Gaussian backward and
+// adds to the same accumulator records; the depth / alpha terms run exactly when one of their gradients is given
+enum bwd_entry { BWD_PLAIN, BWD_AUX, BWD_ABS, BWD_FEATURES };
+struct bwd_features {     // the feature map's side of ggd_backward_features
+  const float* features = nullptr; int C = 0; const float* feature_bg = nullptr;
+  const float* dL_dfeatmap = nullptr; float* dL_dfeatures = nullptr;
+};
+static int check_feature_channels(ggd_ctx* ctx, int C) {
+  if (C < 1 || C > GGD_FEATURES_MAX_CHANNELS)
+    return ggd_fail(ctx, GGD_E_INVALID, "feature channels C = " + std::to_string(C) + " outside 1 .. " + std::to_string(GGD_FEATURES_MAX_CHANNELS));
+  return GGD_OK;
+}
 static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, bwd_entry entry, const ggd_inputs& in,
                          const int32_t* radii, const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
-                         const ggd_pix_grads& pix, const ggd_grads& out) {
+                         const ggd_pix_grads& pix, const ggd_grads& out, const bwd_features* feat = nullptr) {
   (void)hipGetLastError();   // a sticky error another library left in this thread is not ours to report
   int rc = check_params(ctx, prm);
   if (rc != GGD_OK) return rc;
   rc = check_inputs(ctx, prm, in);
   if (rc != GGD_OK) return rc;
   const int P = prm->P;
+  if (feat) {
+    rc = check_feature_channels(ctx, feat->C);
+    if (rc != GGD_OK) return rc;
+    if (P > 0 && (!feat->features || !feat->dL_dfeatmap || !feat->dL_dfeatures))
+      return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward_features: features / dL_dfeatmap / dL_dfeatures is NULL");
+  }
   if (P == 0) return GGD_OK;
   if (!radii || !geom_buf || !img_buf || !pix.dL_dpix || !out.dL_dmeans2D || !out.dL_dcolors || !out.dL_dopacity ||
       !out.dL_dmeans3D || !out.dL_dcov3D || !out.dL_dscales || !out.dL_drots || (prm->M > 0 && !out.dL_dsh) ||
       (R > 0 && !binning_buf))
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward: NULL buffer");
   const bool abs = entry == BWD_ABS;
-  const bool aux = entry == BWD_AUX || (abs && (pix.dL_ddepth || pix.dL_dalpha));
+  const bool aux = entry == BWD_AUX || ((abs || entry == BWD_FEATURES) && (pix.dL_ddepth || pix.dL_dalpha));
   if (abs && !out.dL_dmeans2D_abs) return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward_abs: NULL dL_dmeans2D_abs");
   if (prm->raw_attributes && (!in.opacities || in.cov3D_precomp))
     return ggd_fail(ctx, GGD_E_INVALID, "raw_attributes needs opacities and scales/rotations (no cov3D_precomp)");
@@ -826,12 +843,19 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, bwd_
   }
   if (in.colors_precomp && prm->M > 0 && out.dL_dsh)
     GGD_HIP(hipMemsetAsync(out.dL_dsh, 0, (size_t)P * prm->M * 3 * sizeof(float), s));
+  if (feat) GGD_HIP(hipMemsetAsync(feat->dL_dfeatures, 0, (size_t)P * feat->C * sizeof(float), s));
 
   if (R > 0) {
     StageTimer t(ctx, ST_BLEND_BWD, s);
     rc = ggd_launch_blend_backward(ctx, s, *prm, g.splat, b.list, im.ranges, im.final_T, im.n_contrib, pix, grad_acc, aux,
                                    g.depth_keys, abs);
     if (rc != GGD_OK) return rc;
+    if (feat) {
+      rc = ggd_launch_features_backward(ctx, s, *prm, g.splat, b.list, im.ranges, R > 0xffffffffll ? 0xffffffffu : (uint32_t)R,
+                                        im.final_T, im.n_contrib, feat->features, feat->C, feat->feature_bg, feat->dL_dfeatmap,
+                                        grad_acc, feat->dL_dfeatures);
+      if (rc != GGD_OK) return rc;
+    }
   }
   {
     StageTimer t(ctx, ST_PREPROCESS_BWD, s);
@@ -888,6 +912,49 @@ extern "C" int ggd_backward_abs(ggd_ctx* ctx, void* stream, const ggd_params* pr
                          .dL_dmeans3D = dL_dmeans3D, .dL_dcov3D = dL_dcov3D, .dL_dsh = dL_dsh, .dL_dscales = dL_dscales,
                          .dL_drots = dL_drots, .dL_dmeans2D_abs = dL_dmeans2D_abs};
   return backward_impl(ctx, stream, prm, BWD_ABS, in, radii, geom_buf, binning_buf, img_buf, R, pix, out);
+}
+
+// the feature maps: ggd_forward_features after a completed forward; ggd_backward_features = ggd_backward_aux's arguments + the
+// feature side
+extern "C" int ggd_forward_features(ggd_ctx* ctx, void* stream, const ggd_params* prm, const void* geom_buf,
+                                    const void* binning_buf, const void* img_buf, int64_t R, const float* features, int32_t C,
+                                    const float* feature_bg, float* out_features) {
+  if (!ctx) return GGD_E_INVALID;
+  (void)hipGetLastError();
+  int rc = check_params(ctx, prm);
+  if (rc != GGD_OK) return rc;
+  rc = check_feature_channels(ctx, C);
+  if (rc != GGD_OK) return rc;
+  if (ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, kPendingMsg);
+  if (R < 0) return ggd_fail(ctx, GGD_E_INVALID, "num_rendered < 0");
+  if (!out_features || !img_buf) return ggd_fail(ctx, GGD_E_INVALID, "ggd_forward_features: img_buf / out_features is NULL");
+  if (prm->P > 0 && !features) return ggd_fail(ctx, GGD_E_INVALID, "ggd_forward_features: features is NULL");
+  if (R > 0 && (!geom_buf || !binning_buf)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_forward_features: geom_buf / binning_buf is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const geom_ptrs g = geom_view(prm, geom_buf);
+  const binning_ptrs b = binning_view(R, binning_buf);
+  const img_ptrs im = img_view(prm->width, prm->height, img_buf);
+  return ggd_launch_features_forward(ctx, s, *prm, g.splat, b.list, im.ranges, R > 0xffffffffll ? 0xffffffffu : (uint32_t)R,
+                                     im.n_contrib, features, C, feature_bg, out_features);
+}
+
+extern "C" int ggd_backward_features(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
+                                     const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+                                     const float* rotations, const float* cov3D_precomp, const int32_t* radii,
+                                     const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
+                                     const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, const float* features,
+                                     int32_t C, const float* feature_bg, const float* dL_dfeatmap, float* dL_dmeans2D,
+                                     float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                                     float* dL_dscales, float* dL_drots, float* dL_dfeatures) {
+  const ggd_inputs in = {.means3D = means3D, .shs = shs, .colors_precomp = colors_precomp, .opacities = opacities,
+                         .scales = scales, .rotations = rotations, .cov3D_precomp = cov3D_precomp};
+  const ggd_pix_grads pix = {.dL_dpix = dL_dpix, .dL_ddepth = dL_ddepth, .dL_dalpha = dL_dalpha};
+  const ggd_grads out = {.dL_dmeans2D = dL_dmeans2D, .dL_dcolors = dL_dcolors, .dL_dopacity = dL_dopacity,
+                         .dL_dmeans3D = dL_dmeans3D, .dL_dcov3D = dL_dcov3D, .dL_dsh = dL_dsh, .dL_dscales = dL_dscales,
+                         .dL_drots = dL_drots};
+  const bwd_features feat = {.features = features, .C = C, .feature_bg = feature_bg, .dL_dfeatmap = dL_dfeatmap,
+                             .dL_dfeatures = dL_dfeatures};
+  return backward_impl(ctx, stream, prm, BWD_FEATURES, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, &feat);
 }
 
 extern "C" int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D,

@@ -327,6 +327,17 @@ int ggd_launch_blend_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm
                               const uint32_t* list, const uint32_t* ranges, const float* final_T,
                               const uint32_t* n_contrib, const ggd_pix_grads& pix, float* grad_acc /*[P][GGD_ACC_FLOATS]*/,
                               bool aux, const uint32_t* depth_keys, bool abs);
+// Feature maps (ggd_features.hip; ggd_forward_features / ggd_backward_features): C channels per Gaussian blended over the
+// contributors of a finished colour render.  R: the forward's num_rendered (the list's length); n_contrib / final_T: the image
+// buffer's.  The backward ADDS its conic / opacity / mean2D sums to the accumulator records (between the blend backward and the
+// per-Gaussian backward) and its feature gradients to dL_dfeatures [P, C], which the caller has zero-filled.
+int ggd_launch_features_forward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
+                                const uint32_t* list, const uint32_t* ranges, uint32_t R, const uint32_t* n_contrib,
+                                const float* features, int C, const float* feature_bg /*NULL = 0*/, float* out /*[C, H, W]*/);
+int ggd_launch_features_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
+                                 const uint32_t* list, const uint32_t* ranges, uint32_t R, const float* final_T,
+                                 const uint32_t* n_contrib, const float* features, int C, const float* feature_bg,
+                                 const float* dL_dF /*[C, H, W]*/, float* grad_acc, float* dL_dfeatures /*[P, C]*/);
 // aux: also adds dL/dz (accumulator slot GGD_ACC_DEPTH) times dz/dmean = (view[2], view[6], view[10]) to dL_dmeans3D
 // out.dL_dmeans2D_abs non-null: the absgrad kernels, which write it too
 int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_inputs& in,

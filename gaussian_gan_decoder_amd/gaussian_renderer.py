@@ -52,13 +52,15 @@ def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attri
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           render_depth_alpha=False, antialiasing=False, absgrad=False):
+           render_depth_alpha=False, antialiasing=False, absgrad=False, features=None, feature_bg=None):
     """Stock 3DGS render (reference :19-102).  `pipe` needs .debug, .compute_cov3D_python, .convert_SHs_python.
     render_depth_alpha=True (extension): the dict also holds "depth" (sum alpha_i T_i z_i) and "alpha" (1 - final T),
     differentiable float32 [1, H, W] maps.
     antialiasing=True (extension, upstream's GaussianRasterizationSettings flag): the opacity-compensated 2D filter.
     absgrad=True (extension, gsplat's flag): after backward() `out["viewspace_points"].absgrad` holds the absolute
-    screen-space gradients (float32 [P, 3], overwritten by each backward) for GaussianModel's use_absgrad statistics."""
+    screen-space gradients (float32 [P, 3], overwritten by each backward) for GaussianModel's use_absgrad statistics.
+    features=[P, C] (extension, C <= 32; feature_bg=[C] or None = zeros): the dict also holds "features", the differentiable
+    float32 [C, H, W] map sum alpha_i T_i f_i + T_final feature_bg over the colour's contributors, from the same render pass."""
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, pipe.debug,
                                               render_depth_alpha=render_depth_alpha, antialiasing=antialiasing,
@@ -80,19 +82,22 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
             shs = pc.get_features
     else:
         colors_precomp = override_color
+    feat_kw = {} if features is None and feature_bg is None else dict(features=features, feature_bg=feature_bg)
     out = rasterizer(means3D=pc.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
-                     opacities=pc.get_opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+                     opacities=pc.get_opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, **feat_kw)
     rendered_image, radii = out[0], out[1]
     res = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
            "radii": radii}
     if render_depth_alpha:
         res["depth"], res["alpha"] = out[2], out[3]
+    if features is not None:
+        res["features"] = out[-1]
     return res
 
 
 def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None, scaling_modifier=1.0,
                   override_color=None, debug=False, fused_activations=False, render_depth_alpha=False, antialiasing=False,
-                  absgrad=False):
+                  absgrad=False, features=None, feature_bg=None):
     """Decoder-path render (reference :105-186): scale/rotation always from the model, SH unless override_color.
     "alpha" and "depth" are the radii placeholders the reference returns (:184-185).
     fused_activations=True (extension): hand the RAW `_opacity/_scaling/_rotation` to the
@@ -103,7 +108,9 @@ def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None,
     antialiasing=True (extension): the opacity-compensated 2D filter -- each Gaussian's opacity times
     sqrt(det(cov2D) / det(cov2D + 0.3 I)), so that a Gaussian far smaller than a pixel does not grow brighter and thicker
     when zoomed out; combines with fused_activations and render_depth_alpha.
-    absgrad=True (extension): as in `render`; combines with all of the above."""
+    absgrad=True (extension): as in `render`; combines with all of the above.
+    features=[P, C], feature_bg (extension): as in `render` -- "features" is the [C, H, W] map; combines with everything above but
+    absgrad."""
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug,
                                               raw_attributes=fused_activations, render_depth_alpha=render_depth_alpha,
@@ -120,9 +127,13 @@ def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None,
         opacities, scales, rotations = pc._opacity, pc._scaling, pc._rotation
     else:
         opacities, scales, rotations = pc.get_opacity, pc.get_scaling, pc.get_rotation
+    feat_kw = {} if features is None and feature_bg is None else dict(features=features, feature_bg=feature_bg)
     out = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
-                     opacities=opacities, scales=scales, rotations=rotations, cov3D_precomp=None)
+                     opacities=opacities, scales=scales, rotations=rotations, cov3D_precomp=None, **feat_kw)
     rendered_image, radii = out[0], out[1]
     alpha, depth = (out[3], out[2]) if render_depth_alpha else (radii, radii)
-    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-            "radii": radii, "alpha": alpha, "depth": depth}
+    res = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+           "radii": radii, "alpha": alpha, "depth": depth}
+    if features is not None:
+        res["features"] = out[-1]
+    return res

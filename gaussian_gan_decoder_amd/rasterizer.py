@@ -204,6 +204,27 @@ def _marshal_forward(bg, means3D, colors_precomp, opacities, scales, rotations, 
     return dev, P, inputs, prm, keep
 
 
+def _check_features(features, feature_bg, P: int, absgrad: bool = False):
+    """The feature keywords' refusals (ValueError), before any device call: returns C.  features [P, C] with 1 <= C <=
+    _capi.FEATURES_MAX_CHANNELS, feature_bg None or C elements."""
+    if absgrad:
+        raise ValueError("features cannot be combined with absgrad=True: the absolute screen-space statistic is defined on the "
+                         "colour terms (with the depth / alpha terms), and the feature map's terms are not part of it")
+    if not isinstance(features, torch.Tensor):
+        raise TypeError("features must be a torch.Tensor")
+    if features.dim() != 2 or features.size(0) != P or features.size(1) < 1:
+        raise ValueError(f"features must have dimensions (num_points, C) = ({P}, C) (got {tuple(features.shape)})")
+    Cn = int(features.size(1))
+    if Cn > _capi.FEATURES_MAX_CHANNELS:
+        raise ValueError(f"features has {Cn} channels: at most {_capi.FEATURES_MAX_CHANNELS} are rendered in one pass")
+    if feature_bg is not None:
+        if not isinstance(feature_bg, torch.Tensor):
+            raise TypeError("feature_bg must be a torch.Tensor")
+        if feature_bg.numel() != Cn:
+            raise ValueError(f"feature_bg must have {Cn} elements, one per feature channel (got {feature_bg.numel()})")
+    return Cn
+
+
 def _bytes(n: int, dev) -> torch.Tensor:
     return torch.empty((n,), dtype=torch.uint8, device=dev)
 
@@ -220,14 +241,19 @@ def _alloc_outputs(dev, P: int, W: int, H: int, depth_alpha: bool = False):
 def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier,
                                cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, image_height, image_width,
                                sh, degree, campos, prefiltered, debug, raw_attributes=False, *, render_depth_alpha=False,
-                               antialiasing=False):
+                               antialiasing=False, features=None, feature_bg=None):
     """== upstream `_C.rasterize_gaussians(...)`: returns
     (num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer).  binningBuffer may be larger than
     num_rendered needs (single-call forward with a capacity hint); the sorted list sits at its offset 0 either way, so
     the backward takes num_rendered as R exactly like upstream.  render_depth_alpha=True (extension): the tuple goes on
     with the depth and alpha maps, float32 [1, H, W] each (ggd_forward_aux / ggd_forward_render_aux); everything else is
     bit-identical to the plain call.  antialiasing=True (extension): the opacity-compensated 2D filter (ggd_params.antialiasing);
-    radii and the three buffers' sort / binning contents are those of the plain call, the colour changes."""
+    radii and the three buffers' sort / binning contents are those of the plain call, the colour changes.
+    features (extension; float32 [P, C], C <= 32, with feature_bg float32 [C] or None = zeros): one more launch behind the finished
+    forward (ggd_forward_features) blends the C channels over the colour's contributors; the map, float32 [C, H, W], is appended
+    LAST to the tuple.  Everything in front of it is bit-identical to the call without the keyword."""
+    if features is not None:   # (refused before any device call)
+        n_feat = _check_features(features, feature_bg, means3D.size(0))
     dev, P, inputs, prm, keep = _marshal_forward(
         bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
         tanfovx, tanfovy, image_height, image_width, sh, degree, campos, prefiltered, debug, raw_attributes, antialiasing)
@@ -268,7 +294,17 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     # "last frame x 1.25" every upward swing took the overflow -> exact-retry path, i.e. a host sync
     ctx.capacity_hint[key] = max(int(R.value), int((hint or 0) * _HINT_DECAY))
     out = (int(R.value), color, radii, geom, binning, img)
-    return out + (depth, alpha) if render_depth_alpha else out
+    if render_depth_alpha:
+        out = out + (depth, alpha)
+    if features is not None:
+        feat = _f32c(features, "features", dev)
+        fbg = _f32c(feature_bg, "feature_bg", dev) if feature_bg is not None else None
+        fmap = torch.empty((n_feat, H, W), dtype=torch.float32, device=dev)
+        with _device_guard(dev):
+            ctx.check(lib.ggd_forward_features(ctx.handle, stream, C.byref(prm), _ptr(geom), _ptr(binning), _ptr(img), int(R.value),
+                                               _ptr(feat), n_feat, _ptr(fbg), _ptr(fmap)))
+        out = out + (fmap,)
+    return out
 
 
 class FramePipeline:
@@ -377,7 +413,7 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
                                         cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, dL_dout_color, sh,
                                         degree, campos, geomBuffer, R, binningBuffer, imgBuffer, debug,
                                         raw_attributes=False, opacities=None, *, dL_ddepth=None, dL_dalpha=None,
-                                        antialiasing=False, absgrad=False):
+                                        antialiasing=False, absgrad=False, features=None, feature_bg=None, dL_dfeatmap=None):
     """== upstream `_C.rasterize_gaussians_backward(...)`: returns
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
     dL_ddepth / dL_dalpha (extension, [1, H, W] or [H, W]; None = zero): gradients of the depth and alpha maps of a
@@ -385,7 +421,12 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
     antialiasing=True: the backward of an antialiasing forward; it needs `opacities` (the forward's, as passed to it).
     absgrad=True (extension): the call is ggd_backward_abs and a NINTH tensor follows the eight, dL_dmeans2D_abs [P, 3] =
     (0.5 W sum_pixels |g_x|, 0.5 H sum_pixels |g_y|, 0) with g the per-pixel terms whose signed sums are dL_dmeans2D; the
-    eight are those of ggd_backward (no dL_ddepth / dL_dalpha) or ggd_backward_aux (either given)."""
+    eight are those of ggd_backward (no dL_ddepth / dL_dalpha) or ggd_backward_aux (either given).
+    features (extension; the forward's features [P, C] and feature_bg, with dL_dfeatmap [C, H, W], None = zero): the call is
+    ggd_backward_features, the eight hold the gradients of the colour, depth / alpha (when given) AND feature maps together, and
+    dL_dfeatures [P, C] follows them."""
+    if features is not None:
+        n_feat = _check_features(features, feature_bg, means3D.size(0), absgrad)
     if antialiasing and opacities is None:
         raise ValueError("the antialiasing backward needs the opacities of the forward (opacities=None)")
     H, W = int(dL_dout_color.size(-2)), int(dL_dout_color.size(-1))
@@ -410,6 +451,15 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
     ctx = _capi.context_for(dev)
     # dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations[, dL_dmeans2D_abs]: C order
     shapes = [(P, 3), (P, 3), (P, 1), (P, 3), (P, 6), (P, M, 3), (P, 3), (P, 4)] + ([(P, 3)] if absgrad else [])
+    if features is not None:
+        shapes.append((P, n_feat))
+        feat = _f32c(features, "features", dev)
+        fbg = _f32c(feature_bg, "feature_bg", dev) if feature_bg is not None else None
+        if dL_dfeatmap is None:
+            dL_dfeatmap = torch.zeros((n_feat, H, W), dtype=torch.float32, device=dev)
+        gF = _f32c(dL_dfeatmap, "dL_dfeatmap", dev)
+        if tuple(gF.shape) != (n_feat, H, W):
+            raise ValueError(f"dL_dfeatmap must have dimensions ({n_feat}, {H}, {W}) (got {tuple(gF.shape)})")
     grads = [torch.empty(shape, dtype=torch.float32, device=dev) for shape in shapes]
     if ctx.poison_outputs:   # tests: the library must write every element itself (it does not rely on pre-zeroed arrays)
         for t in grads:
@@ -418,10 +468,14 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
         # the arguments the three entry points share, then the incoming gradients, then the results
         args = [ctx.handle, _stream(dev), C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c), _ptr(op_c), _ptr(sc_c),
                 _ptr(rot_c), _ptr(cov_c), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g)]
-        if aux or absgrad:
+        if aux or absgrad or features is not None:
             args += [_ptr(gD), _ptr(gA)]
+        if features is not None:
+            args += [_ptr(feat), n_feat, _ptr(fbg), _ptr(gF)]
         args += [_ptr(t) for t in grads]
         fn = ctx.lib.ggd_backward_abs if absgrad else (ctx.lib.ggd_backward_aux if aux else ctx.lib.ggd_backward)
+        if features is not None:
+            fn = ctx.lib.ggd_backward_features
         with torch.cuda.device(dev):
             ctx.check(fn(*args))
     return tuple(grads)
@@ -445,20 +499,33 @@ def mark_visible(positions, viewmatrix, projmatrix):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
+                raster_settings, features=None, feature_bg=None):
         rs = raster_settings
         depth_alpha = bool(getattr(rs, "render_depth_alpha", False))
+        # (apply() is called with the feature pair only when features are given: the backward then returns eleven gradients)
+        ctx.has_features = features is not None
+        feat_kw = {}
+        if features is not None:
+            _check_features(features, feature_bg, means3D.size(0), bool(getattr(rs, "absgrad", False)))
+            feat_kw = dict(features=features, feature_bg=feature_bg)
         out = rasterize_gaussians_native(
             rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree,
             rs.campos, rs.prefiltered, rs.debug, getattr(rs, "raw_attributes", False), render_depth_alpha=depth_alpha,
-            **({"antialiasing": True} if getattr(rs, "antialiasing", False) else {}))
+            **({"antialiasing": True} if getattr(rs, "antialiasing", False) else {}), **feat_kw)
         num_rendered, color, radii, geom, binning, img = out[:6]
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
         # absgrad: the backward sets `.absgrad` on the tensor the CALLER holds (inside apply() the inputs are the caller's own
         # objects), so it is kept by reference, not saved for backward
         ctx.means2D_ref = means2D if getattr(rs, "absgrad", False) else None
+        if features is not None:
+            # (feature_bg gets no gradient; saved as given -- None is allowed)
+            ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
+                                  img, opacities, features, feature_bg)
+            ctx.mark_non_differentiable(radii)
+            ctx.set_materialize_grads(False)
+            return (color, radii) + ((out[6], out[7]) if depth_alpha else ()) + (out[-1],)
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
                               img, opacities)
         ctx.mark_non_differentiable(radii)
@@ -469,10 +536,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         return color, radii
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_depth=None, grad_alpha=None):
+    def backward(ctx, grad_out_color, _grad_radii, *grad_maps):
         rs = ctx.raster_settings
-        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img, opacities = \
-            ctx.saved_tensors
+        features = feature_bg = grad_features = None
+        if ctx.has_features:   # the map's gradient is the last one: (depth, alpha,) features
+            *grad_maps, grad_features = grad_maps
+            *saved, features, feature_bg = ctx.saved_tensors
+        else:
+            saved = ctx.saved_tensors
+        grad_depth, grad_alpha = (tuple(grad_maps) + (None, None))[:2]
+        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img, opacities = saved
         raw = getattr(rs, "raw_attributes", False)
         aa = bool(getattr(rs, "antialiasing", False))   # (its backward reads the opacities, raw or not)
         if grad_out_color is None:   # (render_depth_alpha: gradients are not materialised)
@@ -486,6 +559,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         absgrad = bool(getattr(rs, "absgrad", False))
         if absgrad:   # (likewise)
             aux["absgrad"] = True
+        if ctx.has_features:
+            aux.update(features=features, feature_bg=feature_bg, dL_dfeatmap=grad_features)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations, *grad_abs) = rasterize_gaussians_backward_native(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
@@ -493,14 +568,27 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.num_rendered, binning, img, rs.debug, raw, opacities if (raw or aa) else None, **aux)
         if absgrad and isinstance(ctx.means2D_ref, torch.Tensor):
             ctx.means2D_ref.absgrad = grad_abs[0]   # gsplat's convention: overwritten by each backward, not accumulated
-        return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
-                grad_rotations, grad_cov3Ds_precomp, None)
+        grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
+                 grad_rotations, grad_cov3Ds_precomp, None)
+        if ctx.has_features:   # (dL_dfeatures is the last array of ggd_backward_features; feature_bg gets no gradient)
+            grads = grads + (grad_abs[-1], None)
+        return grads
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings):
+                        raster_settings, features=None, feature_bg=None):
+    """features / feature_bg (extension, keywords): C <= 32 per-Gaussian channels [P, C] blended over the colour's contributors; the
+    map [C, H, W] is appended LAST to the returned tuple (colour, radii[, depth, alpha], features) and is differentiable in
+    `features` and in everything alpha and T depend on.  Without `features` the call is exactly what it was."""
+    if features is None:
+        if feature_bg is not None:
+            raise ValueError("feature_bg without features")
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                         cov3Ds_precomp, raster_settings)
+    _check_features(features, feature_bg, means3D.size(0), bool(getattr(raster_settings, "absgrad", False)))
+    _require_cuda(means3D)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings)
+                                     cov3Ds_precomp, raster_settings, features, feature_bg)
 
 
 class GaussianRasterizer(nn.Module):
@@ -514,7 +602,7 @@ class GaussianRasterizer(nn.Module):
             return mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, features=None, feature_bg=None):
         rs = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
@@ -527,5 +615,8 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
+        if features is None and feature_bg is None:
+            return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                       cov3D_precomp, rs)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, rs)
+                                   cov3D_precomp, rs, features=features, feature_bg=feature_bg)

@@ -258,6 +258,49 @@ int ggd_backward_abs(ggd_ctx* ctx, void* stream, const ggd_params* prm,
                      float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots,
                      float* dL_dmeans2D_abs);
 
+/*
+ * Feature maps (opt-in extension; every entry point above is unchanged by it).  C per-Gaussian channels, 1 <= C <=
+ * GGD_FEATURES_MAX_CHANNELS, blended over exactly the contributors of a finished colour render -- front to back, same skip
+ * rules, same stop -- with the colour pass's own alpha_i and T_i (so prm->antialiasing's compensated opacity and
+ * prm->raw_attributes' activations are in them: the pass reads the geometry buffer's per-Gaussian records and is indifferent to
+ * how they were produced):
+ *   F[c][p] = sum_i alpha_i T_i f[i][c] + final_T[p] * feature_bg[c]          c = 0 .. C - 1
+ * features     : float[P,C] (device).  feature_bg : float[C] (device) or NULL = zeros; it gets no gradient.
+ * out_features : float[C,H,W], written in full.
+ *   ggd_forward_features   one launch behind a completed forward (ggd_forward / ggd_forward_render or their _aux forms, same
+ *                          ctx, stream-ordered), on that forward's three buffers and its num_rendered; prm as in that forward.
+ *                          The walk of a pixel is bounded by the forward's stored contributor count; alpha is recomputed with
+ *                          the colour kernels' own expressions for the GGD_OPT_EXP_MODE / GGD_OPT_BLEND_CULL in effect (which
+ *                          must be the forward's), so every (pixel, Gaussian) pair is in or out as it was in the colour.
+ *   ggd_backward_features  == ggd_backward_aux's arguments + features, C, feature_bg, dL_dfeatmap[C,H,W] (device) before the eight
+ *                          gradient arrays and dL_dfeatures[P,C] behind them.  One more launch between the blend backward and
+ *                          the per-Gaussian backward: the feature map's dL/dconic, dL/dopacity and dL/dmean2D are ADDED to
+ *                          those of the colour (and depth / alpha) maps in the library's accumulator records, so the eight
+ *                          arrays hold the gradients of all maps together; dL_dfeatures is written in full (zeros for
+ *                          culled Gaussians).  The depth / alpha terms run exactly when dL_ddepth or dL_dalpha is given;
+ *                          without both the colour part is ggd_backward's arithmetic.
+ * GGD_E_INVALID with a message: C outside 1 .. GGD_FEATURES_MAX_CHANNELS; a NULL features (with P > 0), out_features,
+ * dL_dfeatmap or dL_dfeatures.  P = 0 and num_rendered = 0 are valid: num_rendered = 0 gives F = feature_bg everywhere and
+ * all-zero feature gradients.  Like every blend gradient the sums are float atomics: not bit-reproducible from run to run.
+ * GGD_FEATURES_ROUND: list entries both kernels consume per round (tests place lists at its boundaries).
+ */
+#define GGD_FEATURES_MAX_CHANNELS 32
+#define GGD_FEATURES_ROUND 64
+int ggd_forward_features(ggd_ctx* ctx, void* stream, const ggd_params* prm,
+                         const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t num_rendered,
+                         const float* features, int32_t C, const float* feature_bg /* NULL = 0 */, float* out_features);
+int ggd_backward_features(ggd_ctx* ctx, void* stream, const ggd_params* prm,
+                          const float* means3D, const float* shs, const float* colors_precomp,
+                          const float* opacities /* only read when prm->raw_attributes or prm->antialiasing */,
+                          const float* scales, const float* rotations, const float* cov3D_precomp,
+                          const int32_t* radii,
+                          const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t num_rendered,
+                          const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
+                          const float* features, int32_t C, const float* feature_bg, const float* dL_dfeatmap,
+                          float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                          float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots,
+                          float* dL_dfeatures);
+
 /* present[i] = 1 iff Gaussian i passes the view-space z > 0.2 frustum test. */
 int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D,
                      const float* viewmatrix, const float* projmatrix, uint8_t* present);
