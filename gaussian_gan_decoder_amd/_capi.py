@@ -29,6 +29,7 @@ EXPORTS = [
     "ggd_density_points", "ggd_density_grid", "ggd_density_lattice", "ggd_teacher_render",
     "ggd_adam_sparse",
     "ggd_forward_features", "ggd_backward_features",
+    "ggd_forward_distortion", "ggd_backward_distortion",
 ]
 
 
@@ -44,6 +45,12 @@ class AdamGroup(C.Structure):
     """ggd_adam_group: one [N][width] float32 parameter group of ggd_adam_sparse (grad NULL or width 0: skipped)."""
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
                 ("width", C.c_int32), ("lr", C.c_float), ("eps", C.c_float)]
+
+
+class FeatureSide(C.Structure):
+    """ggd_feature_side: the feature map's side of a backward that carries one (ggd_backward_distortion)."""
+    _fields_ = [("features", C.c_void_p), ("C", C.c_int32), ("feature_bg", C.c_void_p), ("dL_dfeatmap", C.c_void_p),
+                ("dL_dfeatures", C.c_void_p)]
 
 
 class GeomView(C.Structure):
@@ -114,6 +121,10 @@ def load():
         # (features, C, feature_bg, dL_dfeatmap) before the eight gradient arrays and dL_dfeatures behind them
         lib.ggd_forward_features.argtypes = [vp, vp, C.POINTER(Params), vp, vp, vp, i64, vp, i32, vp, vp]
         lib.ggd_backward_features.argtypes = bwd + [vp, vp] + [vp, i32, vp, vp] + [vp] * 9
+        # the distortion map: ctx, stream, params, the three buffers, R, out / ggd_backward_aux's arguments, then dL_ddistortion and
+        # the feature bundle (NULL = none)
+        lib.ggd_forward_distortion.argtypes = [vp, vp, C.POINTER(Params), vp, vp, vp, i64, vp]
+        lib.ggd_backward_distortion.argtypes = lib.ggd_backward_aux.argtypes + [vp, C.POINTER(FeatureSide)]
         lib.ggd_mark_visible.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         lib.ggd_debug_unsorted.argtypes = [vp, vp, vp, vp, i64]
         lib.ggd_selftest_lanes.argtypes = [vp, vp, vp, vp, i32]

@@ -788,7 +788,9 @@ extern "C" int ggd_forward_collect(ggd_ctx* ctx, void* stream, int64_t* num_rend
 // plain backward's arithmetic).  radii and the three buffers are the forward's, R its num_rendered
 // feat (ggd_backward_features): the feature blend's backward runs between the blend backward and the per-Gaussian backward and
 // adds to the same accumulator records; the depth / alpha terms run exactly when one of their gradients is given
-enum bwd_entry { BWD_PLAIN, BWD_AUX, BWD_ABS, BWD_FEATURES };
+// dL_ddist (ggd_backward_distortion): the distortion map's backward runs in the same place; always with the AUX instances, whose
+// per-Gaussian kernel turns the accumulator's z slot into dL_dmeans3D.  It may carry a feature map as well (feat)
+enum bwd_entry { BWD_PLAIN, BWD_AUX, BWD_ABS, BWD_FEATURES, BWD_DISTORTION };
 struct bwd_features {     // the feature map's side of ggd_backward_features
   const float* features = nullptr; int C = 0; const float* feature_bg = nullptr;
   const float* dL_dfeatmap = nullptr; float* dL_dfeatures = nullptr;
@@ -800,7 +802,8 @@ static int check_feature_channels(ggd_ctx* ctx, int C) {
 }
 static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, bwd_entry entry, const ggd_inputs& in,
                          const int32_t* radii, const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
-                         const ggd_pix_grads& pix, const ggd_grads& out, const bwd_features* feat = nullptr) {
+                         const ggd_pix_grads& pix, const ggd_grads& out, const bwd_features* feat = nullptr,
+                         const float* dL_ddist = nullptr) {
   (void)hipGetLastError();   // a sticky error another library left in this thread is not ours to report
   int rc = check_params(ctx, prm);
   if (rc != GGD_OK) return rc;
@@ -813,13 +816,14 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, bwd_
     if (P > 0 && (!feat->features || !feat->dL_dfeatmap || !feat->dL_dfeatures))
       return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward_features: features / dL_dfeatmap / dL_dfeatures is NULL");
   }
+  if (entry == BWD_DISTORTION && !dL_ddist) return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward_distortion: dL_ddistortion is NULL");
   if (P == 0) return GGD_OK;
   if (!radii || !geom_buf || !img_buf || !pix.dL_dpix || !out.dL_dmeans2D || !out.dL_dcolors || !out.dL_dopacity ||
       !out.dL_dmeans3D || !out.dL_dcov3D || !out.dL_dscales || !out.dL_drots || (prm->M > 0 && !out.dL_dsh) ||
       (R > 0 && !binning_buf))
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward: NULL buffer");
   const bool abs = entry == BWD_ABS;
-  const bool aux = entry == BWD_AUX || ((abs || entry == BWD_FEATURES) && (pix.dL_ddepth || pix.dL_dalpha));
+  const bool aux = entry == BWD_AUX || entry == BWD_DISTORTION || ((abs || entry == BWD_FEATURES) && (pix.dL_ddepth || pix.dL_dalpha));
   if (abs && !out.dL_dmeans2D_abs) return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward_abs: NULL dL_dmeans2D_abs");
   if (prm->raw_attributes && (!in.opacities || in.cov3D_precomp))
     return ggd_fail(ctx, GGD_E_INVALID, "raw_attributes needs opacities and scales/rotations (no cov3D_precomp)");
@@ -854,6 +858,11 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, bwd_
       rc = ggd_launch_features_backward(ctx, s, *prm, g.splat, b.list, im.ranges, R > 0xffffffffll ? 0xffffffffu : (uint32_t)R,
                                         im.final_T, im.n_contrib, feat->features, feat->C, feat->feature_bg, feat->dL_dfeatmap,
                                         grad_acc, feat->dL_dfeatures);
+      if (rc != GGD_OK) return rc;
+    }
+    if (dL_ddist) {
+      rc = ggd_launch_distortion_backward(ctx, s, *prm, g.splat, b.list, im.ranges, R > 0xffffffffll ? 0xffffffffu : (uint32_t)R,
+                                          im.final_T, im.n_contrib, g.depth_keys, dL_ddist, grad_acc);
       if (rc != GGD_OK) return rc;
     }
   }
@@ -955,6 +964,46 @@ extern "C" int ggd_backward_features(ggd_ctx* ctx, void* stream, const ggd_param
   const bwd_features feat = {.features = features, .C = C, .feature_bg = feature_bg, .dL_dfeatmap = dL_dfeatmap,
                              .dL_dfeatures = dL_dfeatures};
   return backward_impl(ctx, stream, prm, BWD_FEATURES, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, &feat);
+}
+
+// the distortion map: ggd_forward_distortion after a completed forward; ggd_backward_distortion = ggd_backward_aux's arguments +
+// dL_ddistortion and, optionally, the feature map's side of ggd_backward_features as one bundle
+extern "C" int ggd_forward_distortion(ggd_ctx* ctx, void* stream, const ggd_params* prm, const void* geom_buf,
+                                      const void* binning_buf, const void* img_buf, int64_t R, float* out_distortion) {
+  if (!ctx) return GGD_E_INVALID;
+  (void)hipGetLastError();
+  const int rc = check_params(ctx, prm);
+  if (rc != GGD_OK) return rc;
+  if (ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, kPendingMsg);
+  if (R < 0) return ggd_fail(ctx, GGD_E_INVALID, "num_rendered < 0");
+  if (!out_distortion || !img_buf) return ggd_fail(ctx, GGD_E_INVALID, "ggd_forward_distortion: img_buf / out_distortion is NULL");
+  if (R > 0 && (!geom_buf || !binning_buf)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_forward_distortion: geom_buf / binning_buf is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const geom_ptrs g = geom_view(prm, geom_buf);
+  const binning_ptrs b = binning_view(R, binning_buf);
+  const img_ptrs im = img_view(prm->width, prm->height, img_buf);
+  return ggd_launch_distortion_forward(ctx, s, *prm, g.splat, b.list, im.ranges, R > 0xffffffffll ? 0xffffffffu : (uint32_t)R,
+                                       im.n_contrib, g.depth_keys, out_distortion);
+}
+
+extern "C" int ggd_backward_distortion(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
+                                       const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+                                       const float* rotations, const float* cov3D_precomp, const int32_t* radii,
+                                       const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
+                                       const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, float* dL_dmeans2D,
+                                       float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                                       float* dL_dscales, float* dL_drots, const float* dL_ddistortion,
+                                       const ggd_feature_side* features) {
+  const ggd_inputs in = {.means3D = means3D, .shs = shs, .colors_precomp = colors_precomp, .opacities = opacities,
+                         .scales = scales, .rotations = rotations, .cov3D_precomp = cov3D_precomp};
+  const ggd_pix_grads pix = {.dL_dpix = dL_dpix, .dL_ddepth = dL_ddepth, .dL_dalpha = dL_dalpha};
+  const ggd_grads out = {.dL_dmeans2D = dL_dmeans2D, .dL_dcolors = dL_dcolors, .dL_dopacity = dL_dopacity,
+                         .dL_dmeans3D = dL_dmeans3D, .dL_dcov3D = dL_dcov3D, .dL_dsh = dL_dsh, .dL_dscales = dL_dscales,
+                         .dL_drots = dL_drots};
+  if (!features) return backward_impl(ctx, stream, prm, BWD_DISTORTION, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, nullptr, dL_ddistortion);
+  const bwd_features feat = {.features = features->features, .C = features->C, .feature_bg = features->feature_bg,
+                             .dL_dfeatmap = features->dL_dfeatmap, .dL_dfeatures = features->dL_dfeatures};
+  return backward_impl(ctx, stream, prm, BWD_DISTORTION, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, &feat, dL_ddistortion);
 }
 
 extern "C" int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D,

@@ -318,7 +318,7 @@ int ggd_launch_blend(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const g
 // (zeros for culled Gaussians), so the caller's 8 gradient arrays need no zero-fill passes.
 constexpr int GGD_ACC_FLOATS = 12;   // 48 B: conic A,B,C | opacity | mean2D x,y | colour r,g,b | depth (aux only) | abs mean2D x,y
 constexpr int GGD_ACC_CONIC = 0, GGD_ACC_OPACITY = 3, GGD_ACC_MEAN2D = 4, GGD_ACC_COLOR = 6;
-constexpr int GGD_ACC_DEPTH = 9;     // dL/dz (view-space depth), written only by the depth / alpha backward
+constexpr int GGD_ACC_DEPTH = 9;     // dL/dz (view-space depth), written only by the depth / alpha and the distortion backward
 constexpr int GGD_ACC_ABS = 10;      // sum over pixels of |d/d mean2D x|, |.. y| (slots 10, 11), written only by an absgrad backward
 // aux: the depth / alpha backward (blend_backward_quarter_kernel<..., AUX>, always the quarter form); depth_keys as in
 // ggd_launch_blend, pix.dL_ddepth / pix.dL_dalpha [H, W] (NULL = zero; read only when aux).  abs: the absolute screen-space
@@ -338,6 +338,16 @@ int ggd_launch_features_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& 
                                  const uint32_t* list, const uint32_t* ranges, uint32_t R, const float* final_T,
                                  const uint32_t* n_contrib, const float* features, int C, const float* feature_bg,
                                  const float* dL_dF /*[C, H, W]*/, float* grad_acc, float* dL_dfeatures /*[P, C]*/);
+// Distortion map (ggd_distortion.hip; ggd_forward_distortion / ggd_backward_distortion): D = sum_ij w_i w_j |z_i - z_j| over the
+// contributors of a finished colour render, z from depth_keys as in ggd_launch_blend.  The backward ADDS its conic / opacity /
+// mean2D sums and dL/dz (slot GGD_ACC_DEPTH) to the accumulator records, where the feature blend's backward adds its own.
+int ggd_launch_distortion_forward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
+                                  const uint32_t* list, const uint32_t* ranges, uint32_t R, const uint32_t* n_contrib,
+                                  const uint32_t* depth_keys, float* out /*[H, W]*/);
+int ggd_launch_distortion_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
+                                   const uint32_t* list, const uint32_t* ranges, uint32_t R, const float* final_T,
+                                   const uint32_t* n_contrib, const uint32_t* depth_keys, const float* dL_dD /*[H, W]*/,
+                                   float* grad_acc);
 // aux: also adds dL/dz (accumulator slot GGD_ACC_DEPTH) times dz/dmean = (view[2], view[6], view[10]) to dL_dmeans3D
 // out.dL_dmeans2D_abs non-null: the absgrad kernels, which write it too
 int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_inputs& in,

@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _check_distortion
 from .sh import eval_sh
 
 
@@ -30,8 +30,11 @@ def _screenspace_points(pc):
 
 
 def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attributes=False, render_depth_alpha=False,
-              antialiasing=False, absgrad=False):
+              antialiasing=False, absgrad=False, render_distortion=False):
+    if render_distortion:   # (refused before anything is built; the keyword reaches the settings only when set)
+        _check_distortion(render_depth_alpha, absgrad)
     return GaussianRasterizationSettings(
+        **({"render_distortion": True} if render_distortion else {}),
         raw_attributes=raw_attributes,
         render_depth_alpha=render_depth_alpha,
         antialiasing=antialiasing,
@@ -52,7 +55,8 @@ def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attri
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           render_depth_alpha=False, antialiasing=False, absgrad=False, features=None, feature_bg=None):
+           render_depth_alpha=False, antialiasing=False, absgrad=False, features=None, feature_bg=None,
+           render_distortion=False):
     """Stock 3DGS render (reference :19-102).  `pipe` needs .debug, .compute_cov3D_python, .convert_SHs_python.
     render_depth_alpha=True (extension): the dict also holds "depth" (sum alpha_i T_i z_i) and "alpha" (1 - final T),
     differentiable float32 [1, H, W] maps.
@@ -60,11 +64,14 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     absgrad=True (extension, gsplat's flag): after backward() `out["viewspace_points"].absgrad` holds the absolute
     screen-space gradients (float32 [P, 3], overwritten by each backward) for GaussianModel's use_absgrad statistics.
     features=[P, C] (extension, C <= 32; feature_bg=[C] or None = zeros): the dict also holds "features", the differentiable
-    float32 [C, H, W] map sum alpha_i T_i f_i + T_final feature_bg over the colour's contributors, from the same render pass."""
+    float32 [C, H, W] map sum alpha_i T_i f_i + T_final feature_bg over the colour's contributors, from the same render pass.
+    render_distortion=True (extension; needs render_depth_alpha=True, refuses absgrad): the dict also holds "distortion", the
+    differentiable float32 [1, H, W] map sum_ij w_i w_j |z_i - z_j| (w = alpha T, z the raw view-space depth of "depth") over the
+    colour's contributors -- the distortion loss of Mip-NeRF 360 / 2DGS is its mean times a weight that carries the scene's scale."""
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, pipe.debug,
                                               render_depth_alpha=render_depth_alpha, antialiasing=antialiasing,
-                                              absgrad=absgrad))
+                                              absgrad=absgrad, render_distortion=render_distortion))
     scales = rotations = cov3D_precomp = None
     if pipe.compute_cov3D_python:
         cov3D_precomp = pc.get_covariance(scaling_modifier)
@@ -90,6 +97,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
            "radii": radii}
     if render_depth_alpha:
         res["depth"], res["alpha"] = out[2], out[3]
+    if render_distortion:
+        res["distortion"] = out[4]
     if features is not None:
         res["features"] = out[-1]
     return res
@@ -97,7 +106,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
 
 def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None, scaling_modifier=1.0,
                   override_color=None, debug=False, fused_activations=False, render_depth_alpha=False, antialiasing=False,
-                  absgrad=False, features=None, feature_bg=None):
+                  absgrad=False, features=None, feature_bg=None, render_distortion=False):
     """Decoder-path render (reference :105-186): scale/rotation always from the model, SH unless override_color.
     "alpha" and "depth" are the radii placeholders the reference returns (:184-185).
     fused_activations=True (extension): hand the RAW `_opacity/_scaling/_rotation` to the
@@ -110,11 +119,13 @@ def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None,
     when zoomed out; combines with fused_activations and render_depth_alpha.
     absgrad=True (extension): as in `render`; combines with all of the above.
     features=[P, C], feature_bg (extension): as in `render` -- "features" is the [C, H, W] map; combines with everything above but
-    absgrad."""
+    absgrad.
+    render_distortion=True (extension): as in `render` -- "distortion" is the [1, H, W] map; needs render_depth_alpha=True, combines
+    with everything above but absgrad."""
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug,
                                               raw_attributes=fused_activations, render_depth_alpha=render_depth_alpha,
-                                              antialiasing=antialiasing, absgrad=absgrad))
+                                              antialiasing=antialiasing, absgrad=absgrad, render_distortion=render_distortion))
     means3D = pc.get_xyz
     if xyz_offset is not None:
         means3D = means3D + xyz_offset
@@ -134,6 +145,8 @@ def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None,
     alpha, depth = (out[3], out[2]) if render_depth_alpha else (radii, radii)
     res = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
            "radii": radii, "alpha": alpha, "depth": depth}
+    if render_distortion:
+        res["distortion"] = out[4]
     if features is not None:
         res["features"] = out[-1]
     return res

@@ -61,23 +61,31 @@ class GaussianRasterizationSettings(_SettingsFields):
     screen-space gradients of AbsGS -- per Gaussian the sum over pixels of |each pixel's contribution| to means2D.grad's x
     and y -- and sets them as `means2D.absgrad`, a float32 [P, 3] tensor (third column 0), on the means2D tensor the
     rasterizer was called with.  As in gsplat the attribute is OVERWRITTEN by every backward, not accumulated.  An
-    attribute like antialiasing, for the same reason."""
+    attribute like antialiasing, for the same reason.
+
+    render_distortion (keyword only, default False; needs render_depth_alpha=True, refuses absgrad=True): the rasterizer also
+    returns the differentiable depth-distortion map sum_ij w_i w_j |z_i - z_j| (w = alpha T, raw view-space z), [1, H, W],
+    behind the depth and alpha maps.  An attribute like antialiasing, for the same reason."""
     antialiasing: bool = False   # (instances made without __new__, e.g. by _make, read these class defaults)
     absgrad: bool = False
+    render_distortion: bool = False
 
-    def __new__(cls, *args, antialiasing: bool = False, absgrad: bool = False, **kwargs):
+    def __new__(cls, *args, antialiasing: bool = False, absgrad: bool = False, render_distortion: bool = False, **kwargs):
         self = super().__new__(cls, *args, **kwargs)
         self.antialiasing = bool(antialiasing)
         self.absgrad = bool(absgrad)
+        self.render_distortion = bool(render_distortion)
         return self
 
     def _replace(self, **kwargs):
         aa = kwargs.pop("antialiasing", self.antialiasing)
         ab = kwargs.pop("absgrad", self.absgrad)
-        return type(self)(*super()._replace(**kwargs), antialiasing=aa, absgrad=ab)
+        rd = kwargs.pop("render_distortion", self.render_distortion)
+        return type(self)(*super()._replace(**kwargs), antialiasing=aa, absgrad=ab, render_distortion=rd)
 
     def __repr__(self):
-        return super().__repr__()[:-1] + f", antialiasing={self.antialiasing}, absgrad={self.absgrad})"
+        rd = f", render_distortion={self.render_distortion}" if self.render_distortion else ""
+        return super().__repr__()[:-1] + f", antialiasing={self.antialiasing}, absgrad={self.absgrad}{rd})"
 
 
 def _f32c(t: torch.Tensor, name: str, device) -> torch.Tensor:
@@ -225,6 +233,16 @@ def _check_features(features, feature_bg, P: int, absgrad: bool = False):
     return Cn
 
 
+def _check_distortion(render_depth_alpha: bool, absgrad: bool = False):
+    """The render_distortion keyword's refusals (ValueError), before any device call."""
+    if not render_depth_alpha:
+        raise ValueError("render_distortion=True needs render_depth_alpha=True: its backward extends the depth / alpha backward "
+                         "(the gradient in z travels through the depth map's accumulator slot)")
+    if absgrad:
+        raise ValueError("render_distortion cannot be combined with absgrad=True: the absolute screen-space statistic is defined "
+                         "on the colour terms (with the depth / alpha terms), and the distortion map's terms are not part of it")
+
+
 def _bytes(n: int, dev) -> torch.Tensor:
     return torch.empty((n,), dtype=torch.uint8, device=dev)
 
@@ -241,7 +259,7 @@ def _alloc_outputs(dev, P: int, W: int, H: int, depth_alpha: bool = False):
 def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier,
                                cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, image_height, image_width,
                                sh, degree, campos, prefiltered, debug, raw_attributes=False, *, render_depth_alpha=False,
-                               antialiasing=False, features=None, feature_bg=None):
+                               antialiasing=False, features=None, feature_bg=None, render_distortion=False):
     """== upstream `_C.rasterize_gaussians(...)`: returns
     (num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer).  binningBuffer may be larger than
     num_rendered needs (single-call forward with a capacity hint); the sorted list sits at its offset 0 either way, so
@@ -251,8 +269,13 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     radii and the three buffers' sort / binning contents are those of the plain call, the colour changes.
     features (extension; float32 [P, C], C <= 32, with feature_bg float32 [C] or None = zeros): one more launch behind the finished
     forward (ggd_forward_features) blends the C channels over the colour's contributors; the map, float32 [C, H, W], is appended
-    LAST to the tuple.  Everything in front of it is bit-identical to the call without the keyword."""
-    if features is not None:   # (refused before any device call)
+    LAST to the tuple.  Everything in front of it is bit-identical to the call without the keyword.
+    render_distortion=True (extension; needs render_depth_alpha=True): one more launch behind the finished forward
+    (ggd_forward_distortion) walks the colour's contributors once more; the map, float32 [1, H, W], follows the depth and alpha
+    maps and precedes the feature map.  Everything else is bit-identical to the call without the keyword."""
+    if render_distortion:      # (refused before any device call)
+        _check_distortion(render_depth_alpha)
+    if features is not None:   # (likewise)
         n_feat = _check_features(features, feature_bg, means3D.size(0))
     dev, P, inputs, prm, keep = _marshal_forward(
         bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
@@ -296,6 +319,12 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     out = (int(R.value), color, radii, geom, binning, img)
     if render_depth_alpha:
         out = out + (depth, alpha)
+    if render_distortion:
+        dist = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+        with _device_guard(dev):
+            ctx.check(lib.ggd_forward_distortion(ctx.handle, stream, C.byref(prm), _ptr(geom), _ptr(binning), _ptr(img),
+                                                 int(R.value), _ptr(dist)))
+        out = out + (dist,)
     if features is not None:
         feat = _f32c(features, "features", dev)
         fbg = _f32c(feature_bg, "feature_bg", dev) if feature_bg is not None else None
@@ -413,7 +442,8 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
                                         cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, dL_dout_color, sh,
                                         degree, campos, geomBuffer, R, binningBuffer, imgBuffer, debug,
                                         raw_attributes=False, opacities=None, *, dL_ddepth=None, dL_dalpha=None,
-                                        antialiasing=False, absgrad=False, features=None, feature_bg=None, dL_dfeatmap=None):
+                                        antialiasing=False, absgrad=False, features=None, feature_bg=None, dL_dfeatmap=None,
+                                        dL_ddistortion=None):
     """== upstream `_C.rasterize_gaussians_backward(...)`: returns
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
     dL_ddepth / dL_dalpha (extension, [1, H, W] or [H, W]; None = zero): gradients of the depth and alpha maps of a
@@ -424,14 +454,19 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
     eight are those of ggd_backward (no dL_ddepth / dL_dalpha) or ggd_backward_aux (either given).
     features (extension; the forward's features [P, C] and feature_bg, with dL_dfeatmap [C, H, W], None = zero): the call is
     ggd_backward_features, the eight hold the gradients of the colour, depth / alpha (when given) AND feature maps together, and
-    dL_dfeatures [P, C] follows them."""
+    dL_dfeatures [P, C] follows them.
+    dL_ddistortion (extension, [1, H, W] or [H, W]): the gradient of the distortion map of a render_distortion forward -- the call is
+    ggd_backward_distortion (which carries the feature map's side as well when `features` is given) and the eight hold the
+    gradients of every map together; the depth / alpha instances always run."""
+    if dL_ddistortion is not None:
+        _check_distortion(True, absgrad)
     if features is not None:
         n_feat = _check_features(features, feature_bg, means3D.size(0), absgrad)
     if antialiasing and opacities is None:
         raise ValueError("the antialiasing backward needs the opacities of the forward (opacities=None)")
     H, W = int(dL_dout_color.size(-2)), int(dL_dout_color.size(-1))
     aux = dL_ddepth is not None or dL_dalpha is not None
-    for t, name in ((dL_ddepth, "dL_ddepth"), (dL_dalpha, "dL_dalpha")):
+    for t, name in ((dL_ddepth, "dL_ddepth"), (dL_dalpha, "dL_dalpha"), (dL_ddistortion, "dL_ddistortion")):
         if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) not in ((1, H, W), (H, W))):
             raise ValueError(f"{name} must have dimensions (1, {H}, {W}) or ({H}, {W}) (got "
                              f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__})")
@@ -441,6 +476,7 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
     g = _f32c(dL_dout_color, "dL_dout_color", dev)
     gD = _f32c(dL_ddepth, "dL_ddepth", dev) if dL_ddepth is not None else None
     gA = _f32c(dL_dalpha, "dL_dalpha", dev) if dL_dalpha is not None else None
+    gDist = _f32c(dL_ddistortion, "dL_ddistortion", dev) if dL_ddistortion is not None else None
     rs = GaussianRasterizationSettings(H, W, tanfovx, tanfovy, bg, scale_modifier, viewmatrix, projmatrix, degree,
                                        campos, False, debug, raw_attributes, antialiasing=bool(antialiasing))
     op_c = _f32c(opacities, "opacities", dev) if ((raw_attributes or antialiasing) and opacities is not None) else None
@@ -468,14 +504,22 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
         # the arguments the three entry points share, then the incoming gradients, then the results
         args = [ctx.handle, _stream(dev), C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c), _ptr(op_c), _ptr(sc_c),
                 _ptr(rot_c), _ptr(cov_c), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g)]
-        if aux or absgrad or features is not None:
+        if aux or absgrad or features is not None or gDist is not None:
             args += [_ptr(gD), _ptr(gA)]
-        if features is not None:
-            args += [_ptr(feat), n_feat, _ptr(fbg), _ptr(gF)]
-        args += [_ptr(t) for t in grads]
-        fn = ctx.lib.ggd_backward_abs if absgrad else (ctx.lib.ggd_backward_aux if aux else ctx.lib.ggd_backward)
-        if features is not None:
-            fn = ctx.lib.ggd_backward_features
+        if gDist is not None:   # ggd_backward_aux's arguments, then the map's gradient and the feature bundle (or NULL)
+            side = None
+            if features is not None:
+                side = C.byref(_capi.FeatureSide(feat.data_ptr(), n_feat, None if fbg is None else fbg.data_ptr(), gF.data_ptr(),
+                                                 grads[-1].data_ptr()))
+            args += [_ptr(t) for t in grads[:8]] + [_ptr(gDist), side]
+            fn = ctx.lib.ggd_backward_distortion
+        else:
+            if features is not None:
+                args += [_ptr(feat), n_feat, _ptr(fbg), _ptr(gF)]
+            args += [_ptr(t) for t in grads]
+            fn = ctx.lib.ggd_backward_abs if absgrad else (ctx.lib.ggd_backward_aux if aux else ctx.lib.ggd_backward)
+            if features is not None:
+                fn = ctx.lib.ggd_backward_features
         with torch.cuda.device(dev):
             ctx.check(fn(*args))
     return tuple(grads)
@@ -502,6 +546,9 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raster_settings, features=None, feature_bg=None):
         rs = raster_settings
         depth_alpha = bool(getattr(rs, "render_depth_alpha", False))
+        distortion = bool(getattr(rs, "render_distortion", False))
+        if distortion:
+            _check_distortion(depth_alpha, bool(getattr(rs, "absgrad", False)))
         # (apply() is called with the feature pair only when features are given: the backward then returns eleven gradients)
         ctx.has_features = features is not None
         feat_kw = {}
@@ -512,7 +559,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree,
             rs.campos, rs.prefiltered, rs.debug, getattr(rs, "raw_attributes", False), render_depth_alpha=depth_alpha,
-            **({"antialiasing": True} if getattr(rs, "antialiasing", False) else {}), **feat_kw)
+            **({"antialiasing": True} if getattr(rs, "antialiasing", False) else {}), **feat_kw,
+            **({"render_distortion": True} if distortion else {}))
         num_rendered, color, radii, geom, binning, img = out[:6]
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
@@ -525,14 +573,14 @@ class _RasterizeGaussians(torch.autograd.Function):
                                   img, opacities, features, feature_bg)
             ctx.mark_non_differentiable(radii)
             ctx.set_materialize_grads(False)
-            return (color, radii) + ((out[6], out[7]) if depth_alpha else ()) + (out[-1],)
+            return (color, radii) + tuple(out[6:-1]) + (out[-1],)   # (depth, alpha[, distortion]), features
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning,
                               img, opacities)
         ctx.mark_non_differentiable(radii)
         if depth_alpha:
             # unused outputs arrive as None in the backward: a graph that only reads the colour takes today's backward
             ctx.set_materialize_grads(False)
-            return color, radii, out[6], out[7]
+            return (color, radii) + tuple(out[6:])   # depth, alpha[, distortion]
         return color, radii
 
     @staticmethod
@@ -544,7 +592,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             *saved, features, feature_bg = ctx.saved_tensors
         else:
             saved = ctx.saved_tensors
-        grad_depth, grad_alpha = (tuple(grad_maps) + (None, None))[:2]
+        grad_depth, grad_alpha, grad_distortion = (tuple(grad_maps) + (None, None, None))[:3]
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img, opacities = saved
         raw = getattr(rs, "raw_attributes", False)
         aa = bool(getattr(rs, "antialiasing", False))   # (its backward reads the opacities, raw or not)
@@ -561,6 +609,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             aux["absgrad"] = True
         if ctx.has_features:
             aux.update(features=features, feature_bg=feature_bg, dL_dfeatmap=grad_features)
+        if grad_distortion is not None:   # (a graph that does not read the map takes the backward it took without it)
+            aux["dL_ddistortion"] = grad_distortion
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations, *grad_abs) = rasterize_gaussians_backward_native(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,

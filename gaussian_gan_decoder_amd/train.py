@@ -128,7 +128,8 @@ class DecoderTrainer:
                  scene_streams: bool = False, decoder_precision: str = "bf16", plane_axes: str = "eg3d",
                  triplane_depth=None, fused_planes=None, force_comm=None, antialiasing: bool = False,
                  apply_mask_to_rendering: bool = False, decoder_type: str = "sequential_reversed",
-                 mask_weight: float = 0.0, depth_weight: float = 0.0, geometry_loss_fn=None):
+                 mask_weight: float = 0.0, depth_weight: float = 0.0, geometry_loss_fn=None,
+                 distortion_weight: float = 0.0):
         """plane_axes / triplane_depth: the generator whose planes are decoded -- ("eg3d", None): tri-planes
         [3, C, res, res]; ("panohead", 3): PanoHead's tri-grids [3, C * 3, res, res] sampled with a 3-D grid_sample
         (the reference's default generator: main/train_pano2gaussian_decoder.py:43, PanoHead/train.py:230,318,
@@ -153,7 +154,12 @@ class DecoderTrainer:
         then) and geometry_loss_fn(depth, alpha, teacher_depth, teacher_weights, tanfovx, tanfovy, mask_weight, depth_weight)
         [0] of the same render call is added to the scene's loss; the default geometry_loss_fn is losses.fused_geometry_loss
         (two HIP launches; the torch expression on the CPU).  A batch without the two maps is an error.  The weights are
-        untuned."""
+        untuned.
+        distortion_weight (default 0: off, nothing changes): with a positive weight the scene is rendered with
+        render_depth_alpha=True, render_distortion=True (passed to render_fn only then) and distortion_weight *
+        out["distortion"].mean() is added to the scene's loss -- the distortion loss of Mip-NeRF 360 / 2DGS, which tells a thin
+        surface from a fog of the same expected depth.  The map is in raw view-space depth units, so the weight carries the
+        scene's scale; no value is tuned."""
         import os
         import torch.distributed as dist
         self.force_comm = bool(int(os.environ.get("GGD_FORCE_COMM", "0"))) if force_comm is None else bool(force_comm)
@@ -224,6 +230,11 @@ class DecoderTrainer:
         if self.geometry:
             self.render_kwargs["render_depth_alpha"] = True
         self.geometry_loss_fn = geometry_loss_fn if geometry_loss_fn is not None else fused_geometry_loss
+        self.distortion_weight = float(distortion_weight)
+        if self.distortion_weight < 0:
+            raise ValueError("distortion_weight must not be negative")
+        if self.distortion_weight > 0:
+            self.render_kwargs.update(render_depth_alpha=True, render_distortion=True)
         self.bg =torch.tensor([0.55717, 0.52256, 0.51045], dtype=torch.float32, device=self.device)
         # scene_streams: every local scene's raster + loss on its own HIP stream (own ggd_ctx).  Measured on one MI355X
         # (4 scenes x 500 k points, fused decoder): 21.13 ms / step with and without -- the single-call forward already
@@ -475,6 +486,8 @@ class DecoderTrainer:
             tan = math.tan(fov / 2)
             loss = loss + self.geometry_loss_fn(out["depth"], out["alpha"], batch.teacher_depth[b], batch.teacher_weights[b],
                                                 tan, tan, self.mask_weight, self.depth_weight)[0]
+        if self.distortion_weight > 0:
+            loss = loss + self.distortion_weight * out["distortion"].mean()
         if self.perceptual is not None:
             # the reference evaluates its perceptual network on the whole batch at once (lpips.py:29-31): the rendered
             # images are collected and local_loss makes ONE call on the stack

@@ -301,6 +301,47 @@ int ggd_backward_features(ggd_ctx* ctx, void* stream, const ggd_params* prm,
                           float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots,
                           float* dL_dfeatures);
 
+/*
+ * Depth-distortion map (opt-in extension, the distortion loss of Mip-NeRF 360 / 2DGS; every entry point above is unchanged by
+ * it).  Per pixel, over exactly the contributors of a finished colour render, in list order k = 1 .. n, with w_k = alpha_k T_k
+ * and z_k the view-space depth of the depth plane (raw, not normalised):
+ *   D[p] = sum_i sum_j w_i w_j |z_i - z_j| = 2 sum_k w_k (z_k A_{k-1} - B_{k-1}),   A_k = sum_{j<=k} w_j,  B_k = sum_{j<=k} w_j z_j
+ * The background does not enter; a pixel with fewer than two contributors has D = 0.
+ * out_distortion : float[H,W], written in full.
+ *   ggd_forward_distortion   one launch behind a completed forward (same ctx, stream-ordered), on that forward's three buffers
+ *                            and its num_rendered; prm, GGD_OPT_EXP_MODE and GGD_OPT_BLEND_CULL as in that forward (as for
+ *                            ggd_forward_features).
+ *   ggd_backward_distortion  == ggd_backward_aux's arguments + dL_ddistortion[H,W] (device) + `features`.  One more launch
+ *                            between the blend backward and the per-Gaussian backward ADDS the map's dL/dconic, dL/dopacity,
+ *                            dL/dmean2D and dL/dz to the library's accumulator records; dL/dz reaches dL_dmeans3D as the depth
+ *                            plane's does, so the depth / alpha instances always run (dL_ddepth and dL_dalpha may be NULL).
+ *                            At equal depths the gradient in z is the list order's (the limit of the later record lying behind).
+ *                            features: NULL, or the feature map's side of ggd_backward_features as one bundle -- the call then
+ *                            does that entry point's work as well (ggd_backward_features keeps its signature).
+ * GGD_E_INVALID with a message: a NULL out_distortion, img_buf or dL_ddistortion; NULL geom_buf / binning_buf with
+ * num_rendered > 0; ggd_backward_features' refusals for the bundle.  num_rendered = 0 gives D = 0 everywhere.
+ */
+typedef struct ggd_feature_side {
+  const float* features;      /* [P,C] */
+  int32_t C;
+  const float* feature_bg;    /* [C] or NULL = zeros */
+  const float* dL_dfeatmap;   /* [C,H,W] */
+  float* dL_dfeatures;        /* [P,C], written in full */
+} ggd_feature_side;
+int ggd_forward_distortion(ggd_ctx* ctx, void* stream, const ggd_params* prm,
+                           const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t num_rendered,
+                           float* out_distortion);
+int ggd_backward_distortion(ggd_ctx* ctx, void* stream, const ggd_params* prm,
+                            const float* means3D, const float* shs, const float* colors_precomp,
+                            const float* opacities /* only read when prm->raw_attributes or prm->antialiasing */,
+                            const float* scales, const float* rotations, const float* cov3D_precomp,
+                            const int32_t* radii,
+                            const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t num_rendered,
+                            const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
+                            float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                            float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots,
+                            const float* dL_ddistortion, const ggd_feature_side* features /* NULL = no feature map */);
+
 /* present[i] = 1 iff Gaussian i passes the view-space z > 0.2 frustum test. */
 int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D,
                      const float* viewmatrix, const float* projmatrix, uint8_t* present);
