@@ -30,6 +30,7 @@ EXPORTS = [
     "ggd_adam_sparse",
     "ggd_forward_features", "ggd_backward_features",
     "ggd_forward_distortion", "ggd_backward_distortion",
+    "ggd_backward_camera",
 ]
 
 
@@ -51,6 +52,11 @@ class FeatureSide(C.Structure):
     """ggd_feature_side: the feature map's side of a backward that carries one (ggd_backward_distortion)."""
     _fields_ = [("features", C.c_void_p), ("C", C.c_int32), ("feature_bg", C.c_void_p), ("dL_dfeatmap", C.c_void_p),
                 ("dL_dfeatures", C.c_void_p)]
+
+
+class CameraGrads(C.Structure):
+    """ggd_camera_grads: the three results of ggd_backward_camera (device pointers: [16], [16], [3] floats)."""
+    _fields_ = [("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p)]
 
 
 class GeomView(C.Structure):
@@ -125,6 +131,8 @@ def load():
         # the feature bundle (NULL = none)
         lib.ggd_forward_distortion.argtypes = [vp, vp, C.POINTER(Params), vp, vp, vp, i64, vp]
         lib.ggd_backward_distortion.argtypes = lib.ggd_backward_aux.argtypes + [vp, C.POINTER(FeatureSide)]
+        # the camera's gradients: ggd_backward_distortion's arguments (each map's side may be NULL), then the bundle of the results
+        lib.ggd_backward_camera.argtypes = lib.ggd_backward_distortion.argtypes + [C.POINTER(CameraGrads)]
         lib.ggd_mark_visible.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         lib.ggd_debug_unsorted.argtypes = [vp, vp, vp, vp, i64]
         lib.ggd_selftest_lanes.argtypes = [vp, vp, vp, vp, i32]

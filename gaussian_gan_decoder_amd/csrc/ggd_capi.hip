@@ -790,7 +790,10 @@ extern "C" int ggd_forward_collect(ggd_ctx* ctx, void* stream, int64_t* num_rend
 // adds to the same accumulator records; the depth / alpha terms run exactly when one of their gradients is given
 // dL_ddist (ggd_backward_distortion): the distortion map's backward runs in the same place; always with the AUX instances, whose
 // per-Gaussian kernel turns the accumulator's z slot into dL_dmeans3D.  It may carry a feature map as well (feat)
-enum bwd_entry { BWD_PLAIN, BWD_AUX, BWD_ABS, BWD_FEATURES, BWD_DISTORTION };
+// cam (ggd_backward_camera): the camera's gradients, two more launches behind the per-Gaussian backward on the same accumulator
+// records.  In front of them the call is the one its other arguments describe: dL_ddist as ggd_backward_distortion, else feat as
+// ggd_backward_features, else ggd_backward_aux with a depth or alpha gradient and ggd_backward without
+enum bwd_entry { BWD_PLAIN, BWD_AUX, BWD_ABS, BWD_FEATURES, BWD_DISTORTION, BWD_CAMERA };
 struct bwd_features {     // the feature map's side of ggd_backward_features
   const float* features = nullptr; int C = 0; const float* feature_bg = nullptr;
   const float* dL_dfeatmap = nullptr; float* dL_dfeatures = nullptr;
@@ -803,7 +806,7 @@ static int check_feature_channels(ggd_ctx* ctx, int C) {
 static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, bwd_entry entry, const ggd_inputs& in,
                          const int32_t* radii, const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
                          const ggd_pix_grads& pix, const ggd_grads& out, const bwd_features* feat = nullptr,
-                         const float* dL_ddist = nullptr) {
+                         const float* dL_ddist = nullptr, const ggd_camera_grads* cam = nullptr) {
   (void)hipGetLastError();   // a sticky error another library left in this thread is not ours to report
   int rc = check_params(ctx, prm);
   if (rc != GGD_OK) return rc;
@@ -817,25 +820,36 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, bwd_
       return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward_features: features / dL_dfeatmap / dL_dfeatures is NULL");
   }
   if (entry == BWD_DISTORTION && !dL_ddist) return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward_distortion: dL_ddistortion is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (entry == BWD_CAMERA) {
+    if (!cam || !cam->dL_dviewmatrix || !cam->dL_dprojmatrix || !cam->dL_dcampos)
+      return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward_camera: the camera bundle or one of its members is NULL");
+    if (P == 0 || R <= 0) {   // nothing was blended: every accumulator record is zero, and so are the sums
+      GGD_HIP(hipMemsetAsync(cam->dL_dviewmatrix, 0, 16 * sizeof(float), s));
+      GGD_HIP(hipMemsetAsync(cam->dL_dprojmatrix, 0, 16 * sizeof(float), s));
+      GGD_HIP(hipMemsetAsync(cam->dL_dcampos, 0, 3 * sizeof(float), s));
+    }
+  }
   if (P == 0) return GGD_OK;
   if (!radii || !geom_buf || !img_buf || !pix.dL_dpix || !out.dL_dmeans2D || !out.dL_dcolors || !out.dL_dopacity ||
       !out.dL_dmeans3D || !out.dL_dcov3D || !out.dL_dscales || !out.dL_drots || (prm->M > 0 && !out.dL_dsh) ||
       (R > 0 && !binning_buf))
     return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward: NULL buffer");
   const bool abs = entry == BWD_ABS;
-  const bool aux = entry == BWD_AUX || entry == BWD_DISTORTION || ((abs || entry == BWD_FEATURES) && (pix.dL_ddepth || pix.dL_dalpha));
+  const bool aux = entry == BWD_AUX || entry == BWD_DISTORTION || dL_ddist ||
+                   ((abs || entry == BWD_FEATURES || entry == BWD_CAMERA) && (pix.dL_ddepth || pix.dL_dalpha));
   if (abs && !out.dL_dmeans2D_abs) return ggd_fail(ctx, GGD_E_INVALID, "ggd_backward_abs: NULL dL_dmeans2D_abs");
   if (prm->raw_attributes && (!in.opacities || in.cov3D_precomp))
     return ggd_fail(ctx, GGD_E_INVALID, "raw_attributes needs opacities and scales/rotations (no cov3D_precomp)");
   if (prm->antialiasing && !in.opacities)   // dL/dh of the opacity compensation is dL/do_eff times the opacity
     return ggd_fail(ctx, GGD_E_INVALID, "antialiasing needs the opacities in the backward");
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const geom_ptrs g = geom_view(prm, geom_buf);
   const binning_ptrs b = binning_view(R, binning_buf);
   const img_ptrs im = img_view(prm->width, prm->height, img_buf);
 
   const size_t acc_bytes = (size_t)P * GGD_ACC_FLOATS * sizeof(float);
-  rc = ggd_reserve_scratch(ctx, ggd_align(acc_bytes), s);
+  const bool cam_sums = entry == BWD_CAMERA && R > 0;   // (their partial rows lie behind the accumulator records)
+  rc = ggd_reserve_scratch(ctx, ggd_align(acc_bytes) + (cam_sums ? ggd_align(ggd_camera_tmp_bytes(P)) : 0), s);
   if (rc != GGD_OK) return rc;
   float* grad_acc = static_cast<float*>(ctx->scratch);
   // the only zero-fill of the backward: the accumulator records.  Every caller array is written in full by the
@@ -869,6 +883,11 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, bwd_
   {
     StageTimer t(ctx, ST_PREPROCESS_BWD, s);
     rc = ggd_launch_preprocess_backward(ctx, s, *prm, in, radii, in.shs ? g.clamped : nullptr, grad_acc, out, aux);
+    if (rc != GGD_OK) return rc;
+  }
+  if (cam_sums) {
+    float* partial = reinterpret_cast<float*>(static_cast<char*>(ctx->scratch) + ggd_align(acc_bytes));
+    rc = ggd_launch_camera_backward(ctx, s, *prm, in, radii, in.shs ? g.clamped : nullptr, grad_acc, aux, partial, *cam);
     if (rc != GGD_OK) return rc;
   }
   return GGD_OK;
@@ -1004,6 +1023,27 @@ extern "C" int ggd_backward_distortion(ggd_ctx* ctx, void* stream, const ggd_par
   const bwd_features feat = {.features = features->features, .C = features->C, .feature_bg = features->feature_bg,
                              .dL_dfeatmap = features->dL_dfeatmap, .dL_dfeatures = features->dL_dfeatures};
   return backward_impl(ctx, stream, prm, BWD_DISTORTION, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, &feat, dL_ddistortion);
+}
+
+// the camera's gradients: ggd_backward_distortion's arguments, each map's side optional, + the bundle of the three results
+extern "C" int ggd_backward_camera(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
+                                   const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+                                   const float* rotations, const float* cov3D_precomp, const int32_t* radii,
+                                   const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t R,
+                                   const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, float* dL_dmeans2D,
+                                   float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                                   float* dL_dscales, float* dL_drots, const float* dL_ddistortion,
+                                   const ggd_feature_side* features, const ggd_camera_grads* camera) {
+  const ggd_inputs in = {.means3D = means3D, .shs = shs, .colors_precomp = colors_precomp, .opacities = opacities,
+                         .scales = scales, .rotations = rotations, .cov3D_precomp = cov3D_precomp};
+  const ggd_pix_grads pix = {.dL_dpix = dL_dpix, .dL_ddepth = dL_ddepth, .dL_dalpha = dL_dalpha};
+  const ggd_grads out = {.dL_dmeans2D = dL_dmeans2D, .dL_dcolors = dL_dcolors, .dL_dopacity = dL_dopacity,
+                         .dL_dmeans3D = dL_dmeans3D, .dL_dcov3D = dL_dcov3D, .dL_dsh = dL_dsh, .dL_dscales = dL_dscales,
+                         .dL_drots = dL_drots};
+  if (!features) return backward_impl(ctx, stream, prm, BWD_CAMERA, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, nullptr, dL_ddistortion, camera);
+  const bwd_features feat = {.features = features->features, .C = features->C, .feature_bg = features->feature_bg,
+                             .dL_dfeatmap = features->dL_dfeatmap, .dL_dfeatures = features->dL_dfeatures};
+  return backward_impl(ctx, stream, prm, BWD_CAMERA, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, &feat, dL_ddistortion, camera);
 }
 
 extern "C" int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D,

@@ -353,6 +353,12 @@ int ggd_launch_distortion_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params
 int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_inputs& in,
                                    const int32_t* radii, const uint8_t* clamped, const float* grad_acc, const ggd_grads& out,
                                    bool aux);
+// Camera gradients (ggd_camera.hip; ggd_backward_camera): behind the per-Gaussian backward, on the same accumulator records and
+// inputs.  partial: ggd_camera_tmp_bytes(P) of workspace (one row of sums per workgroup); all 35 values of `out` are written.
+size_t ggd_camera_tmp_bytes(int P);
+int ggd_launch_camera_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_inputs& in, const int32_t* radii,
+                               const uint8_t* clamped, const float* grad_acc, bool aux, float* partial,
+                               const ggd_camera_grads& out);
 
 // ---- device helpers -----------------------------------------------------------------------------------------
 #ifdef __HIPCC__

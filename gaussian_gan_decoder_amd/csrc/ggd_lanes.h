@@ -8,7 +8,8 @@
 // stale register, not a defined value, and v_readlane needs a lane index that is the same in every lane.  As with the shuffles they
 // replace, a call never stands inside a select (`c ? lane_xor<8>(x) : y` may be sunk into a branch by the compiler).
 //
-// 32-bit integers only (uint32_t, int): that is all the front-end kernels move.
+// 32-bit integers (uint32_t, int): that is all the front-end kernels move.  The scan and wave_sum_lane63 also take float (the camera
+// backward's sums): the additions then happen in the scan's fixed tree, so the result is the same from run to run.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,8 +27,9 @@ constexpr int DPP_ROW_BCAST31 = 0x143;   // lane 31 to all lanes of rows 2 and 3
 // `v` moved by CTRL; lanes that the move does not write (outside ROW_MASK / BANK_MASK, or without a source lane) get `old`
 template <int CTRL, int ROW_MASK = 0xf, int BANK_MASK = 0xf, typename T>
 __device__ __forceinline__ T dpp(T old, T v) {
-  static_assert(sizeof(T) == 4 && std::is_integral<T>::value, "32-bit integers");
-  return (T)__builtin_amdgcn_update_dpp((int)old, (int)v, CTRL, ROW_MASK, BANK_MASK, false);
+  static_assert(sizeof(T) == 4 && (std::is_integral<T>::value || std::is_same<T, float>::value), "32-bit integers or float");
+  return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL, ROW_MASK,
+                                                           BANK_MASK, false));
 }
 
 struct op_add { template <typename T> static __device__ __forceinline__ T f(T a, T b) { return a + b; } };

@@ -108,32 +108,8 @@ __device__ __forceinline__ void preprocess_backward_body(
     float abc[3], T[2][3], tc[3];
     bool clx, cly;
     ewa_cov2d(t, fx, fy, tanfovx, tanfovy, c6, V, abc, T, tc, clx, cly);
-    const float x_grad_mul = clx ? 0.0f : 1.0f, y_grad_mul = cly ? 0.0f : 1.0f;
-    const float a = abc[0] + 0.3f, b = abc[1], c = abc[2] + 0.3f;
-    const float denom = a * c - b * b;
-    const float denom2inv = 1.0f / (denom * denom + 0.0000001f);
-    float aa_r = 0.0f;
-    if constexpr (AA) {   // the forward's h, bit for bit (same fp32 expressions, correctly rounded division and square root)
-      aa_r = (abc[0] * abc[2] - abc[1] * abc[1]) / denom;
-      aa_h = sqrtf(fmaxf(2.5e-5f, aa_r));
-    }
-    const float gA = acc0.x, gB = acc0.y, gC = acc0.z;
-    float dL_da = 0.0f, dL_db = 0.0f, dL_dc = 0.0f;
-    if (denom2inv != 0.0f) {
-      dL_da = denom2inv * (-c * c * gA + 2.0f * b * c * gB + (denom - a * c) * gC);
-      dL_dc = denom2inv * (-a * a * gC + 2.0f * a * b * gB + (denom - a * c) * gA);
-      dL_db = denom2inv * 2.0f * (b * c * gA - (denom + 2.0f * b * b) * gB + a * b * gC);
-      // AA: the h chain joins here, so that dc[] and dT below carry it.  Inside the guard: denom2inv == 0 means
-      // denom^2 overflowed, where k (1 / det1^2) is 0 as well
-      if constexpr (AA) {
-        if (aa_r > 2.5e-5f) {
-          const float x = abc[0], z = abc[1], y = abc[2], w = 0.3f;
-          const float k = acc0.w * aa_o / (2.0f * aa_h * denom * denom);
-          dL_da += k * w * (y * y + w * y + z * z);
-          dL_dc += k * w * (x * x + w * x + z * z);
-          dL_db += -2.0f * k * w * z * (x + y + w);
-        }
-      }
+    float dL_da, dL_db, dL_dc;
+    if (cov2d_backward<AA>(abc, acc0.x, acc0.y, acc0.z, acc0.w, aa_o, aa_h, dL_da, dL_db, dL_dc)) {
       dc[0] = T[0][0] * T[0][0] * dL_da + T[0][0] * T[1][0] * dL_db + T[1][0] * T[1][0] * dL_dc;
       dc[3] = T[0][1] * T[0][1] * dL_da + T[0][1] * T[1][1] * dL_db + T[1][1] * T[1][1] * dL_dc;
       dc[5] = T[0][2] * T[0][2] * dL_da + T[0][2] * T[1][2] * dL_db + T[1][2] * T[1][2] * dL_dc;
@@ -144,36 +120,18 @@ __device__ __forceinline__ void preprocess_backward_body(
       dc[4] = 2.0f * T[0][2] * T[0][1] * dL_da + (T[0][1] * T[1][2] + T[0][2] * T[1][1]) * dL_db +
               2.0f * T[1][1] * T[1][2] * dL_dc;
     }
-    const float S[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
-    float dT[2][3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const float s0 = T[0][0] * S[0][j] + T[0][1] * S[1][j] + T[0][2] * S[2][j];
-      const float s1 = T[1][0] * S[0][j] + T[1][1] * S[1][j] + T[1][2] * S[2][j];
-      dT[0][j] = 2.0f * s0 * dL_da + s1 * dL_db;
-      dT[1][j] = 2.0f * s1 * dL_dc + s0 * dL_db;
-    }
-    // W[r][c] = V.m[4c + r]
-    const float dJ00 = V.m[0] * dT[0][0] + V.m[4] * dT[0][1] + V.m[8] * dT[0][2];
-    const float dJ02 = V.m[2] * dT[0][0] + V.m[6] * dT[0][1] + V.m[10] * dT[0][2];
-    const float dJ11 = V.m[1] * dT[1][0] + V.m[5] * dT[1][1] + V.m[9] * dT[1][2];
-    const float dJ12 = V.m[2] * dT[1][0] + V.m[6] * dT[1][1] + V.m[10] * dT[1][2];
-    const float tz = 1.0f / tc[2], tz2 = tz * tz, tz3 = tz2 * tz;
-    const float dtx = x_grad_mul * -fx * tz2 * dJ02;
-    const float dty = y_grad_mul * -fy * tz2 * dJ12;
-    const float dtz = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + (2.0f * fx * tc[0]) * tz3 * dJ02 +
-                      (2.0f * fy * tc[1]) * tz3 * dJ12;
+    float dT[2][3], dt[3];
+    ewa_dT(T, c6, dL_da, dL_db, dL_dc, dT);
+    ewa_dt(V, dT, fx, fy, tc, clx, cly, dt);
+    const float dtx = dt[0], dty = dt[1], dtz = dt[2];
     dmean[0] = V.m[0] * dtx + V.m[1] * dty + V.m[2] * dtz;
     dmean[1] = V.m[4] * dtx + V.m[5] * dty + V.m[6] * dtz;
     dmean[2] = V.m[8] * dtx + V.m[9] * dty + V.m[10] * dtz;
   }
   // (2) screen position through the perspective divide
   {
-    const float h0 = PV.m[0] * p[0] + PV.m[4] * p[1] + PV.m[8] * p[2] + PV.m[12];
-    const float h1 = PV.m[1] * p[0] + PV.m[5] * p[1] + PV.m[9] * p[2] + PV.m[13];
-    const float h3 = PV.m[3] * p[0] + PV.m[7] * p[1] + PV.m[11] * p[2] + PV.m[15];
-    const float m_w = 1.0f / (h3 + 0.0000001f);
-    const float mul1 = h0 * m_w * m_w, mul2 = h1 * m_w * m_w;
+    float m_w, mul1, mul2;
+    divide_terms(PV, p, m_w, mul1, mul2);
     const float g0 = acc1.x, g1 = acc1.y;
     dmean[0] += (PV.m[0] * m_w - PV.m[3] * mul1) * g0 + (PV.m[1] * m_w - PV.m[3] * mul2) * g1;
     dmean[1] += (PV.m[4] * m_w - PV.m[7] * mul1) * g0 + (PV.m[5] * m_w - PV.m[7] * mul2) * g1;
@@ -220,23 +178,17 @@ __device__ __forceinline__ void preprocess_backward_body(
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float gcol = ((cl >> c) & 1u) ? 0.0f : gcol3[c];
-#define SHK(k) sh[(k) * 3 + c]
 #define DSH(k) dsh[(k) * 3 + c]
-      float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+      float dx, dy, dz;
+      sh_dir_grad(deg, sh, c, x, y, z, dx, dy, dz);
       DSH(0) = SH_C0 * gcol;
       if (deg > 0) {
         DSH(1) = -SH_C1 * y * gcol; DSH(2) = SH_C1 * z * gcol; DSH(3) = -SH_C1 * x * gcol;
-        dx = -SH_C1 * SHK(3); dy = -SH_C1 * SHK(1); dz = SH_C1 * SHK(2);
         if (deg > 1) {
           const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
           DSH(4) = SH_C2[0] * xy * gcol; DSH(5) = SH_C2[1] * yz * gcol;
           DSH(6) = SH_C2[2] * (2.0f * zz - xx - yy) * gcol;
           DSH(7) = SH_C2[3] * xz * gcol; DSH(8) = SH_C2[4] * (xx - yy) * gcol;
-          dx += SH_C2[0] * y * SHK(4) + SH_C2[2] * 2.0f * -x * SHK(6) + SH_C2[3] * z * SHK(7) +
-                SH_C2[4] * 2.0f * x * SHK(8);
-          dy += SH_C2[0] * x * SHK(4) + SH_C2[1] * z * SHK(5) + SH_C2[2] * 2.0f * -y * SHK(6) +
-                SH_C2[4] * 2.0f * -y * SHK(8);
-          dz += SH_C2[1] * y * SHK(5) + SH_C2[2] * 4.0f * z * SHK(6) + SH_C2[3] * x * SHK(7);
           if (deg > 2) {
             DSH(9) = SH_C3[0] * y * (3.0f * xx - yy) * gcol;
             DSH(10) = SH_C3[1] * xy * z * gcol;
@@ -245,20 +197,9 @@ __device__ __forceinline__ void preprocess_backward_body(
             DSH(13) = SH_C3[4] * x * (4.0f * zz - xx - yy) * gcol;
             DSH(14) = SH_C3[5] * z * (xx - yy) * gcol;
             DSH(15) = SH_C3[6] * x * (xx - 3.0f * yy) * gcol;
-            dx += SH_C3[0] * SHK(9) * 6.0f * xy + SH_C3[1] * SHK(10) * yz + SH_C3[2] * SHK(11) * -2.0f * xy +
-                  SH_C3[3] * SHK(12) * -6.0f * xz + SH_C3[4] * SHK(13) * (4.0f * zz - 3.0f * xx - yy) +
-                  SH_C3[5] * SHK(14) * 2.0f * xz + SH_C3[6] * SHK(15) * 3.0f * (xx - yy);
-            dy += SH_C3[0] * SHK(9) * 3.0f * (xx - yy) + SH_C3[1] * SHK(10) * xz +
-                  SH_C3[2] * SHK(11) * (4.0f * zz - xx - 3.0f * yy) + SH_C3[3] * SHK(12) * -6.0f * yz +
-                  SH_C3[4] * SHK(13) * -2.0f * xy + SH_C3[5] * SHK(14) * -2.0f * yz +
-                  SH_C3[6] * SHK(15) * -6.0f * xy;
-            dz += SH_C3[1] * SHK(10) * xy + SH_C3[2] * SHK(11) * 8.0f * yz +
-                  SH_C3[3] * SHK(12) * 3.0f * (2.0f * zz - xx - yy) + SH_C3[4] * SHK(13) * 8.0f * xz +
-                  SH_C3[5] * SHK(14) * (xx - yy);
           }
         }
       }
-#undef SHK
 #undef DSH
       ddir[0] += dx * gcol; ddir[1] += dy * gcol; ddir[2] += dz * gcol;
     }
@@ -272,11 +213,10 @@ __device__ __forceinline__ void preprocess_backward_body(
       }
     }
     if (deg > 0) {
-      const float sum2 = v0 * v0 + v1 * v1 + v2 * v2;
-      const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-      dmean[0] += ((sum2 - v0 * v0) * ddir[0] - v1 * v0 * ddir[1] - v2 * v0 * ddir[2]) * invsum32;
-      dmean[1] += (-v0 * v1 * ddir[0] + (sum2 - v1 * v1) * ddir[1] - v2 * v1 * ddir[2]) * invsum32;
-      dmean[2] += (-v0 * v2 * ddir[0] - v1 * v2 * ddir[1] + (sum2 - v2 * v2) * ddir[2]) * invsum32;
+      const float v[3] = {v0, v1, v2};
+      float dv[3];
+      dir_to_point(v, ddir, dv);
+      dmean[0] += dv[0]; dmean[1] += dv[1]; dmean[2] += dv[2];
     }
   }
   if constexpr (AUX) {

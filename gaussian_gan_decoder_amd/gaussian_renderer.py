@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _check_distortion
+from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _check_camera_grad, _check_distortion
 from .sh import eval_sh
 
 
@@ -30,11 +30,14 @@ def _screenspace_points(pc):
 
 
 def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attributes=False, render_depth_alpha=False,
-              antialiasing=False, absgrad=False, render_distortion=False):
+              antialiasing=False, absgrad=False, render_distortion=False, camera_grad=False):
     if render_distortion:   # (refused before anything is built; the keyword reaches the settings only when set)
         _check_distortion(render_depth_alpha, absgrad)
+    if camera_grad:         # (likewise)
+        _check_camera_grad(absgrad)
     return GaussianRasterizationSettings(
         **({"render_distortion": True} if render_distortion else {}),
+        **({"camera_grad": True} if camera_grad else {}),
         raw_attributes=raw_attributes,
         render_depth_alpha=render_depth_alpha,
         antialiasing=antialiasing,
@@ -56,7 +59,7 @@ def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attri
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
            render_depth_alpha=False, antialiasing=False, absgrad=False, features=None, feature_bg=None,
-           render_distortion=False):
+           render_distortion=False, camera_grad=False):
     """Stock 3DGS render (reference :19-102).  `pipe` needs .debug, .compute_cov3D_python, .convert_SHs_python.
     render_depth_alpha=True (extension): the dict also holds "depth" (sum alpha_i T_i z_i) and "alpha" (1 - final T),
     differentiable float32 [1, H, W] maps.
@@ -67,11 +70,14 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     float32 [C, H, W] map sum alpha_i T_i f_i + T_final feature_bg over the colour's contributors, from the same render pass.
     render_distortion=True (extension; needs render_depth_alpha=True, refuses absgrad): the dict also holds "distortion", the
     differentiable float32 [1, H, W] map sum_ij w_i w_j |z_i - z_j| (w = alpha T, z the raw view-space depth of "depth") over the
-    colour's contributors -- the distortion loss of Mip-NeRF 360 / 2DGS is its mean times a weight that carries the scene's scale."""
+    colour's contributors -- the distortion loss of Mip-NeRF 360 / 2DGS is its mean times a weight that carries the scene's scale.
+    camera_grad=True (extension; refuses absgrad): the backward also differentiates the frame in the camera.  The dict is
+    unchanged; the gradients arrive on viewpoint_camera.world_view_transform, .full_proj_transform and .camera_center, and through
+    them on whatever built those with differentiable torch ops (CustomCam's `extr`, for instance).  FoVx / FoVy get none."""
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, pipe.debug,
                                               render_depth_alpha=render_depth_alpha, antialiasing=antialiasing,
-                                              absgrad=absgrad, render_distortion=render_distortion))
+                                              absgrad=absgrad, render_distortion=render_distortion, camera_grad=camera_grad))
     scales = rotations = cov3D_precomp = None
     if pipe.compute_cov3D_python:
         cov3D_precomp = pc.get_covariance(scaling_modifier)
@@ -106,7 +112,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
 
 def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None, scaling_modifier=1.0,
                   override_color=None, debug=False, fused_activations=False, render_depth_alpha=False, antialiasing=False,
-                  absgrad=False, features=None, feature_bg=None, render_distortion=False):
+                  absgrad=False, features=None, feature_bg=None, render_distortion=False, camera_grad=False):
     """Decoder-path render (reference :105-186): scale/rotation always from the model, SH unless override_color.
     "alpha" and "depth" are the radii placeholders the reference returns (:184-185).
     fused_activations=True (extension): hand the RAW `_opacity/_scaling/_rotation` to the
@@ -121,11 +127,14 @@ def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None,
     features=[P, C], feature_bg (extension): as in `render` -- "features" is the [C, H, W] map; combines with everything above but
     absgrad.
     render_distortion=True (extension): as in `render` -- "distortion" is the [1, H, W] map; needs render_depth_alpha=True, combines
-    with everything above but absgrad."""
+    with everything above but absgrad.
+    camera_grad=True (extension): as in `render` -- the dict is unchanged and the camera's tensors receive gradients; combines with
+    everything above but absgrad."""
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug,
                                               raw_attributes=fused_activations, render_depth_alpha=render_depth_alpha,
-                                              antialiasing=antialiasing, absgrad=absgrad, render_distortion=render_distortion))
+                                              antialiasing=antialiasing, absgrad=absgrad, render_distortion=render_distortion,
+                                              camera_grad=camera_grad))
     means3D = pc.get_xyz
     if xyz_offset is not None:
         means3D = means3D + xyz_offset

@@ -65,27 +65,37 @@ class GaussianRasterizationSettings(_SettingsFields):
 
     render_distortion (keyword only, default False; needs render_depth_alpha=True, refuses absgrad=True): the rasterizer also
     returns the differentiable depth-distortion map sum_ij w_i w_j |z_i - z_j| (w = alpha T, raw view-space z), [1, H, W],
-    behind the depth and alpha maps.  An attribute like antialiasing, for the same reason."""
+    behind the depth and alpha maps.  An attribute like antialiasing, for the same reason.
+
+    camera_grad (keyword only, default False; refuses absgrad=True): the backward also differentiates the frame in viewmatrix,
+    projmatrix and campos, and autograd carries the three gradients on to whatever built those tensors (a pose, for instance).
+    The bottom row of viewmatrix and row 2 of projmatrix (maths layout) are read by no kernel and get exactly 0; tanfovx and
+    tanfovy get no gradient.  An attribute like antialiasing, for the same reason."""
     antialiasing: bool = False   # (instances made without __new__, e.g. by _make, read these class defaults)
     absgrad: bool = False
     render_distortion: bool = False
+    camera_grad: bool = False
 
-    def __new__(cls, *args, antialiasing: bool = False, absgrad: bool = False, render_distortion: bool = False, **kwargs):
+    def __new__(cls, *args, antialiasing: bool = False, absgrad: bool = False, render_distortion: bool = False,
+                camera_grad: bool = False, **kwargs):
         self = super().__new__(cls, *args, **kwargs)
         self.antialiasing = bool(antialiasing)
         self.absgrad = bool(absgrad)
         self.render_distortion = bool(render_distortion)
+        self.camera_grad = bool(camera_grad)
         return self
 
     def _replace(self, **kwargs):
         aa = kwargs.pop("antialiasing", self.antialiasing)
         ab = kwargs.pop("absgrad", self.absgrad)
         rd = kwargs.pop("render_distortion", self.render_distortion)
-        return type(self)(*super()._replace(**kwargs), antialiasing=aa, absgrad=ab, render_distortion=rd)
+        cg = kwargs.pop("camera_grad", self.camera_grad)
+        return type(self)(*super()._replace(**kwargs), antialiasing=aa, absgrad=ab, render_distortion=rd, camera_grad=cg)
 
     def __repr__(self):
         rd = f", render_distortion={self.render_distortion}" if self.render_distortion else ""
-        return super().__repr__()[:-1] + f", antialiasing={self.antialiasing}, absgrad={self.absgrad}{rd})"
+        cg = f", camera_grad={self.camera_grad}" if self.camera_grad else ""
+        return super().__repr__()[:-1] + f", antialiasing={self.antialiasing}, absgrad={self.absgrad}{rd}{cg})"
 
 
 def _f32c(t: torch.Tensor, name: str, device) -> torch.Tensor:
@@ -241,6 +251,13 @@ def _check_distortion(render_depth_alpha: bool, absgrad: bool = False):
     if absgrad:
         raise ValueError("render_distortion cannot be combined with absgrad=True: the absolute screen-space statistic is defined "
                          "on the colour terms (with the depth / alpha terms), and the distortion map's terms are not part of it")
+
+
+def _check_camera_grad(absgrad: bool = False):
+    """The camera_grad keyword's refusal (ValueError), before any device call."""
+    if absgrad:
+        raise ValueError("camera_grad cannot be combined with absgrad=True: the absolute screen-space statistic is no gradient "
+                         "of the frame, and the camera's gradients are not defined on it")
 
 
 def _bytes(n: int, dev) -> torch.Tensor:
@@ -443,7 +460,7 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
                                         degree, campos, geomBuffer, R, binningBuffer, imgBuffer, debug,
                                         raw_attributes=False, opacities=None, *, dL_ddepth=None, dL_dalpha=None,
                                         antialiasing=False, absgrad=False, features=None, feature_bg=None, dL_dfeatmap=None,
-                                        dL_ddistortion=None):
+                                        dL_ddistortion=None, camera_grad=False):
     """== upstream `_C.rasterize_gaussians_backward(...)`: returns
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations).
     dL_ddepth / dL_dalpha (extension, [1, H, W] or [H, W]; None = zero): gradients of the depth and alpha maps of a
@@ -457,7 +474,13 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
     dL_dfeatures [P, C] follows them.
     dL_ddistortion (extension, [1, H, W] or [H, W]): the gradient of the distortion map of a render_distortion forward -- the call is
     ggd_backward_distortion (which carries the feature map's side as well when `features` is given) and the eight hold the
-    gradients of every map together; the depth / alpha instances always run."""
+    gradients of every map together; the depth / alpha instances always run.
+    camera_grad=True (extension; refuses absgrad): the call is ggd_backward_camera, which does the work of the entry point the other
+    keywords select and then reduces the camera's gradients from the same accumulator records; (dL_dviewmatrix [4, 4],
+    dL_dprojmatrix [4, 4], dL_dcampos [3]) follow everything else in the tuple.  Entry [i][j] is the derivative in entry [i][j] of
+    the (contiguous) tensor passed in."""
+    if camera_grad:
+        _check_camera_grad(absgrad)
     if dL_ddistortion is not None:
         _check_distortion(True, absgrad)
     if features is not None:
@@ -496,6 +519,9 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
         gF = _f32c(dL_dfeatmap, "dL_dfeatmap", dev)
         if tuple(gF.shape) != (n_feat, H, W):
             raise ValueError(f"dL_dfeatmap must have dimensions ({n_feat}, {H}, {W}) (got {tuple(gF.shape)})")
+    n_per_gaussian = len(shapes)
+    if camera_grad:
+        shapes += [(4, 4), (4, 4), (3,)]
     grads = [torch.empty(shape, dtype=torch.float32, device=dev) for shape in shapes]
     if ctx.poison_outputs:   # tests: the library must write every element itself (it does not rely on pre-zeroed arrays)
         for t in grads:
@@ -504,15 +530,18 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
         # the arguments the three entry points share, then the incoming gradients, then the results
         args = [ctx.handle, _stream(dev), C.byref(prm), _ptr(means3D), _ptr(sh_c), _ptr(col_c), _ptr(op_c), _ptr(sc_c),
                 _ptr(rot_c), _ptr(cov_c), _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer), int(R), _ptr(g)]
-        if aux or absgrad or features is not None or gDist is not None:
+        if aux or absgrad or features is not None or gDist is not None or camera_grad:
             args += [_ptr(gD), _ptr(gA)]
-        if gDist is not None:   # ggd_backward_aux's arguments, then the map's gradient and the feature bundle (or NULL)
+        if gDist is not None or camera_grad:   # ggd_backward_aux's arguments, then the map's gradient and the feature bundle (or NULL)
             side = None
             if features is not None:
                 side = C.byref(_capi.FeatureSide(feat.data_ptr(), n_feat, None if fbg is None else fbg.data_ptr(), gF.data_ptr(),
-                                                 grads[-1].data_ptr()))
+                                                 grads[n_per_gaussian - 1].data_ptr()))
             args += [_ptr(t) for t in grads[:8]] + [_ptr(gDist), side]
             fn = ctx.lib.ggd_backward_distortion
+            if camera_grad:   # ... and the bundle of the three results
+                args.append(C.byref(_capi.CameraGrads(*(t.data_ptr() for t in grads[n_per_gaussian:]))))
+                fn = ctx.lib.ggd_backward_camera
         else:
             if features is not None:
                 args += [_ptr(feat), n_feat, _ptr(fbg), _ptr(gF)]
@@ -522,6 +551,9 @@ def rasterize_gaussians_backward_native(bg, means3D, radii, colors_precomp, scal
                 fn = ctx.lib.ggd_backward_features
         with torch.cuda.device(dev):
             ctx.check(fn(*args))
+    elif camera_grad:   # (no Gaussian: no call, and the sums are empty)
+        for t in grads[n_per_gaussian:]:
+            t.zero_()
     return tuple(grads)
 
 
@@ -543,8 +575,14 @@ def mark_visible(positions, viewmatrix, projmatrix):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, features=None, feature_bg=None):
+                raster_settings, features=None, feature_bg=None, viewmatrix=None, projmatrix=None, campos=None):
         rs = raster_settings
+        # (camera_grad: apply() is called with rs.viewmatrix, rs.projmatrix and rs.campos as three trailing inputs, so that autograd
+        # routes their gradients, and the backward returns fourteen.  The kernels read the three from rs: the same tensors)
+        ctx.n_inputs = 14 if viewmatrix is not None else (11 if features is not None else 9)
+        if viewmatrix is not None:
+            _check_camera_grad(bool(getattr(rs, "absgrad", False)))
+            ctx.camera_shapes = (viewmatrix.shape, projmatrix.shape, campos.shape)
         depth_alpha = bool(getattr(rs, "render_depth_alpha", False))
         distortion = bool(getattr(rs, "render_distortion", False))
         if distortion:
@@ -611,6 +649,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             aux.update(features=features, feature_bg=feature_bg, dL_dfeatmap=grad_features)
         if grad_distortion is not None:   # (a graph that does not read the map takes the backward it took without it)
             aux["dL_ddistortion"] = grad_distortion
+        # (a camera none of whose three tensors needs a gradient takes the backward it took without the flag)
+        want_camera = ctx.n_inputs == 14 and any(ctx.needs_input_grad[11:14])
+        if want_camera:
+            aux["camera_grad"] = True
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations, *grad_abs) = rasterize_gaussians_backward_native(
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
@@ -620,8 +662,15 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.means2D_ref.absgrad = grad_abs[0]   # gsplat's convention: overwritten by each backward, not accumulated
         grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
                  grad_rotations, grad_cov3Ds_precomp, None)
-        if ctx.has_features:   # (dL_dfeatures is the last array of ggd_backward_features; feature_bg gets no gradient)
-            grads = grads + (grad_abs[-1], None)
+        grad_camera = (None, None, None)
+        if want_camera:   # (the three follow everything else)
+            *grad_abs, dview, dproj, dcampos = grad_abs
+            grad_camera = tuple(g.reshape(shape) if need else None for g, shape, need in
+                                zip((dview, dproj, dcampos), ctx.camera_shapes, ctx.needs_input_grad[11:14]))
+        if ctx.n_inputs > 9:   # (dL_dfeatures is the last per-Gaussian array; feature_bg gets no gradient)
+            grads = grads + (grad_abs[-1] if ctx.has_features else None, None)
+        if ctx.n_inputs == 14:
+            grads = grads + grad_camera
         return grads
 
 
@@ -629,16 +678,25 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                         raster_settings, features=None, feature_bg=None):
     """features / feature_bg (extension, keywords): C <= 32 per-Gaussian channels [P, C] blended over the colour's contributors; the
     map [C, H, W] is appended LAST to the returned tuple (colour, radii[, depth, alpha], features) and is differentiable in
-    `features` and in everything alpha and T depend on.  Without `features` the call is exactly what it was."""
+    `features` and in everything alpha and T depend on.  Without `features` the call is exactly what it was.
+    raster_settings.camera_grad (extension): viewmatrix, projmatrix and campos of the settings join the autograd inputs, and a
+    backward also fills the gradients of those of them that require one."""
+    absgrad = bool(getattr(raster_settings, "absgrad", False))
+    camera = bool(getattr(raster_settings, "camera_grad", False))
+    if camera:
+        _check_camera_grad(absgrad)
     if features is None:
         if feature_bg is not None:
             raise ValueError("feature_bg without features")
-        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                         cov3Ds_precomp, raster_settings)
-    _check_features(features, feature_bg, means3D.size(0), bool(getattr(raster_settings, "absgrad", False)))
-    _require_cuda(means3D)
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, features, feature_bg)
+        extra = (None, None) if camera else ()
+    else:
+        _check_features(features, feature_bg, means3D.size(0), absgrad)
+        _require_cuda(means3D)
+        extra = (features, feature_bg)
+    if camera:   # (the feature pair, given or not, then the three camera tensors)
+        extra += (raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos)
+    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                     raster_settings, *extra)
 
 
 class GaussianRasterizer(nn.Module):

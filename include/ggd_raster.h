@@ -342,6 +342,46 @@ int ggd_backward_distortion(ggd_ctx* ctx, void* stream, const ggd_params* prm,
                             float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots,
                             const float* dL_ddistortion, const ggd_feature_side* features /* NULL = no feature map */);
 
+/*
+ * Camera gradients (opt-in extension; every entry point above is unchanged by it): the backward also differentiates the frame in
+ * prm->viewmatrix, prm->projmatrix and prm->campos.
+ *   ggd_backward_camera  == ggd_backward_distortion's arguments + `camera`.  dL_ddistortion and `features` may be NULL, and so may
+ *                        dL_ddepth / dL_dalpha: the call does the work of ggd_backward (all four NULL), ggd_backward_aux (a depth
+ *                        or alpha gradient), ggd_backward_features (the bundle) or ggd_backward_distortion (the map's gradient, with
+ *                        or without the bundle) as given, and then two more launches on the same accumulator records.
+ * Entry k of each gradient is the derivative with respect to flat entry k of the input, m[4c + r] = row r, column c of the maths
+ * matrix.  Per Gaussian with radii > 0, p = (p0, p1, p2, 1), in the per-Gaussian backward's quantities:
+ *   dL_dviewmatrix[4c + r] += dt_r p_c (r = 0..2; dt the gradient of t = V p through the EWA Jacobian, with the depth plane's and
+ *                             the distortion map's dL/dz on dt_2) and, through W in T = J W, for c = 0..2:
+ *                             [4c + 0] += J00 dT[0][c], [4c + 1] += J11 dT[1][c], [4c + 2] += J02 dT[0][c] + J12 dT[1][c]
+ *   dL_dprojmatrix[4c + r] += dh_r p_c for r = 0, 1, 3; dh = (m_w g0, m_w g1, -, -(mul1 g0 + mul2 g1)), g = dL_dmeans2D
+ *   dL_dcampos             -= the term the SH view direction adds to dL_dmeans3D (zero at degree 0 and with colors_precomp)
+ * The bottom row of the view matrix and row 2 of the projection matrix are read by no kernel: exactly 0.  The conventions of the
+ * published backward hold (1 / (det^2 + 1e-7), the half dB slot, clamped x, y independent of z): it is the derivative of the same
+ * surrogate dL_dmeans3D is.  Culling, radii and tile decisions carry no gradient, and tanfovx / tanfovy get none.
+ * All three arrays are device pointers and are written in full, zeros included; P == 0 or num_rendered == 0 writes zeros.  The
+ * sums are reduced in a fixed order without float atomics: given the same accumulator records (which the blend's float atomics
+ * fill) they are bit-identical from run to run.
+ * GGD_E_INVALID with a message: a NULL `camera` or a NULL member; the refusals of the entry point whose work the call does.
+ */
+typedef struct ggd_camera_grads {
+  float* dL_dviewmatrix;   /* [16] */
+  float* dL_dprojmatrix;   /* [16] */
+  float* dL_dcampos;       /* [3] */
+} ggd_camera_grads;
+int ggd_backward_camera(ggd_ctx* ctx, void* stream, const ggd_params* prm,
+                        const float* means3D, const float* shs, const float* colors_precomp,
+                        const float* opacities /* only read when prm->raw_attributes or prm->antialiasing */,
+                        const float* scales, const float* rotations, const float* cov3D_precomp,
+                        const int32_t* radii,
+                        const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t num_rendered,
+                        const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha,
+                        float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                        float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots,
+                        const float* dL_ddistortion /* NULL = no distortion map */,
+                        const ggd_feature_side* features /* NULL = no feature map */,
+                        const ggd_camera_grads* camera);
+
 /* present[i] = 1 iff Gaussian i passes the view-space z > 0.2 frustum test. */
 int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D,
                      const float* viewmatrix, const float* projmatrix, uint8_t* present);
