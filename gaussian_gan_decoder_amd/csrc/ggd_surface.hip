@@ -134,8 +134,13 @@ __global__ __launch_bounds__(256) void surface_sample_kernel(const float* __rest
 
 }  // namespace
 
+// face numbers are uint32_t, a cell emits up to 12 faces: 12 * 710^3 = 4 294 932 000 <= 2^32 - 1 < 12 * 711^3, so n <= 711
+static constexpr int32_t kSurfaceMaxN = 711;
+static_assert(12ull * (kSurfaceMaxN - 1) * (kSurfaceMaxN - 1) * (kSurfaceMaxN - 1) <= 0xFFFFFFFFull &&
+              12ull * kSurfaceMaxN * kSurfaceMaxN * kSurfaceMaxN > 0xFFFFFFFFull, "kSurfaceMaxN");
+
 extern "C" size_t ggd_surface_tmp_bytes(int32_t n) {
-  if (n < 2) return 0;
+  if (n < 2 || n > kSurfaceMaxN) return 0;
   const size_t cells = (size_t)(n - 1) * (n - 1) * (n - 1);
   return 2 * ggd_align(cells * sizeof(uint32_t)) + ggd_align(ggd_scan_tmp_bytes((int64_t)cells)) + 256;
 }
@@ -144,7 +149,7 @@ extern "C" int ggd_surface_sample(ggd_ctx* ctx, void* stream, const float* sigma
                                   int32_t num_points, float thickness, uint64_t seed, float* positions,
                                   uint32_t* num_faces, void* tmp, size_t tmp_bytes) {
   if (!ctx) return GGD_E_INVALID;
-  if (n < 2 || n > 1024 || num_points < 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_surface_sample: bad grid size / point count");
+  if (n < 2 || n > kSurfaceMaxN || num_points < 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_surface_sample: bad grid size / point count");
   if (!sigma || !num_faces || !tmp || (num_points > 0 && !positions)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_surface_sample: NULL pointer");
   if (tmp_bytes < ggd_surface_tmp_bytes(n)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_surface_sample: tmp too small");
   hipStream_t s = static_cast<hipStream_t>(stream);

@@ -524,6 +524,9 @@ int ggd_planes_scatter(ggd_ctx* ctx, void* stream, int32_t C, int32_t D, int32_t
  * (:104-110), in the reference's units (index / n - 0.5, :99-101), scaled by clip(1 + thickness * N(0,1), 0, 1)
  * (:113-116).  No host sync: the face count F stays on the device (*num_faces, a DEVICE uint32; 0 -> positions are
  * zero-filled).  Pure function of (sigma, level, seed).  tmp: ggd_surface_tmp_bytes(n) bytes of device scratch.
+ * 2 <= n <= 711: face numbers are uint32 and a cell emits up to 12 faces, 12 (n - 1)^3 < 2^32 up to n = 711; any other n
+ * (and num_points < 0, a NULL pointer, a short tmp) is refused before anything is launched, and ggd_surface_tmp_bytes
+ * returns 0 for it.
  */
 size_t ggd_surface_tmp_bytes(int32_t n);
 int ggd_surface_sample(ggd_ctx* ctx, void* stream, const float* sigma, int32_t n, float level, int32_t num_points,
