@@ -31,6 +31,7 @@ EXPORTS = [
     "ggd_forward_features", "ggd_backward_features",
     "ggd_forward_distortion", "ggd_backward_distortion",
     "ggd_backward_camera",
+    "ggd_gaussian_normals", "ggd_gaussian_normals_backward", "ggd_normal_loss_tmp_bytes", "ggd_normal_loss",
 ]
 
 
@@ -199,6 +200,11 @@ def load():
         lib.ggd_density_lattice.argtypes = [vp, vp, i32, C.c_double, i32, vp]
         lib.ggd_teacher_render.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp, vp, i32, C.c_double, C.c_double,
                                            vp, i32, i32, vp, vp, i32, C.c_double, i32, vp, vp, vp, vp]
+        # per-Gaussian normals: ctx, stream, P, rotations, scales, means3D, viewmatrix, raw, normals / ..., dL_dnormals, dL_drotations
+        lib.ggd_gaussian_normals.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp]
+        lib.ggd_gaussian_normals_backward.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]
+        lib.ggd_normal_loss_tmp_bytes.restype = sz; lib.ggd_normal_loss_tmp_bytes.argtypes = [i32, i32]
+        lib.ggd_normal_loss.argtypes = [vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, sz]
         _lib = lib
         return lib
 

@@ -361,7 +361,143 @@ __global__ __launch_bounds__(256) void geometry_loss_finalise_kernel(int n_wg, c
 
 static inline size_t geometry_loss_workgroups(int32_t W, int32_t H) { return (size_t)((W + 63) / 64) * (size_t)((H + 3) / 4); }
 
+// ---- normal-consistency loss: the blended splat normals against the normals of the depth map's surface ----
+// Two launches.  Pass 1, per pixel: the surface normal N_s from the central differences dU, dV of the back-projected expected depth
+// of the four axis neighbours, e = A - N_r . N_s, dL/dN_r, the direct part of dL/dA, and dL/ddU, dL/ddV into tmp (zeros wherever the
+// pixel is not valid); one partial sum of e per workgroup.  Pass 2, per pixel: dL/dP gathered from the four neighbours' dL/ddU, dL/ddV
+// (the transposed stencil, so nothing is scattered), chained through P = (x D, y D, D), D = depth / A; its first workgroup adds the
+// partials in a fixed order.  No atomics: bit-identical from run to run.
+
+struct NormalCam { int W, H; float tanx, tany, alpha_min; };
+struct Vec3 { float x, y, z; };
+
+__device__ __forceinline__ Vec3 cross3(const Vec3 a, const Vec3 b) {
+  return Vec3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+__device__ __forceinline__ float pixel_x(const NormalCam& c, int x) { return (2.f * ((float)x + 0.5f) / (float)c.W - 1.f) * c.tanx; }
+__device__ __forceinline__ float pixel_y(const NormalCam& c, int y) { return (2.f * ((float)y + 0.5f) / (float)c.H - 1.f) * c.tany; }
+// the back-projected point of pixel (x, y), whose alpha a is above alpha_min
+__device__ __forceinline__ Vec3 pixel_point(const NormalCam& c, const float* __restrict__ depth, int x, int y, float a) {
+  const float D = depth[(size_t)y * c.W + x] / a;
+  return Vec3{pixel_x(c, x) * D, pixel_y(c, y) * D, D};
+}
+
+__global__ __launch_bounds__(256) void normal_loss_pixel_kernel(NormalCam c, const float* __restrict__ normals,
+                                                                const float* __restrict__ depth, const float* __restrict__ alpha,
+                                                                float inv_n, float* __restrict__ grad_normals,
+                                                                float* __restrict__ grad_alpha, float* __restrict__ surface_normals,
+                                                                float* __restrict__ guv, float* __restrict__ partials) {
+  __shared__ float red[4];
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int W = c.W, H = c.H;
+  float e = 0.f;
+  if (x < W && y < H) {
+    const size_t plane = (size_t)H * W, p = (size_t)y * W + x;
+    Vec3 ns{0.f, 0.f, 0.f}, gdu{0.f, 0.f, 0.f}, gdv{0.f, 0.f, 0.f};
+    bool valid = x > 0 && x < W - 1 && y > 0 && y < H - 1;
+    float a = 0.f, al = 0.f, ar = 0.f, au = 0.f, ad = 0.f;
+    if (valid) {
+      a = alpha[p]; al = alpha[p - 1]; ar = alpha[p + 1]; au = alpha[p - W]; ad = alpha[p + W];
+      valid = a > c.alpha_min && al > c.alpha_min && ar > c.alpha_min && au > c.alpha_min && ad > c.alpha_min;
+    }
+    if (valid) {
+      const Vec3 pl = pixel_point(c, depth, x - 1, y, al), pr = pixel_point(c, depth, x + 1, y, ar);
+      const Vec3 pu = pixel_point(c, depth, x, y - 1, au), pd = pixel_point(c, depth, x, y + 1, ad);
+      const Vec3 dU{pr.x - pl.x, pr.y - pl.y, pr.z - pl.z}, dV{pd.x - pu.x, pd.y - pu.y, pd.z - pu.z};
+      const Vec3 cr = cross3(dV, dU);   // faces the camera: (0, 0, -1) on a fronto-parallel plane
+      const float len = sqrtf((cr.x * cr.x + cr.y * cr.y) + cr.z * cr.z);
+      const Vec3 nr{normals[p], normals[plane + p], normals[2 * plane + p]};
+      float dot = 0.f;
+      if (len > 0.f) {
+        ns = Vec3{cr.x / len, cr.y / len, cr.z / len};
+        dot = (nr.x * ns.x + nr.y * ns.y) + nr.z * ns.z;
+        // dL/dc through N_s = c / |c|: -(N_r - N_s (N_s . N_r)) / (|c| H W)
+        const Vec3 gc{-inv_n * ((nr.x - ns.x * dot) / len), -inv_n * ((nr.y - ns.y * dot) / len),
+                      -inv_n * ((nr.z - ns.z * dot) / len)};
+        gdv = cross3(dU, gc); gdu = cross3(gc, dV);   // c = dV x dU
+      }
+      e = a - dot;
+    }
+    // (0 - ...: a pixel that is not valid gets +0, not -0)
+    grad_normals[p] = 0.f - inv_n * ns.x; grad_normals[plane + p] = 0.f - inv_n * ns.y;
+    grad_normals[2 * plane + p] = 0.f - inv_n * ns.z;
+    grad_alpha[p] = valid ? inv_n : 0.f;
+    if (surface_normals) { surface_normals[p] = ns.x; surface_normals[plane + p] = ns.y; surface_normals[2 * plane + p] = ns.z; }
+    guv[p] = gdu.x; guv[plane + p] = gdu.y; guv[2 * plane + p] = gdu.z;
+    guv[3 * plane + p] = gdv.x; guv[4 * plane + p] = gdv.y; guv[5 * plane + p] = gdv.z;
+  }
+  const float t = block_sum(e, red);
+  if (threadIdx.x == 0) partials[blockIdx.y * gridDim.x + blockIdx.x] = t;
+}
+
+__global__ __launch_bounds__(256) void normal_loss_gather_kernel(NormalCam c, const float* __restrict__ depth,
+                                                                 const float* __restrict__ alpha, const float* __restrict__ guv,
+                                                                 const float* __restrict__ partials, int n_wg, float n_pix,
+                                                                 float* __restrict__ grad_depth, float* __restrict__ grad_alpha,
+                                                                 float* __restrict__ term) {
+  __shared__ float red[4];
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int W = c.W, H = c.H;
+  if (x < W && y < H) {
+    const size_t plane = (size_t)H * W, p = (size_t)y * W + x;
+    const float a = alpha[p];
+    float gd = 0.f;
+    if (a > c.alpha_min) {   // (elsewhere no valid pixel has this one as a neighbour: every term below is zero)
+      float g[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {   // P(p) is the right point of its left neighbour's dU, the left point of its right one's, ...
+        const float* du = guv + k * plane;
+        const float* dv = guv + (3 + k) * plane;
+        const float l = x > 0 ? du[p - 1] : 0.f, r = x < W - 1 ? du[p + 1] : 0.f;
+        const float u = y > 0 ? dv[p - W] : 0.f, d = y < H - 1 ? dv[p + W] : 0.f;
+        g[k] = ((l - r) + u) - d;
+      }
+      const float gD = (pixel_x(c, x) * g[0] + pixel_y(c, y) * g[1]) + g[2];
+      gd = gD / a;
+      grad_alpha[p] = grad_alpha[p] - gd * (depth[p] / a);
+    }
+    grad_depth[p] = gd;
+  }
+  if (blockIdx.x == 0 && blockIdx.y == 0) {   // lane t adds partials t, t + 256, ... in that order, then the block's fixed tree
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n_wg; i += 256) s += partials[i];
+    const float t = block_sum(s, red);
+    if (threadIdx.x == 0) term[0] = t / n_pix;
+  }
+}
+
 }  // namespace
+
+extern "C" size_t ggd_normal_loss_tmp_bytes(int32_t W, int32_t H) {
+  if (W <= 0 || H <= 0) return 0;
+  // one partial per workgroup | dL/ddU and dL/ddV, three planes each
+  return ggd_align(geometry_loss_workgroups(W, H) * sizeof(float)) + ggd_align((size_t)6 * H * W * sizeof(float));
+}
+
+extern "C" int ggd_normal_loss(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, const float* normals, const float* depth,
+                               const float* alpha, float tanfovx, float tanfovy, float alpha_min, float* term,
+                               float* grad_normals, float* grad_depth, float* grad_alpha, float* surface_normals, void* tmp,
+                               size_t tmp_bytes) {
+  if (!ctx) return GGD_E_INVALID;
+  if (W <= 0 || H <= 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_normal_loss: empty image");
+  if (!normals || !depth || !alpha || !term || !grad_normals || !grad_depth || !grad_alpha || !tmp)
+    return ggd_fail(ctx, GGD_E_INVALID, "ggd_normal_loss: NULL pointer");
+  if (!(alpha_min >= 0.f)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_normal_loss: alpha_min must not be negative");
+  if (tmp_bytes < ggd_normal_loss_tmp_bytes(W, H)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_normal_loss: tmp too small");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const NormalCam c{W, H, tanfovx, tanfovy, alpha_min};
+  const float n_pix = (float)H * (float)W;
+  const size_t n_wg = geometry_loss_workgroups(W, H);
+  const dim3 grid((W + 63) / 64, (H + 3) / 4);
+  float* partials = static_cast<float*>(tmp);
+  float* guv = reinterpret_cast<float*>(static_cast<char*>(tmp) + ggd_align(n_wg * sizeof(float)));
+  hipLaunchKernelGGL(normal_loss_pixel_kernel, grid, dim3(256), 0, s, c, normals, depth, alpha, 1.f / n_pix, grad_normals,
+                     grad_alpha, surface_normals, guv, partials);
+  hipLaunchKernelGGL(normal_loss_gather_kernel, grid, dim3(256), 0, s, c, depth, alpha, guv, partials, (int)n_wg, n_pix,
+                     grad_depth, grad_alpha, term);
+  GGD_HIP(hipGetLastError());
+  return GGD_OK;
+}
 
 extern "C" size_t ggd_geometry_loss_tmp_bytes(int32_t W, int32_t H) {
   if (W <= 0 || H <= 0) return 0;

@@ -37,11 +37,17 @@ __device__ __forceinline__ float4 act_normalize(float4 q, float& norm) {
   const float d = fmaxf(norm, 1e-12f);  // torch.nn.functional.normalize: v / max(||v||, eps)
   return make_float4(q.x / d, q.y / d, q.z / d, q.w / d);
 }
+// Its Jacobian, transposed: dq = dL/dq_hat -> dL/dq through q_hat = q / max(||q||, eps): (g - q_hat (q_hat . g)) / max(||q||, eps)
+__device__ __forceinline__ float4 act_normalize_backward(float4 q_hat, float norm, float4 dq) {
+  const float dotg = (q_hat.x * dq.x + q_hat.y * dq.y) + (q_hat.z * dq.z + q_hat.w * dq.w);
+  const float dn = fmaxf(norm, 1e-12f);
+  return make_float4((dq.x - q_hat.x * dotg) / dn, (dq.y - q_hat.y * dotg) / dn, (dq.z - q_hat.z * dotg) / dn,
+                     (dq.w - q_hat.w * dotg) / dn);
+}
 
-// Sigma = R S S R^T, stored (S00,S01,S02,S11,S12,S22); quaternion (w,x,y,z) used as given (not re-normalised).
-__device__ __forceinline__ void cov3d_from_scale_rot(const float s3[3], float mod, const float4 q, float cov6[6]) {
+// The rotation matrix of the quaternion (w,x,y,z), used as given (not re-normalised).
+__device__ __forceinline__ void quat_rotation(const float4 q, float R[3][3]) {
   const float r = q.x, x = q.y, y = q.z, z = q.w;
-  float R[3][3];
   R[0][0] = 1.0f - 2.0f * (y * y + z * z);
   R[0][1] = 2.0f * (x * y - r * z);
   R[0][2] = 2.0f * (x * z + r * y);
@@ -51,6 +57,25 @@ __device__ __forceinline__ void cov3d_from_scale_rot(const float s3[3], float mo
   R[2][0] = 2.0f * (x * z - r * y);
   R[2][1] = 2.0f * (y * z + r * x);
   R[2][2] = 1.0f - 2.0f * (x * x + y * y);
+}
+// dL/d(w,x,y,z) from Q[i][j] = dL/dR[i][j] of R = quat_rotation(q).
+__device__ __forceinline__ float4 quat_rotation_backward(const float4 q, const float Q[3][3]) {
+  const float r = q.x, x = q.y, y = q.z, z = q.w;
+  float4 dq;
+  dq.x = 2.0f * (-z * Q[0][1] + y * Q[0][2] + z * Q[1][0] - x * Q[1][2] - y * Q[2][0] + x * Q[2][1]);
+  dq.y = 2.0f * (y * Q[0][1] + z * Q[0][2] + y * Q[1][0] - 2.0f * x * Q[1][1] - r * Q[1][2] + z * Q[2][0] +
+                 r * Q[2][1] - 2.0f * x * Q[2][2]);
+  dq.z = 2.0f * (-2.0f * y * Q[0][0] + x * Q[0][1] + r * Q[0][2] + x * Q[1][0] + z * Q[1][2] - r * Q[2][0] +
+                 z * Q[2][1] - 2.0f * y * Q[2][2]);
+  dq.w = 2.0f * (-2.0f * z * Q[0][0] - r * Q[0][1] + x * Q[0][2] + r * Q[1][0] - 2.0f * z * Q[1][1] +
+                 y * Q[1][2] + x * Q[2][0] + y * Q[2][1]);
+  return dq;
+}
+
+// Sigma = R S S R^T, stored (S00,S01,S02,S11,S12,S22), R = quat_rotation(q).
+__device__ __forceinline__ void cov3d_from_scale_rot(const float s3[3], float mod, const float4 q, float cov6[6]) {
+  float R[3][3];
+  quat_rotation(q, R);
   const float s[3] = {mod * s3[0], mod * s3[1], mod * s3[2]};
   float M[3][3];
 #pragma unroll

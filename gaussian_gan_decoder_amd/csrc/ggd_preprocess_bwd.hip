@@ -230,11 +230,8 @@ __device__ __forceinline__ void preprocess_backward_body(
 
   // (4) cov3D -> scale, quaternion
   if (!cov3D_precomp) {
-    const float r = q.x, x = q.y, y = q.z, z = q.w;
     float R[3][3];
-    R[0][0] = 1.0f - 2.0f * (y * y + z * z); R[0][1] = 2.0f * (x * y - r * z); R[0][2] = 2.0f * (x * z + r * y);
-    R[1][0] = 2.0f * (x * y + r * z); R[1][1] = 1.0f - 2.0f * (x * x + z * z); R[1][2] = 2.0f * (y * z - r * x);
-    R[2][0] = 2.0f * (x * z - r * y); R[2][1] = 2.0f * (y * z + r * x); R[2][2] = 1.0f - 2.0f * (x * x + y * y);
+    quat_rotation(q, R);
     const float s[3] = {mod * s3[0], mod * s3[1], mod * s3[2]};
     float Mm[3][3];
 #pragma unroll
@@ -262,19 +259,9 @@ __device__ __forceinline__ void preprocess_backward_body(
       dscale[0] *= s3[0]; dscale[1] *= s3[1]; dscale[2] *= s3[2];
     }
     dL_dscales[3 * ii] = dscale[0]; dL_dscales[3 * ii + 1] = dscale[1]; dL_dscales[3 * ii + 2] = dscale[2];
-    float4 dq;
-    dq.x = 2.0f * (-z * Q[0][1] + y * Q[0][2] + z * Q[1][0] - x * Q[1][2] - y * Q[2][0] + x * Q[2][1]);
-    dq.y = 2.0f * (y * Q[0][1] + z * Q[0][2] + y * Q[1][0] - 2.0f * x * Q[1][1] - r * Q[1][2] + z * Q[2][0] +
-                   r * Q[2][1] - 2.0f * x * Q[2][2]);
-    dq.z = 2.0f * (-2.0f * y * Q[0][0] + x * Q[0][1] + r * Q[0][2] + x * Q[1][0] + z * Q[1][2] - r * Q[2][0] +
-                   z * Q[2][1] - 2.0f * y * Q[2][2]);
-    dq.w = 2.0f * (-2.0f * z * Q[0][0] - r * Q[0][1] + x * Q[0][2] + r * Q[1][0] - 2.0f * z * Q[1][1] +
-                   y * Q[1][2] + x * Q[2][0] + y * Q[2][1]);
-    if (raw) {  // through q_hat = q / max(||q||, eps): (g - q_hat (q_hat . g)) / max(||q||, eps)
-      const float dotg = (q.x * dq.x + q.y * dq.y) + (q.z * dq.z + q.w * dq.w);
-      const float dn = fmaxf(q_norm, 1e-12f);
-      dq = make_float4((dq.x - q.x * dotg) / dn, (dq.y - q.y * dotg) / dn, (dq.z - q.z * dotg) / dn,
-                       (dq.w - q.w * dotg) / dn);
+    float4 dq = quat_rotation_backward(q, Q);
+    if (raw) {
+      dq = act_normalize_backward(q, q_norm, dq);
       (void)q_raw;
     }
     reinterpret_cast<float4*>(dL_drots)[i] = dq;

@@ -15,6 +15,8 @@ import math
 
 import torch
 
+from . import _capi
+from .normals import gaussian_normals
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _check_camera_grad, _check_distortion
 from .sh import eval_sh
 
@@ -27,6 +29,43 @@ def _screenspace_points(pc):
     except Exception:
         pass
     return pts
+
+
+def _check_normals(features, feature_bg, absgrad, camera_grad, cov3D_python=False):
+    """The render_normals keyword's refusals (ValueError), before anything is built: returns the caller's channel count C."""
+    if absgrad:
+        raise ValueError("render_normals cannot be combined with absgrad=True: the normals ride the feature pass, which refuses it")
+    if camera_grad:
+        raise ValueError("render_normals cannot be combined with camera_grad=True: the normals' dependence on the view matrix is "
+                         "not differentiated, and the camera's gradient would be silently incomplete")
+    if cov3D_python:
+        raise ValueError("render_normals needs scales and rotations: pipe.compute_cov3D_python hands the rasterizer neither")
+    if features is None and feature_bg is not None:
+        raise ValueError("feature_bg without features")
+    if features is not None and features.dim() != 2:
+        raise ValueError(f"features must have dimensions (num_points, C) (got {tuple(features.shape)})")
+    Cn = 0 if features is None else int(features.shape[1])
+    if Cn + 3 > _capi.FEATURES_MAX_CHANNELS:
+        raise ValueError(f"render_normals adds 3 channels to the caller's {Cn}: at most {_capi.FEATURES_MAX_CHANNELS} are rendered "
+                         "in one pass")
+    return Cn
+
+
+def _with_normals(features, feature_bg, rotations, scales, means3D, viewpoint_camera, raw):
+    """The feature keywords of a render_normals call: the Gaussians' normals as three channels behind the caller's (background 0)."""
+    normals = gaussian_normals(rotations, scales, means3D, viewpoint_camera.world_view_transform, raw=raw)
+    if features is None:
+        return dict(features=normals, feature_bg=None)
+    if feature_bg is not None:
+        feature_bg = torch.cat([feature_bg.reshape(-1), feature_bg.new_zeros(3)])
+    return dict(features=torch.cat([features, normals], 1), feature_bg=feature_bg)
+
+
+def _split_normals(res, fmap, n_feat):
+    """out["features"] (the caller's channels, if any) and out["normals"] from the map of a render_normals call."""
+    if n_feat:
+        res["features"] = fmap[:n_feat]
+    res["normals"] = fmap[n_feat:]
 
 
 def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attributes=False, render_depth_alpha=False,
@@ -59,7 +98,7 @@ def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attri
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
            render_depth_alpha=False, antialiasing=False, absgrad=False, features=None, feature_bg=None,
-           render_distortion=False, camera_grad=False):
+           render_distortion=False, camera_grad=False, render_normals=False):
     """Stock 3DGS render (reference :19-102).  `pipe` needs .debug, .compute_cov3D_python, .convert_SHs_python.
     render_depth_alpha=True (extension): the dict also holds "depth" (sum alpha_i T_i z_i) and "alpha" (1 - final T),
     differentiable float32 [1, H, W] maps.
@@ -73,7 +112,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     colour's contributors -- the distortion loss of Mip-NeRF 360 / 2DGS is its mean times a weight that carries the scene's scale.
     camera_grad=True (extension; refuses absgrad): the backward also differentiates the frame in the camera.  The dict is
     unchanged; the gradients arrive on viewpoint_camera.world_view_transform, .full_proj_transform and .camera_center, and through
-    them on whatever built those with differentiable torch ops (CustomCam's `extr`, for instance).  FoVx / FoVy get none."""
+    them on whatever built those with differentiable torch ops (CustomCam's `extr`, for instance).  FoVx / FoVy get none.
+    render_normals=True (extension; refuses absgrad, camera_grad, pipe.compute_cov3D_python and more than 29 caller's feature
+    channels): the dict also holds "normals", the differentiable float32 [3, H, W] map sum alpha_i T_i n_i of the Gaussians'
+    camera-facing view-space normals (normals.gaussian_normals of the scales and rotations of this call), blended as three more
+    channels of the feature pass -- what normals.fused_normal_loss compares with the depth map's surface."""
+    if render_normals:
+        n_feat = _check_normals(features, feature_bg, absgrad, camera_grad, pipe.compute_cov3D_python)
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, pipe.debug,
                                               render_depth_alpha=render_depth_alpha, antialiasing=antialiasing,
@@ -96,6 +141,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     else:
         colors_precomp = override_color
     feat_kw = {} if features is None and feature_bg is None else dict(features=features, feature_bg=feature_bg)
+    if render_normals:
+        feat_kw = _with_normals(features, feature_bg, rotations, scales, pc.get_xyz, viewpoint_camera, False)
     out = rasterizer(means3D=pc.get_xyz, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
                      opacities=pc.get_opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, **feat_kw)
     rendered_image, radii = out[0], out[1]
@@ -105,14 +152,17 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         res["depth"], res["alpha"] = out[2], out[3]
     if render_distortion:
         res["distortion"] = out[4]
-    if features is not None:
+    if render_normals:
+        _split_normals(res, out[-1], n_feat)
+    elif features is not None:
         res["features"] = out[-1]
     return res
 
 
 def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None, scaling_modifier=1.0,
                   override_color=None, debug=False, fused_activations=False, render_depth_alpha=False, antialiasing=False,
-                  absgrad=False, features=None, feature_bg=None, render_distortion=False, camera_grad=False):
+                  absgrad=False, features=None, feature_bg=None, render_distortion=False, camera_grad=False,
+                  render_normals=False):
     """Decoder-path render (reference :105-186): scale/rotation always from the model, SH unless override_color.
     "alpha" and "depth" are the radii placeholders the reference returns (:184-185).
     fused_activations=True (extension): hand the RAW `_opacity/_scaling/_rotation` to the
@@ -129,7 +179,12 @@ def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None,
     render_distortion=True (extension): as in `render` -- "distortion" is the [1, H, W] map; needs render_depth_alpha=True, combines
     with everything above but absgrad.
     camera_grad=True (extension): as in `render` -- the dict is unchanged and the camera's tensors receive gradients; combines with
-    everything above but absgrad."""
+    everything above but absgrad.
+    render_normals=True (extension): as in `render` -- "normals" is the [3, H, W] map, of the normals of the scales and rotations
+    this call passes on (raw with fused_activations) at the means it passes on (xyz_offset included); combines with everything
+    above but absgrad and camera_grad."""
+    if render_normals:
+        n_feat = _check_normals(features, feature_bg, absgrad, camera_grad)
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug,
                                               raw_attributes=fused_activations, render_depth_alpha=render_depth_alpha,
@@ -148,6 +203,8 @@ def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None,
     else:
         opacities, scales, rotations = pc.get_opacity, pc.get_scaling, pc.get_rotation
     feat_kw = {} if features is None and feature_bg is None else dict(features=features, feature_bg=feature_bg)
+    if render_normals:
+        feat_kw = _with_normals(features, feature_bg, rotations, scales, means3D, viewpoint_camera, fused_activations)
     out = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
                      opacities=opacities, scales=scales, rotations=rotations, cov3D_precomp=None, **feat_kw)
     rendered_image, radii = out[0], out[1]
@@ -156,6 +213,8 @@ def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None,
            "radii": radii, "alpha": alpha, "depth": depth}
     if render_distortion:
         res["distortion"] = out[4]
-    if features is not None:
+    if render_normals:
+        _split_normals(res, out[-1], n_feat)
+    elif features is not None:
         res["features"] = out[-1]
     return res

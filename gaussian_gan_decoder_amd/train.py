@@ -35,6 +35,7 @@ import torch
 from .cameras import CustomCam, look_at_cam2world
 from .decoder import DECODER_TYPES
 from .losses import composite_mask, fused_geometry_loss, fused_image_loss, PerceptualStandIn
+from .normals import fused_normal_loss
 from .gaussian_model import GaussianModel
 
 BUCKET_BYTES = 32 << 20
@@ -129,7 +130,7 @@ class DecoderTrainer:
                  triplane_depth=None, fused_planes=None, force_comm=None, antialiasing: bool = False,
                  apply_mask_to_rendering: bool = False, decoder_type: str = "sequential_reversed",
                  mask_weight: float = 0.0, depth_weight: float = 0.0, geometry_loss_fn=None,
-                 distortion_weight: float = 0.0):
+                 distortion_weight: float = 0.0, normal_weight: float = 0.0):
         """plane_axes / triplane_depth: the generator whose planes are decoded -- ("eg3d", None): tri-planes
         [3, C, res, res]; ("panohead", 3): PanoHead's tri-grids [3, C * 3, res, res] sampled with a 3-D grid_sample
         (the reference's default generator: main/train_pano2gaussian_decoder.py:43, PanoHead/train.py:230,318,
@@ -159,7 +160,12 @@ class DecoderTrainer:
         render_depth_alpha=True, render_distortion=True (passed to render_fn only then) and distortion_weight *
         out["distortion"].mean() is added to the scene's loss -- the distortion loss of Mip-NeRF 360 / 2DGS, which tells a thin
         surface from a fog of the same expected depth.  The map is in raw view-space depth units, so the weight carries the
-        scene's scale; no value is tuned."""
+        scene's scale; no value is tuned.
+        normal_weight (default 0: off, nothing changes): with a positive weight the scene is rendered with
+        render_depth_alpha=True, render_normals=True (passed to render_fn only then) and normal_weight *
+        normals.fused_normal_loss(out["normals"], out["depth"], out["alpha"], tanfov, tanfov)[0] is added to the scene's loss --
+        the normal-consistency loss of 2DGS / gsplat, which turns each splat's shortest axis along the normal of the surface the
+        depth map describes.  No value is tuned, the loss's alpha_min included."""
         import os
         import torch.distributed as dist
         self.force_comm = bool(int(os.environ.get("GGD_FORCE_COMM", "0"))) if force_comm is None else bool(force_comm)
@@ -235,6 +241,11 @@ class DecoderTrainer:
             raise ValueError("distortion_weight must not be negative")
         if self.distortion_weight > 0:
             self.render_kwargs.update(render_depth_alpha=True, render_distortion=True)
+        self.normal_weight = float(normal_weight)
+        if self.normal_weight < 0:
+            raise ValueError("normal_weight must not be negative")
+        if self.normal_weight > 0:
+            self.render_kwargs.update(render_depth_alpha=True, render_normals=True)
         self.bg =torch.tensor([0.55717, 0.52256, 0.51045], dtype=torch.float32, device=self.device)
         # scene_streams: every local scene's raster + loss on its own HIP stream (own ggd_ctx).  Measured on one MI355X
         # (4 scenes x 500 k points, fused decoder): 21.13 ms / step with and without -- the single-call forward already
@@ -488,6 +499,9 @@ class DecoderTrainer:
                                                 tan, tan, self.mask_weight, self.depth_weight)[0]
         if self.distortion_weight > 0:
             loss = loss + self.distortion_weight * out["distortion"].mean()
+        if self.normal_weight > 0:
+            tan = math.tan(fov / 2)
+            loss = loss + self.normal_weight * fused_normal_loss(out["normals"], out["depth"], out["alpha"], tan, tan)[0]
         if self.perceptual is not None:
             # the reference evaluates its perceptual network on the whole batch at once (lpips.py:29-31): the rendered
             # images are collected and local_loss makes ONE call on the stack

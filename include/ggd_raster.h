@@ -680,6 +680,48 @@ int ggd_geometry_loss(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, const fl
                       float* grad_alpha, void* tmp, size_t tmp_bytes);
 
 /*
+ * Per-Gaussian view-space normals (csrc/ggd_normals.hip): a splat's shortest axis, turned towards the camera.  All arrays DEVICE
+ * fp32: rotations [P,4] (w,x,y,z; 16-byte aligned), scales [P,3], means3D [P,3], viewmatrix [16] in the rasterizer's layout
+ * (p_view = p . V[:3,:3] + V[3,:3], V[a][c] = viewmatrix[4a + c]).  Per row:
+ *   raw == 0: q = the quaternion as given (not re-normalised);  raw != 0: q = rotation / max(|rotation|, 1e-12), the rule of the
+ *             rasterizer's fused-activation prologue (a zero quaternion stays zero: R = I), and scales are the raw log-scales
+ *             (exp is monotonic: the same argmin);
+ *   k = argmin_j scales[j], ties to the lowest index;   n_w = column k of R(q), R the matrix the rasterizer builds Sigma = R S S R^T from;
+ *   n_v = n_w . V[:3,:3];   p_v = the view-space mean;   normals[row] = -n_v if n_v . p_v > 0, else n_v   (so n . p_v <= 0).
+ * ggd_gaussian_normals_backward: dL_drotations [P,4] (16-byte aligned) = J^T dL_dnormals, J the derivative of column k of R in
+ * (w,x,y,z) through V and the sign, and through the normalisation when raw.  Scales, means and the view matrix get no gradient:
+ * the argmin and the facing sign are decisions.  One launch each, one thread per Gaussian; no atomics, no scratch, no host wait.
+ * P == 0 is legal and launches nothing; P < 0, a NULL or a misaligned pointer: GGD_E_INVALID, nothing launched.
+ */
+int ggd_gaussian_normals(ggd_ctx* ctx, void* stream, int32_t P, const float* rotations, const float* scales,
+                         const float* means3D, const float* viewmatrix, int32_t raw, float* normals);
+int ggd_gaussian_normals_backward(ggd_ctx* ctx, void* stream, int32_t P, const float* rotations, const float* scales,
+                                  const float* means3D, const float* viewmatrix, int32_t raw, const float* dL_dnormals,
+                                  float* dL_drotations);
+
+/*
+ * Normal-consistency loss (2DGS / gsplat / PGSR): the blended normal map N_r = sum alpha_i T_i n_i (device [3,H,W] fp32,
+ * unnormalised: a feature map of ggd_forward_features over ggd_gaussian_normals) against the normals of the surface that the
+ * depth map describes, and its gradient.  depth = sum alpha_i T_i z_i and alpha A (device [H,W], the aux maps).  Pixel (i, j) has
+ * x_j = (2 (j + 0.5) / W - 1) tanfovx, y_i = (2 (i + 0.5) / H - 1) tanfovy (the rasterizer's pixel centres, as ggd_geometry_loss);
+ *   ok(p) = A(p) > alpha_min;   D = depth / A;   P = (x_j D, y_i D, D);
+ *   at an interior pixel whose own ok and its four axis neighbours' ok hold:
+ *     dU = P(i, j+1) - P(i, j-1),  dV = P(i+1, j) - P(i-1, j),  c = dV x dU  (faces the camera: (0, 0, -1) on a fronto-parallel plane),
+ *     N_s = c / |c| (0 if |c| = 0),  e = A - N_r . N_s;
+ *   everywhere else e = 0 and N_s = 0;   L = sum e / (H W).
+ * term (device, 1 float) = L.  grad_normals [3,H,W], grad_depth, grad_alpha [H,W]: the exact derivative of L as stated -- nothing is
+ * detached, the path through D into the neighbours' N_s included.  surface_normals: NULL, or [3,H,W] that receives N_s.
+ * tmp: device scratch of ggd_normal_loss_tmp_bytes(W, H) bytes.  Two kernel launches (the per-pixel pass; the gather of the
+ * transposed stencil, whose first workgroup also adds the per-workgroup partial sums), no host sync, no float atomics: term and
+ * gradients are bit-identical from run to run.  GGD_E_INVALID, nothing launched: W or H <= 0, a NULL pointer other than
+ * surface_normals, alpha_min < 0 (or NaN), a tmp that is too small.
+ */
+size_t ggd_normal_loss_tmp_bytes(int32_t W, int32_t H);
+int ggd_normal_loss(ggd_ctx* ctx, void* stream, int32_t W, int32_t H, const float* normals, const float* depth,
+                    const float* alpha, float tanfovx, float tanfovy, float alpha_min, float* term, float* grad_normals,
+                    float* grad_depth, float* grad_alpha, float* surface_normals /* or NULL */, void* tmp, size_t tmp_bytes);
+
+/*
  * Exact 3-nearest-neighbour search: the `distCUDA2` of the simple_knn module that gaussian_splatting/scene/gaussian_model.py
  * imports (:20) to seed the scales of a new model (:132, :160).  points: DEVICE float32 [P][3], 4 <= P <= ggd_knn_max_points()
  * (2^26; fewer than 4 points have no three neighbours: GGD_E_INVALID).  For every point i, over all j != i (a different INDEX:
