@@ -169,6 +169,39 @@ def test_depth_and_alpha_gradients_match_reference(native_lib):
     _check_camera(_identity(d, outs, "depth_alpha"), val, b, car, "depth_alpha")
 
 
+def test_antialiasing_with_depth_and_alpha_matches_reference(native_lib):
+    """antialiasing and the depth / alpha maps in one call (camera_partial_kernel<true, true>): the oracle at the opacities the
+    GPU's records carry, the depth / alpha reference on it, the h chain over the JOINED opacity sum and the depth slot on dtz p_c"""
+    import _antialias_ref as AA
+    import _depth_alpha_ref as DA
+    from test_antialiasing_gpu import _gpu_opacity_inputs
+    what = "antialiasing + depth_alpha"
+    d, res, n = _instance(antialiasing=True, render_depth_alpha=True)
+    d_o = _gpu_opacity_inputs(d, n)
+    o = run_oracle(d_o)
+    frag_px, _ = assert_blend_matches(n, o, what=what)
+    g, gD, gA = _upstream(d, frag_px, planes=(1, 1))
+    ref, bud, frag = DA.backward_ref(d_o, o, n, g.numpy(), gD.numpy()[0], gA.numpy()[0])
+    assert int((frag > 0).sum()) == 0
+    gz, gzb = CR.depth_slot(o, gD.numpy()[0], gA.numpy()[0], n)
+    outs = _backward(d, res, g, aa=True, dL_ddepth=gD, dL_dalpha=gA)
+    assert len(outs) == 11
+    op = d["opacities"].numpy()
+    val, b, car, _ = CR.reference(o, ref, bud, gz, gzb, aa_opacity=op)
+    no_chain, _, _, _ = CR.reference(o, ref, bud, gz, gzb)
+    no_slot, _, _, _ = CR.reference(o, ref, bud, aa_opacity=op)
+    scale = np.abs(val[:12]).max()
+    print(f"[camera_grad] {what}: the h chain moves the reference by {np.abs(val - no_chain)[:12].max() / scale:.2e} of its scale, "
+          f"the depth slot by {np.abs(val - no_slot)[:12].max() / scale:.2e}")
+    assert np.abs(val - no_chain)[:12].max() > 1e-3 * scale, "the scene must make the h chain count"
+    assert np.abs(val - no_slot)[:12].max() > 1e-3 * scale, "the depth slot must count"
+    ref8, bud8 = AA.compose_backward(d, ref, bud)
+    worst8 = check_gradients(d, dict(zip(NAMES, outs)), ref8, bud8, frag)
+    print(f"[camera_grad] {what}: eight gradients error / bound {worst8:.4f}")
+    assert worst8 <= 1.0
+    _check_camera(_identity(d, outs, what), val, b, car, what)
+
+
 def test_features_with_distortion_match_reference(native_lib):
     """features C = 5 with the distortion map: three kernels' sums joined in the accumulator records, the map's dL/dz in the depth
     slot.  The distortion reference's budgets enter at its own K (DR.K / KAPPA of the others'), as its composition test does."""
