@@ -1,7 +1,10 @@
 // ggd_blend_math.h -- the device expressions that decide whether a (pixel, record) pair contributes, and with which alpha, stated
-// ONCE for every kernel that walks a tile's list: the colour blend (ggd_blend.hip) and the feature blend (ggd_features.hip).
-// With -ffp-contract=off the same expression gives the same bits in both translation units, so a pass that recomputes alpha
-// takes the colour pass's decision on every pair (the forward and the backward of the colour blend stay in step the same way).
+// ONCE for every kernel that walks a tile's list: the colour blend (ggd_blend.hip) and, through ggd_quarter_walk.h, the passes
+// that blend another map behind it (ggd_features.hip, which also carries the normals, and ggd_distortion.hip).  These are the
+// leaf expressions; the sequence that combines them into a pair's contribution decision is bwd_update / the forward loop in
+// ggd_blend.hip, pair_forward in ggd_quarter_walk.h and the backward kernels of the two passes.  With -ffp-contract=off the same
+// expression gives the same bits in every translation unit, so a pass that recomputes alpha takes the colour pass's decision on
+// every pair (the forward and the backward of the colour blend stay in step the same way).
 // Included inside each file's unnamed namespace: the definitions keep internal linkage.
 #pragma once
 

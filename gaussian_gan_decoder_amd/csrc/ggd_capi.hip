@@ -633,6 +633,9 @@ static int duplicate_sort_ranges(ggd_ctx* ctx, hipStream_t s, const ggd_params* 
   return ggd_launch_ranges(ctx, s, b.keys, R, ranges, T);
 }
 
+// the kernels bound their list positions with a 32-bit R
+static uint32_t list_capacity(int64_t R) { return R > 0xffffffffll ? 0xffffffffu : (uint32_t)R; }
+
 // R: number of instances to process (<= fb.capacity; equal unless the caller over-allocated).  speculative: R is only a CAPACITY
 // (the true num_rendered is still on the device); only the tile-binning path can run that way
 static int render_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, const ggd_frame_bufs& fb, int64_t R,
@@ -649,7 +652,7 @@ static int render_enqueue(ggd_ctx* ctx, void* stream, const ggd_params* prm, con
   const img_ptrs im = img_view(prm->width, prm->height, fb.img_buf);
   const bool tiles = use_tile_binning(ctx, prm, R);
   if (speculative && !tiles) return ggd_fail(ctx, GGD_E_INVALID, "speculative render needs the tile-binning path");
-  const uint32_t capacity = R > 0xffffffffll ? 0xffffffffu : (uint32_t)R;
+  const uint32_t capacity = list_capacity(R);
   rc = (R > 0 && tiles) ? sort_depth_and_bin_tiles(ctx, s, prm, g, b.list, im.ranges, capacity, speculative)
                         : duplicate_sort_ranges(ctx, s, prm, g, b, im.ranges, R);
   if (rc != GGD_OK) return rc;
@@ -798,6 +801,12 @@ struct bwd_features {     // the feature map's side of ggd_backward_features
   const float* features = nullptr; int C = 0; const float* feature_bg = nullptr;
   const float* dL_dfeatmap = nullptr; float* dL_dfeatures = nullptr;
 };
+// the C ABI's bundle as backward_impl takes it, in `store`; NULL (no feature map) stays NULL
+static const bwd_features* feature_side(const ggd_feature_side* f, bwd_features& store) {
+  if (!f) return nullptr;
+  store = {.features = f->features, .C = f->C, .feature_bg = f->feature_bg, .dL_dfeatmap = f->dL_dfeatmap, .dL_dfeatures = f->dL_dfeatures};
+  return &store;
+}
 static int check_feature_channels(ggd_ctx* ctx, int C) {
   if (C < 1 || C > GGD_FEATURES_MAX_CHANNELS)
     return ggd_fail(ctx, GGD_E_INVALID, "feature channels C = " + std::to_string(C) + " outside 1 .. " + std::to_string(GGD_FEATURES_MAX_CHANNELS));
@@ -869,13 +878,13 @@ static int backward_impl(ggd_ctx* ctx, void* stream, const ggd_params* prm, bwd_
                                    g.depth_keys, abs);
     if (rc != GGD_OK) return rc;
     if (feat) {
-      rc = ggd_launch_features_backward(ctx, s, *prm, g.splat, b.list, im.ranges, R > 0xffffffffll ? 0xffffffffu : (uint32_t)R,
+      rc = ggd_launch_features_backward(ctx, s, *prm, g.splat, b.list, im.ranges, list_capacity(R),
                                         im.final_T, im.n_contrib, feat->features, feat->C, feat->feature_bg, feat->dL_dfeatmap,
                                         grad_acc, feat->dL_dfeatures);
       if (rc != GGD_OK) return rc;
     }
     if (dL_ddist) {
-      rc = ggd_launch_distortion_backward(ctx, s, *prm, g.splat, b.list, im.ranges, R > 0xffffffffll ? 0xffffffffu : (uint32_t)R,
+      rc = ggd_launch_distortion_backward(ctx, s, *prm, g.splat, b.list, im.ranges, list_capacity(R),
                                           im.final_T, im.n_contrib, g.depth_keys, dL_ddist, grad_acc);
       if (rc != GGD_OK) return rc;
     }
@@ -962,7 +971,7 @@ extern "C" int ggd_forward_features(ggd_ctx* ctx, void* stream, const ggd_params
   const geom_ptrs g = geom_view(prm, geom_buf);
   const binning_ptrs b = binning_view(R, binning_buf);
   const img_ptrs im = img_view(prm->width, prm->height, img_buf);
-  return ggd_launch_features_forward(ctx, s, *prm, g.splat, b.list, im.ranges, R > 0xffffffffll ? 0xffffffffu : (uint32_t)R,
+  return ggd_launch_features_forward(ctx, s, *prm, g.splat, b.list, im.ranges, list_capacity(R),
                                      im.n_contrib, features, C, feature_bg, out_features);
 }
 
@@ -1001,7 +1010,7 @@ extern "C" int ggd_forward_distortion(ggd_ctx* ctx, void* stream, const ggd_para
   const geom_ptrs g = geom_view(prm, geom_buf);
   const binning_ptrs b = binning_view(R, binning_buf);
   const img_ptrs im = img_view(prm->width, prm->height, img_buf);
-  return ggd_launch_distortion_forward(ctx, s, *prm, g.splat, b.list, im.ranges, R > 0xffffffffll ? 0xffffffffu : (uint32_t)R,
+  return ggd_launch_distortion_forward(ctx, s, *prm, g.splat, b.list, im.ranges, list_capacity(R),
                                        im.n_contrib, g.depth_keys, out_distortion);
 }
 
@@ -1019,10 +1028,9 @@ extern "C" int ggd_backward_distortion(ggd_ctx* ctx, void* stream, const ggd_par
   const ggd_grads out = {.dL_dmeans2D = dL_dmeans2D, .dL_dcolors = dL_dcolors, .dL_dopacity = dL_dopacity,
                          .dL_dmeans3D = dL_dmeans3D, .dL_dcov3D = dL_dcov3D, .dL_dsh = dL_dsh, .dL_dscales = dL_dscales,
                          .dL_drots = dL_drots};
-  if (!features) return backward_impl(ctx, stream, prm, BWD_DISTORTION, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, nullptr, dL_ddistortion);
-  const bwd_features feat = {.features = features->features, .C = features->C, .feature_bg = features->feature_bg,
-                             .dL_dfeatmap = features->dL_dfeatmap, .dL_dfeatures = features->dL_dfeatures};
-  return backward_impl(ctx, stream, prm, BWD_DISTORTION, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, &feat, dL_ddistortion);
+  bwd_features feat;
+  return backward_impl(ctx, stream, prm, BWD_DISTORTION, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, feature_side(features, feat),
+                       dL_ddistortion);
 }
 
 // the camera's gradients: ggd_backward_distortion's arguments, each map's side optional, + the bundle of the three results
@@ -1040,10 +1048,9 @@ extern "C" int ggd_backward_camera(ggd_ctx* ctx, void* stream, const ggd_params*
   const ggd_grads out = {.dL_dmeans2D = dL_dmeans2D, .dL_dcolors = dL_dcolors, .dL_dopacity = dL_dopacity,
                          .dL_dmeans3D = dL_dmeans3D, .dL_dcov3D = dL_dcov3D, .dL_dsh = dL_dsh, .dL_dscales = dL_dscales,
                          .dL_drots = dL_drots};
-  if (!features) return backward_impl(ctx, stream, prm, BWD_CAMERA, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, nullptr, dL_ddistortion, camera);
-  const bwd_features feat = {.features = features->features, .C = features->C, .feature_bg = features->feature_bg,
-                             .dL_dfeatmap = features->dL_dfeatmap, .dL_dfeatures = features->dL_dfeatures};
-  return backward_impl(ctx, stream, prm, BWD_CAMERA, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, &feat, dL_ddistortion, camera);
+  bwd_features feat;
+  return backward_impl(ctx, stream, prm, BWD_CAMERA, in, radii, geom_buf, binning_buf, img_buf, R, pix, out, feature_side(features, feat),
+                       dL_ddistortion, camera);
 }
 
 extern "C" int ggd_mark_visible(ggd_ctx* ctx, void* stream, int32_t P, const float* means3D,

@@ -4,10 +4,9 @@
 //   D = sum_i sum_j w_i w_j |z_i - z_j| = 2 sum_k w_k (z_k A_{k-1} - B_{k-1})      w = alpha T,  A_k = sum_{j<=k} w_j,  B_k = sum_{j<=k} w_j z_j
 //
 // (the second form because a tile's list is sorted by the depth key, a monotone image of z).  The contributors, their alpha and
-// their T are the colour pass's: both kernels walk the tile's sorted list bounded per pixel by the stored n_contrib and recompute
-// alpha with the colour kernels' own expressions (ggd_blend_math.h), as the feature blend does; z_k is the fp32 the preprocess
-// kernel stored in depth_keys.  Shape: one single-wave workgroup per 8x8 quarter, one pixel per lane, 64-entry rounds with the
-// gathering lane's pre-cull and the two-stage gather (ggd_quarter_walk.h); a staged record is two 16-byte words, z and the id.
+// their T are the colour pass's: both kernels are the quarter walk of ggd_quarter_walk.h, as the feature blend is -- the tile's
+// sorted list bounded per pixel by the stored n_contrib, alpha recomputed with the colour kernels' own expressions
+// (ggd_blend_math.h); z_k is the fp32 the preprocess kernel stored in depth_keys, gathered and staged beside the record.
 //
 // Backward, with g = dL/dD of the pixel and S^A_k = A - A_k, S^B_k = B - B_k the sums BEHIND record k:
 //   dD/dz_k = 2 w_k (A_{k-1} - S^A_k)                                          -> accumulator slot GGD_ACC_DEPTH
@@ -25,84 +24,47 @@ namespace {
 #include "ggd_blend_math.h"
 #include "ggd_quarter_walk.h"
 
-constexpr int FLUSH = 32;                   // staged records per chunk of the backward (a record per lane pair in its flush)
-constexpr int WPAD = 65;                    // row stride of the parked [record][pixel] matrices: lane = record reads without bank conflicts
-
 // the record gather with the Gaussian's depth beside it
 struct DepthGather {
   Gather g; const uint32_t* depth_keys;
   uint32_t z = 0;                        // fp32 bits of the view-space depth of the record in g.r0 .. r2
+  __device__ __forceinline__ void load_id(uint32_t pos0) { g.load_id(pos0); }
   __device__ __forceinline__ void load_rec() { g.load_rec(); z = depth_keys[g.id_cur]; }
 };
 
-// One round's records into LDS: lane j < n holds the record of list position pos0 + j, pre-culls it against the quarter's pixel
-// rectangle as the colour kernels' gathering lanes do (when the colour pass ran with its pre-cull) and stages the survivors
-// compacted, order preserved: {x, y, hA, nB} {hC, threshold, opacity, 0-based position in the tile's list}, z and the id.  Then
-// the next round's records and the ids of the one after are requested.  Returns the number of staged records (wave-uniform).
+// One round's records (stage_cull) and their z into LDS; the next round's records and the ids of the one after are requested at
+// once.  Returns the number of staged records (wave-uniform).
 __device__ __forceinline__ int stage_records(float4* s_rec, float* s_z, uint32_t* s_id, DepthGather& ga, int n, uint32_t pos0,
-                                             uint32_t pos_after_next, int cull, float wx0, float wy0) {
-  const int lane = threadIdx.x;
-  __syncthreads();                       // (single-wave workgroup) the previous round's LDS reads are done
-  bool keep = false;
-  const float4 r0 = ga.g.r0, r2 = ga.g.r2;
-  float4 r1 = ga.g.r1;
-  if (lane < n) {
-    keep = cull ? (record_box_hits(r0.x, r0.y, r2.z, r2.w, wx0, wx0 + 7.0f, wy0, wy0 + 7.0f) &&
-                   record_reaches_block(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r2.z, wx0, wx0 + 7.0f, wy0, wy0 + 7.0f))
-                : true;
-    r1.w = __uint_as_float(pos0 + (uint32_t)lane);
-  }
-  const uint64_t kept = __ballot(keep);
-  if (keep) {
-    const int slot = __popcll(kept & ((1ull << lane) - 1ull));
-    s_id[slot] = ga.g.id_cur;
-    s_z[slot] = __uint_as_float(ga.z);
-    s_rec[slot * 2 + 0] = r0; s_rec[slot * 2 + 1] = r1;
-  }
+                                             uint32_t pos_after_next, int cull, const QuarterGeom& g) {
+  const int ns = stage_cull(s_rec, s_id, ga.g, g, n, pos0, cull, [&](int slot) { s_z[slot] = __uint_as_float(ga.z); });
   ga.load_rec();
-  ga.g.load_id(pos_after_next);
+  ga.load_id(pos_after_next);
   __syncthreads();
-  return __popcll(kept);
+  return ns;
 }
 
 // The forward walk of the lane's pixel: A = sum w, B = sum w z, D = sum_k w_k (z_k A_{k-1} - B_{k-1}) (half the map's value).
 // EXP_MODE: the colour forward's (0, 1, 2).
 template <int EXP_MODE>
-__device__ __forceinline__ void walk_totals(float4* s_rec, float* s_z, uint32_t* s_id, const FeatGeom& g, uint32_t lastn,
-                                            uint32_t maxn, int cull, const ggd_splat* __restrict__ splat,
-                                            const uint32_t* __restrict__ list, const uint32_t* __restrict__ depth_keys, float& A,
-                                            float& B, float& D) {
-  const float pxf = (float)g.px, pyf = (float)g.py;
-  float Tr = 1.0f;
+__device__ __forceinline__ void walk_totals(float4* s_rec, float* s_z, uint32_t* s_id, const QuarterGeom& g, int cull,
+                                            const ggd_splat* __restrict__ splat, const uint32_t* __restrict__ list,
+                                            const uint32_t* __restrict__ depth_keys, float& A, float& B, float& D) {
   A = 0.0f; B = 0.0f; D = 0.0f;
-  DepthGather ga = {{splat, list, g.lo, g.lo + maxn - 1u}, depth_keys};
-  if (maxn > 0) { ga.g.load_id(0); ga.load_rec(); ga.g.load_id(ROUND); }
-  for (uint32_t base = 0; base < maxn; base += ROUND) {
-    const int n = (int)min((uint32_t)ROUND, maxn - base);
-    const int ns = stage_records(s_rec, s_z, s_id, ga, n, base, base + 2 * ROUND, cull, (float)g.qx0, (float)g.qy0);
-    for (int j = 0; j < ns; ++j) {
-      const float4 a = s_rec[j * 2 + 0], b = s_rec[j * 2 + 1];   // x y hA nB | hC thr opacity position
-      float dx, dy;
-      const float pw = blend_power(a.x, a.y, a.z, a.w, b.x, pxf, pyf, dx, dy);
-      const float thr = cull ? b.y : -__builtin_huge_valf();
-      const bool need = __float_as_uint(b.w) < lastn && pw >= thr;
-      if (__ballot(need) == 0ull) continue;
-      const float G = blend_exp<EXP_MODE>(pw);
-      const float alpha = fminf(0.99f, G * b.z);
-      const float test_T = Tr * (1.0f - alpha);
-      const bool upd = need && !(pw > 0.0f) && !(alpha < ALPHA_FLOOR) && !(test_T < 0.0001f);
-      const float w = upd ? alpha * Tr : 0.0f;
-      const float z = s_z[j];
-      D = __builtin_fmaf(w, __builtin_fmaf(z, A, -B), D);
-      A = A + w;
-      B = __builtin_fmaf(w, z, B);
-      Tr = upd ? test_T : Tr;
-    }
-  }
+  DepthGather ga = {Gather(splat, list, g), depth_keys};
+  walk_front<EXP_MODE>(
+      s_rec, g, cull, ga,
+      [&](int n, uint32_t pos0, uint32_t pos_after_next) {
+        return stage_records(s_rec, s_z, s_id, ga, n, pos0, pos_after_next, cull, g);
+      },
+      [&](int j, const PairForward& p) {
+        const float z = s_z[j];
+        D = __builtin_fmaf(p.w, __builtin_fmaf(z, A, -B), D);
+        A = A + p.w;
+        B = __builtin_fmaf(p.w, z, B);
+      });
 }
 
 // ---- forward -------------------------------------------------------------------------------------------------------------
-// cull: the colour pass tested `power >= threshold` with the record's stored threshold (GGD_OPT_BLEND_CULL on) or with -inf (off).
 template <int EXP_MODE>
 __global__ __launch_bounds__(64) void distortion_forward_kernel(int W, int H, int gx, int T, int cull,
                                                                 const ggd_splat* __restrict__ splat,
@@ -114,11 +76,9 @@ __global__ __launch_bounds__(64) void distortion_forward_kernel(int W, int H, in
   __shared__ float4 s_rec[ROUND * 2];
   __shared__ float s_z[ROUND];
   __shared__ uint32_t s_id[ROUND];
-  const FeatGeom g((int)blockIdx.x, W, H, gx, T, ranges, R);
-  const uint32_t lastn = g.in ? min(n_contrib[g.pix], g.hi - g.lo) : 0u;   // contributors: list positions 0 .. lastn - 1 of the tile
-  const uint32_t maxn = wave_max(lastn);
+  const QuarterGeom g((int)blockIdx.x, W, H, gx, T, ranges, R, n_contrib);
   float A, B, D;
-  walk_totals<EXP_MODE>(s_rec, s_z, s_id, g, lastn, maxn, cull, splat, list, depth_keys, A, B, D);
+  walk_totals<EXP_MODE>(s_rec, s_z, s_id, g, cull, splat, list, depth_keys, A, B, D);
   if (g.in) out[g.pix] = 2.0f * D;
 }
 
@@ -145,14 +105,13 @@ __global__ __launch_bounds__(64) void distortion_backward_kernel(int W, int H, i
   __shared__ float s_q[FLUSH * WPAD];    // G dL/dalpha    of (record of the chunk, pixel)
   __shared__ float s_v[FLUSH * WPAD];    // g dD/dz        of (record of the chunk, pixel)
   const int lane = threadIdx.x;
-  const FeatGeom g((int)blockIdx.x, W, H, gx, T, ranges, R);
-  const uint32_t lastn = g.in ? min(n_contrib[g.pix], g.hi - g.lo) : 0u;
-  const uint32_t maxn = wave_max(lastn);
+  const QuarterGeom g((int)blockIdx.x, W, H, gx, T, ranges, R, n_contrib);
+  const uint32_t lastn = g.lastn, maxn = g.maxn;
   if (maxn == 0) return;
   const float g2 = g.in ? 2.0f * dL_dD[g.pix] : 0.0f;
   if (__ballot(g2 != 0.0f) == 0ull) return;   // every term below carries the pixel's g
   float A, B, D;
-  walk_totals<(EXP_MODE == 3 ? 1 : EXP_MODE)>(s_rec, s_z, s_id, g, lastn, maxn, cull, splat, list, depth_keys, A, B, D);
+  walk_totals<(EXP_MODE == 3 ? 1 : EXP_MODE)>(s_rec, s_z, s_id, g, cull, splat, list, depth_keys, A, B, D);
 
   const float pxf = (float)g.px, pyf = (float)g.py;
   float Tr = g.in ? final_T[g.pix] : 0.0f;
@@ -162,13 +121,13 @@ __global__ __launch_bounds__(64) void distortion_backward_kernel(int W, int H, i
 
   // the round that ends at position ce (exclusive) starts at round_start(ce); ce = 0: no round, its loads re-read position 0
   auto round_start = [](uint32_t ce) { return ce > (uint32_t)ROUND ? ce - ROUND : 0u; };
-  DepthGather ga = {{splat, list, g.lo, g.lo + maxn - 1u}, depth_keys};
-  ga.g.load_id(round_start(maxn)); ga.load_rec(); ga.g.load_id(round_start(round_start(maxn)));
+  DepthGather ga = {Gather(splat, list, g), depth_keys};
+  ga.load_id(round_start(maxn)); ga.load_rec(); ga.load_id(round_start(round_start(maxn)));
   uint32_t cend = maxn;
   while (cend > 0) {
     const uint32_t cstart = round_start(cend);
     const int n = (int)(cend - cstart);
-    const int ns = stage_records(s_rec, s_z, s_id, ga, n, cstart, round_start(round_start(cstart)), cull, (float)g.qx0, (float)g.qy0);
+    const int ns = stage_records(s_rec, s_z, s_id, ga, n, cstart, round_start(round_start(cstart)), cull, g);
     for (int c1 = ns; c1 > 0; c1 -= FLUSH) {
       const int c0 = c1 > FLUSH ? c1 - FLUSH : 0;   // the chunk: staged records c0 .. c1 - 1
       uint32_t touched = 0;              // wave-uniform: records of the chunk some pixel of the quarter blended
@@ -245,14 +204,11 @@ __global__ __launch_bounds__(64) void distortion_backward_kernel(int W, int H, i
 int ggd_launch_distortion_forward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
                                   const uint32_t* list, const uint32_t* ranges, uint32_t R, const uint32_t* n_contrib,
                                   const uint32_t* depth_keys, float* out) {
-  const int gx = (prm.width + 15) / 16, gy = (prm.height + 15) / 16;
-  const int T = gx * gy;
-  if (T == 0) return GGD_OK;
-  const int em = ctx->opt[GGD_OPT_EXP_MODE] == 3 ? 1 : ctx->opt[GGD_OPT_EXP_MODE];   // as ggd_launch_blend
-  const int cull = ctx->opt[GGD_OPT_BLEND_CULL] != 0;
-  ggd_dispatch<3>(em, [&](auto e) {
-    hipLaunchKernelGGL((distortion_forward_kernel<decltype(e)::value>), dim3(4 * T), dim3(64), 0, s, prm.width, prm.height, gx,
-                       T, cull, splat, list, ranges, R, n_contrib, depth_keys, out);
+  const QuarterLaunch q = quarter_launch(ctx, prm, true);
+  if (q.T == 0) return GGD_OK;
+  ggd_dispatch<3>(q.em, [&](auto e) {
+    hipLaunchKernelGGL((distortion_forward_kernel<decltype(e)::value>), dim3(4 * q.T), dim3(64), 0, s, prm.width, prm.height, q.gx,
+                       q.T, q.cull, splat, list, ranges, R, n_contrib, depth_keys, out);
   });
   GGD_HIP(hipGetLastError());
   return GGD_OK;
@@ -261,14 +217,11 @@ int ggd_launch_distortion_forward(ggd_ctx* ctx, hipStream_t s, const ggd_params&
 int ggd_launch_distortion_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
                                    const uint32_t* list, const uint32_t* ranges, uint32_t R, const float* final_T,
                                    const uint32_t* n_contrib, const uint32_t* depth_keys, const float* dL_dD, float* grad_acc) {
-  const int gx = (prm.width + 15) / 16, gy = (prm.height + 15) / 16;
-  const int T = gx * gy;
-  if (T == 0) return GGD_OK;
-  const int em = ctx->opt[GGD_OPT_EXP_MODE];   // as ggd_launch_blend_backward
-  const int cull = ctx->opt[GGD_OPT_BLEND_CULL] != 0;
-  ggd_dispatch<4>(em, [&](auto e) {
-    hipLaunchKernelGGL((distortion_backward_kernel<decltype(e)::value>), dim3(4 * T), dim3(64), 0, s, prm.width, prm.height, gx,
-                       T, cull, splat, list, ranges, R, final_T, n_contrib, depth_keys, dL_dD, grad_acc);
+  const QuarterLaunch q = quarter_launch(ctx, prm, false);
+  if (q.T == 0) return GGD_OK;
+  ggd_dispatch<4>(q.em, [&](auto e) {
+    hipLaunchKernelGGL((distortion_backward_kernel<decltype(e)::value>), dim3(4 * q.T), dim3(64), 0, s, prm.width, prm.height, q.gx,
+                       q.T, q.cull, splat, list, ranges, R, final_T, n_contrib, depth_keys, dL_dD, grad_acc);
   });
   GGD_HIP(hipGetLastError());
   return GGD_OK;

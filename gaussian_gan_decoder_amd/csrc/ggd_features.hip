@@ -5,26 +5,25 @@
 //
 // The weight w_i = alpha_i T_i of a (pixel, contributor) pair is the colour pass's: both kernels walk the tile's sorted list as the
 // colour blend does, bounded per pixel by the stored n_contrib, and recompute alpha with the colour kernels' own expressions
-// (ggd_blend_math.h: blend_power, blend_exp<MODE>, blend_exp_backward<MODE>, the same skip tests in the same order).  With
-// -ffp-contract=off the same expression gives the same bits, so the set of contributors of a pixel is the colour pass's, pair by
-// pair; inside the n_contrib bound no pixel meets the colour pass's T < 1e-4 stop again (the stop lies behind its last contributor).
+// (ggd_blend_math.h: blend_power, blend_exp<MODE>, blend_exp_backward<MODE>; pair_forward of ggd_quarter_walk.h and the backward
+// kernel below: the same skip tests in the same order).  With -ffp-contract=off the same expression gives the same bits, so the set of contributors of a pixel is the colour
+// pass's, pair by pair; inside the n_contrib bound no pixel meets the colour pass's T < 1e-4 stop again (the stop lies behind its
+// last contributor).
 //
-// Shape of both kernels: one single-wave workgroup per 8x8 quarter of a 16x16 tile, one pixel per lane, the four quarters of a
-// tile in consecutive dispatch slots of one XCD (ggd_block_to_tile).  The list is consumed GGD_FEATURES_ROUND = 64 entries per
-// round: lane j gathers record j (48-byte ggd_splat), pre-culls it against the quarter's rectangle as the colour kernels do
-// and stages the survivors in LDS, then all 64 lanes copy the staged records' feature rows
-// f[id_j][0 .. C) into LDS once ([64][CG] floats, CG = C rounded up to 4 / 8 / 16 / 32; the padding channels are filled with
-// zeros in LDS, never read from `features` and never written anywhere).  The per-(pixel, record) scalar work is the colour
-// kernels'; the C-wide parts are three small dense products per round, done as plain fp32 VALU loops over channels with the
-// record side broadcast from LDS:
+// Shape of both kernels: the quarter walk of ggd_quarter_walk.h -- one single-wave workgroup per 8x8 quarter of a 16x16 tile, one
+// pixel per lane, GGD_FEATURES_ROUND = 64 list entries per round, pre-culled and staged compacted by the gathering lanes.  What is
+// this file's: all 64 lanes copy the staged records' feature rows f[id_j][0 .. C) into LDS once ([64][CG] floats, CG = C rounded up
+// to 4 / 8 / 16 / 32; the padding channels are filled with zeros in LDS, never read from `features` and never written anywhere),
+// and the C-wide parts, three small dense products per round, done as plain fp32 VALU loops over channels with the record side
+// broadcast from LDS:
 //   forward    F[pix, c]  += W[pix, rec] f[rec, c]                  (pixel per lane, F in CG registers)
 //   backward   d[pix, rec] = sum_c G[pix, c] f[rec, c]              (pixel per lane, G = dL/dF of the pixel in CG registers)
 //   backward   dL/df[rec, c] = sum_pix W[pix, rec] G[pix, c]        (record per lane: W parked per round in LDS, G staged once)
 // After the second product the C-channel form of dL/dalpha collapses to the colour backward's scalar recurrence: with
 // S = sum_c G_c acc_c (acc = the features composited behind the record) dL/dalpha's colour part is d - S, and S <- S + alpha (d - S).
 // The per-record geometry sums (conic, opacity, mean) are formed by the record's lane from the parked q = G dL/dalpha and the
-// pixel offsets it recomputes, scaled by bwd_scale and added to the EXISTING accumulator records (GGD_ACC_CONIC / _OPACITY /
-// _MEAN2D), which the per-Gaussian backward reads once for every map.
+// pixel offsets it recomputes, scaled by bwd_scale and added to the EXISTING accumulator records (GGD_ACC_CONIC / _OPACITY / _MEAN2D), which the per-Gaussian
+// backward reads once for every map.
 #include "ggd_common.h"
 
 namespace {
@@ -32,42 +31,16 @@ namespace {
 #include "ggd_blend_math.h"
 #include "ggd_quarter_walk.h"
 
-constexpr int FLUSH = 32;                   // staged records per chunk of the backward (a record per lane pair in its flush)
-constexpr int WPAD = 65;                    // row stride of the parked [record][pixel] matrices: lane = record reads without bank conflicts
-
-// One round's records and feature rows into LDS: lane j < n gathers the record at list position first + j and tests it against
-// the quarter's pixel rectangle as the colour kernels' gathering lanes do (only when the colour pass ran with its pre-cull, which
-// is exact: a record it drops has no pixel with power >= threshold); the survivors are staged compacted, order preserved -- two
-// 16-byte words {x, y, hA, nB} {hC, threshold, opacity, 0-based position in the tile's list} and the Gaussian's id -- and only
-// their feature rows are read.  Returns the number of staged records (wave-uniform).
-//
-// The gather is the colour kernels' two-stage software pipeline: the list entries of round k + 2 and the 48-byte records of round
-// k + 1 are requested (Gather, from clamped positions: unconditional loads, a lane past the round's end re-reads a valid entry
-// and its record is never consumed) right behind round k's feature rows, and are in flight while round k is blended.  The rows
-// themselves depend on the cull's outcome; they are requested eight per lane before the first is waited for.
-// pos0: the 0-based position, in the tile's list, of the round's first entry (the record in ga belongs to position pos0 + lane);
-// pos_after_next: that of the round after the next one (any value for a round that does not exist: the loads are clamped)
+// One round's records (stage_cull) and the survivors' feature rows into LDS.  The rows depend on the cull's outcome; they are
+// requested eight per lane before the first is waited for, and the gather's next loads -- the records of the next round, the list
+// entries of the one after -- right behind the last batch of rows, so that they are in flight while this round is blended.
+// Returns the number of staged records (wave-uniform).
 template <int CG>
 __device__ __forceinline__ int stage_round(float4* s_rec, uint32_t* s_id, float* s_f, Gather& ga, int n, uint32_t pos0,
-                                           uint32_t pos_after_next, int C, int cull, float wx0, float wy0,
+                                           uint32_t pos_after_next, int C, int cull, const QuarterGeom& g,
                                            const float* __restrict__ features) {
   const int lane = threadIdx.x;
-  __syncthreads();                       // (single-wave workgroup) the previous round's LDS reads are done
-  bool keep = false;
-  float4 r1 = ga.r1;
-  if (lane < n) {
-    keep = cull ? (record_box_hits(ga.r0.x, ga.r0.y, ga.r2.z, ga.r2.w, wx0, wx0 + 7.0f, wy0, wy0 + 7.0f) &&
-                   record_reaches_block(ga.r0.x, ga.r0.y, ga.r0.z, ga.r0.w, r1.x, r1.y, ga.r2.z, wx0, wx0 + 7.0f, wy0, wy0 + 7.0f))
-                : true;
-    r1.w = __uint_as_float(pos0 + (uint32_t)lane);
-  }
-  const uint64_t kept = __ballot(keep);
-  if (keep) {
-    const int slot = __popcll(kept & ((1ull << lane) - 1ull));
-    s_id[slot] = ga.id_cur;
-    s_rec[slot * 2 + 0] = ga.r0; s_rec[slot * 2 + 1] = r1;
-  }
-  const int ns = __popcll(kept);
+  const int ns = stage_cull(s_rec, s_id, ga, g, n, pos0, cull, [](int) {});
   __syncthreads();
   for (int t0 = 0; t0 < ns * CG; t0 += 64 * 8) {
     float v[8];
@@ -76,7 +49,7 @@ __device__ __forceinline__ int stage_round(float4* s_rec, uint32_t* s_id, float*
       const int t = t0 + u * 64 + lane, j = t / CG, c = t - j * CG;
       v[u] = (t < ns * CG && c < C) ? features[(size_t)s_id[min(j, ROUND - 1)] * C + c] : 0.0f;
     }
-    if (t0 + 64 * 8 >= ns * CG) {        // behind the last batch of rows: the next round's records, the ids of the one after
+    if (t0 + 64 * 8 >= ns * CG) {        // behind the last batch of rows
       ga.load_rec();
       ga.load_id(pos_after_next);
     }
@@ -95,8 +68,6 @@ __device__ __forceinline__ int stage_round(float4* s_rec, uint32_t* s_id, float*
 }
 
 // ---- forward -------------------------------------------------------------------------------------------------------------
-// EXP_MODE: the colour forward's (0, 1, 2; the default mode 3 runs the forward with the bare exponential, mode 1).  cull: the
-// colour pass tested `power >= threshold` with the record's stored threshold (GGD_OPT_BLEND_CULL on) or with -inf (off).
 template <int EXP_MODE, int CG>
 __global__ __launch_bounds__(64) void features_forward_kernel(int W, int H, int gx, int T, int C, int cull,
                                                               const ggd_splat* __restrict__ splat,
@@ -109,37 +80,22 @@ __global__ __launch_bounds__(64) void features_forward_kernel(int W, int H, int 
   __shared__ float4 s_rec[ROUND * 2];
   __shared__ uint32_t s_id[ROUND];
   __shared__ float s_f[ROUND * CG];
-  const FeatGeom g((int)blockIdx.x, W, H, gx, T, ranges, R);
-  const uint32_t lastn = g.in ? min(n_contrib[g.pix], g.hi - g.lo) : 0u;   // contributors: list positions 0 .. lastn - 1 of the tile
-  const uint32_t maxn = wave_max(lastn);
-  const float pxf = (float)g.px, pyf = (float)g.py;
-  float Tr = 1.0f, F[CG];
+  const QuarterGeom g((int)blockIdx.x, W, H, gx, T, ranges, R, n_contrib);
+  float F[CG];
 #pragma unroll
   for (int c = 0; c < CG; ++c) F[c] = 0.0f;
 
-  Gather ga = {splat, list, g.lo, g.lo + maxn - 1u};
-  if (maxn > 0) { ga.load_id(0); ga.load_rec(); ga.load_id(ROUND); }
-  for (uint32_t base = 0; base < maxn; base += ROUND) {
-    const int n = (int)min((uint32_t)ROUND, maxn - base);
-    const int ns = stage_round<CG>(s_rec, s_id, s_f, ga, n, base, base + 2 * ROUND, C, cull, (float)g.qx0, (float)g.qy0, features);
-    for (int j = 0; j < ns; ++j) {
-      const float4 a = s_rec[j * 2 + 0], b = s_rec[j * 2 + 1];   // x y hA nB | hC thr opacity position
-      float dx, dy;
-      const float pw = blend_power(a.x, a.y, a.z, a.w, b.x, pxf, pyf, dx, dy);
-      const float thr = cull ? b.y : -__builtin_huge_valf();
-      const bool need = __float_as_uint(b.w) < lastn && pw >= thr;
-      if (__ballot(need) == 0ull) continue;
-      const float G = blend_exp<EXP_MODE>(pw);
-      const float alpha = fminf(0.99f, G * b.z);
-      const float test_T = Tr * (1.0f - alpha);
-      const bool upd = need && !(pw > 0.0f) && !(alpha < ALPHA_FLOOR) && !(test_T < 0.0001f);
-      const float w = upd ? alpha * Tr : 0.0f;
-      const float* f = s_f + j * CG;
+  Gather ga(splat, list, g);
+  const float Tr = walk_front<EXP_MODE>(
+      s_rec, g, cull, ga,
+      [&](int n, uint32_t pos0, uint32_t pos_after_next) {
+        return stage_round<CG>(s_rec, s_id, s_f, ga, n, pos0, pos_after_next, C, cull, g, features);
+      },
+      [&](int j, const PairForward& p) {
+        const float* f = s_f + j * CG;
 #pragma unroll
-      for (int c = 0; c < CG; ++c) F[c] = __builtin_fmaf(f[c], w, F[c]);
-      Tr = upd ? test_T : Tr;
-    }
-  }
+        for (int c = 0; c < CG; ++c) F[c] = __builtin_fmaf(f[c], p.w, F[c]);
+      });
   if (!g.in) return;
   const size_t HW = (size_t)H * W;
 #pragma unroll
@@ -174,9 +130,8 @@ __global__ __launch_bounds__(64) void features_backward_kernel(int W, int H, int
   __shared__ float s_w[FLUSH * WPAD];    // alpha T        of (record of the chunk, pixel)
   __shared__ float s_q[FLUSH * WPAD];    // G dL/dalpha    of (record of the chunk, pixel)
   const int lane = threadIdx.x;
-  const FeatGeom g((int)blockIdx.x, W, H, gx, T, ranges, R);
-  const uint32_t lastn = g.in ? min(n_contrib[g.pix], g.hi - g.lo) : 0u;
-  const uint32_t maxn = wave_max(lastn);
+  const QuarterGeom g((int)blockIdx.x, W, H, gx, T, ranges, R, n_contrib);
+  const uint32_t lastn = g.lastn, maxn = g.maxn;
   if (maxn == 0) return;
   const size_t HW = (size_t)H * W;
   const float pxf = (float)g.px, pyf = (float)g.py;
@@ -195,15 +150,14 @@ __global__ __launch_bounds__(64) void features_backward_kernel(int W, int H, int
 
   // the round that ends at position ce (exclusive) starts at round_start(ce); ce = 0: no round, its loads re-read position 0
   auto round_start = [](uint32_t ce) { return ce > (uint32_t)ROUND ? ce - ROUND : 0u; };
-  Gather ga = {splat, list, g.lo, g.lo + maxn - 1u};
+  Gather ga(splat, list, g);
   ga.load_id(round_start(maxn)); ga.load_rec(); ga.load_id(round_start(round_start(maxn)));
   uint32_t cend = maxn;
   while (cend > 0) {
     const uint32_t cstart = round_start(cend);
     const int n = (int)(cend - cstart);
     // (its barriers also order s_g's writes)
-    const int ns = stage_round<CG>(s_rec, s_id, s_f, ga, n, cstart, round_start(round_start(cstart)), C, cull, (float)g.qx0,
-                                   (float)g.qy0, features);
+    const int ns = stage_round<CG>(s_rec, s_id, s_f, ga, n, cstart, round_start(round_start(cstart)), C, cull, g, features);
     for (int c1 = ns; c1 > 0; c1 -= FLUSH) {
       const int c0 = c1 > FLUSH ? c1 - FLUSH : 0;   // the chunk: staged records c0 .. c1 - 1
       uint32_t touched = 0;              // wave-uniform: records of the chunk some pixel of the quarter blended
@@ -306,15 +260,12 @@ inline int channel_group(int C) { return C <= 4 ? 0 : (C <= 8 ? 1 : (C <= 16 ? 2
 int ggd_launch_features_forward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat,
                                 const uint32_t* list, const uint32_t* ranges, uint32_t R, const uint32_t* n_contrib,
                                 const float* features, int C, const float* feature_bg, float* out) {
-  const int gx = (prm.width + 15) / 16, gy = (prm.height + 15) / 16;
-  const int T = gx * gy;
-  if (T == 0) return GGD_OK;
-  const int em = ctx->opt[GGD_OPT_EXP_MODE] == 3 ? 1 : ctx->opt[GGD_OPT_EXP_MODE];   // as ggd_launch_blend
-  const int cull = ctx->opt[GGD_OPT_BLEND_CULL] != 0;
-  ggd_dispatch<3>(em, [&](auto e) {
+  const QuarterLaunch q = quarter_launch(ctx, prm, true);
+  if (q.T == 0) return GGD_OK;
+  ggd_dispatch<3>(q.em, [&](auto e) {
     ggd_dispatch<4>(channel_group(C), [&](auto cg) {
-      hipLaunchKernelGGL((features_forward_kernel<decltype(e)::value, (4 << decltype(cg)::value)>), dim3(4 * T), dim3(64), 0, s,
-                         prm.width, prm.height, gx, T, C, cull, splat, list, ranges, R, n_contrib, features, feature_bg, out);
+      hipLaunchKernelGGL((features_forward_kernel<decltype(e)::value, (4 << decltype(cg)::value)>), dim3(4 * q.T), dim3(64), 0, s,
+                         prm.width, prm.height, q.gx, q.T, C, q.cull, splat, list, ranges, R, n_contrib, features, feature_bg, out);
     });
   });
   GGD_HIP(hipGetLastError());
@@ -325,16 +276,13 @@ int ggd_launch_features_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& 
                                  const uint32_t* list, const uint32_t* ranges, uint32_t R, const float* final_T,
                                  const uint32_t* n_contrib, const float* features, int C, const float* feature_bg,
                                  const float* dL_dF, float* grad_acc, float* dL_dfeatures) {
-  const int gx = (prm.width + 15) / 16, gy = (prm.height + 15) / 16;
-  const int T = gx * gy;
-  if (T == 0) return GGD_OK;
-  const int em = ctx->opt[GGD_OPT_EXP_MODE];   // as ggd_launch_blend_backward
-  const int cull = ctx->opt[GGD_OPT_BLEND_CULL] != 0;
-  ggd_dispatch<4>(em, [&](auto e) {
+  const QuarterLaunch q = quarter_launch(ctx, prm, false);
+  if (q.T == 0) return GGD_OK;
+  ggd_dispatch<4>(q.em, [&](auto e) {
     ggd_dispatch<4>(channel_group(C), [&](auto cg) {
-      hipLaunchKernelGGL((features_backward_kernel<decltype(e)::value, (4 << decltype(cg)::value)>), dim3(4 * T), dim3(64), 0, s,
-                         prm.width, prm.height, gx, T, C, cull, splat, list, ranges, R, final_T, n_contrib, features, feature_bg,
-                         dL_dF, grad_acc, dL_dfeatures);
+      hipLaunchKernelGGL((features_backward_kernel<decltype(e)::value, (4 << decltype(cg)::value)>), dim3(4 * q.T), dim3(64), 0, s,
+                         prm.width, prm.height, q.gx, q.T, C, q.cull, splat, list, ranges, R, final_T, n_contrib, features,
+                         feature_bg, dL_dF, grad_acc, dL_dfeatures);
     });
   });
   GGD_HIP(hipGetLastError());
