@@ -122,8 +122,9 @@ def layout_kinds(name):
 
 
 @functools.lru_cache(maxsize=None)
-def layout_inputs(name):
-    """the activated inputs of a table Q layout (cached: do not modify)"""
+def layout_inputs(name, depth_step=1e-3, seed=None):
+    """the activated inputs of a table Q layout (cached: do not modify).  depth_step: the rise of the view-space depth per index
+    (the footprints stay constant in pixels: the scale follows z); seed: of the centres' jitter, Q_SEED[name] by default"""
     blocks = LAYOUTS[name]
     k = sum(n for _, n, _ in blocks)
     d = scene_inputs(P=k, size=Q_SIZE, seed=7)
@@ -132,7 +133,7 @@ def layout_inputs(name):
     Pm = np.linalg.inv(V) @ d["projmatrix"].double().numpy()   # p_hom = p_view @ Pm
     z0 = float((np.array([0.0, 0.0, 0.0, 1.0]) @ V)[2])       # depth of the look-at point
     focal = W / (2.0 * d["tanfovx"])
-    rng = np.random.RandomState(7100 + Q_SEED[name])
+    rng = np.random.RandomState(7100 + (Q_SEED[name] if seed is None else seed))
     xyz, op, sc = np.zeros((k, 3)), np.zeros((k, 1)), np.zeros((k, 3))
     i = 0
     for q, n, kind in blocks:
@@ -143,7 +144,7 @@ def layout_inputs(name):
                 px, py = qx0 + 3.0, qy0 + 3.0
             else:
                 px, py = qx0 + 3.5 + rng.uniform(-1.0, 1.0), qy0 + 3.5 + rng.uniform(-1.0, 1.0)
-            z = z0 + 1e-3 * i
+            z = z0 + depth_step * i
             nx, ny = (2.0 * px + 1.0) / W - 1.0, (2.0 * py + 1.0) / H - 1.0     # pixel = ((ndc + 1) S - 1) / 2
             # (xv, yv) with p_hom.xy / p_hom.w = (nx, ny) for p_view = (xv, yv, z, 1)
             A = np.array([[Pm[0, 0] - nx * Pm[0, 3], Pm[1, 0] - nx * Pm[1, 3]], [Pm[0, 1] - ny * Pm[0, 3], Pm[1, 1] - ny * Pm[1, 3]]])

@@ -82,8 +82,8 @@ def _reference(key, d_o, o, n, g):
     return _REF[sig]
 
 
-def _check_forward(D, r, frag_px, what):
-    ratio = np.abs(D.astype(np.float64) - r["D"]) / (ATOL + DR.K * EPS32 * r["D_budget"])
+def _check_forward(D, r, frag_px, what, kappa=DR.K):
+    ratio = np.abs(D.astype(np.float64) - r["D"]) / (ATOL + kappa * EPS32 * r["D_budget"])
     worst = float(ratio[~frag_px].max(initial=0.0))
     err = float(np.abs(D - r["D"])[~frag_px].max(initial=0.0))
     print(f"[distortion] {what}: max |dD| = {err:.2e} (D up to {float(r['D'].max()):.3f}), error / bound {worst:.4f}")
@@ -91,9 +91,9 @@ def _check_forward(D, r, frag_px, what):
     assert (D[(r["count"] < 2) & ~frag_px] == 0.0).all(), "fewer than two contributors: D = 0"
 
 
-def _check_backward(d, got, ref, bud, frag, what):
+def _check_backward(d, got, ref, bud, frag, what, kappa=DR.K):
     report = []
-    worst = check_gradients(d, got, ref, bud, frag, kappa=DR.K, report=report)
+    worst = check_gradients(d, got, ref, bud, frag, kappa=kappa, report=report)
     print(f"[distortion] {what}: worst gradient error / bound {worst:.4f} "
           + ", ".join(f"{r['array'][3:]} {r['worst_ratio']:.3f}" for r in report))
     assert worst <= 1.0, report
