@@ -28,6 +28,7 @@ EXPORTS = [
     "ggd_densify_tmp_bytes", "ggd_densify_stats", "ggd_densify_plan", "ggd_prune_plan", "ggd_densify_emit", "ggd_densify_gather",
     "ggd_density_points", "ggd_density_grid", "ggd_density_lattice", "ggd_teacher_render",
     "ggd_adam_sparse",
+    "ggd_mcmc_tmp_bytes", "ggd_mcmc_relocate", "ggd_mcmc_add_plan", "ggd_mcmc_add_emit", "ggd_mcmc_noise", "ggd_compute_relocation",
     "ggd_forward_features", "ggd_backward_features",
     "ggd_forward_distortion", "ggd_backward_distortion",
     "ggd_backward_camera",
@@ -195,7 +196,14 @@ def load():
         lib.ggd_densify_emit.argtypes = [vp, vp, i32, i32, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), vp, vp, sz]
         lib.ggd_densify_gather.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, sz]
         lib.ggd_adam_sparse.argtypes = [vp, vp, i32, i32, C.POINTER(AdamGroup), vp, vp, f32, f32]
-        lib.ggd_density_points.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp, i32, vp, vp]
+        tables = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        lib.ggd_mcmc_tmp_bytes.restype = sz; lib.ggd_mcmc_tmp_bytes.argtypes = [i32, i32]
+        lib.ggd_mcmc_relocate.argtypes = [vp, vp, i32, i32, tables[0], vp, vp, vp, sz]
+        lib.ggd_mcmc_add_plan.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, sz]
+        lib.ggd_mcmc_add_emit.argtypes = [vp, vp, i32, i32, i32] + tables + [vp, sz]
+        lib.ggd_mcmc_noise.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, f32, f32]
+        lib.ggd_compute_relocation.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+        lib.ggd_density_points.argtypes =[vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp, i32, vp, vp]
         lib.ggd_density_grid.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, i32, C.c_double, i32, vp, vp]
         lib.ggd_density_lattice.argtypes = [vp, vp, i32, C.c_double, i32, vp]
         lib.ggd_teacher_render.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp, vp, i32, C.c_double, C.c_double,

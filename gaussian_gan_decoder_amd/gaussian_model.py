@@ -74,6 +74,19 @@ def _device_float(a, device=None) -> torch.Tensor:
     return torch.as_tensor(np.asarray(a)).float().to(device or "cuda")
 
 
+def mcmc_tmp_layout(P, n_dest):
+    """Byte offsets of the arrays in the scratch of ggd_mcmc_relocate / ggd_mcmc_add_plan (include/ggd_raster.h), each
+    aligned to 256 bytes, and the total (= ggd_mcmc_tmp_bytes)."""
+    align = lambda n: (n + 255) // 256 * 256
+    T = (P + 2047) // 2048 * 2048
+    lay, off = {}, 0
+    for name, nbytes in (("weights", 4 * T), ("prefix", 4 * T), ("tiles", 8 * (T // 2048 + 1)), ("counts", 4 * P),
+                         ("sources", 4 * n_dest), ("values", 16 * P)):
+        lay[name], off = off, off + align(nbytes)
+    lay["total"] = off
+    return lay
+
+
 class GaussianModel:
     def __init__(self, sh_degree: int):
         self.active_sh_degree = 0
@@ -332,12 +345,10 @@ class GaussianModel:
         max(max_radii2D, radii) and add_densification_stats' update (use_absgrad: see there)."""
         self._stats("update_densification_stats", viewspace_point_tensor, radii, None, use_absgrad)
 
-    def _regather(self, plan):
-        """plan(context, stream, tmp pointer, tmp bytes, counts) fills the source map and the counts and returns the noise (or
-        None); one launch then writes every parameter and Adam moment at the new size, and the six nn.Parameters and their
-        optimizer state are swapped.  Every tensor is checked BEFORE the plan is launched: the kernels read P rows of the
-        widths below.  Returns (new row count, gather), gather(t) being the rows of another float32 [P, ...] tensor."""
-        from . import _capi
+    def _checked_groups(self, in_place=False):
+        """(P, device, M, shapes by group, [[parameter, exp_avg, exp_avg_sq] per group, None for absent moments]) of the six
+        groups, every tensor checked: float32, on the parameters' device, the group's shape.  in_place: the tensors
+        themselves (which must then be contiguous) instead of contiguous copies."""
         P, dev = int(self._xyz.shape[0]), self._xyz.device
         if self._features_rest.dim() != 3:
             raise ValueError("density control: _features_rest must be [P, M - 1, 3]")
@@ -355,7 +366,18 @@ class GaussianModel:
             for t in ins:
                 if t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != shapes[name]:
                     raise ValueError(f"density control: {attr} and its Adam moments must be float32 {list(shapes[name])} on {dev}")
-            src.append([t.contiguous() for t in ins] + ([] if has else [None, None]))
+                if in_place and not t.is_contiguous():
+                    raise ValueError(f"density control: {attr} and its Adam moments must be contiguous (they are updated in place)")
+            src.append([t if in_place else t.contiguous() for t in ins] + ([] if has else [None, None]))
+        return P, dev, M, shapes, src
+
+    def _regather(self, plan):
+        """plan(context, stream, tmp pointer, tmp bytes, counts) fills the source map and the counts and returns the noise (or
+        None); one launch then writes every parameter and Adam moment at the new size, and the six nn.Parameters and their
+        optimizer state are swapped.  Every tensor is checked BEFORE the plan is launched: the kernels read P rows of the
+        widths below.  Returns (new row count, gather), gather(t) being the rows of another float32 [P, ...] tensor."""
+        from . import _capi
+        P, dev, M, shapes, src = self._checked_groups()
         cx, stream = _capi.context_and_stream(dev)
         nbytes = cx.lib.ggd_densify_tmp_bytes(P)
         if nbytes == 0:
@@ -438,3 +460,127 @@ class GaussianModel:
         _, gather = self._regather(plan)
         for n, t in stats:                                # the same source map, one small launch each, no host wait
             setattr(self, n, gather(t))
+
+    # ---- density control under a fixed budget (csrc/ggd_mcmc.hip) -----------------------------------
+    def _mcmc_argument(self, who, name, t, dtypes, shape):
+        """An optional tensor argument of the three methods below: dtype and shape (ValueError), then the device (RuntimeError)."""
+        if t is None:
+            return None
+        what = f"{who}: {name} must be {' / '.join(str(d).replace('torch.', '') for d in dtypes)} {list(shape)}"
+        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or tuple(t.shape) != tuple(shape):
+            raise ValueError(what)
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {name} must be a HIP device tensor (there is no CPU fallback)")
+        if t.device != self._xyz.device:
+            raise ValueError(what + f" on {self._xyz.device}")
+        return t.contiguous()
+
+    def _mcmc_ready(self, who):
+        P = self._device_rows(who)
+        if self.optimizer is None:
+            raise ValueError(f"{who}: call training_setup first")
+        return P
+
+    @staticmethod
+    def _mcmc_plan_tensors(tmp, P, n_dest):
+        """The plan left in the scratch of a relocate / add call, as int64 device tensors (copies)."""
+        lay = mcmc_tmp_layout(P, n_dest)
+        words = lambda off, n: tmp[off:off + 4 * n].view(torch.int32).to(torch.int64)
+        return {"weights": words(lay["weights"], P), "sources": words(lay["sources"], n_dest), "counts": words(lay["counts"], P)}
+
+    @torch.no_grad()
+    def relocate_gs(self, dead_mask=None, draws=None, return_plan=False):
+        """MCMC relocation (Kheradmand et al. 2024, relocate_gs), in place and without a host read-back: every dead row
+        (dead_mask: bool [P]; None: sigmoid(opacity) <= 0.005, evaluated on the device) becomes a copy of an alive row
+        sampled in proportion to its opacity, source and copies share the relocation values of compute_relocation (N = 1 +
+        the times the source was drawn, at most 51), and the Adam moments of the sources restart at zero.  draws: int64 [P]
+        in [0, 2^32), entry j decides for row j when it is dead (default: torch.randint on the device).  Nothing alive or
+        nothing dead: no tensor changes.  return_plan=True returns {"weights", "sources", "counts"}: int64 device tensors [P],
+        the integer weights (0 on dead rows), each dead row's source (-1 elsewhere) and how often each row was drawn."""
+        who = "relocate_gs"
+        P = int(self._xyz.shape[0]) if isinstance(self._xyz, torch.Tensor) else 0
+        dead_mask = self._mcmc_argument(who, "dead_mask", dead_mask, (torch.bool, torch.uint8), (P,))
+        draws = self._mcmc_argument(who, "draws", draws, (torch.int64,), (P,))
+        P = self._mcmc_ready(who)
+        from . import _capi
+        P, dev, M, _, io = self._checked_groups(in_place=True)
+        if draws is None:
+            draws = torch.randint(0, 1 << 32, (P,), dtype=torch.int64, device=dev)
+        cx, stream = _capi.context_and_stream(dev)
+        nbytes = cx.lib.ggd_mcmc_tmp_bytes(P, P)
+        if P > 0 and nbytes == 0:
+            raise ValueError(f"{who}: at most 2^26 rows (have {P})")
+        tmp = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        if P > 0:
+            mask8 = dead_mask.view(torch.uint8) if dead_mask is not None else None
+            table = (C.c_void_p * 18)(*[t.data_ptr() if t is not None else None for row in io for t in row])
+            with torch.cuda.device(dev):
+                cx.check(cx.lib.ggd_mcmc_relocate(cx.handle, C.c_void_p(stream), P, M, table,
+                                                  C.c_void_p(mask8.data_ptr()) if mask8 is not None else None,
+                                                  C.c_void_p(draws.data_ptr()), C.c_void_p(tmp.data_ptr()), nbytes))
+        if return_plan:
+            return self._mcmc_plan_tensors(tmp, P, P)
+
+    @torch.no_grad()
+    def add_new_gs(self, cap_max, draws=None, return_plan=False):
+        """MCMC growth (add_new_gs): the model grows to min(cap_max, int(1.05 P)) rows; each new row is a copy of a row
+        sampled in proportion to its opacity, with the relocation values shared as in relocate_gs, zero Adam moments for the
+        new rows and the sampled sources, and zero statistics for the new rows.  draws: int64 [num] in [0, 2^32).  Returns
+        the number of rows added (0 at the cap: nothing changes); with return_plan=True, (number, plan) with the plan of
+        relocate_gs (sources: [num]) or None when nothing was added."""
+        who = "add_new_gs"
+        P = int(self._xyz.shape[0]) if isinstance(self._xyz, torch.Tensor) else 0
+        num = max(0, min(int(cap_max), int(1.05 * P)) - P)
+        draws = self._mcmc_argument(who, "draws", draws, (torch.int64,), (num,))
+        P = self._mcmc_ready(who)
+        if num == 0:
+            return (0, None) if return_plan else 0
+        from . import _capi
+        P, dev, M, shapes, src = self._checked_groups()
+        if draws is None:
+            draws = torch.randint(0, 1 << 32, (num,), dtype=torch.int64, device=dev)
+        cx, stream = _capi.context_and_stream(dev)
+        nbytes = cx.lib.ggd_mcmc_tmp_bytes(P, num)
+        if nbytes == 0 or P + num > 1 << 26:
+            raise ValueError(f"{who}: at most 2^26 rows (would have {P + num})")
+        tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        out = [[torch.empty((P + num,) + shapes[name][1:], device=dev) if t is not None else None for t in ins]
+               for (name, _), ins in zip(PARAM_GROUPS, src)]
+        if cx.poison_outputs:                             # tests: an element the launch does not write shows as NaN
+            for t in (t for row in out for t in row if t is not None):
+                t.fill_(float("nan"))
+        table = lambda rows: (C.c_void_p * 18)(*[t.data_ptr() if t is not None else None for row in rows for t in row])
+        st, tp = C.c_void_p(stream), C.c_void_p(tmp.data_ptr())
+        with torch.cuda.device(dev):
+            cx.check(cx.lib.ggd_mcmc_add_plan(cx.handle, st, P, num, C.c_void_p(src[3][0].data_ptr()),
+                                              C.c_void_p(src[4][0].data_ptr()), C.c_void_p(draws.data_ptr()), tp, nbytes))
+            cx.check(cx.lib.ggd_mcmc_add_emit(cx.handle, st, P, num, M, table(src), table(out), tp, nbytes))
+        for (name, attr), (p, m1, m2) in zip(PARAM_GROUPS, out):
+            self._swap(name, attr, p, m1, m2)
+        for n in ("xyz_gradient_accum", "denom", "max_radii2D"):
+            t = getattr(self, n)
+            if isinstance(t, torch.Tensor) and t.shape[:1] == (P,):
+                setattr(self, n, torch.cat((t, torch.zeros((num,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device))))
+        return (num, self._mcmc_plan_tensors(tmp, P, num)) if return_plan else num
+
+    @torch.no_grad()
+    def inject_position_noise(self, noise_lr, xyz_lr=None, noise=None):
+        """The MCMC exploration term, one launch, in place on the positions (call it after optimizer.step):
+        xyz += Sigma (gate * noise_lr * xyz_lr * noise) with Sigma = R S^2 R^T of each row and gate = sigmoid(100 ((1 -
+        opacity) - 0.995)): transparent rows move, opaque ones stay.  xyz_lr=None reads the xyz group's current rate; noise:
+        standard-normal float32 [P, 3] (drawn on the device when None)."""
+        who = "inject_position_noise"
+        P = int(self._xyz.shape[0]) if isinstance(self._xyz, torch.Tensor) else 0
+        noise = self._mcmc_argument(who, "noise", noise, (torch.float32,), (P, 3))
+        P = self._mcmc_ready(who)
+        from . import _capi
+        if xyz_lr is None:
+            xyz_lr = self._own_groups()["xyz"]["lr"]
+        P, dev, _, _, io = self._checked_groups(in_place=True)
+        if noise is None:
+            noise = torch.randn((P, 3), device=dev)
+        cx, stream = _capi.context_and_stream(dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        with torch.cuda.device(dev):
+            cx.check(cx.lib.ggd_mcmc_noise(cx.handle, C.c_void_p(stream), P, ptr(io[0][0]), ptr(io[4][0]), ptr(io[5][0]),
+                                           ptr(io[3][0]), ptr(noise), float(noise_lr), float(xyz_lr)))

@@ -798,6 +798,56 @@ int ggd_densify_gather(ggd_ctx* ctx, void* stream, int32_t P, int32_t new_P, int
                        const void* tmp, size_t tmp_bytes);
 
 /*
+ * Density control under a fixed row budget, "3D Gaussian Splatting as Markov Chain Monte Carlo" (Kheradmand et al. 2024):
+ * its compute_relocation op, relocate_gs, add_new_gs and the per-iteration position noise (csrc/ggd_mcmc.hip), restated from
+ * the published source.  All arrays are DEVICE memory, float32 unless stated; P <= 2^26.  No call waits for the device, reads
+ * anything back or allocates.
+ *
+ * Relocation values of a row with raw opacity x (o = sigmoid(x)) and ratio N in 1..51:
+ *   o' = 1 - (1 - o)^(1/N)     D = sum_{i=1..N} sum_{k=0..i-1} C(i-1, k) (-1)^k / sqrt(k+1) o'^(k+1)     s' = s o / D
+ * evaluated in fp64 from sp = softplus(x): o' = -expm1(-sp / N), new raw opacity = log(expm1(sp / N)) with o' clamped to
+ * [0.005, 1 - 2^-23], new raw scale = raw scale + log(o / D).
+ *
+ * Sampling plan: weight w_i = max(1, round(sigmoid(x_i) * 2^20)) (uint32) on alive rows, 0 on dead ones; W = sum w (64 bits).
+ * A destination with draw d (int64, its low 32 bits are used) picks tau = floor(d W / 2^32) and the source is the row whose
+ * interval [C_i, C_i + w_i) of the exclusive prefix sum C holds tau; count[source] += 1 and N(source) = min(51, 1 + count).
+ * Integer arithmetic only: the plan is a pure function of the weights and the draws.  W == 0 or no destination: nothing moves.
+ *
+ * ggd_mcmc_relocate: in place on io18 (the table of ggd_densify_emit: [3 g + 0] parameter, [3 g + 1] exp_avg, [3 g + 2]
+ * exp_avg_sq of group g; P rows each; a group's moments may both be NULL).  Destinations are the dead rows: dead_mask[i] != 0
+ * (uint8 [P]) or, with dead_mask NULL, sigmoid(x_i) <= 0.005.  draws: int64 [P], entry j is read when row j is dead.  Five
+ * launches: weights, tile prefixes, sample, values (into tmp), then: a destination copies its source's xyz, f_dc, f_rest and
+ * rotation and takes the source's new raw opacity and scales; a sampled source takes the same values and both Adam moments of
+ * its row become 0 in all six groups; a destination's moments and every other row stay as they are.
+ * ggd_mcmc_add_plan: the same plan with every row alive and num destinations (draws: int64 [num]), launches 1 - 4.
+ * ggd_mcmc_add_emit: one launch that writes out18 (P + num rows) from in18 (P rows) and the plan in tmp: old rows copied, sampled
+ * sources with their new raw opacity and scales and zero moments, row P + k a copy of source s_k with the new values and zero
+ * moments.  num > 0 in both.
+ * tmp: ggd_mcmc_tmp_bytes(P, n_dest) bytes, 16-byte aligned; n_dest = P for ggd_mcmc_relocate, num for the add pair.  It holds,
+ * in this order and each aligned to 256 bytes: uint32 weights [T], uint32 in-tile prefixes [T] (T = P rounded up to 2048),
+ * uint64 tile prefixes [T / 2048 + 1] (the last is W), uint32 counts [P], uint32 sources [n_dest] (0xFFFFFFFF: no destination),
+ * float new values [P][4].
+ *
+ * ggd_mcmc_noise: one launch, xyz += Sigma (((xi * gate) * noise_lr) * xyz_lr) per row, Sigma = R S^2 R^T with R of the raw
+ * quaternion normalised as the rasterizer does, S = exp(raw scale), gate = 1 / (1 + exp(-100 ((1 - o) - 0.995))) and
+ * 1 - o = sigmoid(-x); noise: [P][3] standard-normal numbers of the caller.  rotation must be 16-byte aligned.
+ *
+ * ggd_compute_relocation: the op on activated values: new_opacities [n] = o', new_scales [n][3] = s' (no clamp), ratios int32 [n]
+ * clamped to 1..51.
+ */
+size_t ggd_mcmc_tmp_bytes(int32_t P, int32_t n_dest);
+int ggd_mcmc_relocate(ggd_ctx* ctx, void* stream, int32_t P, int32_t M, float* const* io18, const uint8_t* dead_mask /* or NULL */,
+                      const int64_t* draws, void* tmp, size_t tmp_bytes);
+int ggd_mcmc_add_plan(ggd_ctx* ctx, void* stream, int32_t P, int32_t num, const float* opacity, const float* scaling,
+                      const int64_t* draws, void* tmp, size_t tmp_bytes);
+int ggd_mcmc_add_emit(ggd_ctx* ctx, void* stream, int32_t P, int32_t num, int32_t M, const float* const* in18,
+                      float* const* out18, const void* tmp, size_t tmp_bytes);
+int ggd_mcmc_noise(ggd_ctx* ctx, void* stream, int32_t P, float* xyz, const float* scaling, const float* rotation,
+                   const float* opacity, const float* noise, float noise_lr, float xyz_lr);
+int ggd_compute_relocation(ggd_ctx* ctx, void* stream, int32_t n, const float* opacities, const float* scales,
+                           const int32_t* ratios, float* new_opacities, float* new_scales);
+
+/*
  * Sparse Adam of the fitting loop (csrc/ggd_adam.hip): the published adamUpdate rule of the accelerated 3DGS rasterizer
  * (SparseGaussianAdam) over up to 8 parameter groups in ONE launch, in place, with no host wait, no allocation and no
  * device-side table (`groups` is HOST memory and travels by value in the kernel arguments).
