@@ -37,8 +37,10 @@ __device__ __forceinline__ float4 act_normalize(float4 q, float& norm) {
   const float d = fmaxf(norm, 1e-12f);  // torch.nn.functional.normalize: v / max(||v||, eps)
   return make_float4(q.x / d, q.y / d, q.z / d, q.w / d);
 }
-// Its Jacobian, transposed: dq = dL/dq_hat -> dL/dq through q_hat = q / max(||q||, eps): (g - q_hat (q_hat . g)) / max(||q||, eps)
+// Its Jacobian, transposed: dq = dL/dq_hat -> dL/dq through q_hat = q / max(||q||, eps): (g - q_hat (q_hat . g)) / ||q||, and
+// g / eps under the clamp, where the divisor is a constant and there is no projection term (as torch's autograd has it)
 __device__ __forceinline__ float4 act_normalize_backward(float4 q_hat, float norm, float4 dq) {
+  if (norm < 1e-12f) return make_float4(dq.x / 1e-12f, dq.y / 1e-12f, dq.z / 1e-12f, dq.w / 1e-12f);
   const float dotg = (q_hat.x * dq.x + q_hat.y * dq.y) + (q_hat.z * dq.z + q_hat.w * dq.w);
   const float dn = fmaxf(norm, 1e-12f);
   return make_float4((dq.x - q_hat.x * dotg) / dn, (dq.y - q_hat.y * dotg) / dn, (dq.z - q_hat.z * dotg) / dn,
