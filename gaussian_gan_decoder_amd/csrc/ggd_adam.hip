@@ -16,12 +16,12 @@
 // elements one by one, so the promise above holds per row and not per chunk.  Every group owns a range of workgroups computed
 // on the host; the table travels by value in the kernel arguments.  No workgroup waits on another.
 #include "ggd_common.h"
+#include "ggd_groups.h"
 
 namespace {
 
 constexpr int AD_MAX_GROUPS = 8;
 constexpr int AD_THREADS = 256;
-constexpr int AD_MAX_POINTS = 1 << 26;
 
 struct ad_group {
   float* param; const float* grad; float* m; float* v;
@@ -73,11 +73,7 @@ __device__ __forceinline__ void ad_one(const ad_group& g, uint32_t e, float b1, 
 }
 
 __global__ void __launch_bounds__(AD_THREADS) adam_sparse_kernel(ad_args a) {
-  int G = 0;
-#pragma unroll
-  for (int k = 1; k < AD_MAX_GROUPS; ++k)
-    if (blockIdx.x >= a.g[k].first_block) G = k;
-  const ad_group& g = a.g[G];
+  const ad_group& g = a.g[ggd_block_group(a.g)];
   const uint32_t t = (blockIdx.x - g.first_block) * AD_THREADS + threadIdx.x;
   const float b1 = a.b1, b2 = a.b2, c1 = 1.0f - a.b1, c2 = 1.0f - a.b2;
   if (t >= g.n_chunks) {                                 // head, then tail, one element per thread
@@ -124,7 +120,7 @@ __global__ void __launch_bounds__(AD_THREADS) adam_sparse_kernel(ad_args a) {
 extern "C" int ggd_adam_sparse(ggd_ctx* ctx, void* stream, int32_t N, int32_t n_groups, const ggd_adam_group* groups,
                                const uint8_t* visible, const int32_t* radii, float beta1, float beta2) {
   if (!ctx) return GGD_E_INVALID;
-  if (N < 0 || N > AD_MAX_POINTS) return ggd_fail(ctx, GGD_E_INVALID, "ggd_adam_sparse: N must be in [0, 2^26]");
+  if (N < 0 || N > GG_MAX_POINTS) return ggd_fail(ctx, GGD_E_INVALID, "ggd_adam_sparse: N must be in [0, 2^26]");
   if (n_groups < 1 || n_groups > AD_MAX_GROUPS) return ggd_fail(ctx, GGD_E_INVALID, "ggd_adam_sparse: n_groups must be in [1, 8]");
   if (!groups) return ggd_fail(ctx, GGD_E_INVALID, "ggd_adam_sparse: NULL group table");
   if ((visible != nullptr) == (radii != nullptr))

@@ -16,6 +16,7 @@
 // restated; max_screen_size only switches the world-size test on.)
 // No workgroup waits on another one anywhere in this file: every dependency is a kernel boundary.
 #include "ggd_common.h"
+#include "ggd_groups.h"
 #include "ggd_lanes.h"
 
 namespace {
@@ -25,9 +26,6 @@ namespace {
 constexpr uint32_t DF_KEEP = 1u, DF_CLONE = 2u, DF_CHILD = 4u;   // per-row flag byte
 constexpr int DF_KIND_SHIFT = 30;                                // source map word: segment kind << 30 | parent row
 constexpr uint32_t DF_ROW_MASK = (1u << DF_KIND_SHIFT) - 1u;
-constexpr int DF_MAX_POINTS = 1 << 26;
-constexpr int DF_GROUPS = 6;                                     // xyz, f_dc, f_rest, opacity, scaling, rotation
-constexpr int DF_XYZ = 0, DF_SCALING = 4, DF_ROTATION = 5;
 constexpr float DF_SPLIT_DIV = 1.6f;                             // 0.8 * N, N = 2 children
 
 struct df_layout { size_t flags, sums, counts, src, total; int nb; };
@@ -157,14 +155,8 @@ __global__ void __launch_bounds__(SCAN_THREADS) densify_map_kernel(const uint8_t
 }
 
 // ------------------------------------------------------------------------------------------------------ emit --
-struct df_group {
-  const float* in[3];        // parameter, exp_avg, exp_avg_sq (moments NULL: this group has no optimizer state yet)
-  float* out[3];
-  uint32_t width;            // floats per row
-  uint32_t first_block;      // this group's first workgroup of the launch
-};
 struct df_emit_args {
-  df_group g[DF_GROUPS];
+  ggd_row_group g[GG_GROUPS];
   const uint32_t* src;
   const uint32_t* counts;
   const float* noise;        // [2][P0][3]
@@ -173,8 +165,8 @@ struct df_emit_args {
 
 // xyz of a child: R(q / |q|) (s * noise) + xyz, component c, in the operation order of build_rotation
 __device__ __forceinline__ float densify_child_xyz(const df_emit_args& a, uint32_t parent, uint32_t child, uint32_t c) {
-  const float* q = a.g[DF_ROTATION].in[0] + 4 * (size_t)parent;
-  const float* sc = a.g[DF_SCALING].in[0] + 3 * (size_t)parent;
+  const float* q = a.g[GG_ROTATION].in[0] + 4 * (size_t)parent;
+  const float* sc = a.g[GG_SCALING].in[0] + 3 * (size_t)parent;
   const float* nz = a.noise + 3 * ((size_t)child * a.P0 + parent);
   const float norm = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
   const float r = q[0] / norm, x = q[1] / norm, y = q[2] / norm, z = q[3] / norm;
@@ -183,31 +175,23 @@ __device__ __forceinline__ float densify_child_xyz(const df_emit_args& a, uint32
   if (c == 0) { r0 = 1.0f - 2.0f * (y * y + z * z); r1 = 2.0f * (x * y - r * z); r2 = 2.0f * (x * z + r * y); }
   else if (c == 1) { r0 = 2.0f * (x * y + r * z); r1 = 1.0f - 2.0f * (x * x + z * z); r2 = 2.0f * (y * z - r * x); }
   else { r0 = 2.0f * (x * z - r * y); r1 = 2.0f * (y * z + r * x); r2 = 1.0f - 2.0f * (x * x + y * y); }
-  return ((r0 * v0 + r1 * v1) + r2 * v2) + a.g[DF_XYZ].in[0][3 * (size_t)parent + c];
+  return ((r0 * v0 + r1 * v1) + r2 * v2) + a.g[GG_XYZ].in[0][3 * (size_t)parent + c];
 }
 
-// One thread per output float of one group (its parameter and both moments).  Workgroup b of group G covers that group's
-// elements [256 b, 256 b + 256): the stores are contiguous, the loads follow the source map, which is monotone inside a segment.
+// One thread per output float of one group (its parameter and both moments; the walk: ggd_groups.h).  The stores are
+// contiguous, the loads follow the source map, which is monotone inside a segment.
 __global__ void __launch_bounds__(256) densify_emit_kernel(df_emit_args a) {
-  int G = 0;
-#pragma unroll
-  for (int k = 1; k < DF_GROUPS; ++k)
-    if (blockIdx.x >= a.g[k].first_block) G = k;
-  const df_group& grp = a.g[G];
+  const auto [G, row, col] = ggd_group_walk(a.g);
+  const ggd_row_group& grp = a.g[G];
   const uint32_t w = grp.width;
-  const uint64_t e0 = (uint64_t)(blockIdx.x - grp.first_block) * 256u;
-  const uint32_t row0 = (uint32_t)(e0 / w);                                  // (uniform)
-  const uint32_t off = (uint32_t)(e0 - (uint64_t)row0 * w) + threadIdx.x;    // < w + 256
-  const uint32_t dr = off / w;
-  const uint32_t row = row0 + dr, col = off - dr * w;
   if (row >= min(a.newP, a.counts[3])) return;
   const uint32_t s = a.src[row];
   const uint32_t kind = s >> DF_KIND_SHIFT, parent = s & DF_ROW_MASK;
   if (parent >= a.P0 || (kind >= 2u && !a.noise)) return;   // (a map of ggd_prune_plan has no children and needs no noise)
   const size_t o = (size_t)row * w + col, i = (size_t)parent * w + col;
   float v;
-  if (kind >= 2u && G == DF_XYZ) v = densify_child_xyz(a, parent, kind - 2u, col);
-  else if (kind >= 2u && G == DF_SCALING) v = logf(expf(grp.in[0][i]) / DF_SPLIT_DIV);
+  if (kind >= 2u && G == GG_XYZ) v = densify_child_xyz(a, parent, kind - 2u, col);
+  else if (kind >= 2u && G == GG_SCALING) v = logf(expf(grp.in[0][i]) / DF_SPLIT_DIV);
   else v = grp.in[0][i];
   grp.out[0][o] = v;
   if (grp.out[1]) {
@@ -226,13 +210,6 @@ __global__ void __launch_bounds__(256) densify_gather_kernel(const float* __rest
   const uint32_t parent = src[row] & DF_ROW_MASK;
   if (parent >= P0) return;
   out[e] = in[(size_t)parent * w + col];
-}
-
-int densify_check_tmp(ggd_ctx* ctx, const char* who, int32_t P, const void* tmp, size_t tmp_bytes) {
-  if (P < 0 || P > DF_MAX_POINTS) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": P must be in [0, 2^26]");
-  if (!tmp || (reinterpret_cast<uintptr_t>(tmp) & 15u)) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": tmp is NULL or not 16-byte aligned");
-  if (tmp_bytes < densify_layout(P).total) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": tmp too small");
-  return GGD_OK;
 }
 
 // classify + scan + map on `s`, then the read-back of {kept, clones, split parents kept, new P}
@@ -264,7 +241,7 @@ int densify_plan(ggd_ctx* ctx, hipStream_t s, int32_t P, const float* accum, con
 
 }  // namespace
 
-extern "C" size_t ggd_densify_tmp_bytes(int32_t P) { return (P < 0 || P > DF_MAX_POINTS) ? 0 : densify_layout(P).total; }
+extern "C" size_t ggd_densify_tmp_bytes(int32_t P) { return (P < 0 || P > GG_MAX_POINTS) ? 0 : densify_layout(P).total; }
 
 extern "C" int ggd_densify_stats(ggd_ctx* ctx, void* stream, int32_t P, const float* grad_means2D, const int32_t* radii,
                                  const uint8_t* filter, float* accum, float* denom, float* max_radii2D) {
@@ -286,7 +263,7 @@ extern "C" int ggd_densify_plan(ggd_ctx* ctx, void* stream, int32_t P, const flo
                                 int64_t* counts4) {
   if (!ctx) return GGD_E_INVALID;
   if (!counts4) return ggd_fail(ctx, GGD_E_INVALID, "ggd_densify_plan: NULL counts");
-  if (int rc = densify_check_tmp(ctx, "ggd_densify_plan", P, tmp, tmp_bytes)) return rc;
+  if (int rc = ggd_check_tmp(ctx, "ggd_densify_plan", P, tmp, tmp_bytes, densify_layout(P).total)) return rc;
   if (!(max_grad > 0.0f)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_densify_plan: max_grad must be > 0 (a clone's zero statistic would split)");
   if (P > 0 && (!accum || !denom || !scaling || !opacity)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_densify_plan: NULL pointer");
   const df_rule rule = {max_grad, split_threshold, min_opacity, world_size, use_world_size != 0};
@@ -297,7 +274,7 @@ extern "C" int ggd_prune_plan(ggd_ctx* ctx, void* stream, int32_t P, const uint8
                               int64_t* counts4) {
   if (!ctx) return GGD_E_INVALID;
   if (!counts4) return ggd_fail(ctx, GGD_E_INVALID, "ggd_prune_plan: NULL counts");
-  if (int rc = densify_check_tmp(ctx, "ggd_prune_plan", P, tmp, tmp_bytes)) return rc;
+  if (int rc = ggd_check_tmp(ctx, "ggd_prune_plan", P, tmp, tmp_bytes, densify_layout(P).total)) return rc;
   if (P > 0 && !mask) return ggd_fail(ctx, GGD_E_INVALID, "ggd_prune_plan: NULL mask");
   return densify_plan<true>(ctx, static_cast<hipStream_t>(stream), P, nullptr, nullptr, nullptr, nullptr, mask, df_rule(), tmp, counts4);
 }
@@ -305,11 +282,10 @@ extern "C" int ggd_prune_plan(ggd_ctx* ctx, void* stream, int32_t P, const uint8
 extern "C" int ggd_densify_emit(ggd_ctx* ctx, void* stream, int32_t P, int32_t new_P, int32_t M, const float* const* in18,
                                 float* const* out18, const float* noise, const void* tmp, size_t tmp_bytes) {
   if (!ctx) return GGD_E_INVALID;
-  if (int rc = densify_check_tmp(ctx, "ggd_densify_emit", P, tmp, tmp_bytes)) return rc;
+  if (int rc = ggd_check_tmp(ctx, "ggd_densify_emit", P, tmp, tmp_bytes, densify_layout(P).total)) return rc;
   if (new_P < 0 || (int64_t)new_P > 2 * (int64_t)P) return ggd_fail(ctx, GGD_E_INVALID, "ggd_densify_emit: new_P must be in [0, 2 P]");
-  if (M < 1 || M > 16) return ggd_fail(ctx, GGD_E_INVALID, "ggd_densify_emit: M (SH coefficients per channel) must be in [1, 16]");
+  if (int rc = ggd_groups_check_M(ctx, "ggd_densify_emit", M)) return rc;
   if (new_P == 0) return GGD_OK;
-  if (!in18 || !out18) return ggd_fail(ctx, GGD_E_INVALID, "ggd_densify_emit: NULL pointer table");
   const df_layout t = densify_layout(P);
   const char* p = static_cast<const char*>(tmp);
   df_emit_args a;
@@ -318,21 +294,8 @@ extern "C" int ggd_densify_emit(ggd_ctx* ctx, void* stream, int32_t P, int32_t n
   a.noise = noise;
   a.P0 = (uint32_t)P;
   a.newP = (uint32_t)new_P;
-  const uint32_t widths[DF_GROUPS] = {3u, 3u, 3u * (uint32_t)(M - 1), 1u, 3u, 4u};
-  uint64_t blocks = 0;
-  for (int g = 0; g < DF_GROUPS; ++g) {
-    df_group& d = a.g[g];
-    d.width = widths[g];
-    d.first_block = (uint32_t)blocks;
-    for (int k = 0; k < 3; ++k) { d.in[k] = in18[3 * g + k]; d.out[k] = out18[3 * g + k]; }
-    if (d.width == 0) continue;
-    if (!d.in[0] || !d.out[0]) return ggd_fail(ctx, GGD_E_INVALID, "ggd_densify_emit: NULL parameter pointer");
-    const bool moments = d.out[1] != nullptr;
-    if ((d.out[2] != nullptr) != moments || (moments && (!d.in[1] || !d.in[2])))
-      return ggd_fail(ctx, GGD_E_INVALID, "ggd_densify_emit: a group's moments are given together or not at all");
-    blocks += ((uint64_t)new_P * d.width + 255u) / 256u;
-  }
-  if (blocks > 0x7FFFFFFFull) return ggd_fail(ctx, GGD_E_INVALID, "ggd_densify_emit: too many elements for one launch");
+  uint64_t blocks;
+  if (int rc = ggd_groups_fill(ctx, "ggd_densify_emit", M, new_P, in18, out18, a.g, blocks)) return rc;
   hipLaunchKernelGGL(densify_emit_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   GGD_HIP(hipGetLastError());
   return GGD_OK;
@@ -341,7 +304,7 @@ extern "C" int ggd_densify_emit(ggd_ctx* ctx, void* stream, int32_t P, int32_t n
 extern "C" int ggd_densify_gather(ggd_ctx* ctx, void* stream, int32_t P, int32_t new_P, int32_t width, const float* in,
                                   float* out, const void* tmp, size_t tmp_bytes) {
   if (!ctx) return GGD_E_INVALID;
-  if (int rc = densify_check_tmp(ctx, "ggd_densify_gather", P, tmp, tmp_bytes)) return rc;
+  if (int rc = ggd_check_tmp(ctx, "ggd_densify_gather", P, tmp, tmp_bytes, densify_layout(P).total)) return rc;
   if (new_P < 0 || (int64_t)new_P > 2 * (int64_t)P) return ggd_fail(ctx, GGD_E_INVALID, "ggd_densify_gather: new_P must be in [0, 2 P]");
   if (width < 1 || width > 64) return ggd_fail(ctx, GGD_E_INVALID, "ggd_densify_gather: width must be in [1, 64]");
   if (new_P == 0) return GGD_OK;

@@ -25,6 +25,7 @@
 // of alternating sign; their cancellation reaches four digits at N = 51, and the pass (which runs on the sampled rows only, once
 // per relocation) evaluates the whole rule in fp64.
 #include "ggd_common.h"
+#include "ggd_groups.h"
 #include "ggd_lanes.h"
 #include "ggd_math.h"
 
@@ -35,14 +36,11 @@ using namespace ggdm;
 #include "ggd_scan.inc"
 
 constexpr int MC_NMAX = 51;
-constexpr int MC_MAX_POINTS = 1 << 26;
 constexpr uint32_t MC_NONE = 0xFFFFFFFFu;                // sources[]: "this row is no destination"
 constexpr float MC_WEIGHT_ONE = 1048576.0f;              // 2^20: a 2048-row tile's sum fits 32 bits
 constexpr float MC_DEAD_OPACITY = 0.005f;
 // smallest float >= logit(0.005) and largest float <= logit(1 - 2^-23): sigmoid of the clamped raw opacity stays inside the bounds
 constexpr float MC_RAW_LO = -0x1.52c58p+2f, MC_RAW_HI = 0x1.fe2804p+3f;
-constexpr int MC_GROUPS = 6;                             // xyz, f_dc, f_rest, opacity, scaling, rotation
-constexpr int MC_OPACITY = 3, MC_SCALING = 4;
 
 // C(n, k) for n <= 51, exact in fp64 (C(51, 25) < 2^48), built once at compile time
 struct mc_binom_table {
@@ -194,34 +192,20 @@ __global__ void __launch_bounds__(256) mcmc_values_kernel(int P, const float* __
 }
 
 // ------------------------------------------------------------------------------------------------------- emit --
-struct mc_group {
-  const float* in[3];        // parameter, exp_avg, exp_avg_sq (moments NULL: this group has no optimizer state yet)
-  float* out[3];             // relocate: the same arrays
-  uint32_t width;            // floats per row
-  uint32_t first_block;      // this group's first workgroup of the launch
-};
 struct mc_emit_args {
-  mc_group g[MC_GROUPS];
+  ggd_row_group g[GG_GROUPS];   // relocate: in and out are the same arrays
   const uint32_t* sources;
   const uint32_t* counts;
   const float* newv;
   uint32_t P, rows;          // rows the launch covers: P (relocate) or P + num (add)
 };
 
-// One thread per float of one group's rows (its parameter and both moments), as densify_emit_kernel.
+// One thread per float of one group's rows (its parameter and both moments; the walk: ggd_groups.h).
 template <bool ADD>
 __global__ void __launch_bounds__(256) mcmc_emit_kernel(mc_emit_args a) {
-  int G = 0;
-#pragma unroll
-  for (int k = 1; k < MC_GROUPS; ++k)
-    if (blockIdx.x >= a.g[k].first_block) G = k;
-  const mc_group& grp = a.g[G];
+  const auto [G, row, col] = ggd_group_walk(a.g);
+  const ggd_row_group& grp = a.g[G];
   const uint32_t w = grp.width;
-  const uint64_t e0 = (uint64_t)(blockIdx.x - grp.first_block) * 256u;
-  const uint32_t row0 = (uint32_t)(e0 / w);                                  // (uniform)
-  const uint32_t off = (uint32_t)(e0 - (uint64_t)row0 * w) + threadIdx.x;    // < w + 256
-  const uint32_t dr = off / w;
-  const uint32_t row = row0 + dr, col = off - dr * w;
   if (row >= a.rows) return;
   uint32_t src = row;
   bool dest = false;
@@ -235,9 +219,9 @@ __global__ void __launch_bounds__(256) mcmc_emit_kernel(mc_emit_args a) {
   const bool sampled = a.counts[src] != 0u;
   if (!ADD && !dest && !sampled) return;                                     // relocate: the row is not touched
   const size_t o = (size_t)row * w + col, i = (size_t)src * w + col;
-  const bool fresh = sampled && (G == MC_OPACITY || G == MC_SCALING);
+  const bool fresh = sampled && (G == GG_OPACITY || G == GG_SCALING);
   if (ADD || dest || fresh)
-    grp.out[0][o] = fresh ? a.newv[4 * (size_t)src + (G == MC_SCALING ? 1u + col : 0u)] : grp.in[0][i];
+    grp.out[0][o] = fresh ? a.newv[4 * (size_t)src + (G == GG_SCALING ? 1u + col : 0u)] : grp.in[0][i];
   if (!grp.out[1]) return;
   if (ADD) {
     grp.out[1][o] = (dest || sampled) ? 0.0f : grp.in[1][i];
@@ -291,11 +275,9 @@ __global__ void __launch_bounds__(256) mcmc_relocation_kernel(int n, const float
 }
 
 int mcmc_check_tmp(ggd_ctx* ctx, const char* who, int32_t P, int32_t n_dest, const void* tmp, size_t tmp_bytes) {
-  if (P < 0 || P > MC_MAX_POINTS) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": P must be in [0, 2^26]");
-  if (n_dest < 0 || n_dest > MC_MAX_POINTS) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": the number of destinations must be in [0, 2^26]");
-  if (!tmp || (reinterpret_cast<uintptr_t>(tmp) & 15u)) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": tmp is NULL or not 16-byte aligned");
-  if (tmp_bytes < mcmc_layout(P, n_dest).total) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": tmp too small");
-  return GGD_OK;
+  const bool P_ok = P >= 0 && P <= GG_MAX_POINTS;        // (a refused P is reported first, by the shared check)
+  if (P_ok && (n_dest < 0 || n_dest > GG_MAX_POINTS)) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": the number of destinations must be in [0, 2^26]");
+  return ggd_check_tmp(ctx, who, P, tmp, tmp_bytes, mcmc_layout(P, n_dest).total);
 }
 
 struct mc_views { uint32_t *w, *cw; uint64_t* tile; uint32_t *counts, *sources; float* newv; int nb; };
@@ -319,35 +301,10 @@ void mcmc_plan(hipStream_t s, int32_t P, int32_t n_dest, const float* opacity, c
   hipLaunchKernelGGL(mcmc_values_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, opacity, scaling, v.counts, v.newv);
 }
 
-// the emit launch's argument block from the two pointer tables; rows = the rows it covers
-int mcmc_emit_args_of(ggd_ctx* ctx, const char* who, int32_t P, int32_t rows, int32_t M, const float* const* in18,
-                      float* const* out18, const mc_views& v, mc_emit_args& a, uint64_t& blocks) {
-  if (M < 1 || M > 16) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": M (SH coefficients per channel) must be in [1, 16]");
-  if (!in18 || !out18) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": NULL pointer table");
-  a.sources = v.sources; a.counts = v.counts; a.newv = v.newv;
-  a.P = (uint32_t)P; a.rows = (uint32_t)rows;
-  const uint32_t widths[MC_GROUPS] = {3u, 3u, 3u * (uint32_t)(M - 1), 1u, 3u, 4u};
-  blocks = 0;
-  for (int g = 0; g < MC_GROUPS; ++g) {
-    mc_group& d = a.g[g];
-    d.width = widths[g];
-    d.first_block = (uint32_t)blocks;
-    for (int k = 0; k < 3; ++k) { d.in[k] = in18[3 * g + k]; d.out[k] = out18[3 * g + k]; }
-    if (d.width == 0) continue;
-    if (!d.in[0] || !d.out[0]) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": NULL parameter pointer");
-    const bool moments = d.out[1] != nullptr;
-    if ((d.out[2] != nullptr) != moments || (moments && (!d.in[1] || !d.in[2])))
-      return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": a group's moments are given together or not at all");
-    blocks += ((uint64_t)rows * d.width + 255u) / 256u;
-  }
-  if (blocks > 0x7FFFFFFFull) return ggd_fail(ctx, GGD_E_INVALID, std::string(who) + ": too many elements for one launch");
-  return GGD_OK;
-}
-
 }  // namespace
 
 extern "C" size_t ggd_mcmc_tmp_bytes(int32_t P, int32_t n_dest) {
-  return (P < 0 || P > MC_MAX_POINTS || n_dest < 0 || n_dest > MC_MAX_POINTS) ? 0 : mcmc_layout(P, n_dest).total;
+  return (P < 0 || P > GG_MAX_POINTS || n_dest < 0 || n_dest > GG_MAX_POINTS) ? 0 : mcmc_layout(P, n_dest).total;
 }
 
 extern "C" int ggd_mcmc_relocate(ggd_ctx* ctx, void* stream, int32_t P, int32_t M, float* const* io18, const uint8_t* dead_mask,
@@ -355,13 +312,14 @@ extern "C" int ggd_mcmc_relocate(ggd_ctx* ctx, void* stream, int32_t P, int32_t 
   if (!ctx) return GGD_E_INVALID;
   if (int rc = mcmc_check_tmp(ctx, "ggd_mcmc_relocate", P, P, tmp, tmp_bytes)) return rc;
   const mc_views v = mcmc_views(tmp, P, P);
-  mc_emit_args a;
+  mc_emit_args a = {{}, v.sources, v.counts, v.newv, (uint32_t)P, (uint32_t)P};
   uint64_t blocks;
-  if (int rc = mcmc_emit_args_of(ctx, "ggd_mcmc_relocate", P, P, M, io18, io18, v, a, blocks)) return rc;
+  if (int rc = ggd_groups_check_M(ctx, "ggd_mcmc_relocate", M)) return rc;
+  if (int rc = ggd_groups_fill(ctx, "ggd_mcmc_relocate", M, P, io18, io18, a.g, blocks)) return rc;
   if (P == 0) return GGD_OK;
   if (!draws) return ggd_fail(ctx, GGD_E_INVALID, "ggd_mcmc_relocate: NULL draws");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  mcmc_plan<true>(s, P, P, a.g[MC_OPACITY].in[0], a.g[MC_SCALING].in[0], dead_mask, draws, v);
+  mcmc_plan<true>(s, P, P, a.g[GG_OPACITY].in[0], a.g[GG_SCALING].in[0], dead_mask, draws, v);
   hipLaunchKernelGGL(mcmc_emit_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, a);
   GGD_HIP(hipGetLastError());
   return GGD_OK;
@@ -386,9 +344,10 @@ extern "C" int ggd_mcmc_add_emit(ggd_ctx* ctx, void* stream, int32_t P, int32_t 
   if (P == 0 && num > 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_mcmc_add_emit: no row to sample from");
   if (num == 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_mcmc_add_emit: num must be > 0 (without new rows there is no plan in tmp)");
   const mc_views v = mcmc_views(const_cast<void*>(tmp), P, num);
-  mc_emit_args a;
+  mc_emit_args a = {{}, v.sources, v.counts, v.newv, (uint32_t)P, (uint32_t)(P + num)};
   uint64_t blocks;
-  if (int rc = mcmc_emit_args_of(ctx, "ggd_mcmc_add_emit", P, P + num, M, in18, out18, v, a, blocks)) return rc;
+  if (int rc = ggd_groups_check_M(ctx, "ggd_mcmc_add_emit", M)) return rc;
+  if (int rc = ggd_groups_fill(ctx, "ggd_mcmc_add_emit", M, P + num, in18, out18, a.g, blocks)) return rc;
   hipLaunchKernelGGL(mcmc_emit_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   GGD_HIP(hipGetLastError());
   return GGD_OK;
@@ -397,7 +356,7 @@ extern "C" int ggd_mcmc_add_emit(ggd_ctx* ctx, void* stream, int32_t P, int32_t 
 extern "C" int ggd_mcmc_noise(ggd_ctx* ctx, void* stream, int32_t P, float* xyz, const float* scaling, const float* rotation,
                               const float* opacity, const float* noise, float noise_lr, float xyz_lr) {
   if (!ctx) return GGD_E_INVALID;
-  if (P < 0 || P > MC_MAX_POINTS) return ggd_fail(ctx, GGD_E_INVALID, "ggd_mcmc_noise: P must be in [0, 2^26]");
+  if (P < 0 || P > GG_MAX_POINTS) return ggd_fail(ctx, GGD_E_INVALID, "ggd_mcmc_noise: P must be in [0, 2^26]");
   if (P == 0) return GGD_OK;
   if (!xyz || !scaling || !rotation || !opacity || !noise) return ggd_fail(ctx, GGD_E_INVALID, "ggd_mcmc_noise: NULL pointer");
   if (reinterpret_cast<uintptr_t>(rotation) & 15u) return ggd_fail(ctx, GGD_E_INVALID, "ggd_mcmc_noise: rotation must be 16-byte aligned");

@@ -74,6 +74,14 @@ def _device_float(a, device=None) -> torch.Tensor:
     return torch.as_tensor(np.asarray(a)).float().to(device or "cuda")
 
 
+_ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # a tensor's device address for the C ABI (None: NULL)
+
+
+def _group_table(groups):
+    """The C ABI's 18-pointer table of a [[parameter, exp_avg, exp_avg_sq] x 6] list (None: NULL, a group without moments)."""
+    return (C.c_void_p * 18)(*[t.data_ptr() if t is not None else None for row in groups for t in row])
+
+
 def mcmc_tmp_layout(P, n_dest):
     """Byte offsets of the arrays in the scratch of ggd_mcmc_relocate / ggd_mcmc_add_plan (include/ggd_raster.h), each
     aligned to 256 bytes, and the total (= ggd_mcmc_tmp_bytes)."""
@@ -275,6 +283,20 @@ class GaussianModel:
         setattr(self, attr, new)
         return new
 
+    def _adopt_groups(self, groups):
+        """_swap of all six groups: a [[parameter, exp_avg, exp_avg_sq] x 6] list in the order of PARAM_GROUPS."""
+        for (name, attr), (p, m1, m2) in zip(PARAM_GROUPS, groups):
+            self._swap(name, attr, p, m1, m2)
+
+    @staticmethod
+    def _fresh_groups(src, rows, cx):
+        """Uninitialised arrays of `rows` rows for every tensor of src (a list of _checked_groups)."""
+        out = [[torch.empty((rows,) + tuple(t.shape[1:]), device=t.device) if t is not None else None for t in ins] for ins in src]
+        if cx.poison_outputs:                             # tests: an element the launch does not write shows as NaN
+            for t in (t for row in out for t in row if t is not None):
+                t.fill_(float("nan"))
+        return out
+
     def replace_tensor_to_optimizer(self, tensor, name):
         """Replaces group `name`'s parameter by `tensor` and zeroes its Adam moments; returns {name: new parameter}."""
         attr = dict(PARAM_GROUPS)[name]
@@ -327,10 +349,9 @@ class GaussianModel:
                 raise ValueError(f"{who}: max_radii2D must be a contiguous float32 device tensor [{P}]")
             max_radii = self.max_radii2D
         cx, stream = _capi.context_and_stream(grad.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         with torch.cuda.device(grad.device):
-            cx.check(cx.lib.ggd_densify_stats(cx.handle, C.c_void_p(stream), P, ptr(grad), ptr(radii), ptr(filt),
-                                              ptr(self.xyz_gradient_accum), ptr(self.denom), ptr(max_radii)))
+            cx.check(cx.lib.ggd_densify_stats(cx.handle, C.c_void_p(stream), P, _ptr(grad), _ptr(radii), _ptr(filt),
+                                              _ptr(self.xyz_gradient_accum), _ptr(self.denom), _ptr(max_radii)))
 
     def add_densification_stats(self, viewspace_point_tensor, update_filter, use_absgrad=False):
         """On the rows of the bool filter: xyz_gradient_accum += |grad[:, :2]|, denom += 1.  One launch, no host wait.
@@ -346,9 +367,9 @@ class GaussianModel:
         self._stats("update_densification_stats", viewspace_point_tensor, radii, None, use_absgrad)
 
     def _checked_groups(self, in_place=False):
-        """(P, device, M, shapes by group, [[parameter, exp_avg, exp_avg_sq] per group, None for absent moments]) of the six
-        groups, every tensor checked: float32, on the parameters' device, the group's shape.  in_place: the tensors
-        themselves (which must then be contiguous) instead of contiguous copies."""
+        """(P, device, M, [[parameter, exp_avg, exp_avg_sq] per group, None for absent moments]) of the six groups, every
+        tensor checked: float32, on the parameters' device, the group's shape.  in_place: the tensors themselves (which
+        must then be contiguous) instead of contiguous copies."""
         P, dev = int(self._xyz.shape[0]), self._xyz.device
         if self._features_rest.dim() != 3:
             raise ValueError("density control: _features_rest must be [P, M - 1, 3]")
@@ -369,7 +390,7 @@ class GaussianModel:
                 if in_place and not t.is_contiguous():
                     raise ValueError(f"density control: {attr} and its Adam moments must be contiguous (they are updated in place)")
             src.append([t if in_place else t.contiguous() for t in ins] + ([] if has else [None, None]))
-        return P, dev, M, shapes, src
+        return P, dev, M, src
 
     def _regather(self, plan):
         """plan(context, stream, tmp pointer, tmp bytes, counts) fills the source map and the counts and returns the noise (or
@@ -377,34 +398,26 @@ class GaussianModel:
         optimizer state are swapped.  Every tensor is checked BEFORE the plan is launched: the kernels read P rows of the
         widths below.  Returns (new row count, gather), gather(t) being the rows of another float32 [P, ...] tensor."""
         from . import _capi
-        P, dev, M, shapes, src = self._checked_groups()
+        P, dev, M, src = self._checked_groups()
         cx, stream = _capi.context_and_stream(dev)
         nbytes = cx.lib.ggd_densify_tmp_bytes(P)
         if nbytes == 0:
             raise ValueError(f"density control: at most 2^26 rows (have {P})")
         tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
         counts = (C.c_int64 * 4)()
-        st, tp = C.c_void_p(stream), C.c_void_p(tmp.data_ptr())
+        st, tp = C.c_void_p(stream), _ptr(tmp)
         with torch.cuda.device(dev):
             noise = plan(cx, st, tp, nbytes, counts)
             new_P = int(counts[3])
-            out = [[torch.empty((new_P,) + shapes[name][1:], device=dev) if t is not None else None for t in ins]
-                   for (name, _), ins in zip(PARAM_GROUPS, src)]
-            if cx.poison_outputs:                         # tests: an element the launch does not write shows as NaN
-                for t in (t for row in out for t in row if t is not None):
-                    t.fill_(float("nan"))
-            table = lambda rows: (C.c_void_p * 18)(*[t.data_ptr() if t is not None else None for row in rows for t in row])
-            cx.check(cx.lib.ggd_densify_emit(cx.handle, st, P, new_P, M, table(src), table(out),
-                                             C.c_void_p(noise.data_ptr()) if noise is not None else None, tp, nbytes))
-        for (name, attr), (p, m1, m2) in zip(PARAM_GROUPS, out):
-            self._swap(name, attr, p, m1, m2)
+            out = self._fresh_groups(src, new_P, cx)
+            cx.check(cx.lib.ggd_densify_emit(cx.handle, st, P, new_P, M, _group_table(src), _group_table(out), _ptr(noise), tp, nbytes))
+        self._adopt_groups(out)
 
         def gather(t, plan_buffer=tmp):                  # (holds the scratch with the source map alive)
             t = t.contiguous()
             res = torch.empty((new_P,) + tuple(t.shape[1:]), device=dev)
             with torch.cuda.device(dev):
-                cx.check(cx.lib.ggd_densify_gather(cx.handle, st, P, new_P, t.numel() // max(P, 1) or 1, C.c_void_p(t.data_ptr()),
-                                                   C.c_void_p(res.data_ptr()), tp, nbytes))
+                cx.check(cx.lib.ggd_densify_gather(cx.handle, st, P, new_P, t.numel() // max(P, 1) or 1, _ptr(t), _ptr(res), tp, nbytes))
             return res
         return new_P, gather
 
@@ -426,12 +439,11 @@ class GaussianModel:
         elif noise.dtype != torch.float32 or tuple(noise.shape) != (2, P, 3):
             raise ValueError(f"densify_and_prune: noise must be float32 [2, {P}, 3]")
         noise = noise.contiguous()
-        ptr = lambda t: C.c_void_p(t.data_ptr())
         accum, denom = self.xyz_gradient_accum.contiguous(), self.denom.contiguous()
         scaling, opacity = self._scaling.detach().contiguous(), self._opacity.detach().contiguous()
 
         def plan(cx, stream, tmp, nbytes, counts):
-            cx.check(cx.lib.ggd_densify_plan(cx.handle, stream, P, ptr(accum), ptr(denom), ptr(scaling), ptr(opacity),
+            cx.check(cx.lib.ggd_densify_plan(cx.handle, stream, P, _ptr(accum), _ptr(denom), _ptr(scaling), _ptr(opacity),
                                              float(max_grad), float(self.percent_dense * extent), float(min_opacity),
                                              int(bool(max_screen_size)), float(0.1 * extent), tmp, nbytes, counts))
             return noise
@@ -450,7 +462,7 @@ class GaussianModel:
         m8 = mask.contiguous().view(torch.uint8)
 
         def plan(cx, stream, tmp, nbytes, counts):
-            cx.check(cx.lib.ggd_prune_plan(cx.handle, stream, P, C.c_void_p(m8.data_ptr()), tmp, nbytes, counts))
+            cx.check(cx.lib.ggd_prune_plan(cx.handle, stream, P, _ptr(m8), tmp, nbytes, counts))
             return None
         stats = [(n, getattr(self, n)) for n in ("xyz_gradient_accum", "denom", "max_radii2D")]
         stats = [(n, t) for n, t in stats if isinstance(t, torch.Tensor) and t.shape[:1] == (P,)]
@@ -503,7 +515,7 @@ class GaussianModel:
         draws = self._mcmc_argument(who, "draws", draws, (torch.int64,), (P,))
         P = self._mcmc_ready(who)
         from . import _capi
-        P, dev, M, _, io = self._checked_groups(in_place=True)
+        P, dev, M, io = self._checked_groups(in_place=True)
         if draws is None:
             draws = torch.randint(0, 1 << 32, (P,), dtype=torch.int64, device=dev)
         cx, stream = _capi.context_and_stream(dev)
@@ -513,11 +525,9 @@ class GaussianModel:
         tmp = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
         if P > 0:
             mask8 = dead_mask.view(torch.uint8) if dead_mask is not None else None
-            table = (C.c_void_p * 18)(*[t.data_ptr() if t is not None else None for row in io for t in row])
             with torch.cuda.device(dev):
-                cx.check(cx.lib.ggd_mcmc_relocate(cx.handle, C.c_void_p(stream), P, M, table,
-                                                  C.c_void_p(mask8.data_ptr()) if mask8 is not None else None,
-                                                  C.c_void_p(draws.data_ptr()), C.c_void_p(tmp.data_ptr()), nbytes))
+                cx.check(cx.lib.ggd_mcmc_relocate(cx.handle, C.c_void_p(stream), P, M, _group_table(io), _ptr(mask8), _ptr(draws),
+                                                  _ptr(tmp), nbytes))
         if return_plan:
             return self._mcmc_plan_tensors(tmp, P, P)
 
@@ -536,7 +546,7 @@ class GaussianModel:
         if num == 0:
             return (0, None) if return_plan else 0
         from . import _capi
-        P, dev, M, shapes, src = self._checked_groups()
+        P, dev, M, src = self._checked_groups()
         if draws is None:
             draws = torch.randint(0, 1 << 32, (num,), dtype=torch.int64, device=dev)
         cx, stream = _capi.context_and_stream(dev)
@@ -544,19 +554,12 @@ class GaussianModel:
         if nbytes == 0 or P + num > 1 << 26:
             raise ValueError(f"{who}: at most 2^26 rows (would have {P + num})")
         tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        out = [[torch.empty((P + num,) + shapes[name][1:], device=dev) if t is not None else None for t in ins]
-               for (name, _), ins in zip(PARAM_GROUPS, src)]
-        if cx.poison_outputs:                             # tests: an element the launch does not write shows as NaN
-            for t in (t for row in out for t in row if t is not None):
-                t.fill_(float("nan"))
-        table = lambda rows: (C.c_void_p * 18)(*[t.data_ptr() if t is not None else None for row in rows for t in row])
-        st, tp = C.c_void_p(stream), C.c_void_p(tmp.data_ptr())
+        st, tp = C.c_void_p(stream), _ptr(tmp)
         with torch.cuda.device(dev):
-            cx.check(cx.lib.ggd_mcmc_add_plan(cx.handle, st, P, num, C.c_void_p(src[3][0].data_ptr()),
-                                              C.c_void_p(src[4][0].data_ptr()), C.c_void_p(draws.data_ptr()), tp, nbytes))
-            cx.check(cx.lib.ggd_mcmc_add_emit(cx.handle, st, P, num, M, table(src), table(out), tp, nbytes))
-        for (name, attr), (p, m1, m2) in zip(PARAM_GROUPS, out):
-            self._swap(name, attr, p, m1, m2)
+            cx.check(cx.lib.ggd_mcmc_add_plan(cx.handle, st, P, num, _ptr(src[3][0]), _ptr(src[4][0]), _ptr(draws), tp, nbytes))
+            out = self._fresh_groups(src, P + num, cx)
+            cx.check(cx.lib.ggd_mcmc_add_emit(cx.handle, st, P, num, M, _group_table(src), _group_table(out), tp, nbytes))
+        self._adopt_groups(out)
         for n in ("xyz_gradient_accum", "denom", "max_radii2D"):
             t = getattr(self, n)
             if isinstance(t, torch.Tensor) and t.shape[:1] == (P,):
@@ -576,11 +579,10 @@ class GaussianModel:
         from . import _capi
         if xyz_lr is None:
             xyz_lr = self._own_groups()["xyz"]["lr"]
-        P, dev, _, _, io = self._checked_groups(in_place=True)
+        P, dev, _, io = self._checked_groups(in_place=True)
         if noise is None:
             noise = torch.randn((P, 3), device=dev)
         cx, stream = _capi.context_and_stream(dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
         with torch.cuda.device(dev):
-            cx.check(cx.lib.ggd_mcmc_noise(cx.handle, C.c_void_p(stream), P, ptr(io[0][0]), ptr(io[4][0]), ptr(io[5][0]),
-                                           ptr(io[3][0]), ptr(noise), float(noise_lr), float(xyz_lr)))
+            cx.check(cx.lib.ggd_mcmc_noise(cx.handle, C.c_void_p(stream), P, _ptr(io[0][0]), _ptr(io[4][0]), _ptr(io[5][0]),
+                                           _ptr(io[3][0]), _ptr(noise), float(noise_lr), float(xyz_lr)))
