@@ -9,3 +9,4 @@ from gaussian_gan_decoder_amd.rasterizer import (  # noqa: F401
     rasterize_gaussians_native, rasterize_gaussians_backward_native)
 from gaussian_gan_decoder_amd.sparse_adam import SparseGaussianAdam  # noqa: F401
 from gaussian_gan_decoder_amd.mcmc import compute_relocation  # noqa: F401
+from gaussian_gan_decoder_amd.contribution import ContributionStats  # noqa: F401

@@ -32,6 +32,7 @@ EXPORTS = [
     "ggd_forward_features", "ggd_backward_features",
     "ggd_forward_distortion", "ggd_backward_distortion",
     "ggd_backward_camera",
+    "ggd_contribution",
     "ggd_gaussian_normals", "ggd_gaussian_normals_backward", "ggd_normal_loss_tmp_bytes", "ggd_normal_loss",
 ]
 
@@ -80,6 +81,7 @@ STAT_L1_COUNTED_FRAMES = 104
 SPLAT_BYTES = 48
 FEATURES_MAX_CHANNELS = 32   # GGD_FEATURES_MAX_CHANNELS
 FEATURES_ROUND = 64          # GGD_FEATURES_ROUND: list entries the feature kernels consume per round
+CONTRIB_SCALE_LOG2 = 24      # GGD_CONTRIB_SCALE_LOG2: the fixed-point scale of ggd_contribution's weight sum
 LANES_SELFTEST_WORDS = 156   # GGD_LANES_SELFTEST_WORDS
 SPLAT_FIELDS = ("x", "y", "hA", "nB", "hC", "thr", "opacity", "r", "g", "b", "ex", "ey")
 
@@ -135,6 +137,8 @@ def load():
         lib.ggd_backward_distortion.argtypes = lib.ggd_backward_aux.argtypes + [vp, C.POINTER(FeatureSide)]
         # the camera's gradients: ggd_backward_distortion's arguments (each map's side may be NULL), then the bundle of the results
         lib.ggd_backward_camera.argtypes = lib.ggd_backward_distortion.argtypes + [C.POINTER(CameraGrads)]
+        # the contribution statistics: ctx, stream, params, the three buffers, R, stats (int64 [P, 3], accumulated in place)
+        lib.ggd_contribution.argtypes = [vp, vp, C.POINTER(Params), vp, vp, vp, i64, vp]
         lib.ggd_mark_visible.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         lib.ggd_debug_unsorted.argtypes = [vp, vp, vp, vp, i64]
         lib.ggd_selftest_lanes.argtypes = [vp, vp, vp, vp, i32]

@@ -1014,6 +1014,27 @@ extern "C" int ggd_forward_distortion(ggd_ctx* ctx, void* stream, const ggd_para
                                        im.n_contrib, g.depth_keys, out_distortion);
 }
 
+// the contribution statistics: ggd_contribution after a completed forward, accumulated into stats [P][3]
+extern "C" int ggd_contribution(ggd_ctx* ctx, void* stream, const ggd_params* prm, const void* geom_buf,
+                                const void* binning_buf, const void* img_buf, int64_t R, int64_t* stats) {
+  if (!ctx) return GGD_E_INVALID;
+  (void)hipGetLastError();
+  const int rc = check_params(ctx, prm);
+  if (rc != GGD_OK) return rc;
+  if (ctx->pending.valid) return ggd_fail(ctx, GGD_E_INVALID, kPendingMsg);
+  if (R < 0) return ggd_fail(ctx, GGD_E_INVALID, "num_rendered < 0");
+  if (prm->P > 0 && !stats) return ggd_fail(ctx, GGD_E_INVALID, "ggd_contribution: stats is NULL");
+  if (reinterpret_cast<uintptr_t>(stats) % 8 != 0) return ggd_fail(ctx, GGD_E_INVALID, "ggd_contribution: stats is not 8-byte aligned");
+  if (!img_buf) return ggd_fail(ctx, GGD_E_INVALID, "ggd_contribution: img_buf is NULL");
+  if (R > 0 && (!geom_buf || !binning_buf)) return ggd_fail(ctx, GGD_E_INVALID, "ggd_contribution: geom_buf / binning_buf is NULL");
+  if (prm->P == 0 || R == 0) return GGD_OK;   // no pair: nothing to add
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const geom_ptrs g = geom_view(prm, geom_buf);
+  const binning_ptrs b = binning_view(R, binning_buf);
+  const img_ptrs im = img_view(prm->width, prm->height, img_buf);
+  return ggd_launch_contribution(ctx, s, *prm, g.splat, b.list, im.ranges, list_capacity(R), im.n_contrib, stats);
+}
+
 extern "C" int ggd_backward_distortion(ggd_ctx* ctx, void* stream, const ggd_params* prm, const float* means3D,
                                        const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
                                        const float* rotations, const float* cov3D_precomp, const int32_t* radii,

@@ -348,6 +348,10 @@ int ggd_launch_distortion_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params
                                    const uint32_t* list, const uint32_t* ranges, uint32_t R, const float* final_T,
                                    const uint32_t* n_contrib, const uint32_t* depth_keys, const float* dL_dD /*[H, W]*/,
                                    float* grad_acc);
+// Contribution statistics (ggd_contribution.hip; ggd_contribution): per Gaussian the fixed-point sum, the count and the maximum of
+// w = alpha T over the (pixel, record) pairs of a finished colour render, ACCUMULATED into stats [P][3] with integer atomics.
+int ggd_launch_contribution(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_splat* splat, const uint32_t* list,
+                            const uint32_t* ranges, uint32_t R, const uint32_t* n_contrib, int64_t* stats /*[P][3]*/);
 // aux: also adds dL/dz (accumulator slot GGD_ACC_DEPTH) times dz/dmean = (view[2], view[6], view[10]) to dL_dmeans3D
 // out.dL_dmeans2D_abs non-null: the absgrad kernels, which write it too
 int ggd_launch_preprocess_backward(ggd_ctx* ctx, hipStream_t s, const ggd_params& prm, const ggd_inputs& in,

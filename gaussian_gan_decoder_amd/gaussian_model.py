@@ -473,6 +473,56 @@ class GaussianModel:
         for n, t in stats:                                # the same source map, one small launch each, no host wait
             setattr(self, n, gather(t))
 
+    # ---- pruning by what the rendered frames used (contribution.py, csrc/ggd_contribution.hip) -------
+    def _contribution_stats(self, who, stats):
+        from .contribution import ContributionStats
+        P = int(self._xyz.shape[0])
+        if not isinstance(stats, ContributionStats):
+            raise ValueError(f"{who}: stats must be a ContributionStats (got {type(stats).__name__})")
+        if stats.P != P or stats.raw.device != self._xyz.device:
+            raise ValueError(f"{who}: stats hold {stats.P} rows on {stats.raw.device}, the model {P} on {self._xyz.device}")
+        return P
+
+    def importance(self, stats, kind="sum", volume_power=0.1):
+        """float32 [P]: the score a pruning ranks by, from the accumulated contribution statistics of rendered frames.  "sum": the
+        summed blend weight (Mini-Splatting, gsplat); "max": the largest blend weight (RadSplat); "count": the pixel count;
+        "lightgaussian": LightGaussian's global significance, pixel_count * opacity * clamp(V / V_90, 0, 1)^volume_power with V the
+        product of the activated scales and V_90 its 90th percentile -- that project's code is not part of the reference tree, so
+        the rule is restated here from the paper (Fan et al. 2023, section 3.2)."""
+        self._contribution_stats("importance", stats)
+        if kind != "lightgaussian":
+            return stats.score(kind)
+        with torch.no_grad():
+            volume = self.get_scaling.detach().to(torch.float32).prod(dim=1)
+            v90 = torch.quantile(volume, 0.9) if volume.numel() else volume.new_zeros(())
+            norm = torch.clamp(volume / v90, 0.0, 1.0) ** float(volume_power)
+            return stats.pixel_count.to(torch.float32) * self.get_opacity.detach().to(torch.float32).reshape(-1) * norm
+
+    def contribution_prune_mask(self, stats, keep_fraction=None, min_max_weight=None, kind="sum"):
+        """bool [P], set where prune_by_contribution drops the row: weight_max < min_max_weight, and / or outside the top
+        ceil(keep_fraction P) rows by importance(kind) (ties: the lower index first, by a stable sort).  Torch ops only."""
+        P = self._contribution_stats("prune_by_contribution", stats)
+        if keep_fraction is None and min_max_weight is None:
+            raise ValueError("prune_by_contribution: give keep_fraction, min_max_weight or both")
+        drop = torch.zeros((P,), dtype=torch.bool, device=self._xyz.device)
+        if min_max_weight is not None:
+            drop |= stats.weight_max < float(min_max_weight)
+        if keep_fraction is not None:
+            if not 0.0 <= float(keep_fraction) <= 1.0:
+                raise ValueError(f"prune_by_contribution: keep_fraction must lie in [0, 1] (got {keep_fraction})")
+            keep = min(P, int(math.ceil(float(keep_fraction) * P)))
+            order = torch.sort(self.importance(stats, kind), descending=True, stable=True).indices
+            drop[order[keep:]] = True
+        return drop
+
+    def prune_by_contribution(self, stats, keep_fraction=None, min_max_weight=None, kind="sum"):
+        """Drops the rows the accumulated statistics mark as unused -- contribution_prune_mask's rule -- from every parameter, Adam
+        moment and statistic (prune_points).  Returns the number of rows kept.  `stats` describe the rows before the call: reset
+        or rebuild them afterwards."""
+        mask = self.contribution_prune_mask(stats, keep_fraction, min_max_weight, kind)
+        self.prune_points(mask)
+        return int(self._xyz.shape[0])
+
     # ---- density control under a fixed budget (csrc/ggd_mcmc.hip, DESIGN.md section 6zg) -----------------------------------
     def _mcmc_argument(self, who, name, t, dtypes, shape):
         """An optional tensor argument of the three methods below: dtype and shape (ValueError), then the device (RuntimeError)."""

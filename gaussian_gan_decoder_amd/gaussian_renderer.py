@@ -16,6 +16,7 @@ import math
 import torch
 
 from . import _capi
+from .contribution import resolve as _resolve_contribution
 from .normals import gaussian_normals
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _check_camera_grad, _check_distortion
 from .sh import eval_sh
@@ -69,7 +70,7 @@ def _split_normals(res, fmap, n_feat):
 
 
 def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attributes=False, render_depth_alpha=False,
-              antialiasing=False, absgrad=False, render_distortion=False, camera_grad=False):
+              antialiasing=False, absgrad=False, render_distortion=False, camera_grad=False, contribution=None):
     if render_distortion:   # (refused before anything is built; the keyword reaches the settings only when set)
         _check_distortion(render_depth_alpha, absgrad)
     if camera_grad:         # (likewise)
@@ -77,6 +78,7 @@ def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attri
     return GaussianRasterizationSettings(
         **({"render_distortion": True} if render_distortion else {}),
         **({"camera_grad": True} if camera_grad else {}),
+        **({"contribution": contribution.raw} if contribution is not None else {}),
         raw_attributes=raw_attributes,
         render_depth_alpha=render_depth_alpha,
         antialiasing=antialiasing,
@@ -98,7 +100,7 @@ def _settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug, raw_attri
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
            render_depth_alpha=False, antialiasing=False, absgrad=False, features=None, feature_bg=None,
-           render_distortion=False, camera_grad=False, render_normals=False):
+           render_distortion=False, camera_grad=False, contribution=None, render_normals=False):
     """Stock 3DGS render (reference :19-102).  `pipe` needs .debug, .compute_cov3D_python, .convert_SHs_python.
     render_depth_alpha=True (extension): the dict also holds "depth" (sum alpha_i T_i z_i) and "alpha" (1 - final T),
     differentiable float32 [1, H, W] maps.
@@ -116,13 +118,21 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     render_normals=True (extension; refuses absgrad, camera_grad, pipe.compute_cov3D_python and more than 29 caller's feature
     channels): the dict also holds "normals", the differentiable float32 [3, H, W] map sum alpha_i T_i n_i of the Gaussians'
     camera-facing view-space normals (normals.gaussian_normals of the scales and rotations of this call), blended as three more
-    channels of the feature pass -- what normals.fused_normal_loss compares with the depth map's surface."""
+    channels of the feature pass -- what normals.fused_normal_loss compares with the depth map's surface.
+    contribution=stats (extension; a contribution.ContributionStats of pc's size on its device, or True for a fresh one): the
+    frame's per-Gaussian statistics -- summed blend weight alpha T, pixel count, largest blend weight -- are ACCUMULATED into it by
+    one more forward-only launch, and the dict holds the object as "contribution".  Everything else in the dict, and the backward,
+    are those of the call without it; combines with every keyword above, absgrad included, with or without gradients enabled."""
+    stats = None
+    if contribution is not None and contribution is not False:   # (refused before anything is built; only then is pc looked at)
+        stats = _resolve_contribution(contribution, pc.get_xyz.shape[0], pc.get_xyz.device)
     if render_normals:
         n_feat = _check_normals(features, feature_bg, absgrad, camera_grad, pipe.compute_cov3D_python)
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, pipe.debug,
                                               render_depth_alpha=render_depth_alpha, antialiasing=antialiasing,
-                                              absgrad=absgrad, render_distortion=render_distortion, camera_grad=camera_grad))
+                                              absgrad=absgrad, render_distortion=render_distortion, camera_grad=camera_grad,
+                                              contribution=stats))
     scales = rotations = cov3D_precomp = None
     if pipe.compute_cov3D_python:
         cov3D_precomp = pc.get_covariance(scaling_modifier)
@@ -156,13 +166,16 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         _split_normals(res, out[-1], n_feat)
     elif features is not None:
         res["features"] = out[-1]
+    if stats is not None:
+        stats.frames += 1
+        res["contribution"] = stats
     return res
 
 
 def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None, scaling_modifier=1.0,
                   override_color=None, debug=False, fused_activations=False, render_depth_alpha=False, antialiasing=False,
                   absgrad=False, features=None, feature_bg=None, render_distortion=False, camera_grad=False,
-                  render_normals=False):
+                  contribution=None, render_normals=False):
     """Decoder-path render (reference :105-186): scale/rotation always from the model, SH unless override_color.
     "alpha" and "depth" are the radii placeholders the reference returns (:184-185).
     fused_activations=True (extension): hand the RAW `_opacity/_scaling/_rotation` to the
@@ -182,14 +195,19 @@ def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None,
     everything above but absgrad.
     render_normals=True (extension): as in `render` -- "normals" is the [3, H, W] map, of the normals of the scales and rotations
     this call passes on (raw with fused_activations) at the means it passes on (xyz_offset included); combines with everything
-    above but absgrad and camera_grad."""
+    above but absgrad and camera_grad.
+    contribution=stats or True (extension): as in `render` -- "contribution" is the ContributionStats the frame was accumulated
+    into; combines with everything above."""
+    stats = None
+    if contribution is not None and contribution is not False:   # (refused before anything is built; only then is pc looked at)
+        stats = _resolve_contribution(contribution, pc.get_xyz.shape[0], pc.get_xyz.device)
     if render_normals:
         n_feat = _check_normals(features, feature_bg, absgrad, camera_grad)
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(_settings(viewpoint_camera, pc, bg_color, scaling_modifier, debug,
                                               raw_attributes=fused_activations, render_depth_alpha=render_depth_alpha,
                                               antialiasing=antialiasing, absgrad=absgrad, render_distortion=render_distortion,
-                                              camera_grad=camera_grad))
+                                              camera_grad=camera_grad, contribution=stats))
     means3D = pc.get_xyz
     if xyz_offset is not None:
         means3D = means3D + xyz_offset
@@ -217,4 +235,7 @@ def render_simple(viewpoint_camera, pc, bg_color: torch.Tensor, xyz_offset=None,
         _split_normals(res, out[-1], n_feat)
     elif features is not None:
         res["features"] = out[-1]
+    if stats is not None:
+        stats.frames += 1
+        res["contribution"] = stats
     return res

@@ -29,6 +29,7 @@ import torch
 from torch import nn
 
 from . import _capi
+from .contribution import check_raw as _check_contribution
 
 
 class _SettingsFields(NamedTuple):
@@ -70,19 +71,26 @@ class GaussianRasterizationSettings(_SettingsFields):
     camera_grad (keyword only, default False; refuses absgrad=True): the backward also differentiates the frame in viewmatrix,
     projmatrix and campos, and autograd carries the three gradients on to whatever built those tensors (a pose, for instance).
     The bottom row of viewmatrix and row 2 of projmatrix (maths layout) are read by no kernel and get exactly 0; tanfovx and
-    tanfovy get no gradient.  An attribute like antialiasing, for the same reason."""
+    tanfovy get no gradient.  An attribute like antialiasing, for the same reason.
+
+    contribution (keyword only, default None): an int64 [P, 3] device tensor (contribution.ContributionStats.raw) into which the
+    forward ACCUMULATES the frame's per-Gaussian contribution statistics -- fixed-point sum, count and maximum of the blend weight
+    alpha T over the pixels (ggd_contribution).  No autograd input or output: the returned tuple and the backward are those of
+    the call without it.  An attribute like antialiasing, for the same reason."""
     antialiasing: bool = False   # (instances made without __new__, e.g. by _make, read these class defaults)
     absgrad: bool = False
     render_distortion: bool = False
     camera_grad: bool = False
+    contribution: Optional[torch.Tensor] = None
 
     def __new__(cls, *args, antialiasing: bool = False, absgrad: bool = False, render_distortion: bool = False,
-                camera_grad: bool = False, **kwargs):
+                camera_grad: bool = False, contribution: Optional[torch.Tensor] = None, **kwargs):
         self = super().__new__(cls, *args, **kwargs)
         self.antialiasing = bool(antialiasing)
         self.absgrad = bool(absgrad)
         self.render_distortion = bool(render_distortion)
         self.camera_grad = bool(camera_grad)
+        self.contribution = contribution
         return self
 
     def _replace(self, **kwargs):
@@ -90,12 +98,15 @@ class GaussianRasterizationSettings(_SettingsFields):
         ab = kwargs.pop("absgrad", self.absgrad)
         rd = kwargs.pop("render_distortion", self.render_distortion)
         cg = kwargs.pop("camera_grad", self.camera_grad)
-        return type(self)(*super()._replace(**kwargs), antialiasing=aa, absgrad=ab, render_distortion=rd, camera_grad=cg)
+        co = kwargs.pop("contribution", self.contribution)
+        return type(self)(*super()._replace(**kwargs), antialiasing=aa, absgrad=ab, render_distortion=rd, camera_grad=cg,
+                          contribution=co)
 
     def __repr__(self):
         rd = f", render_distortion={self.render_distortion}" if self.render_distortion else ""
         cg = f", camera_grad={self.camera_grad}" if self.camera_grad else ""
-        return super().__repr__()[:-1] + f", antialiasing={self.antialiasing}, absgrad={self.absgrad}{rd}{cg})"
+        co = ", contribution=int64[%d, 3]" % self.contribution.shape[0] if isinstance(self.contribution, torch.Tensor) else ""
+        return super().__repr__()[:-1] + f", antialiasing={self.antialiasing}, absgrad={self.absgrad}{rd}{cg}{co})"
 
 
 def _f32c(t: torch.Tensor, name: str, device) -> torch.Tensor:
@@ -276,7 +287,8 @@ def _alloc_outputs(dev, P: int, W: int, H: int, depth_alpha: bool = False):
 def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier,
                                cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, image_height, image_width,
                                sh, degree, campos, prefiltered, debug, raw_attributes=False, *, render_depth_alpha=False,
-                               antialiasing=False, features=None, feature_bg=None, render_distortion=False):
+                               antialiasing=False, features=None, feature_bg=None, render_distortion=False,
+                               contribution=None):
     """== upstream `_C.rasterize_gaussians(...)`: returns
     (num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer).  binningBuffer may be larger than
     num_rendered needs (single-call forward with a capacity hint); the sorted list sits at its offset 0 either way, so
@@ -289,9 +301,14 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
     LAST to the tuple.  Everything in front of it is bit-identical to the call without the keyword.
     render_distortion=True (extension; needs render_depth_alpha=True): one more launch behind the finished forward
     (ggd_forward_distortion) walks the colour's contributors once more; the map, float32 [1, H, W], follows the depth and alpha
-    maps and precedes the feature map.  Everything else is bit-identical to the call without the keyword."""
+    maps and precedes the feature map.  Everything else is bit-identical to the call without the keyword.
+    contribution (extension; a contiguous int64 [P, 3] tensor on the inputs' device): one more launch behind the finished forward
+    and the two above (ggd_contribution) ACCUMULATES the frame's per-Gaussian statistics into it -- sum of rint(w 2^24), count and
+    largest fp32 bits of w = alpha T over the pixels that blended the Gaussian.  The returned tuple is unchanged."""
     if render_distortion:      # (refused before any device call)
         _check_distortion(render_depth_alpha)
+    if contribution is not None:   # (likewise)
+        _check_contribution(contribution, means3D.size(0), means3D.device)
     if features is not None:   # (likewise)
         n_feat = _check_features(features, feature_bg, means3D.size(0))
     dev, P, inputs, prm, keep = _marshal_forward(
@@ -350,6 +367,10 @@ def rasterize_gaussians_native(bg, means3D, colors_precomp, opacities, scales, r
             ctx.check(lib.ggd_forward_features(ctx.handle, stream, C.byref(prm), _ptr(geom), _ptr(binning), _ptr(img), int(R.value),
                                                _ptr(feat), n_feat, _ptr(fbg), _ptr(fmap)))
         out = out + (fmap,)
+    if contribution is not None:
+        with _device_guard(dev):
+            ctx.check(lib.ggd_contribution(ctx.handle, stream, C.byref(prm), _ptr(geom), _ptr(binning), _ptr(img), int(R.value),
+                                           _ptr(contribution)))
     return out
 
 
@@ -587,6 +608,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         distortion = bool(getattr(rs, "render_distortion", False))
         if distortion:
             _check_distortion(depth_alpha, bool(getattr(rs, "absgrad", False)))
+        # (the statistics tensor is no autograd input: it is accumulated into behind the forward and the backward never sees it)
+        contribution = getattr(rs, "contribution", None)
         # (apply() is called with the feature pair only when features are given: the backward then returns eleven gradients)
         ctx.has_features = features is not None
         feat_kw = {}
@@ -598,7 +621,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree,
             rs.campos, rs.prefiltered, rs.debug, getattr(rs, "raw_attributes", False), render_depth_alpha=depth_alpha,
             **({"antialiasing": True} if getattr(rs, "antialiasing", False) else {}), **feat_kw,
-            **({"render_distortion": True} if distortion else {}))
+            **({"render_distortion": True} if distortion else {}),
+            **({"contribution": contribution} if contribution is not None else {}))
         num_rendered, color, radii, geom, binning, img = out[:6]
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered

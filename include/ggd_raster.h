@@ -343,6 +343,31 @@ int ggd_backward_distortion(ggd_ctx* ctx, void* stream, const ggd_params* prm,
                             const float* dL_ddistortion, const ggd_feature_side* features /* NULL = no feature map */);
 
 /*
+ * Contribution statistics (opt-in extension; every entry point above is unchanged by it): which Gaussians a frame used, and how
+ * much -- what pruning and compaction of a trained model rank by (hit counts, summed blend weights, the largest blend weight).
+ * Over exactly the (pixel, Gaussian) pairs the finished colour render blended, with w = alpha T the colour pass's own weight of
+ * the pair (bit for bit, as for ggd_forward_features), per Gaussian i:
+ *   stats[i][0] += rint(w * 2^GGD_CONTRIB_SCALE_LOG2)   the summed weight in fixed point (ties to even: each term is within
+ *                                                       2^-25 of w; the scaling is exact in fp32)
+ *   stats[i][1] += 1                                    the number of pixels that blended i
+ *   stats[i][2]  = max(stats[i][2], bits of w)          the largest weight: w > 0, so the fp32 bit pattern, zero-extended, orders
+ *                                                       as the value does
+ * stats : int64[P,3] (device, 8-byte aligned), ACCUMULATED in place: zero it once, then call per frame and per camera.  Rows of
+ * Gaussians no pixel blended are neither read nor written.  All three updates are integer atomics: the result does not depend on
+ * the order of arrival and is bit-identical from run to run.
+ *   ggd_contribution   one launch behind a completed forward (ggd_forward / ggd_forward_render or their _aux forms, same ctx,
+ *                      stream-ordered), on that forward's three buffers and its num_rendered; prm, GGD_OPT_EXP_MODE and
+ *                      GGD_OPT_BLEND_CULL as in that forward (as for ggd_forward_features).  Forward only: it has no gradient and
+ *                      changes nothing a backward reads.
+ * GGD_E_INVALID with a message, before any launch: a NULL stats with P > 0; a stats that is not 8-byte aligned; a NULL img_buf;
+ * NULL geom_buf / binning_buf with num_rendered > 0.  P = 0 and num_rendered = 0 are valid and change nothing.
+ */
+#define GGD_CONTRIB_SCALE_LOG2 24
+int ggd_contribution(ggd_ctx* ctx, void* stream, const ggd_params* prm,
+                     const void* geom_buf, const void* binning_buf, const void* img_buf, int64_t num_rendered,
+                     int64_t* stats /* [P][3], ACCUMULATED in place */);
+
+/*
  * Camera gradients (opt-in extension; every entry point above is unchanged by it): the backward also differentiates the frame in
  * prm->viewmatrix, prm->projmatrix and prm->campos.
  *   ggd_backward_camera  == ggd_backward_distortion's arguments + `camera`.  dL_ddistortion and `features` may be NULL, and so may
