@@ -34,6 +34,7 @@ EXPORTS = [
     "ggd_backward_camera",
     "ggd_contribution",
     "ggd_gaussian_normals", "ggd_gaussian_normals_backward", "ggd_normal_loss_tmp_bytes", "ggd_normal_loss",
+    "ggd_perceptual_tmp_bytes", "ggd_perceptual_loss", "ggd_perceptual_features",
 ]
 
 
@@ -60,6 +61,18 @@ class FeatureSide(C.Structure):
 class CameraGrads(C.Structure):
     """ggd_camera_grads: the three results of ggd_backward_camera (device pointers: [16], [16], [3] floats)."""
     _fields_ = [("dL_dviewmatrix", C.c_void_p), ("dL_dprojmatrix", C.c_void_p), ("dL_dcampos", C.c_void_p)]
+
+
+PERC_CONVS, PERC_TAPS = 13, 5    # GGD_PERC_CONVS, GGD_PERC_TAPS
+PERC_TIERS = {"bf16": 0, "fp32": 1}   # GGD_PERC_BF16, GGD_PERC_FP32
+
+
+class PerceptualDesc(C.Structure):
+    """ggd_perceptual_desc: shapes, input affine and the device pointers of one trunk (ggd_perceptual_*)."""
+    _fields_ = [("tier", C.c_int32), ("B", C.c_int32), ("H_in", C.c_int32), ("W_in", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("widths", C.c_int32 * PERC_CONVS), ("scale", C.c_float * 3), ("shift", C.c_float * 3),
+                ("w0", C.c_void_p), ("w0_t", C.c_void_p), ("bias", C.c_void_p * PERC_CONVS),
+                ("w_fwd", C.c_void_p * PERC_CONVS), ("w_bwd", C.c_void_p * PERC_CONVS), ("lin", C.c_void_p * PERC_TAPS)]
 
 
 class GeomView(C.Structure):
@@ -217,6 +230,11 @@ def load():
         lib.ggd_gaussian_normals_backward.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]
         lib.ggd_normal_loss_tmp_bytes.restype = sz; lib.ggd_normal_loss_tmp_bytes.argtypes = [i32, i32]
         lib.ggd_normal_loss.argtypes = [vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp, vp, sz]
+        # the perceptual term: desc, images in the forward, with_grad / ctx, stream, desc, image, target, loss, grad, tmp, bytes /
+        # ctx, stream, desc, image, features, tmp, bytes
+        lib.ggd_perceptual_tmp_bytes.restype = sz; lib.ggd_perceptual_tmp_bytes.argtypes = [C.POINTER(PerceptualDesc), i32, i32]
+        lib.ggd_perceptual_loss.argtypes = [vp, vp, C.POINTER(PerceptualDesc), vp, vp, vp, vp, vp, sz]
+        lib.ggd_perceptual_features.argtypes = [vp, vp, C.POINTER(PerceptualDesc), vp, vp, vp, sz]
         _lib = lib
         return lib
 

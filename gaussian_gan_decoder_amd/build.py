@@ -20,7 +20,7 @@ CSRC = os.path.join(_PKG, "csrc")
 LIB_PATH = os.path.join(_PKG, "libggd_raster.so")
 SOURCES = ["ggd_capi.hip", "ggd_preprocess.hip", "ggd_binning.hip", "ggd_rowbin.hip", "ggd_blend.hip", "ggd_triplane.hip", "ggd_mlp.hip", "ggd_imgloss.hip",
            "ggd_preprocess_bwd.hip", "ggd_surface.hip", "ggd_knn.hip", "ggd_densify.hip", "ggd_density.hip", "ggd_teacher.hip", "ggd_adam.hip", "ggd_features.hip",
-           "ggd_distortion.hip", "ggd_camera.hip", "ggd_normals.hip", "ggd_mcmc.hip", "ggd_contribution.hip"]
+           "ggd_distortion.hip", "ggd_camera.hip", "ggd_normals.hip", "ggd_mcmc.hip", "ggd_contribution.hip", "ggd_perceptual.hip"]
 HEADERS = ["ggd_common.h", "ggd_spec.h", "ggd_binning_layout.h", "ggd_lookback.inc", "ggd_math.h", "ggd_mlp_bwd.inc", "ggd_mlp_wgrad.inc", "ggd_mlp_pack.inc", "ggd_mlp_hl.inc", "ggd_mlp_gelu.inc", "ggd_scan.inc", "ggd_rowbin_wide.inc", "ggd_msd_finish.inc", "ggd_blend_bwd_quarter.inc", "ggd_planes.h", "ggd_density_launch.h", "ggd_lanes.h", "ggd_blend_math.h", "ggd_quarter_walk.h", "ggd_groups.h"]
 ARCH = "gfx950"
 

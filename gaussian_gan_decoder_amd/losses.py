@@ -17,6 +17,9 @@ stand-in is a FIXED, seeded, random-initialised network of the same shape (VGG16
 conv1_2 / 2_2 / 3_3 / 4_3 / 5_3, channel-normalised, per-channel weights), so that the training step carries the same
 amount of convolution work and the same kind of gradient path into the rendered image.  It runs in PyTorch-ROCm (MIOpen)
 like the reference's own VGG.  The identity term needs ArcFace and stays out.
+`FusedPerceptual`: the same term on HIP kernels (csrc/ggd_perceptual.hip) -- NHWC activations, the twelve
+convolutions behind conv1_1 and their backward-data passes as one implicit-GEMM MFMA kernel, pools, taps and the loss in a fixed
+summation order; opt-in (DecoderTrainer(fused_perceptual=True)), two precision tiers like the fused decoder's.
 """
 from __future__ import annotations
 
@@ -290,3 +293,203 @@ class PerceptualStandIn(torch.nn.Module):
         with torch.no_grad():
             ft = self.features(target)
         return (self.features(image) - ft).square().sum()
+
+
+# ---- the perceptual term on the device (csrc/ggd_perceptual.hip) ------------------------------------------------------------
+_PERC_POOLS_AFTER = (1, 3, 6, 9)      # a 2x2 max pool follows these convolutions (PerceptualStandIn.CFG)
+_PERC_FORMATS = {"f16": torch.float16, "bf16": torch.bfloat16, "split": torch.bfloat16}
+
+
+def pack_conv_weights(weight, fmt):
+    """weight [Cout, Cin, 3, 3] (Cin a multiple of 32) -> the image ggd_perceptual_* reads: [9 Cin / 32 K steps][parts][Cout' / 16
+    tiles][64 lanes][8], Cout' = Cout rounded up to 64 (zero columns); K step = tap (ky * 3 + kx) * (Cin / 32) + channel chunk, lane
+    l of tile t holds k = 8 (l >> 4) + j of the chunk for output channel 16 t + (l & 15): the A operand of
+    v_mfma_f32_16x16x32.  fmt "f16" / "bf16": one part in that format; "split": two bf16 parts, hi = bf16(w), lo = bf16(w - hi)."""
+    if fmt not in _PERC_FORMATS:
+        raise ValueError(f"pack_conv_weights: fmt must be one of {tuple(_PERC_FORMATS)} (got {fmt!r})")
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or cin % 32 != 0:
+        raise ValueError(f"pack_conv_weights: [Cout, Cin, 3, 3] with Cin a multiple of 32 expected, got {tuple(weight.shape)}")
+    pad = -cout % 64
+    w = F.pad(weight.detach().float().permute(2, 3, 1, 0).reshape(9, cin, cout), (0, pad))          # [tap][ci][co']
+    tiles = (cout + pad) // 16
+    w = w.reshape(9, cin // 32, 4, 8, tiles, 16).permute(0, 1, 4, 2, 5, 3).reshape(9 * cin // 32, 1, tiles, 64, 8)
+    if fmt == "split":
+        hi = w.to(torch.bfloat16)
+        return torch.cat([hi, (w - hi.float()).to(torch.bfloat16)], 1).contiguous()
+    return w.to(_PERC_FORMATS[fmt]).contiguous()
+
+
+def unpack_conv_weights(packed, cout, cin):
+    """The inverse of pack_conv_weights, as float32 [cout, cin, 3, 3] (the sum of the parts)."""
+    tiles = int(packed.shape[2])
+    w = packed.float().sum(1).reshape(9, cin // 32, tiles, 4, 16, 8).permute(0, 1, 3, 5, 2, 4).reshape(9, cin, tiles * 16)
+    return w[:, :, :cout].reshape(3, 3, cin, cout).permute(3, 2, 0, 1).contiguous()
+
+
+class _FusedPerceptualFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, target, owner):
+        loss, grad = owner._launch_loss(image, target, ctx.needs_input_grad[0])
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+class FusedPerceptual(torch.nn.Module):
+    """PerceptualStandIn.forward(image, target) -> scalar on the HIP kernels of csrc/ggd_perceptual.hip:
+    same definition, summed over the batch, gradient into `image` only, no float atomics, bit-identical from run to run.
+    module: a PerceptualStandIn or anything of its shape -- 13 `convs` (3x3, padding 1), 5 `lin` vectors, pools and taps at the
+        stand-in's places; its weights are packed once (`repack()` re-reads them).
+    precision: "bf16" -- f16 operands forward, bf16 operands backward, fp32 accumulation; "fp32" -- split-bf16 operands (three
+        MFMAs per product) both ways.
+    max_size: a side above it is area-averaged down to it (the reference's 256; an integer factor only).
+    input_affine: (scale[3], shift[3]) applied to the image before the trunk; default (2, -1), the stand-in's img * 2 - 1.
+    Device tensors take the kernels, CPU tensors the wrapped module (which knows neither max_size nor input_affine).
+    ValueError, before any native call: a module of another shape; a width that is not a multiple of 32 (or above 512; the first
+    above 64); H or W that is not a multiple of 16; a side above max_size that is not a multiple of it."""
+    TAPS = PerceptualStandIn.TAPS
+
+    def __init__(self, module, precision="fp32", max_size=256, input_affine=None):
+        super().__init__()
+        from . import _capi
+        if precision not in _capi.PERC_TIERS:
+            raise ValueError(f"FusedPerceptual: precision must be 'fp32' or 'bf16' (got {precision!r})")
+        self.widths = self._check_module(module)
+        if int(max_size) <= 0 or int(max_size) % 16 != 0:
+            raise ValueError(f"FusedPerceptual: max_size must be a positive multiple of 16 (got {max_size})")
+        scale, shift = ((2.0, 2.0, 2.0), (-1.0, -1.0, -1.0)) if input_affine is None else input_affine
+        scale, shift = [float(v) for v in scale], [float(v) for v in shift]
+        if len(scale) != 3 or len(shift) != 3:
+            raise ValueError("FusedPerceptual: input_affine must be (scale[3], shift[3])")
+        self.module, self.precision, self.max_size, self.input_affine = module, precision, int(max_size), (scale, shift)
+        self._packed = None
+
+    @staticmethod
+    def _check_module(module):
+        convs, lin = getattr(module, "convs", None), getattr(module, "lin", None)
+        if convs is None or lin is None or len(convs) != 13 or len(lin) != 5:
+            raise ValueError("FusedPerceptual: the module must have 13 `convs` and 5 `lin` vectors")
+        if tuple(getattr(module, "TAPS", PerceptualStandIn.TAPS)) != PerceptualStandIn.TAPS or \
+                [v == "M" for v in getattr(module, "CFG", PerceptualStandIn.CFG)] != [v == "M" for v in PerceptualStandIn.CFG]:
+            raise ValueError("FusedPerceptual: pools and taps must sit at PerceptualStandIn's places")
+        cin, widths = 3, []
+        for i, conv in enumerate(convs):
+            w = getattr(conv, "weight", None)
+            if w is None or w.dim() != 4 or tuple(w.shape[1:]) != (cin, 3, 3) or getattr(conv, "bias", None) is None or \
+                    tuple(getattr(conv, "padding", (1, 1))) != (1, 1) or tuple(getattr(conv, "stride", (1, 1))) != (1, 1):
+                raise ValueError(f"FusedPerceptual: convs[{i}] must be a biased 3x3 convolution, padding 1, of {cin} channels")
+            cin = int(w.shape[0])
+            widths.append(cin)
+        for k, t in enumerate(PerceptualStandIn.TAPS):
+            if tuple(lin[k].shape) != (widths[t],):
+                raise ValueError(f"FusedPerceptual: lin[{k}] must have {widths[t]} entries")
+        if any(w % 32 != 0 or w > 512 for w in widths) or widths[0] > 64:
+            raise ValueError(f"FusedPerceptual: every width must be a multiple of 32 up to 512 (the first up to 64), got {widths}")
+        return widths
+
+    def trunk_size(self, H, W):
+        """(H', W') at which the trunk runs an H x W input; the refusals of the class docstring."""
+        H, W = int(H), int(W)
+        if H > self.max_size:           # the stand-in's rule (lpips.py:23-26): decided by the height, both sides resized
+            if H % self.max_size != 0 or W % self.max_size != 0:
+                raise ValueError(f"FusedPerceptual: a side above max_size = {self.max_size} must be a multiple of it, got {H} x {W}")
+            H = W = self.max_size
+        if H <= 0 or W <= 0 or H % 16 != 0 or W % 16 != 0:
+            raise ValueError(f"FusedPerceptual: H and W must be multiples of 16 (four 2x2 pools), got {H} x {W}")
+        return H, W
+
+    def _batch(self, img, what):
+        x = img if img.dim() == 4 else img.unsqueeze(0)
+        if x.dim() != 4 or int(x.shape[1]) != 3 or int(x.shape[0]) == 0:
+            raise ValueError(f"FusedPerceptual: {what} must be [3,H,W] or [B,3,H,W], got {tuple(img.shape)}")
+        return x, self.trunk_size(x.shape[2], x.shape[3])
+
+    def repack(self, device=None):
+        """Re-read the module's weights into the kernels' images (on `device`, default: the module's)."""
+        m = self.module
+        dev = torch.device(device) if device is not None else m.convs[0].weight.device
+        fwd, bwd = ("f16", "bf16") if self.precision == "bf16" else ("split", "split")
+        w = [c.weight.detach().to(dev, torch.float32) for c in m.convs]
+        self._packed = dict(
+            device=dev,
+            w0=w[0].permute(2, 3, 1, 0).reshape(27, -1).contiguous(),
+            w0_t=w[0].permute(2, 3, 0, 1).reshape(9, -1, 3).contiguous(),
+            bias=[c.bias.detach().to(dev, torch.float32).contiguous() for c in m.convs],
+            w_fwd=[None] + [pack_conv_weights(x, fwd) for x in w[1:]],
+            w_bwd=[None] + [pack_conv_weights(x.flip(2, 3).transpose(0, 1), bwd) for x in w[1:]],
+            lin=[p.detach().to(dev, torch.float32).contiguous() for p in m.lin])
+        return self
+
+    def _desc(self, B, H_in, W_in, H, W, dev):
+        from . import _capi
+        if self._packed is None or self._packed["device"] != dev:
+            self.repack(dev)
+        pk, d = self._packed, _capi.PerceptualDesc()
+        d.tier, d.B, d.H_in, d.W_in, d.H, d.W = _capi.PERC_TIERS[self.precision], B, H_in, W_in, H, W
+        d.widths[:] = self.widths
+        d.scale[:], d.shift[:] = self.input_affine
+        d.w0, d.w0_t = pk["w0"].data_ptr(), pk["w0_t"].data_ptr()
+        for l in range(13):
+            d.bias[l] = pk["bias"][l].data_ptr()
+            d.w_fwd[l] = pk["w_fwd"][l].data_ptr() if l else None
+            d.w_bwd[l] = pk["w_bwd"][l].data_ptr() if l else None
+        for k in range(5):
+            d.lin[k] = pk["lin"][k].data_ptr()
+        return d
+
+    def _launch_loss(self, image, target, with_grad):
+        from . import _capi
+        dev = image.device
+        img, tgt = image.detach().contiguous().float(), target.detach().contiguous().float()
+        B, _, H_in, W_in = (int(n) for n in img.shape)
+        H, W = self.trunk_size(H_in, W_in)
+        d = self._desc(B, H_in, W_in, H, W, dev)
+        cx = _capi.context_for(dev)
+        nbytes = cx.lib.ggd_perceptual_tmp_bytes(C.byref(d), 2 * B, int(with_grad))
+        if nbytes == 0:
+            raise ValueError("FusedPerceptual: ggd_perceptual_tmp_bytes refuses this shape")
+        tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        grad = torch.empty_like(img) if with_grad else None
+        with torch.cuda.device(dev):
+            cx.check(cx.lib.ggd_perceptual_loss(cx.handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.byref(d),
+                                                C.c_void_p(img.data_ptr()), C.c_void_p(tgt.data_ptr()), C.c_void_p(loss.data_ptr()),
+                                                C.c_void_p(grad.data_ptr()) if with_grad else None, C.c_void_p(tmp.data_ptr()), nbytes))
+        return loss[0].clone(), (grad if with_grad else torch.zeros((), device=dev))
+
+    def features(self, img):
+        """[B, F] rows as PerceptualStandIn.features returns them (no gradient on the device path)."""
+        x, (H, W) = self._batch(img, "img")
+        if not x.is_cuda:
+            return self.module.features(img)
+        from . import _capi
+        dev = x.device
+        x = x.detach().contiguous().float()
+        B, _, H_in, W_in = (int(n) for n in x.shape)
+        d = self._desc(B, H_in, W_in, H, W, dev)
+        cx = _capi.context_for(dev)
+        nbytes = cx.lib.ggd_perceptual_tmp_bytes(C.byref(d), B, 0)
+        tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        n_feat = sum(self.widths[t] * (H >> k) * (W >> k) for k, t in enumerate(self.TAPS))
+        feat = torch.empty((B, n_feat), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            cx.check(cx.lib.ggd_perceptual_features(cx.handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.byref(d),
+                                                    C.c_void_p(x.data_ptr()), C.c_void_p(feat.data_ptr()), C.c_void_p(tmp.data_ptr()),
+                                                    nbytes))
+        return feat
+
+    def forward(self, image, target):
+        x, size = self._batch(image, "image")
+        t, size_t = self._batch(target, "target")
+        if tuple(x.shape) != tuple(t.shape):
+            raise ValueError(f"FusedPerceptual: image {tuple(image.shape)} and target {tuple(target.shape)} must have one shape")
+        if x.device != t.device:
+            raise RuntimeError("FusedPerceptual: image and target must live on one device")
+        if not x.is_cuda:
+            return self.module(image, target)
+        return _FusedPerceptualFn.apply(x, t, self)

@@ -130,7 +130,8 @@ class DecoderTrainer:
                  triplane_depth=None, fused_planes=None, force_comm=None, antialiasing: bool = False,
                  apply_mask_to_rendering: bool = False, decoder_type: str = "sequential_reversed",
                  mask_weight: float = 0.0, depth_weight: float = 0.0, geometry_loss_fn=None,
-                 distortion_weight: float = 0.0, normal_weight: float = 0.0):
+                 distortion_weight: float = 0.0, normal_weight: float = 0.0, fused_perceptual: bool = False,
+                 perceptual_precision=None):
         """plane_axes / triplane_depth: the generator whose planes are decoded -- ("eg3d", None): tri-planes
         [3, C, res, res]; ("panohead", 3): PanoHead's tri-grids [3, C * 3, res, res] sampled with a 3-D grid_sample
         (the reference's default generator: main/train_pano2gaussian_decoder.py:43, PanoHead/train.py:230,318,
@@ -165,7 +166,11 @@ class DecoderTrainer:
         render_depth_alpha=True, render_normals=True (passed to render_fn only then) and normal_weight *
         normals.fused_normal_loss(out["normals"], out["depth"], out["alpha"], tanfov, tanfov)[0] is added to the scene's loss --
         the normal-consistency loss of 2DGS / gsplat, which turns each splat's shortest axis along the normal of the surface the
-        depth map describes.  No value is tuned, the loss's alpha_min included."""
+        depth map describes.  No value is tuned, the loss's alpha_min included.
+        fused_perceptual (default False: nothing changes): with perceptual_weight > 0 on a HIP device the perceptual stand-in
+        runs on the kernels of csrc/ggd_perceptual.hip (losses.FusedPerceptual) instead of thirteen MIOpen convolutions;
+        perceptual_precision "bf16" / "fp32" is its tier, None follows decoder_precision.  The stand-in's widths must then be
+        multiples of 32 (perceptual_width_div 1 or 2)."""
         import os
         import torch.distributed as dist
         self.force_comm = bool(int(os.environ.get("GGD_FORCE_COMM", "0"))) if force_comm is None else bool(force_comm)
@@ -209,6 +214,10 @@ class DecoderTrainer:
             self.perceptual = PerceptualStandIn(seed=seed + 99, width_div=perceptual_width_div).to(self.device)
             if self.device.type == "cuda":
                 self.perceptual = self.perceptual.to(memory_format=torch.channels_last)
+        self.perceptual_fn = self.perceptual
+        if fused_perceptual and self.perceptual is not None and self.device.type == "cuda":
+            from .losses import FusedPerceptual
+            self.perceptual_fn = FusedPerceptual(self.perceptual, precision=perceptual_precision or decoder_precision)
         # fused_decoder: the MFMA decoder kernels (forward, activation backward, weight gradients) instead of the PyTorch
         # module; decoder_precision "bf16" (operands rounded to bf16) or "fp32" (split operands: the reference's precision)
         self.decoder_fwd = self.decoder
@@ -552,7 +561,7 @@ class DecoderTrainer:
             images, targets = torch.stack(self._perc_images), batch.target[:B]
             if self.apply_mask_to_rendering:
                 images, targets = composite_mask(images, batch.mask[:B]), composite_mask(targets, batch.mask[:B])
-            total = total + self.perceptual_weight * self.perceptual(images, targets)
+            total = total + self.perceptual_weight * self.perceptual_fn(images, targets)
             self._perc_images = []
         total = total / B
         if self.backbone is not None:

@@ -1005,6 +1005,51 @@ int ggd_teacher_render(ggd_ctx* ctx, void* stream, const float* grids_cl, int32_
                        int32_t use_crop, double crop_limit, int32_t white_back, float* features, float* depth, float* weights,
                        float* samples /* NULL = workspace */);
 
+/*
+ * The perceptual term (csrc/ggd_perceptual.hip): losses.PerceptualStandIn -- perc() of main/loss_utils/lpips.py:16-34 with a
+ * VGG16-shaped trunk of 13 3x3 convolutions (padding 1, ReLU), 2x2 max pools behind convolutions 1, 3, 6, 9 and five taps behind
+ * 1, 3, 6, 9, 12 -- as HIP kernels: the forward, sum over the taps of |n_img - n_tgt|^2 with n = x / (|x|_c + 1e-10) *
+ * sqrt(lin_c / (H W)), and the gradient into the image.  The twelve convolutions behind the first run on MFMA.
+ *   tier GGD_PERC_BF16: f16 operands forward (clamped to +-65504), bf16 operands backward, fp32 accumulation;
+ *   tier GGD_PERC_FP32: split-bf16 operands (hi + lo, three MFMAs per product) in both directions.
+ * desc (HOST struct, DEVICE pointers inside):
+ *   image [B][3][H_in][W_in] fp32 in; x = mean over (H_in / H) x (W_in / W) blocks of scale[c] * image + shift[c] enters the trunk
+ *   at H x W (both multiples of 16 and divisors of H_in, W_in); widths[13]: output channels, each a multiple of 32, <= 512
+ *   (widths[0] <= 64);
+ *   w0 [27][widths[0]] fp32, row (ky * 3 + kx) * 3 + ci; w0_t [9][widths[0]][3] fp32, W[co][ci][ky][kx] at [ky * 3 + kx][co][ci];
+ *   bias[l] [widths[l]] fp32; lin[k] [width of tap k] fp32;
+ *   w_fwd[l], w_bwd[l] (l = 1..12): the weight images in MFMA fragment order -- losses.pack_conv_weights of the layer's weights,
+ *   and of the flipped, transposed weights; f16 / bf16 for GGD_PERC_BF16, bf16 hi and lo for GGD_PERC_FP32.
+ * ggd_perceptual_loss: target [B][3][H_in][W_in] goes through the forward with the image as one batch of 2 B; loss (device, 1
+ * float) = the sum over the batch; grad_image (device [B][3][H_in][W_in], or NULL: forward only) = dloss/dimage.  No gradient
+ * for the target or the weights.  ggd_perceptual_features: features [B][F] = the rows of PerceptualStandIn.features (per tap
+ * [C][H_k][W_k] flattened, taps concatenated).  tmp: ggd_perceptual_tmp_bytes(desc, images in the forward (2 B for the loss, B for
+ * the features), with_grad) bytes of device scratch; 0 for a shape, width or tier the kernels do not take, which the entries
+ * refuse with GGD_E_INVALID before anything is launched.  No host sync, no float atomics: bit-identical from run to run.
+ */
+#define GGD_PERC_CONVS 13
+#define GGD_PERC_TAPS 5
+enum { GGD_PERC_BF16 = 0, GGD_PERC_FP32 = 1 };
+typedef struct ggd_perceptual_desc {
+  int32_t tier;
+  int32_t B;
+  int32_t H_in, W_in;
+  int32_t H, W;
+  int32_t widths[GGD_PERC_CONVS];
+  float scale[3], shift[3];
+  const float* w0;
+  const float* w0_t;
+  const float* bias[GGD_PERC_CONVS];
+  const void* w_fwd[GGD_PERC_CONVS];   /* [0] unused */
+  const void* w_bwd[GGD_PERC_CONVS];   /* [0] unused */
+  const float* lin[GGD_PERC_TAPS];
+} ggd_perceptual_desc;
+size_t ggd_perceptual_tmp_bytes(const ggd_perceptual_desc* desc, int32_t n_images, int32_t with_grad);
+int ggd_perceptual_loss(ggd_ctx* ctx, void* stream, const ggd_perceptual_desc* desc, const float* image, const float* target,
+                        float* loss, float* grad_image /* or NULL */, void* tmp, size_t tmp_bytes);
+int ggd_perceptual_features(ggd_ctx* ctx, void* stream, const ggd_perceptual_desc* desc, const float* image, float* features,
+                            void* tmp, size_t tmp_bytes);
+
 /* Per-stage device time (ms, hipEvent pairs on `stream`) of the most recent forward_geometry / forward_render /
  * backward call when profiling is on.  Stage names: ggd_stage_name(i), i in [0, ggd_stage_count()). */
 int ggd_set_profiling(ggd_ctx* ctx, int enabled);
